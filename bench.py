@@ -13,13 +13,18 @@ batch 16 x 448 x 448 per GPU (weak scaling).
 
 The headline `value` is measured in the trainer's default mode -- the cheapest teacher-operand mode with no failed plane on the committed
 accuracy record under the pre-registered criterion (`conformance()` below; since round 6: fp16x3, hi + lo fp16 halves and three MFMA terms per
-product), student on an fp32 residual stream: top-level `tolerance_met` is read from that record and confirmed in the run.  `fast_mode` = the
+product), student on an fp32 residual stream: with --full, `tolerance_met` is read from that record and confirmed in the run.  `fast_mode` = the
 same step with the bf16-operand teacher of configs[1] read literally (faster, out of tolerance); `other_modes`: fp16c8-x2 (round 5's default:
 25 % faster, fails the float64-bounded exemption on planes of conditioning > 100), uniform fp16c8, bf16x3.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-  roofline      the dominant hand-written kernel, timed with HIP events inside the timed steps
+Rank 0 prints ONE JSON line: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and the run's `config`.
+A plain run does nothing else: set-up, W warm-up steps, K timed steps, the line.  With --full the line also carries, among others:
+  roofline      the dominant hand-written kernel, device-clock spans of its launches inside the timed steps
+  tolerance_met the accuracy record of the benchmarked mode and the in-run check (`accuracy_vs_fp32_cpu_oracle`, `accuracy_live`)
+  par_refine, bilateral, vit_forward, teacher_attention, evaluation, input_pipeline   stand-alone timings of their own
+  fast_mode, other_modes   the same step with other teacher-operand modes (N=1 only)
   cpu_baseline  the CPU oracle's step on a bounded sample (N=1 only), timed on the host cores
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -48,7 +53,12 @@ def parse():
     ap.add_argument("--dataset", default="VOC12", choices=["VOC12", "COCO"])
     ap.add_argument("--usepar", action="store_true", help="PAR(T=10, 6 dilations) as cam2mask's refine_model")
     ap.add_argument("--usegmm", action="store_true", help="adaptive thresholds: 3-component mixture fitted to the CAM queue every step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: kernel rooflines, the accuracy record and in-run check, PAR / bilateral / "
+                         "evaluation / input-pipeline timings, the other teacher-operand modes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--teacher-precision", default="auto", type=_mode_arg,
                     metavar="{auto,bf16,fp16,bf16x3,fp16x3,fp16c8[-N[mK]|-xN[mK]],fp16c4[...]}",
                     help="MFMA operand precision of the teacher's no-grad passes in the HEADLINE run (DESIGN.md section 3).  The default (`auto`) is the "
@@ -57,7 +67,7 @@ def parse():
                          "mIoU >= 0.999; >= 64 draws): train_step.resolve_teacher_precision; "
                          "`bf16` is BASELINE configs[1] read literally and does not meet it (measured beside the headline as `fast_mode`)")
     ap.add_argument("--no-secondary", "--no-parity-grade", dest="no_secondary", action="store_true",
-                    help="skip the secondary measurements (`fast_mode`: bf16-operand teacher; `other_modes`)")
+                    help="with --full: skip the secondary measurements (`fast_mode`: bf16-operand teacher; `other_modes`)")
     ap.add_argument("--student-stream", default="fp32", choices=["fp32", "bf16"],
                     help="residual stream of the student's training path: fp32 like the reference (default) or the bf16 stream of rounds 1-3")
     ap.add_argument("--defer-groups", type=int, default=0,
@@ -623,7 +633,118 @@ def eval_images_per_s(trainer, dev, C, crop, n=20):
             "sample": f"{n} images ~375x500 from a batch-1 loader, 5 scales x 2 flips"}
 
 
+DUMP_MAX_ELEMS = 1 << 22         # float32 entries per dumped array (16 MB): a larger output is written as a fixed, seeded sample
+PARAM_SAMPLE = 1 << 20           # entries of the updated student parameters in the dump
+
+
+def _seeded_sample(flat, n, seed):
+    """n entries of the 1-D tensor `flat` at indices drawn from a CPU generator seeded with `seed`: the same for the same size and seed"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, logs, student):
+    """--dump-outputs: what the last timed step computed, as <path>/<name>.npy in float32 -- every tensor the step returns (the five losses
+    and their sum, the label map `mask` of the main CAMs, the class logits) and `student_params_sample`, a seeded sample of the student's
+    parameters after the step's AdamW update.  An array of more than DUMP_MAX_ELEMS entries is written as a seeded sample of its flattened
+    values: the label map of the bench batch (16 x 448^2) is written whole, and the directory stays far below 64 MB at any batch."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach() for k, v in logs.items() if torch.is_tensor(v)}
+    flat = torch.cat([p.detach().reshape(-1).float() for p in student.parameters()])
+    arrays["student_params_sample"] = _seeded_sample(flat, min(PARAM_SAMPLE, flat.numel()), 0)
+    del flat
+    for name, t in arrays.items():
+        t = t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            t = _seeded_sample(t.reshape(-1), DUMP_MAX_ELEMS, 1)
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 _keep_stamp_buffers = []
+
+
+def full_report(out, opt, trainer, prof, dt, ips, world, dev, C, wimg, simg, lab, box, n_iter):
+    """--full: everything the line carries beyond the headline (module docstring), added to `out`"""
+    from cosa_amd import nn_ops
+    flop_img = FLOP_PER_IMG_448 if opt.crop == 448 else None
+    # dominant hand-written kernels: the persistent projection GEMM (three epilogue instantiations of one kernel) and the
+    # fused attention forward.  Their launches sit inside the teacher's hipGraph, where HIP events cannot be recorded
+    # on ROCm, so every launch stamps the 100 MHz device clock itself (min start / max end over its workgroups); the
+    # numbers below are the launches of the LAST timed step.  `roofline` is the family with the larger share of the step.
+    def family(st, name, pmc_file, ev_key):
+        n_launch, secs, flops = st.read()
+        if not n_launch:
+            return None
+        traffic = None
+        try:        # HBM bytes of the dominant launch shape from the newest committed PMC passes (profiles/, separate --pmc runs)
+            f = newest_profile(pmc_file)
+            pmc = json.load(open(f))
+            traffic = {"hbm_bytes": pmc["hbm_bytes_per_launch"], "algorithmic_bytes": pmc["algorithmic_bytes_per_launch"],
+                       "launch": pmc["launch"], "source": "profiles/" + os.path.basename(f)}
+        except Exception:
+            pass
+        ev_n, ev_ms = prof.get(ev_key, (0, 0.0))     # HIP events around the eager (student) launches, for comparison
+        ach = flops / secs / 1e12
+        issued = getattr(st, "last_issued", flops)   # MFMA work issued: the correction terms of the fp16c8 / fp16c4 / bf16x3 operand formats on top
+        return {"kernel": name, "bound": "mfma", "achieved": round(ach, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
+                "frac": round(ach * 1e12 / PEAK_BF16, 4), "issued_mfma_frac": round(issued / secs / PEAK_BF16, 4),
+                "note": "achieved / frac: ALGORITHMIC FLOPs (2 M N K per launch) over the launches' device time; issued_mfma_frac: the bf16-"
+                        "equivalent MFMA work the launches issue (fp16c4: 19 K-tiles per 12, fp16c8: 25 per 12, fp16x3 / bf16x3: 37 per 12) over the same time",
+                "traffic": traffic, "launches": n_launch,
+                "avg_launch_ms": round(secs * 1e3 / n_launch, 4), "share_of_step": round(secs / (dt / opt.steps), 4),
+                "timer": "device s_memrealtime spans, last timed step" + ("" if opt.teacher_sync else
+                                                                               " (teacher graph on a side stream: spans include sharing the GPU with the student's forward)"),
+                "hip_event_avg_ms_eager_launches": round(ev_ms / ev_n, 4) if ev_n else None}
+    c4mode = opt.teacher_precision.startswith("fp16c4")
+    fams = [family(nn_ops.gemm_stamps, "gemm_bf16_v6_kernel (persistent 256x256 MFMA GEMM: qkv / proj+residual / fc1+GELU / fc2+residual; teacher "
+                   "launches on " + ("fp16c4" if c4mode else opt.teacher_precision.split("-")[0]) + " operands, student launches on bf16)",
+                   "gemm_c4_pmc.json" if c4mode else ("gemm_c8_pmc.json" if opt.teacher_precision.startswith("fp16c8") else
+                                                      ("gemm_x3_pmc.json" if opt.teacher_precision.endswith("x3") else "gemm_v6_pmc.json")), "gemm_bf16"),
+            family(nn_ops.stamps, ("attn_fwd_x3_kernel (teacher, three-term operands) + attn_fwd2_kernel (student)" if opt.teacher_precision.endswith("x3")
+                                   else "attn_fwd2_kernel (fused attention forward)"),
+                   "attn_x3_pmc.json" if opt.teacher_precision.endswith("x3") else "attn_fwd_pmc.json", "attn_fwd")]
+    fams = sorted([f for f in fams if f], key=lambda f: -f["share_of_step"])
+    # the remaining legs time their own launches: stamping off (the buffers stay alive: the teacher's captured launches still write to them)
+    _keep_stamp_buffers.extend([nn_ops.stamps, nn_ops.gemm_stamps])
+    nn_ops.stamps = nn_ops.gemm_stamps = None
+    # does the mode `value` was measured in meet BASELINE.json's tolerance (1e-3 relative on fp32 CAMs, mask IoU >= 0.999 against the
+    # fp32 CPU oracle)?  Read from the committed accuracy record of that mode (worst over every draw on record; the GPU tests that write
+    # it assert the same bars, and the record must name the kernel sources of this tree: conformance()).  The default headline mode
+    # does; the bf16-operand teacher (`fast_mode`) does not.
+    acc = conformance(opt.teacher_precision, opt.crop)
+    out["tolerance_met"] = acc["tolerance_met"]          # (and the live check below: set after it ran)
+    out["accuracy_vs_fp32_cpu_oracle"] = acc
+    out["roofline"] = fams[0] if fams else None
+    if len(fams) > 1:
+        out["roofline_second"] = fams[1]
+    if flop_img:
+        out["step_mfma"] = {"achieved_TFLOPs": round(ips * flop_img / 1e12, 2), "peak_TFLOPs": PEAK_BF16 / 1e12 * world,
+                            "frac": round(ips * flop_img / (PEAK_BF16 * world), 4), "flop_per_img": flop_img}
+    out["tolerance_planes"] = {k: acc.get(k) for k in ("planes", "planes_exempt", "planes_failed", "draws")}          # how many planes took the conditioning exemption
+    try:
+        out["accuracy_live"] = live_accuracy_check(trainer, wimg, lab, box)
+        out["tolerance_met"] = bool(out["tolerance_met"] and (out["accuracy_live"]["gross_error_ok"] or opt.teacher_precision == "bf16x3"))
+    except Exception as e:          # (never lose the bench line to the side check -- but a check that could not run is not a pass: ADVICE r5)
+        out["accuracy_live"] = {"error": repr(e)[:200]}
+        out["tolerance_met"] = False
+        out["tolerance_note"] = "the in-run accuracy check raised: tolerance not confirmed in this run"
+    vf = vit_forward_roofline(trainer, wimg, dev, opt.crop)
+    if vf:
+        out["vit_forward"] = vf
+    ta = teacher_attention_roofline(dev, opt.batch, opt.crop, opt.teacher_precision)
+    if ta:
+        out["teacher_attention"] = ta
+    out["par_refine"] = par_refine_ms_per_img(trainer, simg, lab, box, dev, opt, C)
+    out["bilateral"] = out["par_refine"].pop("bilateral")
+    if world == 1 and not opt.no_secondary:
+        out.update(secondary_modes(opt, dev, C, wimg, simg, lab, box, n_iter))
+    if world == 1 and opt.crop == 448:
+        out["evaluation"] = eval_images_per_s(trainer, dev, C, opt.crop)
+        out["input_pipeline"] = input_pipeline_images_per_s(dev, opt.batch, opt.crop)
+    if world == 1 and not opt.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(opt, trainer.student.state_dict(), C)
 
 
 def main():
@@ -660,8 +781,9 @@ def main():
     args = default_args(opt.dataset, crop_size=opt.crop, batch_size=opt.batch, usepar=opt.usepar, usegmm=opt.usegmm,
                         teacher_precision=opt.teacher_precision,
                         teacher_async=not (opt.teacher_sync or shared_card or os.environ.get("COSA_TEACHER_SYNC", "0") not in ("0", "")))
-    nn_ops.stamps = nn_ops.KernelStamps(dev)          # device-side launch spans of the two dominant kernels (work inside hipGraphs)
-    nn_ops.gemm_stamps = nn_ops.KernelStamps(dev)
+    if opt.full:
+        nn_ops.stamps = nn_ops.KernelStamps(dev)          # device-side launch spans of the two dominant kernels (work inside hipGraphs)
+        nn_ops.gemm_stamps = nn_ops.KernelStamps(dev)
     trainer = CoSATrainer(args, dev, ddp=world > 1, seed=0)
     configure_student(trainer, opt)
     if opt.grid_policy >= 0:
@@ -682,14 +804,15 @@ def main():
     for _ in range(opt.warmup):
         trainer.step(wimg, simg, lab, box, n_iter)
     sync()
-    nn_ops._flops.clear()
-    _C.profile_start()
+    if opt.full:
+        nn_ops._flops.clear()
+        _C.profile_start()
     t0 = time.perf_counter()
     for _ in range(opt.steps):
         logs = trainer.step(wimg, simg, lab, box, n_iter)
     sync()
     dt = time.perf_counter() - t0
-    prof = _C.profile_stop()
+    prof = _C.profile_stop() if opt.full else None
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -697,104 +820,30 @@ def main():
     loss = float(logs["overall_loss"])
 
     if rank == 0:
+        if opt.dump_outputs:
+            dump_outputs(opt.dump_outputs, logs, trainer.student)
         imgs = opt.batch * world * opt.steps
         ips = imgs / dt
-        flop_img = FLOP_PER_IMG_448 if opt.crop == 448 else None
-        # dominant hand-written kernels: the persistent projection GEMM (three epilogue instantiations of one kernel) and the
-        # fused attention forward.  Their launches sit inside the teacher's hipGraph, where HIP events cannot be recorded
-        # on ROCm, so every launch stamps the 100 MHz device clock itself (min start / max end over its workgroups); the
-        # numbers below are the launches of the LAST timed step.  `roofline` is the family with the larger share of the step.
-        def family(st, name, pmc_file, ev_key):
-            n_launch, secs, flops = st.read()
-            if not n_launch:
-                return None
-            traffic = None
-            try:        # HBM bytes of the dominant launch shape from the newest committed PMC passes (profiles/, separate --pmc runs)
-                f = newest_profile(pmc_file)
-                pmc = json.load(open(f))
-                traffic = {"hbm_bytes": pmc["hbm_bytes_per_launch"], "algorithmic_bytes": pmc["algorithmic_bytes_per_launch"],
-                           "launch": pmc["launch"], "source": "profiles/" + os.path.basename(f)}
-            except Exception:
-                pass
-            ev_n, ev_ms = prof.get(ev_key, (0, 0.0))     # HIP events around the eager (student) launches, for comparison
-            ach = flops / secs / 1e12
-            issued = getattr(st, "last_issued", flops)   # MFMA work issued: the correction terms of the fp16c8 / fp16c4 / bf16x3 operand formats on top
-            return {"kernel": name, "bound": "mfma", "achieved": round(ach, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
-                    "frac": round(ach * 1e12 / PEAK_BF16, 4), "issued_mfma_frac": round(issued / secs / PEAK_BF16, 4),
-                    "note": "achieved / frac: ALGORITHMIC FLOPs (2 M N K per launch) over the launches' device time; issued_mfma_frac: the bf16-"
-                            "equivalent MFMA work the launches issue (fp16c4: 19 K-tiles per 12, fp16c8: 25 per 12, fp16x3 / bf16x3: 37 per 12) over the same time",
-                    "traffic": traffic, "launches": n_launch,
-                    "avg_launch_ms": round(secs * 1e3 / n_launch, 4), "share_of_step": round(secs / (dt / opt.steps), 4),
-                    "timer": "device s_memrealtime spans, last timed step" + ("" if opt.teacher_sync else
-                                                                                   " (teacher graph on a side stream: spans include sharing the GPU with the student's forward)"),
-                    "hip_event_avg_ms_eager_launches": round(ev_ms / ev_n, 4) if ev_n else None}
-        c4mode = opt.teacher_precision.startswith("fp16c4")
-        fams = [family(nn_ops.gemm_stamps, "gemm_bf16_v6_kernel (persistent 256x256 MFMA GEMM: qkv / proj+residual / fc1+GELU / fc2+residual; teacher "
-                       "launches on " + ("fp16c4" if c4mode else opt.teacher_precision.split("-")[0]) + " operands, student launches on bf16)",
-                       "gemm_c4_pmc.json" if c4mode else ("gemm_c8_pmc.json" if opt.teacher_precision.startswith("fp16c8") else
-                                                          ("gemm_x3_pmc.json" if opt.teacher_precision.endswith("x3") else "gemm_v6_pmc.json")), "gemm_bf16"),
-                family(nn_ops.stamps, ("attn_fwd_x3_kernel (teacher, three-term operands) + attn_fwd2_kernel (student)" if opt.teacher_precision.endswith("x3")
-                                       else "attn_fwd2_kernel (fused attention forward)"),
-                       "attn_x3_pmc.json" if opt.teacher_precision.endswith("x3") else "attn_fwd_pmc.json", "attn_fwd")]
-        fams = sorted([f for f in fams if f], key=lambda f: -f["share_of_step"])
-        roof = fams[0] if fams else None
-        # the remaining legs time their own launches: stamping off (the buffers stay alive: the teacher's captured launches still write to them)
-        _keep_stamp_buffers.extend([nn_ops.stamps, nn_ops.gemm_stamps])
-        nn_ops.stamps = nn_ops.gemm_stamps = None
+        enc = trainer.student.encoder
         out = {
             "metric": "training images/sec at 448x448 ViT-B", "value": round(ips, 3), "unit": "images/s", "n_gpus": world,
             "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(dt / opt.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",        # dtype: the student's MFMA operands (the teacher's: config.teacher_operands)
-            # does the mode `value` was measured in meet BASELINE.json's tolerance (1e-3 relative on fp32 CAMs, mask IoU >= 0.999 against the
-            # fp32 CPU oracle)?  Read from the committed accuracy record of that mode (worst over every draw on record; the GPU tests that write
-            # it assert the same bars, and the record must name the kernel sources of this tree: conformance()).  The default headline mode
-            # does; the bf16-operand teacher (`fast_mode`) does not.
-            "tolerance_met": conformance(opt.teacher_precision, opt.crop)["tolerance_met"],          # (and the live check below: set after it ran)
-            "accuracy_vs_fp32_cpu_oracle": conformance(opt.teacher_precision, opt.crop),
             "config": {"workload": f"{opt.dataset} {C + 1}-class, ViT-B/16 bf16, batch {opt.batch}/GPU x {opt.crop}x{opt.crop}, "
                                    f"teacher 3 scales x 2 flips + student fwd/bwd + cam2mask x2 + 5 losses + AdamW + EMA"
                                    f"{' + PAR' if opt.usepar else ''}{' + adaptive thresholds (GMM)' if opt.usegmm else ''}",
                        "global_batch": opt.batch * world, "parallelism": f"dp{world}", "final_loss": round(loss, 5),
                        "dist_backend": (dist.get_backend() + f" (world size seen by the collective library: {dist.get_world_size()})") if world > 1 else None,
+                       "teacher_operands": opt.teacher_precision + ": " + MODE_TEXT[opt.teacher_precision],
+                       "teacher_graph": {"captured": trainer._graph is not None, "side_stream": bool(trainer.teacher_async), "error": trainer.graph_error,
+                                         "fallbacks": "COSA_TEACHER_SYNC=1 (replay on the main stream), COSA_TEACHER_GRAPH=0 (eager teacher)"},
+                       "student": f"bf16 MFMA operands, {enc.residual_stream} residual stream and gradient sums, fp32 master weights / AdamW / EMA",
+                       "defer_groups": enc._n_defer_groups() if enc.defer_wgrad else 0,
+                       "grid_policy": opt.grid_policy if opt.grid_policy >= 0 else ("balanced (trainer default under DDP)" if world > 1 else "full grid"),
                        },
-            "roofline": roof,
         }
-        if len(fams) > 1:
-            out["roofline_second"] = fams[1]
-        if flop_img:
-            out["step_mfma"] = {"achieved_TFLOPs": round(ips * flop_img / 1e12, 2), "peak_TFLOPs": PEAK_BF16 / 1e12 * world,
-                                "frac": round(ips * flop_img / (PEAK_BF16 * world), 4), "flop_per_img": flop_img}
-        acc = out["accuracy_vs_fp32_cpu_oracle"]
-        out["tolerance_planes"] = {k: acc.get(k) for k in ("planes", "planes_exempt", "planes_failed", "draws")}          # how many planes took the conditioning exemption
-        try:
-            out["accuracy_live"] = live_accuracy_check(trainer, wimg, lab, box)
-            out["tolerance_met"] = bool(out["tolerance_met"] and (out["accuracy_live"]["gross_error_ok"] or opt.teacher_precision == "bf16x3"))
-        except Exception as e:          # (never lose the bench line to the side check -- but a check that could not run is not a pass: ADVICE r5)
-            out["accuracy_live"] = {"error": repr(e)[:200]}
-            out["tolerance_met"] = False
-            out["tolerance_note"] = "the in-run accuracy check raised: tolerance not confirmed in this run"
-        vf = vit_forward_roofline(trainer, wimg, dev, opt.crop)
-        if vf:
-            out["vit_forward"] = vf
-        ta = teacher_attention_roofline(dev, opt.batch, opt.crop, opt.teacher_precision)
-        if ta:
-            out["teacher_attention"] = ta
-        out["config"]["teacher_operands"] = opt.teacher_precision + ": " + MODE_TEXT[opt.teacher_precision]
-        out["config"]["teacher_graph"] = {"captured": trainer._graph is not None, "side_stream": bool(trainer.teacher_async), "error": trainer.graph_error,
-                                          "fallbacks": "COSA_TEACHER_SYNC=1 (replay on the main stream), COSA_TEACHER_GRAPH=0 (eager teacher)"}
-        enc = trainer.student.encoder
-        out["config"]["student"] = f"bf16 MFMA operands, {enc.residual_stream} residual stream and gradient sums, fp32 master weights / AdamW / EMA"
-        out["config"]["defer_groups"] = enc._n_defer_groups() if enc.defer_wgrad else 0
-        out["par_refine"] = par_refine_ms_per_img(trainer, simg, lab, box, dev, opt, C)
-        out["bilateral"] = out["par_refine"].pop("bilateral")
-        out["config"]["grid_policy"] = opt.grid_policy if opt.grid_policy >= 0 else ("balanced (trainer default under DDP)" if world > 1 else "full grid")
-        if world == 1 and not opt.no_secondary:
-            out.update(secondary_modes(opt, dev, C, wimg, simg, lab, box, n_iter))
-        if world == 1 and opt.crop == 448:
-            out["evaluation"] = eval_images_per_s(trainer, dev, C, opt.crop)
-            out["input_pipeline"] = input_pipeline_images_per_s(dev, opt.batch, opt.crop)
-        if world == 1 and not opt.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(opt, trainer.student.state_dict(), C)
+        if opt.full:
+            full_report(out, opt, trainer, prof, dt, ips, world, dev, C, wimg, simg, lab, box, n_iter)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -149,6 +149,22 @@ def gen_bilateral(rng):
     np.savez_compressed(os.path.join(OUT, "bilateral.npz"), **out)
 
 
+def bilateral_live_input():
+    """the input of tests/test_oracle_golden.py::test_bilateral_against_compiled_reference_live"""
+    rng = np.random.default_rng(5)
+    N, K, H, W = 1, 2, 24, 40
+    img = rng.uniform(0, 255, (N, 3, H, W)).astype(np.float32)
+    seg = rng.uniform(0, 1, (N, K, H, W)).astype(np.float32)
+    return img, seg
+
+
+def gen_bilateral_live():
+    img, seg = bilateral_live_input()
+    ref = np.zeros(seg.size, np.float32)
+    c_oracle.ref_bilateralfilter_batch(img, seg, ref, *seg.shape, 15.0, 50.0)
+    np.savez_compressed(os.path.join(OUT, "bilateral_live.npz"), out=ref.reshape(seg.shape))
+
+
 def gen_misc(rng):
     sh = ref_loader.seg_helper()
     th = ref_loader.torch_helper_fns()
@@ -514,6 +530,7 @@ def main():
     gen_cam2mask(np.random.default_rng(12))
     gen_camseg(np.random.default_rng(13))
     gen_bilateral(np.random.default_rng(14))
+    gen_bilateral_live()
     gen_misc(np.random.default_rng(15))
     gen_vit(np.random.default_rng(16))
     gen_eval(np.random.default_rng(17))

@@ -241,3 +241,41 @@ def test_no_inline_asm_valu_on_mfma_accumulators():
         src = re.sub(r"//[^\n]*", "", src)          # (comments may quote the old statement)
         ops = set(re.findall(r'asm(?:\s+volatile)?\s*\(\s*"\s*(v_[a-z0-9_]+)', src))
         assert ops <= set(ok), (f, ops - set(ok))
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: a plain run is the headline alone (--full off by default); --dump-outputs writes every tensor the step returns and a sample of
+    the updated parameters as float32 .npy, an array over the size cap as a seeded sample that is the same on every call"""
+    import importlib.util
+    import os
+    import sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    opt = bench.parse()
+    assert opt.steps == 7 and opt.warmup == 2 and not opt.full and opt.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    opt = bench.parse()
+    assert opt.full and opt.dump_outputs == str(tmp_path)
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    monkeypatch.setattr(bench, "PARAM_SAMPLE", 300)
+    student = torch.nn.Sequential(torch.nn.Linear(30, 20), torch.nn.Linear(20, 5))
+    g = torch.Generator().manual_seed(0)
+    logs = {"overall_loss": torch.tensor(0.5), "mask": torch.randint(0, 21, (2, 30, 30), generator=g), "cls_logits": torch.randn(2, 20, generator=g),
+            "note": "not an array"}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), logs, student)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert set(a) == {"overall_loss", "mask", "cls_logits", "student_params_sample"}
+    assert all(v.dtype == np.float32 for v in a.values()) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert float(a["overall_loss"]) == 0.5 and np.array_equal(a["cls_logits"], logs["cls_logits"].numpy())
+    flat_mask = logs["mask"].reshape(-1).float().numpy()
+    assert a["mask"].shape == (1000,) and np.isin(a["mask"], flat_mask).all()          # 1800 entries > the cap: a sample of the values
+    flat = torch.cat([p.detach().reshape(-1) for p in student.parameters()]).numpy()
+    assert a["student_params_sample"].shape == (300,) and np.isin(a["student_params_sample"], flat).all()

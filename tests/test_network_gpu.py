@@ -447,14 +447,14 @@ def test_teacher_pass_flip_equivariance_at_bench_size():
 
 @pytest.mark.parametrize("flags", [["--steps", "1", "--warmup", "0"], ["--steps", "2", "--warmup", "1", "--usepar", "--usegmm", "--no-secondary"]])
 def test_bench_contract_small(flags):
-    """bench.py as the driver calls it (own process), tiny configuration, warm-up counts below the graph-capture threshold: prints ONE JSON
+    """bench.py --full (own process), tiny configuration, warm-up counts below the graph-capture threshold: prints ONE JSON
     line with the contract's keys (profiling events must not be taken inside the teacher's graph capture)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "2", "--crop", "224", "--no-cpu-baseline"] + flags,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "2", "--crop", "224", "--no-cpu-baseline", "--full"] + flags,
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -468,6 +468,37 @@ def test_bench_contract_small(flags):
     live = d["accuracy_live"]
     assert "error" not in live and live["label_agreement"] >= 0.999 and live["mask_miou"] >= 0.998 and "gross_error_ok" in live, live
     assert set(d["tolerance_planes"]) == {"planes", "planes_exempt", "planes_failed", "draws"}          # the exemption count is in the line
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """bench.py without --full (own process), tiny configuration: ONE JSON line with the headline and nothing measured beside it, exactly
+    --steps timed steps, and --dump-outputs writes what the last timed step computed as float32 .npy files"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "2", "--crop", "224", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]         # images/s and ms per step are the same timed steps
+    for k in ("roofline", "accuracy_live", "tolerance_met", "par_refine", "vit_forward", "fast_mode", "other_modes", "evaluation", "cpu_baseline"):
+        assert k not in d, k
+    arrays = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert set(arrays) == {"overall_loss", "cls_loss", "cls_aux_loss", "seg_loss", "cam_loss", "reg_loss", "mask", "cls_logits", "cls_aux_logits",
+                           "student_params_sample"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(os.path.getsize(dump / f) for f in os.listdir(dump)) <= 64 << 20
+    assert arrays["mask"].shape == (2, 224, 224) and set(np.unique(arrays["mask"])) <= set(range(21)) | {255}
+    assert arrays["cls_logits"].size == 2 * 20 and arrays["student_params_sample"].size == 1 << 20
+    assert float(arrays["overall_loss"]) == pytest.approx(d["config"]["final_loss"], abs=1e-5)
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

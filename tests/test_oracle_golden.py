@@ -53,16 +53,17 @@ def test_bilateral_bit_exact_vs_reference_cpp(oracle_c, golden):
         assert (M > 0).all()
 
 
-def test_bilateral_against_compiled_reference_live(oracle_c):
-    """oracle/_ref (the reference's own C++) on a fresh input, when it has been built."""
-    if oracle_c.ref_lib() is None:
-        pytest.skip("oracle/_ref not built here")
-    rng = np.random.default_rng(5)
-    N, K, H, W = 1, 2, 24, 40
-    img = rng.uniform(0, 255, (N, 3, H, W)).astype(np.float32)
-    seg = rng.uniform(0, 1, (N, K, H, W)).astype(np.float32)
-    ref = np.zeros(seg.size, np.float32)
-    oracle_c.ref_bilateralfilter_batch(img, seg, ref, N, K, H, W, 15.0, 50.0)
+def test_bilateral_against_compiled_reference_live(oracle_c, golden):
+    """the reference's own C++ on a fresh uniform-noise input: its output is stored in tests/golden/bilateral_live.npz (oracle/gen_golden.py);
+    where oracle/_ref has been built, the live call gives that output too."""
+    from oracle.gen_golden import bilateral_live_input
+    img, seg = bilateral_live_input()
+    N, K, H, W = seg.shape
+    ref = golden("bilateral_live")["out"].reshape(-1)
+    if oracle_c.ref_lib() is not None:
+        live = np.zeros(seg.size, np.float32)
+        oracle_c.ref_bilateralfilter_batch(img, seg, live, N, K, H, W, 15.0, 50.0)
+        assert np.array_equal(live, ref)
     out, _ = oracle_c.bilateralfilter_batch(img, seg, N, K, H, W, 15.0, 50.0)
     assert np.array_equal(out.reshape(-1), ref)
 
