@@ -9,6 +9,7 @@
 // softmax and scatters d loss / d logits straight into the [b,K,h,w] gradient (LDS-privatised float atomics).
 //
 // Thread = one 2x2 full-res quad (= one pixel of the energy grid); block = 16x16 quads = 32x32 pixels.
+// (At the end: the weight gradient of the student's patch projection at K % 64, for the 8-pixel-patch encoder.)
 #include "kernels.hpp"
 
 namespace cosa {
@@ -738,6 +739,136 @@ extern "C" int cosa_softmax_halfres_backward(const float *logit, const float *gr
     const dim3 grid((W / 2 + 63) / 64, (H / 2 + 3) / 4, B);
     if (K <= 24) hipLaunchKernelGGL(softmax_half_bwd_reg_kernel<24>, grid, dim3(256), 0, as_stream(stream), logit, grad_out, grad_logit, K, H, W);
     else hipLaunchKernelGGL(softmax_half_bwd_kernel, grid, dim3(256), 0, as_stream(stream), logit, grad_out, grad_logit, K, H, W);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+// ---- the student's patch-projection weight gradient at K % 64 (an 8-pixel-patch ViT: K = 3 * 8 * 8 = 192) ----------------------------
+// dW[N,K] (fp32) = dY[M,N]^T X[M,K],  db[N] = column sums of dY  (bf16 operands).  The 256 x 128-tile weight-gradient kernel of
+// gemm_kernels.hip takes K % 128 only; this is ~15 GFLOP per step at 448^2 x 16 (against ~43 TFLOP for the student), so a plain VALU kernel:
+// pass 1, grid (N/64, K/64, S): a 256-thread workgroup sums its slice of rows into a 64 x 64 partial tile (4 x 4 per thread, rows staged
+// through LDS 32 at a time) and writes slab s of the workspace; pass 2 adds the S slabs in slab order.  No atomics: the same bits every run.
+namespace cosa {
+namespace {
+
+constexpr int PW_T = 64, PW_R = 32;
+
+__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
+
+__global__ __launch_bounds__(256) void patch_wgrad_partial_kernel(const unsigned short *__restrict__ dY, const unsigned short *__restrict__ X,
+                                                                  float *__restrict__ part, float *__restrict__ dbpart, int M, int N, int K,
+                                                                  int rows_per)
+{
+    __shared__ float sY[PW_R][PW_T + 1], sX[PW_R][PW_T + 1];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int n0 = blockIdx.x * PW_T, k0 = blockIdx.y * PW_T, s = blockIdx.z;
+    const int m0 = s * rows_per, m1 = min(M, m0 + rows_per);
+    const int lr = tid >> 3, lc = (tid & 7) * 8;                 // staging: one 16-byte piece (8 columns) of one row per thread
+    float acc[4][4], dbacc[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        dbacc[i] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[i][j] = 0.f;
+    }
+    for (int r0 = m0; r0 < m1; r0 += PW_R) {
+        const int r = r0 + lr;
+        uint4 qy = make_uint4(0, 0, 0, 0), qx = make_uint4(0, 0, 0, 0);
+        if (r < m1) {
+            qy = *reinterpret_cast<const uint4 *>(dY + (size_t)r * N + n0 + lc);
+            qx = *reinterpret_cast<const uint4 *>(X + (size_t)r * K + k0 + lc);
+        }
+        __syncthreads();                                         // the previous stage's reads are done
+        const unsigned wy[4] = {qy.x, qy.y, qy.z, qy.w}, wx[4] = {qx.x, qx.y, qx.z, qx.w};
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            sY[lr][lc + 2 * q] = bf16_lo(wy[q]);
+            sY[lr][lc + 2 * q + 1] = bf16_hi(wy[q]);
+            sX[lr][lc + 2 * q] = bf16_lo(wx[q]);
+            sX[lr][lc + 2 * q + 1] = bf16_hi(wx[q]);
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int rr = 0; rr < PW_R; rr++) {
+            float a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) a[i] = sY[rr][ty + 16 * i];
+#pragma unroll
+            for (int j = 0; j < 4; j++) b[j] = sX[rr][tx + 16 * j];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                dbacc[i] += a[i];
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+            }
+        }
+    }
+    float *slab = part + (size_t)s * N * K;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) slab[(size_t)(n0 + ty + 16 * i) * K + k0 + tx + 16 * j] = acc[i][j];
+    if (dbpart && blockIdx.y == 0 && tx == 0)
+#pragma unroll
+        for (int i = 0; i < 4; i++) dbpart[(size_t)s * N + n0 + ty + 16 * i] = dbacc[i];
+}
+
+__global__ void patch_wgrad_reduce_kernel(const float *__restrict__ part, const float *__restrict__ dbpart, float *__restrict__ dW,
+                                          float *__restrict__ db, int S, int N, int K)
+{
+    const long long NK = (long long)N * K, i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < NK) {
+        float v = 0.f;
+        for (int s = 0; s < S; s++) v += part[(size_t)s * NK + i];
+        dW[i] = v;
+    } else if (db && i < NK + N) {
+        const int n = (int)(i - NK);
+        float v = 0.f;
+        for (int s = 0; s < S; s++) v += dbpart[(size_t)s * N + n];
+        db[n] = v;
+    }
+}
+
+int patch_wgrad_splits(int M, int N, int K, int *rows_per)
+{
+    const int tiles = (N / PW_T) * (K / PW_T);
+    int S = (2048 + tiles - 1) / tiles;                          // ~2048 workgroups (8 per CU)
+    S = max(1, min(S, (M + 255) / 256));                         // at least 256 rows per slab
+    int per = (M + S - 1) / S;
+    per = (per + PW_R - 1) / PW_R * PW_R;
+    if (rows_per) *rows_per = per;
+    return (M + per - 1) / per;
+}
+
+}  // namespace
+}  // namespace cosa
+
+extern "C" size_t cosa_patch_wgrad_workspace_bytes(int M, int N, int K)
+{
+    if (M <= 0 || N <= 0 || K <= 0 || N % cosa::PW_T || K % cosa::PW_T) return 0;
+    const int S = cosa::patch_wgrad_splits(M, N, K, nullptr);
+    return cosa::align_up((size_t)S * ((size_t)N * K + N) * sizeof(float), 256);
+}
+
+extern "C" int cosa_patch_wgrad_bf16(const void *dY, const void *X, float *dW, float *db, int M, int N, int K, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    using namespace cosa;
+    COSA_REQUIRE(dY && X && dW && workspace && M > 0 && N > 0 && K > 0, "cosa_patch_wgrad_bf16: bad arguments");
+    COSA_REQUIRE(N % PW_T == 0 && K % PW_T == 0, "cosa_patch_wgrad_bf16: N and K must be multiples of 64 (got %d, %d)", N, K);
+    COSA_REQUIRE(((uintptr_t)dY & 15) == 0 && ((uintptr_t)X & 15) == 0, "cosa_patch_wgrad_bf16: dY and X must be 16-byte aligned");
+    int per = 0;
+    const int S = patch_wgrad_splits(M, N, K, &per);
+    const size_t need = (size_t)S * ((size_t)N * K + N) * sizeof(float);
+    COSA_REQUIRE(workspace_bytes >= need, "cosa_patch_wgrad_bf16: workspace too small (%zu < %zu)", workspace_bytes, need);
+    float *part = static_cast<float *>(workspace), *dbpart = db ? part + (size_t)S * N * K : nullptr;
+    const hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(patch_wgrad_partial_kernel, dim3(N / PW_T, K / PW_T, S), dim3(256), 0, st, static_cast<const unsigned short *>(dY),
+                       static_cast<const unsigned short *>(X), part, dbpart, M, N, K, per);
+    COSA_LAUNCH_CHECK();
+    const long long nv = (long long)N * K + (db ? N : 0);
+    hipLaunchKernelGGL(patch_wgrad_reduce_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, part, dbpart, dW, db, S, N, K);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

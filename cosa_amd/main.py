@@ -23,6 +23,7 @@ from . import args as cosa_args
 from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
+from .models.backbones import get_backbone
 from .train_step import CoSATrainer, default_args
 from .utils import torch_helper
 
@@ -65,6 +66,7 @@ def check_supported(args):
         raise NotImplementedError("--turnon_rawcam: raw-CAM dumps (evaluate(save_rawcam=True)) are not part of the device evaluation path")
     if args.model != 'vit' or args.decoder != 'LargeFOV':
         raise NotImplementedError("only --model vit --decoder LargeFOV (the run scripts' configuration) is built")
+    get_backbone(args.backbone)                                   # NotImplementedError listing the built encoders
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from .. import _C, nn_ops
 from . import vit as vitencoder
+from .backbones import get_backbone
 from .PAR import PAR  # noqa: F401
 
 
@@ -74,8 +75,9 @@ class VITNetwork(nn.Module):
         super().__init__()
         assert decoder in ['LargeFOV'], "cosa_amd builds the LargeFOV decoder (the run scripts' default)"
         self.num_classes = num_classes
-        self.encoder = getattr(vitencoder, backbone)(pretrained=pretrained, pretrained_path=pretrained_path, aux_layer=aux_layer,
-                                                     compute_dtype=compute_dtype)
+        self.backbone = backbone
+        self.encoder = get_backbone(backbone)(pretrained=pretrained, pretrained_path=pretrained_path, aux_layer=aux_layer,
+                                              compute_dtype=compute_dtype)
         self.in_channels = [self.encoder.embed_dim] * 4
         self.isgap = isgap
         self.decoder = LargeFOV(in_planes=self.in_channels[-1], out_planes=self.num_classes)
@@ -88,6 +90,15 @@ class VITNetwork(nn.Module):
         self.compute_dtype = dt
         self.encoder.compute_dtype = dt
         return self
+
+    def check_nograd_precision(self, mode):
+        """NotImplementedError for an operand mode this encoder's geometry is not built for: the fp16c8 / fp16c4 families need the patch
+        projection's K = C*P*P % 128 (their im2col writes c8 rows; cosa_gemm_f16c8) -- the 8-pixel patch has K = 192.  Refused at set-up,
+        not mid-step by a kernel's argument check."""
+        kp = self.encoder.patch_embed.proj.weight[0].numel()
+        if mode.partition("-")[0] in ("fp16c8", "fp16c4") and kp % 128:
+            raise NotImplementedError(f"teacher precision {mode!r} is not built for --backbone {self.backbone} (patch projection K = {kp}; the "
+                                      f"fp16c8 / fp16c4 families need K % 128 == 0): use fp16x3 (auto), bf16x3, bf16 or fp16")
 
     def set_nograd_precision(self, mode):
         """operand precision of the no-grad passes (teacher pseudo-labels, evaluation): "bf16" (8 significant bits), "fp16" (11; the
@@ -104,6 +115,7 @@ class VITNetwork(nn.Module):
         #                       the blocks from index 6 on take qkv / fc1 / fc2 on fp16c4 operands (fp16c8 base only)
         assert base in ("bf16", "fp16", "bf16x3", "fp16x3", "fp16c8", "fp16c4") and (bool(tail) == bool(sep)) and \
             (not tail or (base in ("fp16c8", "fp16c4") and (m or mx))), mode
+        self.check_nograd_precision(mode)
         self.set_compute_dtype(torch.float16 if base in ("fp16", "fp16x3", "fp16c8", "fp16c4") else torch.bfloat16)
         # "fp16x3" (round 6): the three-term path with fp16 halves (hi + lo: 11 + 11 significant bits; bf16x3: 8 + 8) -- same kernels, same cost
         self.encoder.precision = "bf16x3" if base == "fp16x3" else (base if base in ("bf16x3", "fp16c8", "fp16c4") else None)

@@ -706,6 +706,26 @@ def gemm_wgrad(dy2, x2, want_bias=False):
     return (dw, db) if want_bias else dw
 
 
+def patch_wgrad(dy2, x2):
+    """(dW [N,K] fp32, db [N] fp32) = (dy2^T x2, column sums of dy2) for K % 64 == 0: the patch projection of an 8-pixel-patch encoder
+    ([768, 192]), which the 256 x 128-tile weight-gradient kernel (K % 128) does not take.  Deterministic (cosa_patch_wgrad_bf16)."""
+    M, N = dy2.shape
+    K = x2.shape[1]
+    assert dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and dy2.is_contiguous() and x2.is_contiguous()
+    dw = _wgrad_alloc(N * K, dy2.device)
+    db = _wgrad_alloc(N, dy2.device) if dw is not None else None
+    if dw is None or db is None:
+        dw = torch.empty((N, K), device=dy2.device, dtype=torch.float32)
+        db = torch.empty((N,), device=dy2.device, dtype=torch.float32)
+    else:
+        dw = dw.view(N, K)
+    ws = _C.workspace(_C.lib().cosa_patch_wgrad_workspace_bytes(M, N, K), dy2.device, "patch_wgrad")
+    with _C.profiled("gemm_wgrad"):
+        _C.check(_C.lib().cosa_patch_wgrad_bf16(_C.ptr(dy2), _C.ptr(x2), _C.ptr(dw), _C.ptr(db), M, N, K, _C.ptr(ws), ws.numel(),
+                                                _C.stream_ptr()), "cosa_patch_wgrad_bf16")
+    return dw, db
+
+
 class _WgradItem(ctypes.Structure):
     _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("db", ctypes.c_void_p), ("N", ctypes.c_int),
                 ("K", ctypes.c_int)]
@@ -921,18 +941,22 @@ class LinearShadowFn(Function):
         if ctx.needs_input_grad[1]:
             if ctx.collect is not None:
                 ctx.collect[0].add(ctx.collect[1], dy2, x2)                 # computed with the others when the backward reaches DeferredWgrad
-            else:
+            elif K % 128 == 0:
                 dw, db = gemm_wgrad(dy2, x2, want_bias=True)
+            else:
+                dw, db = patch_wgrad(dy2, x2)                                # K % 64: the 8-pixel patch projection [768, 192]
         return dx, dw, db, None, None, None, None
 
 
 def linear_view2d(x, weight, bias, dtype):
     """nn.Linear with a weight parameter of more than two dimensions used as its [out, -1] view (the patch projection's conv weight):
-    LinearShadowFn; the parameter needs registered shadows (bf16 copy and bf16 transposed copy of the 2-D view)"""
+    LinearShadowFn; the parameter needs registered shadows (bf16 copy and bf16 transposed copy of the 2-D view).  K % 64 (the 8-pixel
+    patch: K = 192) is taken when no input gradient is asked for (the image needs none): the forward GEMM takes K % 64 and the weight
+    gradient then runs on cosa_patch_wgrad_bf16; the input-gradient GEMM would need K % 128."""
     ew, eb, et = _shadows.get(id(weight)), _shadows.get(id(bias)), _transposed.get(id(weight))
     w2 = weight.view(weight.shape[0], -1)
     if ew is not None and eb is not None and et is not None and ew[0] is weight and eb[0] is bias and et[0] is weight \
-            and w2.shape[0] % 128 == 0 and w2.shape[1] % 128 == 0:
+            and w2.shape[0] % 128 == 0 and (w2.shape[1] % 128 == 0 or (w2.shape[1] % 64 == 0 and not x.requires_grad)):
         return LinearShadowFn.apply(x, w2, bias, ew[1].view(w2.shape), eb[1], et[1], False)
     return reference_op("linear", f"linear_view2d (weight {tuple(w2.shape)}, {dtype}; shadows registered: {ew is not None and et is not None})",
                         x, cast_param(weight, dtype).view(w2.shape), cast_param(bias, dtype))

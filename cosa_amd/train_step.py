@@ -136,6 +136,7 @@ class CoSATrainer:
         # needs bf16's range for its gradients, stays bf16.
         tp = resolve_teacher_precision(getattr(args, "teacher_precision", "auto"), args.crop_size, bool(getattr(args, "usepar", False)))
         args.teacher_precision = tp
+        self.model_AN.check_nograd_precision(tp)          # (on the host too: a mode the encoder is not built for fails here, not in a step)
         if on:
             self.model_AN.set_nograd_precision(tp)
         tdt = self.model_AN.compute_dtype if on else args.compute_dtype

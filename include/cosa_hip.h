@@ -229,6 +229,12 @@ int cosa_gemm_wgrad_bf16(const void *dY, const void *X, float *dW, float *db, in
  * no atomics, the same bits every run.  `items`: host array, read during the call.                                                        */
 typedef struct CosaWgradItem { const void *dY, *X; float *dW, *db; int N, K; } CosaWgradItem;
 int cosa_gemm_wgrad_batched(const CosaWgradItem *items, int n_items, int M, void *stream);
+/* The weight / bias gradient of the patch projection when K % 128 != 0 (an 8-pixel-patch ViT: [768, 3*8*8]): dW[N,K] and db[N] (optional)
+ * OVERWRITTEN with dY[M,N]^T X[M,K] and the column sums of dY (bf16 operands, 16-byte aligned).  N % 64 == 0, K % 64 == 0.  Rows split over
+ * workgroups, fp32 partial slabs in `workspace` (cosa_patch_wgrad_workspace_bytes) added in slab order: deterministic (loss_kernels.hip). */
+size_t cosa_patch_wgrad_workspace_bytes(int M, int N, int K);
+int cosa_patch_wgrad_bf16(const void *dY, const void *X, float *dW, float *db, int M, int N, int K, void *workspace, size_t workspace_bytes,
+                          void *stream);
 /* models/decoder/conv_head.py:11-41  LargeFOV's 3x3 dilated, bias-free convolution on NHWC tokens (implicit GEMM, optional ReLU):
  *   X: image b = rows [b*img_rows + row_off, +h*w) of a [*, ldx] bf16 matrix (so the token tensor minus its cls row needs no copy)
  *   Wt [9][Cout][Cin] bf16 (tap-major: t = ky*3 + kx);  Y [B*h*w, Cout] bf16;  padding = dilation                               */
