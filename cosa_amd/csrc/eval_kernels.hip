@@ -149,6 +149,96 @@ __global__ __launch_bounds__(256) void confusion_kernel(const uint8_t *__restric
         if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
 }
 
+// ---- export: every file product of ONE image in one packed record at the image's own H x W -----------------
+// A thread owns four consecutive pixels of one row (one dword of each uint8 product); the source rows and their weights are computed
+// once per thread, the source columns and weights once per pixel, and reused for every plane of every product.  seg calls the same
+// src_index_r / bilerp in the same order as eval_labels_kernel, so it holds that kernel's lab_vd (lab_ps without a label row) bits.
+struct ExportArgs {
+    const float *cam, *cam_aux, *seg, *cls;
+    uint8_t *seg_out, *pseudo[2];           // [H,W]
+    float *raw[2];                          // [K_live,H,W]
+    int32_t *raw_idx[2];                    // [K_live]
+    int C, S, H, W, K_live;
+    float sy, sx, hi, lo;
+    int ignore;
+};
+
+__device__ __forceinline__ void store_u8x4(uint8_t *__restrict__ row, int X, int W, const uint8_t (&v)[4], bool dword_ok)
+{
+    if (dword_ok && X + 4 <= W) {
+        *reinterpret_cast<uint32_t *>(row + X) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+    } else {
+        for (int k = 0; k < 4 && X + k < W; k++) row[X + k] = v[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void export_maps_kernel(const ExportArgs a)
+{
+    const int W4 = (a.W + 3) >> 2;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.H * W4) return;
+    const int Y = t / W4, X = (t - Y * W4) * 4;
+    const int S = a.S, C = a.C, W = a.W;
+    const size_t ss = (size_t)S * S, hw = (size_t)a.H * W;
+    const bool dword_ok = (W & 3) == 0;     // rows start dword-aligned (the products are 16-byte aligned in the record)
+    int y0, y1, x0[4], x1[4];
+    float ly0, ly1, lx0[4], lx1[4];
+    src_index_r(Y, S, a.sy, y0, y1, ly0, ly1);
+#pragma unroll
+    for (int k = 0; k < 4; k++) src_index_r(X + k < W ? X + k : W - 1, S, a.sx, x0[k], x1[k], lx0[k], lx1[k]);
+    if (a.seg_out) {
+        float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint8_t iv[4] = {0, 0, 0, 0};
+        for (int c = 0; c <= C; c++) {
+            const bool present = c == 0 || !a.cls || a.cls[c - 1] != 0.0f;      // seg_validation: an absent class is -1e5, its plane unread
+            const float *pl = a.seg + c * ss;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float v = present ? bilerp(pl, S, y0, y1, x0[k], x1[k], ly0, ly1, lx0[k], lx1[k]) : -1e5f;
+                if (c == 0 || v > bv[k]) { bv[k] = v; iv[k] = (uint8_t)c; }
+            }
+        }
+        store_u8x4(a.seg_out + (size_t)Y * W, X, W, iv, dword_ok);
+    }
+    for (int g = 0; g < 2; g++) {
+        const float *cams = g ? a.cam_aux : a.cam;
+        if (!a.pseudo[g] && !a.raw[g]) continue;
+        float best[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int bi[4] = {-1, -1, -1, -1};
+        int live = 0;
+        for (int c = 0; c < C; c++) {
+            const float l = a.cls[c];
+            if (l == 0.0f) continue;         // planes of absent classes are never read
+            const float *pl = cams + c * ss;
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                v[k] = l * bilerp(pl, S, y0, y1, x0[k], x1[k], ly0, ly1, lx0[k], lx1[k]);      // cam_validation
+                if (bi[k] < 0 || v[k] > best[k]) { best[k] = v[k]; bi[k] = c; }
+            }
+            if (a.raw[g] && live < a.K_live) {
+                float *o = a.raw[g] + (size_t)live * hw + (size_t)Y * W + X;
+                if (dword_ok) {
+                    *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
+                } else {
+                    for (int k = 0; k < 4 && X + k < W; k++) o[k] = v[k];
+                }
+                if (t == 0) a.raw_idx[g][live] = c;
+            }
+            live++;
+        }
+        if (a.pseudo[g]) {
+            // cam2mask without a refine model, per pixel: the threshold plane is key 0 and wins ties (first maximum), so the "high" map
+            // names the class iff its value exceeds hi, likewise "low"; mask = class | ignore where only "low" names one | 0
+            uint8_t m[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                m[k] = (bi[k] >= 0 && best[k] > a.hi) ? (uint8_t)(bi[k] + 1) : ((bi[k] >= 0 && best[k] > a.lo) ? (uint8_t)a.ignore : (uint8_t)0);
+            store_u8x4(a.pseudo[g] + (size_t)Y * W, X, W, m, dword_ok);
+        }
+    }
+}
+
 }  // namespace
 }  // namespace cosa
 
@@ -189,6 +279,64 @@ extern "C" int cosa_confusion_hist(const uint8_t *gt, const uint8_t *pred, size_
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), gt, pred, n, num_classes, pseudo, hist);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+// One definition of the record for the device and the host: offsets[i] (bytes, 16-byte aligned) of product i in the order of the
+// COSA_EXPORT_* bits (seg, pseudo, pseudo_aux, rawcam, rawcam_aux, rawcam_idx, rawcam_aux_idx); (size_t)-1 for a product not asked for.
+// Returns the record's size, or 0 on bad arguments.
+extern "C" size_t cosa_export_record_layout(int C, int H, int W, int K_live, unsigned what, size_t *offsets)
+{
+    if (!offsets || C < 1 || C >= 255 || H < 1 || W < 1 || K_live < 0 || K_live > C || (what & ~(unsigned)COSA_EXPORT_ALL) || !what) {
+        set_error("cosa_export_record_layout: bad arguments (C %d, H %d, W %d, K_live %d, what 0x%x)", C, H, W, K_live, what);
+        return 0;
+    }
+    const size_t hw = (size_t)H * W;
+    const size_t sizes[COSA_EXPORT_SLOTS] = {hw, hw, hw, hw * K_live * 4, hw * K_live * 4, (size_t)K_live * 4, (size_t)K_live * 4};
+    const unsigned bits[COSA_EXPORT_SLOTS] = {COSA_EXPORT_SEG, COSA_EXPORT_PSEUDO, COSA_EXPORT_PSEUDO_AUX, COSA_EXPORT_RAWCAM,
+                                              COSA_EXPORT_RAWCAM_AUX, COSA_EXPORT_RAWCAM, COSA_EXPORT_RAWCAM_AUX};
+    size_t off = 0;
+    for (int i = 0; i < COSA_EXPORT_SLOTS; i++) {
+        if (what & bits[i]) {
+            offsets[i] = off;
+            off += (sizes[i] + 15) & ~(size_t)15;
+        } else {
+            offsets[i] = (size_t)-1;
+        }
+    }
+    return off < 16 ? 16 : off;
+}
+
+extern "C" int cosa_export_maps(const float *cam, const float *cam_aux, const float *seg, const float *cls_label, int C, int S, int H, int W,
+                                int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, void *record,
+                                size_t record_bytes, void *stream)
+{
+    COSA_REQUIRE(record && what && !(what & ~(unsigned)COSA_EXPORT_ALL), "cosa_export_maps: bad arguments (what 0x%x)", what);
+    COSA_REQUIRE(C > 0 && C < 255 && S > 0, "cosa_export_maps: C must be in 1..254 and S >= 1 (got C %d, S %d)", C, S);
+    COSA_REQUIRE(H >= 1 && W >= 1 && (size_t)H * W < 0x7fffffffull, "cosa_export_maps: bad size %d x %d", H, W);
+    COSA_REQUIRE(ignore_index >= 0 && ignore_index <= 255, "cosa_export_maps: ignore_index %d does not fit a byte", ignore_index);
+    const unsigned cam_bits = what & ~(unsigned)COSA_EXPORT_SEG;
+    COSA_REQUIRE(!cam_bits || cls_label, "cosa_export_maps: pseudo / rawcam products need the image-level label row");
+    COSA_REQUIRE(!(what & COSA_EXPORT_SEG) || seg, "cosa_export_maps: seg asked for without logits");
+    COSA_REQUIRE(!(what & (COSA_EXPORT_PSEUDO | COSA_EXPORT_RAWCAM)) || cam, "cosa_export_maps: main-CAM product without the main CAM");
+    COSA_REQUIRE(!(what & (COSA_EXPORT_PSEUDO_AUX | COSA_EXPORT_RAWCAM_AUX)) || cam_aux, "cosa_export_maps: auxiliary-CAM product without the auxiliary CAM");
+    COSA_REQUIRE(K_live >= 0 && K_live <= C, "cosa_export_maps: K_live %d outside 0..C", K_live);
+    COSA_REQUIRE(((size_t)record & 15) == 0, "cosa_export_maps: the record must be 16-byte aligned");
+    size_t off[COSA_EXPORT_SLOTS];
+    const size_t need = cosa_export_record_layout(C, H, W, K_live, what, off);
+    COSA_REQUIRE(need && record_bytes >= need, "cosa_export_maps: record of %zu bytes, %zu needed", record_bytes, need);
+    uint8_t *r = (uint8_t *)record;
+    auto at = [&](int i) -> uint8_t * { return off[i] == (size_t)-1 ? nullptr : r + off[i]; };
+    ExportArgs a;
+    a.cam = cam; a.cam_aux = cam_aux; a.seg = seg; a.cls = cls_label;
+    a.seg_out = at(0); a.pseudo[0] = at(1); a.pseudo[1] = at(2);
+    a.raw[0] = K_live ? (float *)at(3) : nullptr; a.raw[1] = K_live ? (float *)at(4) : nullptr;
+    a.raw_idx[0] = (int32_t *)at(5); a.raw_idx[1] = (int32_t *)at(6);
+    a.C = C; a.S = S; a.H = H; a.W = W; a.K_live = K_live;
+    a.sy = (float)S / (float)H; a.sx = (float)S / (float)W; a.hi = high_thre; a.lo = low_thre; a.ignore = ignore_index;
+    const int threads = H * ((W + 3) / 4);
+    hipLaunchKernelGGL(export_maps_kernel, dim3((threads + 255) / 256), dim3(256), 0, as_stream(stream), a);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

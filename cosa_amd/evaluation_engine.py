@@ -17,13 +17,18 @@ high = 1 - t, low = t) of the main and the auxiliary CAMs at the ground truth's 
 softmax -> one mean-field step of the dense CRF (`seg_helper.crf_inference_infv2`: two permutohedral-lattice filters on the device) ->
 argmax, scored as the row `Seg_crf`.  Parity of that row with pydensecrf is unpinned (see seg_helper.DenseCRF).
 
-Not built: image / CAM dumps (`save_result`, `save_rawcam`); asking for them raises NotImplementedError.
+`evaluate` itself writes no files (`save_result`, `save_rawcam` raise NotImplementedError); `export_predictions` below does: the same
+forward, one `cosa_export_maps` record per image at the image's own size, one asynchronous copy to pinned memory, a pool of writer
+threads (command line: `python -m cosa_amd.predict`).
 """
+import time
+
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from .utils import evaluation, seg_helper, torch_helper
+from .utils import evaluation, export_io, seg_helper, torch_helper
+from .utils.export_io import export_shard                         # noqa: F401  (the sharding rule, part of this module's surface)
 
 EVAL_SCALES = [1.0, 0.5, 1.5, 0.75, 1.25]          # evaluation_engine.py:84
 
@@ -59,7 +64,8 @@ class _GraphedCamSeg:
 def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=False, epoch=None, threshold_filters=None, getcrf=False,
              s_or_t='t', get_camiou=False, isfinal=False, class_list=None, use_graph=True, eval_group=4):
     if save_result or save_rawcam:
-        raise NotImplementedError("evaluate: save_result / save_rawcam (image dumps) are not part of the device path")
+        raise NotImplementedError("evaluate: save_result / save_rawcam (image dumps) are not part of the device path of evaluate(); "
+                                  "files are written by evaluation_engine.export_predictions / python -m cosa_amd.predict")
     threshold_filters = list(threshold_filters) if threshold_filters else []
     assert s_or_t in ['s', 't']
     distributed = dist.is_available() and dist.is_initialized()
@@ -186,3 +192,184 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
     if get_camiou:
         return tab_results, seg_vd_miou, cam_miou, df, cls_aps
     return tab_results, seg_vd_miou, df, cls_aps
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# export: segmentation / pseudo-label PNGs and raw-CAM dictionaries
+# ---------------------------------------------------------------------------------------------------------------------------------
+EXPORT_PRODUCTS = tuple(seg_helper.EXPORT_BITS)                   # seg, pseudo, pseudo_aux, rawcam, rawcam_aux
+CAM_PRODUCTS = tuple(p for p in EXPORT_PRODUCTS if p != "seg")    # these need the image-level label row
+
+
+class _ExportSlot:
+    """one record in flight: the device record `cosa_export_maps` writes, its pinned host copy, the event that says the copy is done
+    and the writer job that still reads the host copy"""
+
+    def __init__(self, device):
+        self.device = device
+        self.dev = self.host = None
+        self.event = torch.cuda.Event()
+        self.job = None
+
+    def reserve(self, nbytes):
+        if self.job is not None:                   # the host copy is still being encoded: the only place the loop waits for a writer
+            job, self.job = self.job, None
+            job.result()
+        if self.dev is None or self.dev.numel() < nbytes:
+            size = max(int(nbytes), 1 << 20)
+            self.dev = torch.empty(size, device=self.device, dtype=torch.uint8)
+            self.host = torch.empty(size, dtype=torch.uint8).pin_memory()
+
+
+_EXPORT_SLOTS = {}                                  # str(device) -> [slots], grow-only: a second call reuses the records
+
+
+def _export_slots(device, n):
+    slots = _EXPORT_SLOTS.setdefault(str(device), [])
+    while len(slots) < n:
+        slots.append(_ExportSlot(device))
+    return slots[:n]
+
+
+def _sharded(data_loader, rank, world):
+    """every item exactly once over the ranks: index % world == rank (export_shard), not DistributedSampler(drop_last=True)"""
+    if world == 1:
+        return data_loader
+    ds = getattr(data_loader, "dataset", None)
+    if ds is not None and isinstance(data_loader, torch.utils.data.DataLoader):
+        return torch.utils.data.DataLoader(dataset=ds, batch_size=1, shuffle=False, sampler=export_shard(len(ds), rank, world),
+                                           num_workers=data_loader.num_workers, pin_memory=False, drop_last=False)
+    items = list(data_loader)
+    return [items[i] for i in export_shard(len(items), rank, world)]
+
+
+def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=False, high_thre=None, low_thre=None, eval_group=4,
+                       use_graph=True, writers=4, settings=None):
+    """Write the predictions of `model` over `data_loader` (items `(name, image [1,3,H,W], labels, cls_label [1,C])` as the evaluation
+    loaders give them; an item without a label row -- `cls_label` None or not 2-D, the `test` stage -- can only give `seg`) into
+    `out_dir` (layout: utils/export_io.py).  The forward is evaluate()'s: resize to crop_size, the captured multi-scale pass, groups of
+    `eval_group` items, batch-invariant heads -- what is written is what evaluate() scores.  `what`: out of EXPORT_PRODUCTS;
+    `getcrf` adds `seg_crf` (the lines of evaluate()'s Seg_crf row).  Thresholds default to args.high_thre / args.low_thre.
+    Returns {"images", "seconds", "img_per_s", "bytes_written"} of this process."""
+    what = tuple(what)
+    mask = seg_helper.export_what_mask(what)
+    writers = export_io.check_writers(writers)
+    if getattr(args, "usepar", False):
+        raise NotImplementedError("export_predictions: PAR-refined export (--usepar) is not built: the fused cosa_cam2mask refines square "
+                                  "S x S maps only")
+    high_thre = float(args.high_thre if high_thre is None else high_thre)
+    low_thre = float(args.low_thre if low_thre is None else low_thre)
+    ignore_index = int(getattr(args, "ignore_index", 255))
+    distributed = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(), dist.get_world_size()) if distributed else (0, 1)
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError("export_predictions runs on the GPU (HIP kernels); no CPU path")
+    C = args.num_classes - 1
+    products = what + (("seg_crf",) if getcrf else ())
+    writer = export_io.PredictionWriter(out_dir, products, writers)
+    slots = _export_slots(device, writers + 1)
+    was_training = model.training
+    model.eval()
+    net = model.module if hasattr(model, "module") else model
+    heads_before = getattr(net, "batch_invariant_heads", None)
+    if heads_before is not None:
+        net.batch_invariant_heads = True
+        net.decoder.batch_invariant = True
+    camseg = _GraphedCamSeg(model, EVAL_SCALES, enabled=use_graph and getattr(model, "can_forward_multi", None) is not None)
+    count = 0
+
+    def host_products(slot, H, W, k_live, item_mask, crf_off):
+        def get():
+            slot.event.synchronize()                # in the writer thread: the loop itself never waits for a copy
+            rec = slot.host.numpy()
+            v = seg_helper.export_record_views(rec, C, H, W, k_live, item_mask)
+            out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux") if p in v}
+            for p in ("rawcam", "rawcam_aux"):
+                if p in v:
+                    out[p] = (v[p], v[p + "_idx"])
+            if crf_off is not None:
+                out["seg_crf"] = rec[crf_off:crf_off + H * W].reshape(H, W)
+            return out
+        return get
+
+    def flush(group):
+        nonlocal count
+        if not group:
+            return
+        cams, cams_aux, seg_ps, _, _ = camseg(torch.cat([g[1] for g in group], dim=0))
+        for i, (name, _, cls_dev, k_live, img_org) in enumerate(group):
+            H, W = int(img_org.shape[-2]), int(img_org.shape[-1])
+            item_mask = mask if cls_dev is not None else seg_helper.EXPORT_BITS["seg"]
+            _, nbytes = seg_helper.export_record_layout(C, H, W, k_live, item_mask)
+            crf_off, total = None, nbytes
+            if getcrf:
+                crf_off, total = nbytes, nbytes + ((H * W + 15) & ~15)
+            slot = slots[count % len(slots)]
+            slot.reserve(total)
+            seg_helper.export_maps(cams[i] if item_mask & 0x0a else None, cams_aux[i] if item_mask & 0x14 else None, seg_ps[i], cls_dev, (H, W),
+                                   item_mask, high_thre, low_thre, ignore_index=ignore_index, out=slot.dev, k_live=k_live)
+            if getcrf:                              # evaluate()'s Seg_crf lines
+                rs = F.interpolate(seg_ps[i:i + 1], size=(H, W), mode='bilinear', align_corners=False)
+                vd = seg_helper.seg_validation(rs, cls_dev).softmax(dim=1)[0]
+                ori = torch_helper.denormalize_img_(img_org)[0].permute(1, 2, 0)
+                q = seg_helper.crf_inference_infv2(ori, vd.contiguous())
+                slot.dev[crf_off:crf_off + H * W].copy_(q.argmax(dim=0).to(torch.uint8).reshape(-1))
+            slot.host[:total].copy_(slot.dev[:total], non_blocking=True)          # the one device-to-host copy of the image
+            slot.event.record()
+            slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off))
+            count += 1
+
+    t0 = time.perf_counter()
+    try:
+        with torch.no_grad():
+            group = []
+            for data in _sharded(data_loader, rank, world):
+                names, img_org, _, cls_label = data
+                names = [names] if isinstance(names, str) else list(names)
+                has_cls = torch.is_tensor(cls_label) and cls_label.dim() == 2
+                if not has_cls and (mask & ~seg_helper.EXPORT_BITS["seg"]):
+                    raise ValueError(f"export_predictions: item {names[0]!r} has no image-level label row; only 'seg' can be exported "
+                                     f"for it (asked for {list(what)})")
+                k_lives = (cls_label != 0).sum(dim=1).tolist() if has_cls else [0] * len(names)      # the loader's host tensor: no device wait
+                cls_dev = cls_label.to(device, non_blocking=True).float() if has_cls else None
+                img_org = img_org.to(device, non_blocking=True)
+                inputs = F.interpolate(img_org, size=[args.crop_size, args.crop_size], mode='bilinear', align_corners=False)
+                for i in range(inputs.shape[0]):
+                    group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if has_cls else None, int(k_lives[i]),
+                                  img_org[i:i + 1]))
+                    if len(group) >= max(1, int(eval_group)):
+                        flush(group)
+                        group = []
+            flush(group)
+        writer.drain()
+    finally:
+        for s in slots:
+            s.job = None
+        if heads_before is not None:
+            net.batch_invariant_heads = heads_before
+            net.decoder.batch_invariant = heads_before
+        if was_training:
+            model.train()
+        if writer.futures:                          # an error on the way: let the threads finish before it propagates
+            try:
+                writer.drain()
+            except BaseException:                   # noqa: B902  (the first error is the one being raised)
+                pass
+        writer.pool.shutdown(wait=True)
+    seconds = time.perf_counter() - t0
+    images = writer.images
+    if distributed:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, images)
+        images = sorted(x for part in gathered for x in part)
+        dist.barrier()                              # every rank's files are on disk
+    if rank == 0:
+        info = {"split": getattr(data_loader.dataset, "split", None) if hasattr(data_loader, "dataset") else None,
+                "products": list(products), "high_thre": high_thre, "low_thre": low_thre, "ignore_index": ignore_index,
+                "crop_size": args.crop_size, "scales": EVAL_SCALES, "backbone": getattr(args, "backbone", None),
+                "num_classes": args.num_classes, "world_size": world}
+        info.update(settings or {})
+        export_io.write_manifest_file(out_dir, info, images)
+    return {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,
+            "bytes_written": writer.bytes_written}

@@ -230,6 +230,84 @@ def eval_label_maps(cam, seg, cls_label, size, bkg_thre):
     return lc, lp, lv
 
 
+EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16}          # COSA_EXPORT_* of include/cosa_hip.h
+_EXPORT_SLOTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "rawcam_idx", "rawcam_aux_idx")
+
+
+def export_what_mask(what):
+    """("seg", "pseudo", ...) or a ready bit mask -> the COSA_EXPORT_* mask; unknown names are an error"""
+    if isinstance(what, int):
+        return what
+    unknown = [w for w in what if w not in EXPORT_BITS]
+    if unknown or not len(what):
+        raise ValueError(f"export products must be some of {sorted(EXPORT_BITS)}, got {list(what)}")
+    m = 0
+    for w in what:
+        m |= EXPORT_BITS[w]
+    return m
+
+
+def export_record_layout(C, H, W, k_live, what):
+    """cosa_export_record_layout: ({slot name: byte offset} of the products asked for, record size in bytes).  Needs no device."""
+    off = (ctypes.c_size_t * len(_EXPORT_SLOTS))()
+    n = _C.lib().cosa_export_record_layout(int(C), int(H), int(W), int(k_live), export_what_mask(what), off)
+    if n == 0:
+        _C.check(1, "cosa_export_record_layout")
+    none = ctypes.c_size_t(-1).value
+    return {k: int(o) for k, o in zip(_EXPORT_SLOTS, off) if o != none}, int(n)
+
+
+def export_record_views(record, C, H, W, k_live, what):
+    """the products inside a packed record (a uint8 tensor on any device, or a numpy uint8 array), as views: uint8 [H,W] maps,
+    rawcam* float32 [k_live,H,W] and rawcam*_idx int32 [k_live]"""
+    offs, _ = export_record_layout(C, H, W, k_live, what)
+    out = {}
+    for k, o in offs.items():
+        if k in ("rawcam", "rawcam_aux"):
+            out[k] = record[o:o + 4 * k_live * H * W].view(torch.float32 if torch.is_tensor(record) else np.float32).reshape(k_live, H, W)
+        elif k.endswith("_idx"):
+            out[k] = record[o:o + 4 * k_live].view(torch.int32 if torch.is_tensor(record) else np.int32)
+        else:
+            out[k] = record[o:o + H * W].reshape(H, W)
+    return out
+
+
+def export_maps(cam, cam_aux, seg, cls_label, size, what, high_thre, low_thre, ignore_index=255, out=None, k_live=None):
+    """Every file product of ONE image in one launch and one packed record (cosa_export_maps).
+    cam / cam_aux [1,C,S,S] or [C,S,S], seg [1,C+1,S,S] or [C+1,S,S] as multi_scale_camsegv3 returns them, cls_label [1,C] / [C] or
+    None (no image-level labels: "seg" only, the plain argmax).  `what`: names out of seg, pseudo, pseudo_aux, rawcam, rawcam_aux.
+    `out`: a caller-owned uint8 device record to write into (at least the layout's size); `k_live`: the number of present classes when the
+    caller knows it on the host -- without it the label row is counted here, which waits for the device.
+    Returns views into the record (export_record_views): uint8 [H,W] maps, rawcam* float32 [k_live,H,W], rawcam*_idx int32 [k_live]."""
+    H, W = int(size[0]), int(size[1])
+    mask = export_what_mask(what)
+    ref = seg if seg is not None else (cam if cam is not None else cam_aux)
+    if ref is None:
+        raise ValueError("export_maps: no input maps")
+    _C.require_cuda(cam, cam_aux, seg, cls_label, out)
+    S = ref.shape[-1]
+    prep = lambda t: t.contiguous().float() if t is not None else None
+    cam, cam_aux, seg, cls = prep(cam), prep(cam_aux), prep(seg), prep(cls_label)
+    if cls is not None:
+        C = cls.numel()
+    else:
+        C = seg.shape[-3] - 1 if seg is not None else ref.shape[-3]
+    for t, ch, nm in ((cam, C, "cam"), (cam_aux, C, "cam_aux"), (seg, C + 1, "seg")):
+        if t is not None and (t.numel() != ch * S * S or tuple(t.shape[-3:]) != (ch, S, S)):
+            raise ValueError(f"export_maps: {nm} must be one image's [{ch},{S},{S}], got {tuple(t.shape)}")
+    if k_live is None:
+        k_live = int((cls != 0).sum()) if cls is not None else 0
+    offs, nbytes = export_record_layout(C, H, W, k_live, mask)
+    if out is None:
+        out = torch.empty(nbytes, device=ref.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes:
+        raise ValueError(f"export_maps: `out` must be a contiguous uint8 record of at least {nbytes} bytes")
+    _C.check(_C.lib().cosa_export_maps(_C.ptr(cam), _C.ptr(cam_aux), _C.ptr(seg), _C.ptr(cls), C, S, H, W, int(k_live), mask,
+                                       float(high_thre if high_thre is not None else 0.0), float(low_thre if low_thre is not None else 0.0),
+                                       int(ignore_index), _C.ptr(out), out.numel(), _C.stream_ptr()), "cosa_export_maps")
+    return export_record_views(out, C, H, W, k_live, mask)
+
+
 # --------------------------------------------------------------------------------------------
 # cam_validation / cam2mask  (utils/seg_helper.py:547-551, 721-797)
 # --------------------------------------------------------------------------------------------

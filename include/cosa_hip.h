@@ -532,6 +532,32 @@ int cosa_cam_to_label(const float *cam, const float *cls_label, int B, int C, in
 int cosa_confusion_hist(const uint8_t *gt, const uint8_t *pred, size_t n, int num_classes, int pseudo,
                         unsigned long long *hist, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Export: every file product of ONE image, at the image's own (generally non-square) H x W, in one
+ * packed record, from what multi_scale_camsegv3 returns for it: cam / cam_aux [C,S,S], seg [C+1,S,S], cls_label [C] or
+ * NULL (no image-level labels: seg only, plain argmax).  `what` is a mask of COSA_EXPORT_* bits:
+ *   SEG         uint8 [H,W]   argmax of the logits resized to H x W, absent classes masked first (the bits of
+ *                             cosa_eval_labels' lab_vd; lab_ps without a label row)
+ *   PSEUDO(_AUX) uint8 [H,W]  v = cls * resized CAM; m = max over present classes: m > high_thre -> class + 1, else
+ *                             m > low_thre -> ignore_index, else 0 (cam2mask without refine model, whole image box)
+ *   RAWCAM(_AUX) fp32 [K_live,H,W] + int32 [K_live]: the planes v of the present classes in class order and their indices
+ * K_live = number of non-zero entries of cls_label (the host knows it: it sizes the record).
+ * cosa_export_record_layout: offsets[COSA_EXPORT_SLOTS] (bytes from the record's start, each 16-byte aligned; (size_t)-1
+ * when not asked for) in the order seg, pseudo, pseudo_aux, rawcam, rawcam_aux, rawcam indices, rawcam_aux indices;
+ * returns the record's size in bytes, 0 on bad arguments.  Host and device use this one definition.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_EXPORT_SEG 1u
+#define COSA_EXPORT_PSEUDO 2u
+#define COSA_EXPORT_PSEUDO_AUX 4u
+#define COSA_EXPORT_RAWCAM 8u
+#define COSA_EXPORT_RAWCAM_AUX 16u
+#define COSA_EXPORT_ALL 31u
+#define COSA_EXPORT_SLOTS 7
+size_t cosa_export_record_layout(int C, int H, int W, int K_live, unsigned what, size_t *offsets);
+int cosa_export_maps(const float *cam, const float *cam_aux, const float *seg, const float *cls_label, int C, int S, int H, int W,
+                     int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, void *record,
+                     size_t record_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
