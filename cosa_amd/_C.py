@@ -149,28 +149,26 @@ _SIGS.update({
                                 c_int, c_void_p]),
 })
 
-# the fp16-operand builds of the GEMM / attention translation units export the same signatures under *_f16 names
-for _bf, _f in (("cosa_gemm_bf16", "cosa_gemm_f16"), ("cosa_gemm_wgrad_bf16", "cosa_gemm_wgrad_f16"), ("cosa_layernorm", "cosa_layernorm_f16"),
-                ("cosa_conv3x3_dilated_nhwc", "cosa_conv3x3_dilated_nhwc_f16"), ("cosa_conv3x3_dilated_wgrad", "cosa_conv3x3_dilated_wgrad_f16"),
-                ("cosa_gemm_set_variant", "cosa_gemm_set_variant_f16"), ("cosa_gemm_set_stamp_slot", "cosa_gemm_set_stamp_slot_f16"),
-                ("cosa_attn_workspace_bytes", "cosa_attn_workspace_bytes_f16"), ("cosa_attn_prepare_vt", "cosa_attn_prepare_vt_f16"),
-                ("cosa_attn_fwd", "cosa_attn_fwd_f16"), ("cosa_attn_bwd_workspace_bytes", "cosa_attn_bwd_workspace_bytes_f16"),
-                ("cosa_attn_bwd", "cosa_attn_bwd_f16"),
-                # fp16x3 (round 6): the split-row producers and the three-term GEMM / attention with fp16 halves
-                ("cosa_split_rows", "cosa_split_rows_f16"), ("cosa_layernorm_split", "cosa_layernorm_split_f16"),
-                ("cosa_gemm_bf16x3", "cosa_gemm_f16x3"), ("cosa_attn_fwd_bf16x3", "cosa_attn_fwd_f16x3")):
-    _SIGS[_f] = _SIGS[_bf]
+# the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose
+# name is not `name + "_f16"` (fn16 resolves through it); the regular ones are listed for their signatures
+_F16_TWIN = {"cosa_gemm_bf16": "cosa_gemm_f16", "cosa_gemm_wgrad_bf16": "cosa_gemm_wgrad_f16",
+             # fp16x3 (round 6): the three-term GEMM / attention with fp16 halves
+             "cosa_gemm_bf16x3": "cosa_gemm_f16x3", "cosa_attn_fwd_bf16x3": "cosa_attn_fwd_f16x3"}
+for _bf in list(_F16_TWIN) + ["cosa_layernorm", "cosa_conv3x3_dilated_nhwc", "cosa_conv3x3_dilated_wgrad", "cosa_gemm_set_variant",
+                              "cosa_gemm_set_stamp_slot", "cosa_attn_workspace_bytes", "cosa_attn_prepare_vt", "cosa_attn_fwd",
+                              "cosa_attn_bwd_workspace_bytes", "cosa_attn_bwd", "cosa_split_rows", "cosa_layernorm_split"]:
+    _SIGS[_F16_TWIN.get(_bf, _bf + "_f16")] = _SIGS[_bf]
 
 # entry points added by later translation units register themselves here (vit / gemm / attention)
 EXTRA_SIGS = {}
 
 
 def fn16(name, dtype):
-    """the entry point `name` for 16-bit operands of torch dtype `dtype`: bf16 -> name, fp16 -> its *_f16 twin"""
+    """the entry point `name` for 16-bit operands (or split halves: bf16x3 -> fp16x3) of torch dtype `dtype`: bf16 -> name, fp16 -> its twin"""
     if dtype == torch.bfloat16:
         return getattr(lib(), name)
     if dtype == torch.float16:
-        return getattr(lib(), {"cosa_gemm_bf16": "cosa_gemm_f16", "cosa_gemm_wgrad_bf16": "cosa_gemm_wgrad_f16"}.get(name, name + "_f16"))
+        return getattr(lib(), _F16_TWIN.get(name, name + "_f16"))
     raise CosaError(f"{name}: operands must be bfloat16 or float16, got {dtype}")
 
 

@@ -4,12 +4,12 @@ Every op here is an explicit torch.autograd.Function around C-ABI calls (no trac
 Triton, no library GEMM).  Shapes / dtypes outside the HIP kernels' envelope RAISE; torch's own
 operators exist only in the test-suite (tests/torch_reference.py installs them for the host-logic tests: reference_op below).
 """
+import contextlib
 import ctypes
 import math
-
 import os
-
 import time
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -346,20 +346,23 @@ def layernorm_f32(x, g, b, eps, want_bf16=True, want_f32=False):
 # bf16x3 ("split") operands: the parity-grade precision of the no-grad passes (include/cosa_hip.h; csrc/split_kernels.hip)
 #   a split row of logical width K: [hi (K) | lo (K) | aug (64)] bf16, row stride 2K + 64
 # --------------------------------------------------------------------------------------------
-_zero_bias = {}
+_zero_vectors = {}     # (device, dtype) -> [zero vectors, the last one the longest]
+
+
+def _zeros(dev, dtype, n=8192):
+    """>= n zeros of `dtype` on `dev` (the unused bias operand of a GEMM).  Grow-only: a longer request adds a vector and the earlier ones
+    stay, so an address handed to a captured launch is valid for the life of the process"""
+    bufs = _zero_vectors.setdefault((dev, dtype), [])
+    if not bufs or bufs[-1].numel() < n:
+        bufs.append(torch.zeros(max(n, 8192), device=dev, dtype=dtype))
+    return bufs[-1]
 
 
 def split_ld(K):
     return 2 * K + 64
 
 
-def _x3_fn(name, dtype):
-    """entry point of the three-term ("x3") path for halves of `dtype`: bf16 -> bf16x3, fp16 -> fp16x3 (round 6)"""
-    if dtype == torch.bfloat16:
-        return getattr(_C.lib(), name)
-    if dtype == torch.float16:
-        return getattr(_C.lib(), {"cosa_gemm_bf16x3": "cosa_gemm_f16x3", "cosa_attn_fwd_bf16x3": "cosa_attn_fwd_f16x3"}.get(name, name + "_f16"))
-    raise _C.CosaError(f"{name}: split halves must be bfloat16 or float16, got {dtype}")
+_x3_fn = _C.fn16       # entry point of the three-term ("x3") path for halves of `dtype`: bf16 -> bf16x3, fp16 -> fp16x3 (one table: _C._F16_TWIN)
 
 
 def split_rows(src, bias=None, ones=False, out=None, dtype=torch.bfloat16):
@@ -388,9 +391,7 @@ def gemm_x3(xs, ws, M, N, K, epilogue=EPI_BIAS, residual=None, out=None, ldy=Non
     epilogue 2: fp32 [M, N] = residual + . (in place allowed)"""
     dev, dt = xs.device, xs.dtype
     assert ws.dtype == dt
-    z = _zero_bias.get((dev, dt))
-    if z is None:
-        z = _zero_bias[(dev, dt)] = torch.zeros(8192, device=dev, dtype=dt)
+    z = _zeros(dev, dt)
     if epilogue == EPI_RESIDUAL:
         ldy = N
         if out is None:
@@ -424,9 +425,6 @@ def attn_fwd_x3(qkv_s, B, N, H, out_s, lse=None):
 #   a c8 row of logical width K, in bytes: [hi fp16 (2K) | lo8 e5m2 (K) | hi8 e5m2 (K) | aug fp16 (128)]; held as fp16 tensors of
 #   2K + 64 columns (the same stride as a bf16x3 row)
 # --------------------------------------------------------------------------------------------
-_c8_zero_bias = {}
-
-
 def c8_rows(src, bias=None, ones=False, out=None):
     """fp32 [R, K] (unit column stride; any row stride; K % 128 == 0) -> c8 rows [R, 2K + 64] (fp16 units); aug block = (bias_hi,
     bias_lo, 0..) per row, (1, 1, 0..) with ones=True, zeros otherwise"""
@@ -451,9 +449,7 @@ def gemm_c8(xs, ws, M, N, K, epilogue=EPI_BIAS, residual=None, out=None, ldy=Non
     """xs [M, 2K+64], ws [N, 2K+64] c8 rows (bias inside ws).  epilogue 0: plain fp16 [M, ldy >= N]; 1 (GELU): c8 rows [M, 2N + 64]
     (hi | lo8 | hi8 written; the caller owns the aug block); 2: fp32 [M, N] = residual + . (in place allowed)"""
     dev = xs.device
-    z = _c8_zero_bias.get(dev)
-    if z is None:
-        z = _c8_zero_bias[dev] = torch.zeros(8192, device=dev, dtype=torch.float16)
+    z = _zeros(dev, torch.float16)
     if epilogue == EPI_RESIDUAL:
         ldy = N
         if out is None:
@@ -507,9 +503,7 @@ def gemm_c4(xs, xsc, ws, wsc, M, N, K, epilogue=EPI_BIAS, residual=None, out=Non
     """xs [M, 2K+64] / ws [N, 2K+64] c4 rows with their scale tensors (bias inside ws).  epilogue 0: plain fp16 [M, ldy >= N]; 1 (GELU):
     c4 rows [M, 2N + 64] + out_scales (c4_scales(M, N)); 2: fp32 [M, N] = residual + . (in place allowed)"""
     dev = xs.device
-    z = _c8_zero_bias.get(dev)
-    if z is None:
-        z = _c8_zero_bias[dev] = torch.zeros(8192, device=dev, dtype=torch.float16)
+    z = _zeros(dev, torch.float16)
     if epilogue == EPI_RESIDUAL:
         ldy = N
         if out is None:
@@ -560,70 +554,135 @@ def attn_fwd_c8(qkv, B, N, H, out_c8, lse=None, q_prescaled=False):
 # --------------------------------------------------------------------------------------------
 # small helpers
 # --------------------------------------------------------------------------------------------
-_shadows = {}          # id(param) -> (param, persistent 16-bit shadow at a fixed address; refreshed explicitly, hipGraph-safe)
+_owner_of = weakref.WeakValueDictionary()      # id(param) -> the WeightShadows holding its copies.  Weak: when an owner is dropped (with its
+#                                                module, its trainer) its entries go with it, and so do the copies -- nothing else holds them
 
 
-class ShadowSet:
-    """Persistent 16-bit copies of a module's fp32 parameters, refreshed with ONE multi-tensor copy.
+class WeightShadows:
+    """THE owner of a module's weight shadows: a persistent 16-bit copy of every fp32 parameter at a fixed address, refreshed with ONE
+    multi-tensor copy, and (add_transposed) bf16 W^T copies of chosen weights, rebuilt by ONE batched launch.
 
-    The teacher is read 6x per step and written once (EMA).  Keeping fixed-address shadows (a) casts every weight
-    exactly once per step and (b) makes the whole teacher pass capturable in a hipGraph: the refresh is the first node
-    of the graph, the kernels after it read fixed addresses."""
+    The teacher is read 6x per step and written once (EMA).  Keeping fixed-address shadows (a) casts every weight exactly once per step and
+    (b) makes the whole teacher pass capturable in a hipGraph: the refresh is the first node of the graph, the kernels after it read fixed
+    addresses.  With W^T the input-gradient GEMM dX = dY W of an nn.Linear is the forward GEMM kernel applied to W^T: no NN kernel family,
+    no library call.  Consumers find a parameter's copies through shadow_entry(); nothing but this object keeps them alive."""
 
     def __init__(self, module, dtype=torch.bfloat16):
         self.params = [p for p in module.parameters()]
         self.dtype = dtype
         self.shadows = [torch.empty_like(p, dtype=dtype) for p in self.params]
-        for p, s in zip(self.params, self.shadows):
-            _shadows[id(p)] = (p, s)
+        self.index = {id(p): i for i, p in enumerate(self.params)}
+        self.optimizer_owned = False     # an optimizer kernel rewrites the 16-bit copies every step and has their addresses in its records
+        #                                  (CoSATrainer: fused AdamW + EMA); refresh() then leaves them alone and they cannot be replaced
+        self.fresh = 0                   # depth of `with shadows_fresh(module)`
+        self.t16, self.wT, self.d_rec = [], {}, None          # W^T copies in the order asked for / by parameter index; their record table
+        for p in self.params:
+            _owner_of[id(p)] = self
         self.refresh()
 
+    def add_transposed(self, weights):
+        """bf16 W^T copies of `weights` (fp32 parameters of this owner; a conv weight counts as its [out, -1] view)"""
+        import numpy as np
+        dev = weights[0].device
+        self.t16 = [torch.empty((w.numel() // w.shape[0], w.shape[0]), device=dev, dtype=torch.bfloat16) for w in weights]
+        self.wT = {self.index[id(w)]: t for w, t in zip(weights, self.t16)}
+        rec_dt = np.dtype([("src", "u8"), ("dst", "u8"), ("rows", "i4"), ("cols", "i4"), ("tile0", "i4"), ("tiles_c", "i4")])
+        assert rec_dt.itemsize == _C.lib().cosa_transpose_record_bytes()
+        rec = np.zeros(len(weights), rec_dt)
+        tiles = 0
+        for i, (w, t) in enumerate(zip(weights, self.t16)):
+            assert w.dtype == torch.float32 and w.is_contiguous()
+            rows, cols = w.shape[0], w.numel() // w.shape[0]
+            tr, tc = (rows + 63) // 64, (cols + 63) // 64
+            rec[i] = (w.data_ptr(), t.data_ptr(), rows, cols, tiles, tc)
+            tiles += tr * tc
+        self.total_tiles = tiles
+        self.d_rec = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        self.refresh()
+        return self
+
     @torch.no_grad()
-    def refresh(self):
-        torch._foreach_copy_(self.shadows, self.params)
+    def refresh(self, force=False):
+        """bring everything held here up to date with the masters: the 16-bit copies (left to the optimizer kernel when it owns them, unless
+        `force`: the masters were written behind its back -- load_state_dict, DDP's parameter broadcast), then W^T"""
+        if force or not self.optimizer_owned:
+            torch._foreach_copy_(self.shadows, self.params)
+        if self.d_rec is not None:
+            _C.check(_C.lib().cosa_transpose_cast_batched(_C.ptr(self.d_rec), len(self.t16), self.total_tiles, _C.stream_ptr()),
+                     "cosa_transpose_cast_batched")
+
+    def __reduce__(self):
+        return type(None), ()            # a copied / unpickled module starts without an owner: the addresses belong to this module's tensors
+
+
+ShadowSet = WeightShadows
+
+
+def TransposedShadows(weights):
+    """bf16 W^T copies of `weights`, held by the WeightShadows that already owns their 16-bit copies (returned)"""
+    return _owner_of[id(weights[0])].add_transposed(weights)
+
+
+def shadow_entry(p, dtype=None):
+    """THE lookup: -> (16-bit copy, bf16 W^T | None) of parameter `p`, or None unless a live owner holds copies of this very tensor, on
+    its device and (when `dtype` is given) of that type"""
+    sh = _owner_of.get(id(p))
+    i = sh.index.get(id(p)) if sh is not None else None
+    if i is None or sh.params[i] is not p or sh.shadows[i].device != p.device or (dtype is not None and sh.shadows[i].dtype != dtype):
+        return None
+    return sh.shadows[i], sh.wT.get(i)
+
+
+def _shadowed(weight, bias, transposed=False):
+    """-> (W, b, W^T | None) bf16 copies of a layer's two parameters, or None when one of them (with `transposed`: or W^T) is not registered"""
+    ew, eb = shadow_entry(weight, torch.bfloat16), shadow_entry(bias, torch.bfloat16)
+    if ew is None or eb is None or (transposed and ew[1] is None):
+        return None
+    return ew[0], eb[0], ew[1]
 
 
 def ensure_shadows(module, dtype=torch.bfloat16):
-    """Shadows of ALL parameters of `module` (a VITNetwork, possibly DDP-wrapped), created on first use, and -- unless an optimizer
-    kernel keeps them current (`module._cosa_shadow_auto = False`, set by CoSATrainer with the fused AdamW+EMA step) -- refreshed
-    here with one multi-tensor copy.  Called at the start of every no-grad entry point (multi_scale_camseg*, evaluate,
-    VITNetwork.forward under no_grad), so weights written by ANY route (optimizer.step, load_state_dict, the reference loop's
-    `param.data.mul_().add_()` EMA, which does not bump `_version`) are seen by the next forward: nothing is cached by version."""
+    """The WeightShadows of `module` (a VITNetwork, possibly DDP-wrapped), built on first use, and -- unless an optimizer kernel keeps the
+    copies current (`optimizer_owned`, set by CoSATrainer with the fused AdamW+EMA step) -- refreshed here with one multi-tensor copy.
+    Called at the start of every no-grad entry point (multi_scale_camseg*, evaluate, VITNetwork.forward under no_grad), so weights written
+    by ANY route (optimizer.step, load_state_dict, the reference loop's `param.data.mul_().add_()` EMA, which does not bump `_version`)
+    are seen by the next forward: nothing is cached by version."""
     module = getattr(module, "module", module)
-    ss = module.__dict__.get("_cosa_shadowset")
-    if ss is not None and shadows_fresh.depth > 0:
-        return ss
-    if ss is None or ss.dtype != dtype or any(a is not b for a, b in zip(ss.params, module.parameters())) \
-            or (ss.params and ss.params[0].device != ss.shadows[0].device):
-        if ss is not None and not module.__dict__.get("_cosa_shadow_auto", True):
+    sh = module.__dict__.get("_weight_shadows")
+    if sh is not None and sh.fresh > 0:
+        return sh
+    if sh is None or sh.dtype != dtype or any(a is not b for a, b in zip(sh.params, module.parameters())) \
+            or (sh.params and shadow_entry(sh.params[0]) is None):
+        if sh is not None and sh.optimizer_owned:
             # a trainer has baked the addresses / dtype of the existing shadows into its fused optimizer records and its captured teacher
-            # graph (CoSATrainer): replacing the set would leave both writing to and reading from freed memory, and the new shadows would
+            # graph (CoSATrainer): replacing them would leave both writing to and reading from freed memory, and the new shadows would
             # never be refreshed
             raise RuntimeError("ensure_shadows: this module's 16-bit shadows are owned by a CoSATrainer (fused AdamW + EMA step, captured "
                                "teacher graph); changing its compute dtype / precision or its parameters after the trainer was built is "
                                "not supported -- build a new trainer, or evaluate a copy of the network")
-        ss = ShadowSet(module, dtype)
-        module.__dict__["_cosa_shadowset"] = ss
-        return ss
-    if module.__dict__.get("_cosa_shadow_auto", True):
-        ss.refresh()
-    return ss
+        sh = module.__dict__["_weight_shadows"] = WeightShadows(module, dtype)
+        return sh
+    sh.refresh()
+    return sh
 
 
-class shadows_fresh:
-    """`with shadows_fresh():` -- nested no-grad entry points skip their own refresh (one refresh per multi-scale pass, not per scale)"""
-    depth = 0
-
-    def __enter__(self):
-        shadows_fresh.depth += 1
-
-    def __exit__(self, *exc):
-        shadows_fresh.depth -= 1
+@contextlib.contextmanager
+def shadows_fresh(module):
+    """`with shadows_fresh(model):` -- the model's shadows are current: its no-grad entry points skip their own refresh inside (one refresh
+    per multi-scale pass, not per scale)"""
+    sh = getattr(getattr(module, "module", module), "__dict__", {}).get("_weight_shadows")
+    if sh is not None:
+        sh.fresh += 1
+    try:
+        yield
+    finally:
+        if sh is not None:
+            sh.fresh -= 1
 
 
 def shadow_of(p):
-    ent = _shadows.get(id(p))
-    return ent[1] if ent is not None and ent[0] is p else None
+    ent = shadow_entry(p)
+    return ent[0] if ent is not None else None
 
 
 def cast_param(p, dtype):
@@ -634,10 +693,8 @@ def cast_param(p, dtype):
         return p
     if torch.is_grad_enabled() and p.requires_grad:
         return p.to(dtype)
-    ent = _shadows.get(id(p))
-    if ent is not None and ent[0] is p and ent[1].dtype == dtype and ent[1].device == p.device:
-        return ent[1]
-    return p.detach().to(dtype)
+    ent = shadow_entry(p, dtype)
+    return ent[0] if ent is not None else p.detach().to(dtype)
 
 
 _MM_OUT_DTYPE = None      # does torch.mm(bf16, bf16, out_dtype=fp32) work on this build?  probed on first use
@@ -845,55 +902,10 @@ def defer_wgrads(x, linears):
     return DeferredWgrad.apply(x, c, *params), c
 
 
-class TransposedShadows:
-    """bf16 W^T copies of the student's projection weights, rebuilt from the fp32 masters by ONE batched launch per step (after the
-    optimizer).  With them the input-gradient GEMM dX = dY W of an nn.Linear is the forward GEMM kernel applied to W^T: no NN kernel
-    family, no library call."""
-
-    def __init__(self, weights):
-        import numpy as np
-        self.weights = list(weights)
-        dev = self.weights[0].device
-        self.t16 = [torch.empty((w.numel() // w.shape[0], w.shape[0]), device=dev, dtype=torch.bfloat16) for w in self.weights]
-        rec_dt = np.dtype([("src", "u8"), ("dst", "u8"), ("rows", "i4"), ("cols", "i4"), ("tile0", "i4"), ("tiles_c", "i4")])
-        assert rec_dt.itemsize == _C.lib().cosa_transpose_record_bytes()
-        rec = np.zeros(len(self.weights), rec_dt)
-        tiles = 0
-        for i, (w, t) in enumerate(zip(self.weights, self.t16)):
-            assert w.dtype == torch.float32 and w.is_contiguous()
-            rows, cols = w.shape[0], w.numel() // w.shape[0]                 # (a conv weight counts as its [out, -1] view)
-            tr, tc = (rows + 63) // 64, (cols + 63) // 64
-            rec[i] = (w.data_ptr(), t.data_ptr(), rows, cols, tiles, tc)
-            tiles += tr * tc
-            _transposed[id(w)] = (w, t)
-        self.total_tiles = tiles
-        self.d_rec = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-        self.refresh()
-
-    def refresh(self):
-        _C.check(_C.lib().cosa_transpose_cast_batched(_C.ptr(self.d_rec), len(self.weights), self.total_tiles, _C.stream_ptr()),
-                 "cosa_transpose_cast_batched")
-
-
-_transposed = {}       # id(weight) -> (weight, bf16 W^T)
-_zeros16 = {}
-
-
-def _zero_bias16(n, dev):
-    z = _zeros16.get(dev)
-    if z is None or z.numel() < n:
-        z = _zeros16[dev] = torch.zeros(max(n, 8192), device=dev, dtype=torch.bfloat16)
-    return z
-
-
-def _own_gemm_ok(M, N, K):
-    return N % 128 == 0 and K % 64 == 0
-
-
 class LinearShadowFn(Function):
     """y = x W^T + b (act = 1: gelu(.) of it, mlp.fc1) with the bf16 SHADOW of the fp32 master weight, forward and backward on the
     MFMA GEMM kernels of this repository: forward = cosa_gemm_bf16 (fc1: the dual epilogue that also keeps the pre-activation),
-    dX = the same kernel on the transposed shadow W^T (TransposedShadows), dW / db = the TN weight-gradient kernel in fp32.
+    dX = the same kernel on the transposed shadow W^T (WeightShadows.add_transposed), dW / db = the TN weight-gradient kernel in fp32.
     Gradients are routed to the masters (w, b)."""
 
     @staticmethod
@@ -935,7 +947,7 @@ class LinearShadowFn(Function):
         K = x2.shape[1]
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = gemm_bf16(dy2, wT16, _zero_bias16(K, dy2.device)[:K], EPI_BIAS).view(ctx.xshape)      # [M,N] x (W^T [K,N])^T
+            dx = gemm_bf16(dy2, wT16, _zeros(dy2.device, torch.bfloat16, K)[:K], EPI_BIAS).view(ctx.xshape)      # [M,N] x (W^T [K,N])^T
         # (running the weight-gradient GEMM on a side stream next to the input-gradient GEMM, which often leaves CUs idle, was measured
         #  on one box in both issue orders: 324.4 / 322.3 img/s against 323.0 -- no gain, not kept)
         if ctx.needs_input_grad[1]:
@@ -953,12 +965,11 @@ def linear_view2d(x, weight, bias, dtype):
     LinearShadowFn; the parameter needs registered shadows (bf16 copy and bf16 transposed copy of the 2-D view).  K % 64 (the 8-pixel
     patch: K = 192) is taken when no input gradient is asked for (the image needs none): the forward GEMM takes K % 64 and the weight
     gradient then runs on cosa_patch_wgrad_bf16; the input-gradient GEMM would need K % 128."""
-    ew, eb, et = _shadows.get(id(weight)), _shadows.get(id(bias)), _transposed.get(id(weight))
+    sh = _shadowed(weight, bias, transposed=True)
     w2 = weight.view(weight.shape[0], -1)
-    if ew is not None and eb is not None and et is not None and ew[0] is weight and eb[0] is bias and et[0] is weight \
-            and w2.shape[0] % 128 == 0 and (w2.shape[1] % 128 == 0 or (w2.shape[1] % 64 == 0 and not x.requires_grad)):
-        return LinearShadowFn.apply(x, w2, bias, ew[1].view(w2.shape), eb[1], et[1], False)
-    return reference_op("linear", f"linear_view2d (weight {tuple(w2.shape)}, {dtype}; shadows registered: {ew is not None and et is not None})",
+    if sh is not None and w2.shape[0] % 128 == 0 and (w2.shape[1] % 128 == 0 or (w2.shape[1] % 64 == 0 and not x.requires_grad)):
+        return LinearShadowFn.apply(x, w2, bias, sh[0].view(w2.shape), sh[1], sh[2], False)
+    return reference_op("linear", f"linear_view2d (weight {tuple(w2.shape)}, {dtype}; shadows registered: {sh is not None})",
                         x, cast_param(weight, dtype).view(w2.shape), cast_param(bias, dtype))
 
 
@@ -966,11 +977,9 @@ def linear(x, weight, bias, dtype, act=False):
     """nn.Linear (+ GELU with act=True) on `dtype` operands from fp32 masters.  Training on the GPU with registered shadows (bf16 W, b and
     W^T): LinearShadowFn, every GEMM an own kernel; anything else (fp32 parity mode, odd shapes) is outside the envelope."""
     if torch.is_grad_enabled() and weight.requires_grad and dtype == torch.bfloat16 and x.is_cuda:
-        ew, eb, et = _shadows.get(id(weight)), _shadows.get(id(bias)), _transposed.get(id(weight))
-        if ew is not None and eb is not None and et is not None and ew[0] is weight and eb[0] is bias and et[0] is weight \
-                and _own_gemm_ok(x.numel() // x.shape[-1], weight.shape[0], weight.shape[1]) and weight.shape[0] % 64 == 0 \
-                and weight.shape[0] % 128 == 0 and weight.shape[1] % 128 == 0:
-            return LinearShadowFn.apply(x, weight, bias, ew[1], eb[1], et[1], bool(act))
+        sh = _shadowed(weight, bias, transposed=True)
+        if sh is not None and weight.shape[0] % 128 == 0 and weight.shape[1] % 128 == 0:
+            return LinearShadowFn.apply(x, weight, bias, *sh, bool(act))
     return reference_op("linear", f"linear (weight {tuple(weight.shape)}, {dtype}, grad {torch.is_grad_enabled()})",
                         x, cast_param(weight, dtype), cast_param(bias, dtype), act=act)
 
@@ -1042,11 +1051,7 @@ class LayerNormFn(Function):
 
 def add_layernorm(x, delta, weight, bias, eps):
     """-> (x + delta, LayerNorm(x + delta)); delta may be None.  bf16 [.., 768] on the GPU only."""
-    ew, eb = _shadows.get(id(weight)), _shadows.get(id(bias))
-    if ew is not None and eb is not None and ew[0] is weight and eb[0] is bias:
-        w16, b16 = ew[1], eb[1]
-    else:
-        w16, b16 = weight.detach().to(torch.bfloat16), bias.detach().to(torch.bfloat16)
+    w16, b16 = _gamma16(weight, bias)
     if delta is None:
         return x, LayerNormFn.apply(x, weight, bias, w16, b16, eps)
     return AddLayerNormFn.apply(x, delta, weight, bias, w16, b16, eps)
@@ -1062,10 +1067,9 @@ def add_layernorm(x, delta, weight, bias, eps):
 # also emits the bf16 copy that the projection's input- / weight-gradient GEMMs take as dY.
 # --------------------------------------------------------------------------------------------
 def _gamma16(weight, bias):
-    ew, eb = _shadows.get(id(weight)), _shadows.get(id(bias))
-    if ew is not None and eb is not None and ew[0] is weight and eb[0] is bias and ew[1].dtype == torch.bfloat16:
-        return ew[1], eb[1]
-    return weight.detach().to(torch.bfloat16), bias.detach().to(torch.bfloat16)
+    """bf16 gamma / beta of a LayerNorm: the registered copies, or a cast"""
+    sh = _shadowed(weight, bias)
+    return sh[:2] if sh is not None else (weight.detach().to(torch.bfloat16), bias.detach().to(torch.bfloat16))
 
 
 def _ln_backward_f32(dy, x, g16, eps, dskip, want16):
@@ -1153,7 +1157,7 @@ class ResidualLinearLNFn(Function):
         K = a2.shape[1]
         da = dw = db = None
         if ctx.needs_input_grad[0]:
-            da = gemm_bf16(dxt16, wT16, _zero_bias16(K, dxt16.device)[:K], EPI_BIAS).view(ctx.ashape)
+            da = gemm_bf16(dxt16, wT16, _zeros(dxt16.device, torch.bfloat16, K)[:K], EPI_BIAS).view(ctx.ashape)
         if ctx.needs_input_grad[2]:
             if ctx.collect is not None:
                 ctx.collect[0].add(ctx.collect[1], dxt16, a2)
@@ -1166,13 +1170,12 @@ def residual_linear_ln(a, x, lin, norm, y_f32=False):
     """x' = x + lin(a) on the fp32 stream and y = norm(x') (bf16; fp32 with y_f32) -> (x', y); `lin` an nn.Linear with registered shadows,
     `norm` an nn.LayerNorm"""
     weight, bias = lin.weight, lin.bias
-    ew, eb, et = _shadows.get(id(weight)), _shadows.get(id(bias)), _transposed.get(id(weight))
-    if not (ew is not None and eb is not None and et is not None and ew[0] is weight and eb[0] is bias and et[0] is weight
-            and ew[1].dtype == torch.bfloat16 and weight.shape[0] % 128 == 0 and weight.shape[1] % 128 == 0):
+    sh = _shadowed(weight, bias, transposed=True)
+    if sh is None or weight.shape[0] % 128 != 0 or weight.shape[1] % 128 != 0:
         raise _C.CosaError("residual_linear_ln: the projection needs registered bf16 shadows (W, b, W^T) and 128-aligned shapes "
-                           "(CoSATrainer / nn_ops.ensure_shadows + TransposedShadows register them)")
+                           "(CoSATrainer / nn_ops.ensure_shadows(module).add_transposed register them)")
     gw16, gb16 = _gamma16(norm.weight, norm.bias)
-    return ResidualLinearLNFn.apply(a, x, weight, bias, ew[1], eb[1], et[1], norm.weight, norm.bias, gw16, gb16, norm.eps, bool(y_f32))
+    return ResidualLinearLNFn.apply(a, x, weight, bias, *sh, norm.weight, norm.bias, gw16, gb16, norm.eps, bool(y_f32))
 
 
 class PatchFanoutFn(Function):

@@ -140,7 +140,7 @@ class CoSATrainer:
         if on:
             self.model_AN.set_nograd_precision(tp)
         tdt = self.model_AN.compute_dtype if on else args.compute_dtype
-        self._shadows = nn_ops.ensure_shadows(self.model_AN, tdt) if on else None
+        self._teacher_shadows = nn_ops.ensure_shadows(self.model_AN, tdt) if on else None
         self._student_shadows = nn_ops.ensure_shadows(self.student) if on else None
         # AdamW + EMA + shadow refresh as one multi-tensor kernel: it rewrites every shadow each step, so the no-grad entry points
         # need not refresh them (nn_ops.ensure_shadows); without it they do
@@ -148,17 +148,15 @@ class CoSATrainer:
         if on and getattr(args, "fused_optimizer", True):
             self._fused_step = torch_helper.FusedAdamWEMAStep(self.optimizer, self._ema_pairs[1], self._ema_pairs[0], args.momentum,
                                                               shadow_of=nn_ops.shadow_of)
-        for m in (self.student, self.model_AN):
-            m.__dict__["_cosa_shadow_auto"] = self._fused_step is None
-        # bf16 W^T copies of the student's block projections (the input-gradient GEMMs run the forward kernel on them)
-        self._student_wT = None
         if on:
+            self._teacher_shadows.optimizer_owned = self._student_shadows.optimizer_owned = self._fused_step is not None
+            # bf16 W^T copies of the student's block projections (the input-gradient GEMMs run the forward kernel on them)
             ws = [self.student.encoder.patch_embed.proj.weight]
             for blk in self.student.encoder.blocks:
                 ws += [blk.attn.qkv.weight, blk.attn.proj.weight, blk.mlp.fc1.weight, blk.mlp.fc2.weight]
-            self._student_wT = nn_ops.TransposedShadows(ws)
+            self._student_shadows.add_transposed(ws)
         # COSA_TEACHER_GRAPH=0 / COSA_TEACHER_SYNC=1: fallbacks reachable from any launcher's command line (first multi-GPU runs)
-        self.use_graph = bool(getattr(args, "teacher_graph", True)) and self._shadows is not None and os.environ.get("COSA_TEACHER_GRAPH", "1") != "0"
+        self.use_graph = bool(getattr(args, "teacher_graph", True)) and on and os.environ.get("COSA_TEACHER_GRAPH", "1") != "0"
         self.graph_error = None              # why the capture was abandoned, if it was (the teacher then runs eagerly)
         self.fused_losses = bool(getattr(args, "fused_losses", True)) and device.type == "cuda" and not args.after_softmax
         self._graph = None
@@ -329,6 +327,8 @@ class CoSATrainer:
                     self._join_teacher()
             torch.cuda.synchronize()
         self.model_ON = wrap_ddp(self.student, self.device)
+        if self._student_shadows is not None:
+            self._student_shadows.refresh(force=True)    # the wrap broadcast rank 0's masters: the copies were made from this rank's own
         self._ddp_pending = False
 
     def step(self, wimg, simg, cls_label, img_box, n_iter):
@@ -339,15 +339,11 @@ class CoSATrainer:
         loss.backward()
         if self._fused_step is not None:
             self._fused_step.step()
-            if self._student_wT is not None:
-                self._student_wT.refresh()
         else:
             self.optimizer.step()
-            if self._student_shadows is not None:
-                self._student_shadows.refresh()
-            if self._student_wT is not None:
-                self._student_wT.refresh()
             torch_helper.ema_update(self._ema_pairs[0], self._ema_pairs[1], self.args.momentum)
+        if self._student_shadows is not None:
+            self._student_shadows.refresh()              # W^T, and the 16-bit copies unless the fused kernel has just written them
         return logs
 
 

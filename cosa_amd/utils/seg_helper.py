@@ -99,7 +99,7 @@ def multi_scale_camseg(model, imgs, scales, _active_labels=None, _seg_scales=Fal
             multi, inputs = None, [torch.cat([x_, x_.flip(-1)], dim=0) for x_ in scaled]
             _refresh_once(model)
         for si, s in enumerate(scales):
-            with nn_ops.shadows_fresh():
+            with nn_ops.shadows_fresh(model):
                 _, _, _, _seg, _cam, _cam_aux = multi[si] if multi is not None else model(inputs[si], cam_only=False)
             if cam is None:
                 if act is not None and _buffers is not None:
@@ -146,7 +146,7 @@ def multi_scale_camsegv3(model, imgs, scales, getcls=False, _per_image_cls=False
             multi, inputs = None, [torch.cat([x_, x_.flip(-1)], dim=0) for x_ in scaled]
             _refresh_once(model)
         for si, s in enumerate(scales):
-            with nn_ops.shadows_fresh():
+            with nn_ops.shadows_fresh(model):
                 cls_f, cls_a, _, _seg, _cam, _cam_aux = multi[si] if multi is not None else model(inputs[si], cam_only=False)
             if cam is None:
                 cam = torch.empty((b, _cam.shape[1], h, w), device=imgs.device, dtype=torch.float32)

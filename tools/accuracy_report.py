@@ -28,7 +28,7 @@ for name, dt in (("fp32 parity mode", torch.float32), ("bf16 throughput mode", t
         closs, cl = cpu.losses(wimg, simg, lab, box.numpy(), args.warmup_iters + 1)
     else:
         tr.student.load_state_dict(sd); tr.model_AN.load_state_dict(sd)
-        if tr._shadows is not None: tr._shadows.refresh()
+        if tr._teacher_shadows is not None: tr._teacher_shadows.refresh(force=True)
     with torch.no_grad():
         cam, cam_aux, _ = seg_helper.multi_scale_camseg(tr.model_AN, wimg.to(dev), args.pseudo_scales)
     loss, lg = tr.forward_losses(wimg.to(dev), simg.to(dev), lab.to(dev), box, args.warmup_iters + 1)

@@ -31,6 +31,8 @@ def main():
                     "capture happens before DistributedDataParallel is constructed: CoSATrainer.prepare_ddp); the run FAILS if it was not captured")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group and wrap the student in DDP even in a world of one "
                     "(one rank over RCCL: the watchdog thread, the comm stream and the bucket all-reduces are the real ones)")
+    ap.add_argument("--rank-seeds", action="store_true", help="build rank r's networks from seed r (the reference's --random_seed under DDP): the "
+                    "wrap's broadcast then REWRITES the masters of ranks > 0; the student's 16-bit copies are saved as well")
     opt = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1")) if not opt.single else 1
     rank = int(os.environ.get("RANK", "0")) if not opt.single else 0
@@ -51,7 +53,7 @@ def main():
     wimg, simg, lab = (torch.cat([s[i] for s in shards]) for i in range(3))
     box = torch.cat([s[3] for s in shards])
     args = default_args("VOC12", crop_size=opt.crop, batch_size=wimg.shape[0], teacher_graph=opt.teacher_graph, lr=1e-3)
-    tr = CoSATrainer(args, dev, ddp=use_dist, seed=0)
+    tr = CoSATrainer(args, dev, ddp=use_dist, seed=rank if opt.rank_seeds else 0)
     if use_dist:
         tr.prepare_ddp(wimg, lab)          # teacher capture first, then the DDP wrap
         assert isinstance(tr.model_ON, torch.nn.parallel.DistributedDataParallel)
@@ -83,6 +85,8 @@ def main():
              "loss": float(logs["overall_loss"]), "world": dist.get_world_size() if use_dist else 1, "events": events,
              "defer_groups": tr.student.encoder._n_defer_groups(), "graph_captured": tr._graph is not None,
              "backend": dist.get_backend() if use_dist else None, "teacher_async": tr.teacher_async}
+    if opt.rank_seeds:
+        state["student16"] = {k: nn_ops.shadow_of(v).cpu() for k, v in tr.student.named_parameters()}
     torch.save(state, os.path.join(opt.out, "single.pt" if opt.single else f"rank{rank}.pt"))
     if use_dist:
         dist.barrier()
