@@ -12,6 +12,7 @@
 // which is how ATen's CPU kernel evaluates F.interpolate(bilinear, align_corners=False) at image sizes: the label maps are
 // bit-identical to the reference's on the golden vectors (tests/golden/eval.npz).
 #include "kernels.hpp"
+#include "spec_math.hpp"
 
 namespace cosa {
 namespace {
@@ -239,6 +240,177 @@ __global__ __launch_bounds__(256) void export_maps_kernel(const ExportArgs a)
     }
 }
 
+// ---- PAR-refined pseudo labels at the image's own H x W (pseudo_par / pseudo_aux_par) ----------------------------
+// cam2mask (utils/seg_helper.py:721-797) read literally at h != w, every resize by spec R:
+//   v = cls * resize(CAM, (H, W));  [thr | v] -> resize to (h, w) = (H / 2, W / 2)  (downscale 0: h = H, w = W, no resize)
+//   -> softmax over threshold plane + present classes (hi and lo thresholds) -> PAR on the (h, w) image -> resize to (H, W)
+//   -> first-max argmax -> key -> m = hi; m[hi == 0] = ignore; m[hi + lo == 0] = 0
+// Stack layout P[2 * set + {hi, lo}][K1][h * w], K1 = K_live + 1 (plane 0: the threshold), sets = the CAM sets asked for.
+struct RefineArgs {
+    const float *cams[2];                   // the CAM sets asked for, [C,S,S] each
+    const float *cls;                       // [C]
+    uint8_t *out[2];                        // [H,W] per set
+    float *P;
+    int sets, C, S, H, W, h, w, K1;
+    float cy, cx;                           // S / H, S / W: CAM -> image
+    float dy, dx;                           // H / h, W / w: image -> PAR grid
+    float uy, ux;                           // h / H, w / W: PAR grid -> image
+    float hi, lo;
+    int ignore;
+};
+
+__device__ __forceinline__ float blend4(float p00, float p01, float p10, float p11, float ly0, float ly1, float lx0, float lx1)
+{
+    const float r0 = __builtin_fmaf(p00, lx0, p01 * lx1);
+    const float r1 = __builtin_fmaf(p10, lx0, p11 * lx1);
+    return __builtin_fmaf(r0, ly0, r1 * ly1);
+}
+
+// One thread per PAR-grid pixel and CAM set.  DS = 2 composes the two resamplings: the four image-grid taps of the pixel, each four
+// taps of the (S,S) CAM times the label -- the [C+1,H,W] tensors are never written.  The values of the present classes are parked in
+// their hi planes (each thread re-reads only what it wrote itself), then both softmaxes are written over them, sums in class order.
+template <int DS>
+__global__ __launch_bounds__(256) void refine_softmax_kernel(const RefineArgs a)
+{
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    const int hw = a.h * a.w;
+    if (pix >= hw) return;
+    const int g = blockIdx.y;
+    const int y = pix / a.w, x = pix - y * a.w;
+    const int S = a.S, nk = a.K1 - 1;
+    const size_t ss = (size_t)S * S;
+    float *Phi = a.P + (size_t)(2 * g) * a.K1 * hw + pix;
+    float *Plo = Phi + (size_t)a.K1 * hw;
+    constexpr int NT = DS ? 2 : 1;          // image-grid taps per axis
+    int Yi[2] = {y, y}, Xi[2] = {x, x};
+    float wy[2] = {1.0f, 0.0f}, wx[2] = {1.0f, 0.0f};
+    float thi = a.hi, tlo = a.lo;
+    if (DS) {
+        src_index_r(y, a.H, a.dy, Yi[0], Yi[1], wy[0], wy[1]);
+        src_index_r(x, a.W, a.dx, Xi[0], Xi[1], wx[0], wx[1]);
+        thi = blend4(thi, thi, thi, thi, wy[0], wy[1], wx[0], wx[1]);       // the constant plane goes through the same resize
+        tlo = blend4(tlo, tlo, tlo, tlo, wy[0], wy[1], wx[0], wx[1]);
+    }
+    int cy0[2], cy1[2], cx0[2], cx1[2];
+    float ly0[2], ly1[2], lx0[2], lx1[2];
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+        src_index_r(Yi[i], S, a.cy, cy0[i], cy1[i], ly0[i], ly1[i]);
+        src_index_r(Xi[i], S, a.cx, cx0[i], cx1[i], lx0[i], lx1[i]);
+    }
+    float mc = -INFINITY;
+    int live = 0;
+    for (int c = 0; c < a.C && live < nk; c++) {
+        const float l = a.cls[c];
+        if (l == 0.0f) continue;
+        const float *pl = a.cams[g] + c * ss;
+        float v;
+        if (DS) {
+            float u[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) u[i][j] = l * bilerp(pl, S, cy0[i], cy1[i], cx0[j], cx1[j], ly0[i], ly1[i], lx0[j], lx1[j]);
+            v = blend4(u[0][0], u[0][1], u[1][0], u[1][1], wy[0], wy[1], wx[0], wx[1]);
+        } else {
+            v = l * bilerp(pl, S, cy0[0], cy1[0], cx0[0], cx1[0], ly0[0], ly1[0], lx0[0], lx1[0]);
+        }
+        live++;
+        Phi[(size_t)live * hw] = v;
+        mc = v > mc ? v : mc;
+    }
+    const float mhi = mc > thi ? mc : thi, mlo = mc > tlo ? mc : tlo;
+    const float ehi0 = spec_expf(thi - mhi), elo0 = spec_expf(tlo - mlo);
+    float shi = 0.0f + ehi0, slo = 0.0f + elo0;
+    for (int k = 1; k <= live; k++) {
+        const float v = Phi[(size_t)k * hw];
+        shi = shi + spec_expf(v - mhi);
+        slo = slo + spec_expf(v - mlo);
+    }
+    Phi[0] = ehi0 / shi;
+    Plo[0] = elo0 / slo;
+    for (int k = 1; k <= live; k++) {
+        const float v = Phi[(size_t)k * hw];
+        Phi[(size_t)k * hw] = spec_expf(v - mhi) / shi;
+        Plo[(size_t)k * hw] = spec_expf(v - mlo) / slo;
+    }
+    for (int k = live + 1; k <= nk; k++) {          // K_live above the label row's count: planes that can never win the argmax
+        Phi[(size_t)k * hw] = 0.0f;
+        Plo[(size_t)k * hw] = 0.0f;
+    }
+}
+
+// planes [n,H,W] -> [n,h,w] by spec R (the [0,1] image onto the PAR grid)
+__global__ __launch_bounds__(256) void resize_planes_r_kernel(const float *__restrict__ src, float *__restrict__ dst, int planes, int H, int W,
+                                                             int h, int w, float sy, float sx)
+{
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= h * w) return;
+    const int y = pix / w, x = pix - y * w;
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+    src_index_r(y, H, sy, y0, y1, ly0, ly1);
+    src_index_r(x, W, sx, x0, x1, lx0, lx1);
+    for (int p = 0; p < planes; p++)
+        dst[(size_t)p * h * w + pix] = bilerp(src + (size_t)p * H * W, W, y0, y1, x0, x1, ly0, ly1, lx0, lx1);
+}
+
+// Refined stacks -> label bytes.  A thread owns four pixels of a row (one dword of each map), as export_maps_kernel; the key of a plane
+// is found by walking the label row in the order the softmax kernel numbered the planes.  P == nullptr: no present class, all zero.
+__global__ __launch_bounds__(256) void refine_merge_kernel(const RefineArgs a, const float *__restrict__ P)
+{
+    const int W4 = (a.W + 3) >> 2;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.H * W4) return;
+    const int Y = t / W4, X = (t - Y * W4) * 4;
+    const int W = a.W, w = a.w, nk = a.K1 - 1;
+    const size_t hw = (size_t)a.h * w;
+    const bool dword_ok = (W & 3) == 0;
+    if (!P) {
+        const uint8_t z[4] = {0, 0, 0, 0};
+        for (int g = 0; g < a.sets; g++) store_u8x4(a.out[g] + (size_t)Y * W, X, W, z, dword_ok);
+        return;
+    }
+    int y0, y1, x0[4], x1[4];
+    float ly0, ly1, lx0[4], lx1[4];
+    src_index_r(Y, a.h, a.uy, y0, y1, ly0, ly1);
+#pragma unroll
+    for (int k = 0; k < 4; k++) src_index_r(X + k < W ? X + k : W - 1, w, a.ux, x0[k], x1[k], lx0[k], lx1[k]);
+    for (int g = 0; g < a.sets; g++) {
+        int key[2][4];
+        for (int half = 0; half < 2; half++) {
+            const float *Pb = P + (size_t)(2 * g + half) * a.K1 * hw;
+            float best[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                best[k] = bilerp(Pb, w, y0, y1, x0[k], x1[k], ly0, ly1, lx0[k], lx1[k]);
+                key[half][k] = 0;
+            }
+            int live = 0;
+            for (int c = 0; c < a.C && live < nk; c++) {
+                if (a.cls[c] == 0.0f) continue;
+                live++;
+                const float *pl = Pb + (size_t)live * hw;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float v = bilerp(pl, w, y0, y1, x0[k], x1[k], ly0, ly1, lx0[k], lx1[k]);
+                    if (v > best[k]) { best[k] = v; key[half][k] = c + 1; }          // first maximum wins
+                }
+            }
+        }
+        uint8_t m[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) m[k] = key[0][k] ? (uint8_t)key[0][k] : (key[1][k] ? (uint8_t)a.ignore : (uint8_t)0);
+        store_u8x4(a.out[g] + (size_t)Y * W, X, W, m, dword_ok);
+    }
+}
+
+__global__ __launch_bounds__(256) void spec_expf_kernel(const float *__restrict__ x, float *__restrict__ y, long long n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = spec_expf(x[i]);
+}
+
 }  // namespace
 }  // namespace cosa
 
@@ -283,19 +455,20 @@ extern "C" int cosa_confusion_hist(const uint8_t *gt, const uint8_t *pred, size_
     return COSA_OK;
 }
 
-// One definition of the record for the device and the host: offsets[i] (bytes, 16-byte aligned) of product i in the order of the
-// COSA_EXPORT_* bits (seg, pseudo, pseudo_aux, rawcam, rawcam_aux, rawcam_idx, rawcam_aux_idx); (size_t)-1 for a product not asked for.
-// Returns the record's size, or 0 on bad arguments.
+// One definition of the record for the device and the host: offsets[i] (bytes, 16-byte aligned) of product i in the order seg, pseudo,
+// pseudo_aux, rawcam, rawcam_aux, rawcam_idx, rawcam_aux_idx, pseudo_par, pseudo_aux_par; (size_t)-1 for a product not asked for.  The
+// PAR products come last, so a record without them is laid out as before they existed.  Returns the record's size, or 0 on bad arguments.
 extern "C" size_t cosa_export_record_layout(int C, int H, int W, int K_live, unsigned what, size_t *offsets)
 {
-    if (!offsets || C < 1 || C >= 255 || H < 1 || W < 1 || K_live < 0 || K_live > C || (what & ~(unsigned)COSA_EXPORT_ALL) || !what) {
+    if (!offsets || C < 1 || C >= 255 || H < 1 || W < 1 || K_live < 0 || K_live > C || (what & ~(unsigned)COSA_EXPORT_EVERY) || !what) {
         set_error("cosa_export_record_layout: bad arguments (C %d, H %d, W %d, K_live %d, what 0x%x)", C, H, W, K_live, what);
         return 0;
     }
     const size_t hw = (size_t)H * W;
-    const size_t sizes[COSA_EXPORT_SLOTS] = {hw, hw, hw, hw * K_live * 4, hw * K_live * 4, (size_t)K_live * 4, (size_t)K_live * 4};
+    const size_t sizes[COSA_EXPORT_SLOTS] = {hw, hw, hw, hw * K_live * 4, hw * K_live * 4, (size_t)K_live * 4, (size_t)K_live * 4, hw, hw};
     const unsigned bits[COSA_EXPORT_SLOTS] = {COSA_EXPORT_SEG, COSA_EXPORT_PSEUDO, COSA_EXPORT_PSEUDO_AUX, COSA_EXPORT_RAWCAM,
-                                              COSA_EXPORT_RAWCAM_AUX, COSA_EXPORT_RAWCAM, COSA_EXPORT_RAWCAM_AUX};
+                                              COSA_EXPORT_RAWCAM_AUX, COSA_EXPORT_RAWCAM, COSA_EXPORT_RAWCAM_AUX,
+                                              COSA_EXPORT_PSEUDO_PAR, COSA_EXPORT_PSEUDO_AUX_PAR};
     size_t off = 0;
     for (int i = 0; i < COSA_EXPORT_SLOTS; i++) {
         if (what & bits[i]) {
@@ -337,6 +510,125 @@ extern "C" int cosa_export_maps(const float *cam, const float *cam_aux, const fl
     a.sy = (float)S / (float)H; a.sx = (float)S / (float)W; a.hi = high_thre; a.lo = low_thre; a.ignore = ignore_index;
     const int threads = H * ((W + 3) / 4);
     hipLaunchKernelGGL(export_maps_kernel, dim3((threads + 255) / 256), dim3(256), 0, as_stream(stream), a);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+// ---- PAR-refined pseudo labels ------------------------------------------------------------------------------------------------------
+namespace {
+inline int refine_sets(unsigned what) { return ((what & COSA_EXPORT_PSEUDO_PAR) ? 1 : 0) + ((what & COSA_EXPORT_PSEUDO_AUX_PAR) ? 1 : 0); }
+}
+
+// workspace of cosa_export_refine: P | P2 ([2 * sets][K_live + 1][h * w] each) | image on the PAR grid [3][h * w] | aff [8 n_dil][h * w];
+// 0 on bad arguments
+extern "C" size_t cosa_export_refine_workspace_bytes(int H, int W, int K_live, unsigned what, int downscale, int n_dil)
+{
+    const int sets = refine_sets(what);
+    if (H < 1 || W < 1 || K_live < 0 || K_live >= 255 || !sets || (downscale != 0 && downscale != 2) || n_dil < 1 || n_dil > kMaxDil) {
+        set_error("cosa_export_refine_workspace_bytes: bad arguments (H %d, W %d, K_live %d, what 0x%x, downscale %d, n_dil %d)", H, W, K_live,
+                  what, downscale, n_dil);
+        return 0;
+    }
+    const size_t hw = (size_t)(downscale ? H / 2 : H) * (size_t)(downscale ? W / 2 : W);
+    const size_t stack = align_up((size_t)2 * sets * (K_live + 1) * hw * sizeof(float), 256);
+    return 2 * stack + align_up(3 * hw * sizeof(float), 256) + align_up((size_t)n_dil * 8 * hw * sizeof(float), 256);
+}
+
+// image [3,H,W] in [0,1] (cosa_denormalize_img), cam / cam_aux [C,S,S], cls_label [C] with exactly K_live non-zero entries.  `what` is
+// the mask the record was laid out with; only the slots of COSA_EXPORT_PSEUDO_PAR / _AUX_PAR are written.
+extern "C" int cosa_export_refine(const float *image, const float *cam, const float *cam_aux, const float *cls_label, int C, int S, int H,
+                                  int W, int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, int downscale,
+                                  const int *dilations, int n_dil, int par_iters, void *record, size_t record_bytes, void *workspace,
+                                  size_t workspace_bytes, void *stream)
+{
+    const int sets = refine_sets(what);
+    COSA_REQUIRE(record && what && !(what & ~(unsigned)COSA_EXPORT_EVERY) && sets, "cosa_export_refine: bad arguments (what 0x%x names no PAR product)", what);
+    COSA_REQUIRE(image && cls_label && workspace, "cosa_export_refine: the image, the image-level label row and a workspace are needed");
+    COSA_REQUIRE(C > 0 && C < 255 && S > 0, "cosa_export_refine: C must be in 1..254 and S >= 1 (got C %d, S %d)", C, S);
+    COSA_REQUIRE(H >= COSA_EXPORT_REFINE_MIN_SIDE && W >= COSA_EXPORT_REFINE_MIN_SIDE && (size_t)H * W < 0x7fffffffull,
+                 "cosa_export_refine: size %d x %d outside the envelope (each side >= %d)", H, W, COSA_EXPORT_REFINE_MIN_SIDE);
+    COSA_REQUIRE(ignore_index >= 0 && ignore_index <= 255, "cosa_export_refine: ignore_index %d does not fit a byte", ignore_index);
+    COSA_REQUIRE(downscale == 0 || downscale == 2, "cosa_export_refine: downscale must be 0 or 2 (got %d)", downscale);
+    COSA_REQUIRE(dilations && n_dil >= 1 && n_dil <= kMaxDil, "cosa_export_refine: PAR takes 1..%d dilations (got %d)", kMaxDil, n_dil);
+    COSA_REQUIRE(par_iters >= 0, "cosa_export_refine: par_iters < 0");
+    COSA_REQUIRE(!(what & COSA_EXPORT_PSEUDO_PAR) || cam, "cosa_export_refine: main-CAM product without the main CAM");
+    COSA_REQUIRE(!(what & COSA_EXPORT_PSEUDO_AUX_PAR) || cam_aux, "cosa_export_refine: auxiliary-CAM product without the auxiliary CAM");
+    COSA_REQUIRE(K_live >= 0 && K_live <= C, "cosa_export_refine: K_live %d outside 0..C", K_live);
+    COSA_REQUIRE(((size_t)record & 15) == 0, "cosa_export_refine: the record must be 16-byte aligned");
+    size_t off[COSA_EXPORT_SLOTS];
+    const size_t need = cosa_export_record_layout(C, H, W, K_live, what, off);
+    COSA_REQUIRE(need && record_bytes >= need, "cosa_export_refine: record of %zu bytes, %zu needed", record_bytes, need);
+    const size_t ws_need = cosa_export_refine_workspace_bytes(H, W, K_live, what, downscale, n_dil);
+    if (!ws_need || workspace_bytes < ws_need) {
+        set_error("cosa_export_refine: workspace of %zu bytes, %zu needed", workspace_bytes, ws_need);
+        return COSA_ENOMEM;
+    }
+    ParPlan plan;
+    int rc = par_make_plan(dilations, n_dil, &plan);
+    if (rc) return rc;
+    hipStream_t st = as_stream(stream);
+    RefineArgs a;
+    a.sets = 0;
+    a.cams[1] = nullptr; a.out[1] = nullptr;
+    if (what & COSA_EXPORT_PSEUDO_PAR) { a.cams[a.sets] = cam; a.out[a.sets] = (uint8_t *)record + off[7]; a.sets++; }
+    if (what & COSA_EXPORT_PSEUDO_AUX_PAR) { a.cams[a.sets] = cam_aux; a.out[a.sets] = (uint8_t *)record + off[8]; a.sets++; }
+    a.cls = cls_label;
+    a.C = C; a.S = S; a.H = H; a.W = W; a.K1 = K_live + 1;
+    a.h = downscale ? H / 2 : H; a.w = downscale ? W / 2 : W;
+    a.cy = (float)S / (float)H; a.cx = (float)S / (float)W;
+    a.dy = (float)H / (float)a.h; a.dx = (float)W / (float)a.w;
+    a.uy = (float)a.h / (float)H; a.ux = (float)a.w / (float)W;
+    a.hi = high_thre; a.lo = low_thre; a.ignore = ignore_index;
+    const size_t hw = (size_t)a.h * a.w;
+    const int planes = 2 * a.sets * a.K1;
+    const dim3 gm((unsigned)((H * ((W + 3) / 4) + 255) / 256));
+    if (K_live == 0) {                       // no present class: cam2mask's softmax over the threshold plane alone names key 0 everywhere
+        a.P = nullptr;
+        hipLaunchKernelGGL(refine_merge_kernel, gm, dim3(256), 0, st, a, static_cast<const float *>(nullptr));
+        COSA_LAUNCH_CHECK();
+        return COSA_OK;
+    }
+    Carver cv(workspace);
+    float *P = cv.take<float>((size_t)planes * hw);
+    float *P2 = cv.take<float>((size_t)planes * hw);
+    float *img_lo = cv.take<float>(3 * hw);
+    float *aff = cv.take<float>((size_t)n_dil * 8 * hw);
+    a.P = P;
+    const dim3 gl((unsigned)((hw + 255) / 256), a.sets);
+    if (downscale)
+        hipLaunchKernelGGL(refine_softmax_kernel<2>, gl, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(refine_softmax_kernel<0>, gl, dim3(256), 0, st, a);
+    COSA_LAUNCH_CHECK();
+    const float *Pfinal = P;
+    if (par_iters > 0) {
+        const float *im = image;
+        if (downscale) {
+            hipLaunchKernelGGL(resize_planes_r_kernel, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, st, image, img_lo, 3, H, W, a.h, a.w,
+                               a.dy, a.dx);
+            COSA_LAUNCH_CHECK();
+            im = img_lo;
+        }
+        rc = par_launch_affinity(im, aff, 1, a.h, a.w, plan, st);          // once for the hi and lo stacks of every set
+        if (rc) return rc;
+        float *src = P, *dst = P2;
+        for (int it = 0; it < par_iters; it++) {
+            rc = par_launch_step(aff, src, dst, 1, planes, nullptr, 1, (size_t)planes * hw, a.h, a.w, plan, st);      // every plane is live
+            if (rc) return rc;
+            float *t = src; src = dst; dst = t;
+        }
+        Pfinal = src;
+    }
+    hipLaunchKernelGGL(refine_merge_kernel, gm, dim3(256), 0, st, a, Pfinal);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+// spec E as this translation unit computes it (test hook: y[i] = expf(x[i]))
+extern "C" int cosa_spec_expf(const float *x, float *y, long long n, void *stream)
+{
+    COSA_REQUIRE(x && y && n > 0 && n < (1ll << 31), "cosa_spec_expf: bad arguments");
+    hipLaunchKernelGGL(spec_expf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), x, y, n);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

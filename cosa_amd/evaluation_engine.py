@@ -197,12 +197,12 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
 # ---------------------------------------------------------------------------------------------------------------------------------
 # export: segmentation / pseudo-label PNGs and raw-CAM dictionaries
 # ---------------------------------------------------------------------------------------------------------------------------------
-EXPORT_PRODUCTS = tuple(seg_helper.EXPORT_BITS)                   # seg, pseudo, pseudo_aux, rawcam, rawcam_aux
+EXPORT_PRODUCTS = tuple(seg_helper.EXPORT_BITS)                   # seg, pseudo, pseudo_aux, rawcam, rawcam_aux, pseudo_par, pseudo_aux_par
 CAM_PRODUCTS = tuple(p for p in EXPORT_PRODUCTS if p != "seg")    # these need the image-level label row
 
 
 class _ExportSlot:
-    """one record in flight: the device record `cosa_export_maps` writes, its pinned host copy, the event that says the copy is done
+    """one record in flight: the device record `cosa_export_maps` / `cosa_export_refine` write, its pinned host copy, the event that says the copy is done
     and the writer job that still reads the host copy"""
 
     def __init__(self, device):
@@ -250,13 +250,19 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     `out_dir` (layout: utils/export_io.py).  The forward is evaluate()'s: resize to crop_size, the captured multi-scale pass, groups of
     `eval_group` items, batch-invariant heads -- what is written is what evaluate() scores.  `what`: out of EXPORT_PRODUCTS;
     `getcrf` adds `seg_crf` (the lines of evaluate()'s Seg_crf row).  Thresholds default to args.high_thre / args.low_thre.
+    `pseudo_par` / `pseudo_aux_par` are the labels CoSA trains on: cam2mask with PAR(num_iter=10, dilations=[1,2,4,8,12,24]) at
+    `args.par_downscale` (2 or 0) on the image's own size (seg_helper.export_refine), into the same record as the other products.
     Returns {"images", "seconds", "img_per_s", "bytes_written"} of this process."""
     what = tuple(what)
     mask = seg_helper.export_what_mask(what)
     writers = export_io.check_writers(writers)
     if getattr(args, "usepar", False):
-        raise NotImplementedError("export_predictions: PAR-refined export (--usepar) is not built: the fused cosa_cam2mask refines square "
-                                  "S x S maps only")
+        raise NotImplementedError("export_predictions: `usepar` does not select an export product; the PAR-refined labels are the products "
+                                  "pseudo_par / pseudo_aux_par (--what pseudo_par)")
+    par_mask = mask & seg_helper.EXPORT_PAR_MASK
+    par_downscale = int(getattr(args, "par_downscale", 2) or 0)
+    if par_mask and par_downscale not in (0, 2):
+        raise ValueError(f"export_predictions: pseudo_par / pseudo_aux_par are built for par_downscale 2 and 0 (got {par_downscale})")
     high_thre = float(args.high_thre if high_thre is None else high_thre)
     low_thre = float(args.low_thre if low_thre is None else low_thre)
     ignore_index = int(getattr(args, "ignore_index", 255))
@@ -284,7 +290,7 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
             slot.event.synchronize()                # in the writer thread: the loop itself never waits for a copy
             rec = slot.host.numpy()
             v = seg_helper.export_record_views(rec, C, H, W, k_live, item_mask)
-            out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux") if p in v}
+            out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par") if p in v}
             for p in ("rawcam", "rawcam_aux"):
                 if p in v:
                     out[p] = (v[p], v[p + "_idx"])
@@ -307,8 +313,14 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 crf_off, total = nbytes, nbytes + ((H * W + 15) & ~15)
             slot = slots[count % len(slots)]
             slot.reserve(total)
-            seg_helper.export_maps(cams[i] if item_mask & 0x0a else None, cams_aux[i] if item_mask & 0x14 else None, seg_ps[i], cls_dev, (H, W),
-                                   item_mask, high_thre, low_thre, ignore_index=ignore_index, out=slot.dev, k_live=k_live)
+            maps_mask = item_mask & seg_helper.EXPORT_MAPS_MASK
+            if maps_mask:
+                seg_helper.export_maps(cams[i] if maps_mask & 0x0a else None, cams_aux[i] if maps_mask & 0x14 else None, seg_ps[i], cls_dev, (H, W),
+                                       maps_mask, high_thre, low_thre, ignore_index=ignore_index, out=slot.dev, k_live=k_live)
+            if item_mask & seg_helper.EXPORT_PAR_MASK:          # the PAR slots lie behind the others: the same record, the same one copy
+                seg_helper.export_refine(torch_helper.denormalize_img(img_org), cams[i] if item_mask & 0x20 else None,
+                                         cams_aux[i] if item_mask & 0x40 else None, cls_dev, item_mask, high_thre, low_thre,
+                                         ignore_index=ignore_index, downscale=par_downscale, out=slot.dev, k_live=k_live)
             if getcrf:                              # evaluate()'s Seg_crf lines
                 rs = F.interpolate(seg_ps[i:i + 1], size=(H, W), mode='bilinear', align_corners=False)
                 vd = seg_helper.seg_validation(rs, cls_dev).softmax(dim=1)[0]
@@ -369,6 +381,8 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 "products": list(products), "high_thre": high_thre, "low_thre": low_thre, "ignore_index": ignore_index,
                 "crop_size": args.crop_size, "scales": EVAL_SCALES, "backbone": getattr(args, "backbone", None),
                 "num_classes": args.num_classes, "world_size": world}
+        if par_mask:
+            info["par"] = {"num_iter": seg_helper.PAR_NUM_ITER, "dilations": list(seg_helper.PAR_DILATIONS), "downscale": par_downscale}
         info.update(settings or {})
         export_io.write_manifest_file(out_dir, info, images)
     return {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,

@@ -1,10 +1,11 @@
 """Write a trained model's predictions as files:
 
     python -m cosa_amd.predict NAME --checkpoint best_seg.pth --dataset VOC12 --voc12_root $VOC --split val|test|train|train_aug \
-        --out DIR --what seg[,pseudo,pseudo_aux,rawcam,rawcam_aux] [--crf] [--high_thre H --low_thre L] [--writers N]
+        --out DIR --what seg[,pseudo,pseudo_aux,pseudo_par,pseudo_aux_par,rawcam,rawcam_aux] [--crf] [--high_thre H --low_thre L] [--writers N]
 
 Segmentation PNGs of `val` / `test` (what the VOC evaluation server takes), pseudo-label PNGs of `train_aug` / `train` for a second-stage
-network, raw CAMs as `.npy` dictionaries.  Every flag of the training launcher is accepted (cosa_amd/args.py: `--backbone`,
+network (`pseudo`: thresholds only; `pseudo_par`: refined by PAR(num_iter=10, dilations=[1,2,4,8,12,24]) at `--par_downscale` 2 or 0, the
+labels CoSA itself trains on), raw CAMs as `.npy` dictionaries.  Every flag of the training launcher is accepted (cosa_amd/args.py: `--backbone`,
 `--crop_size`, `--num_classes`, `--name_list_dir`, ...); the thresholds default to the run's `--high_thre` / `--low_thre`.  The
 checkpoint is loaded strictly, as `finaleval` loads it.  `--split test` has no ground truth and no image-level labels: `seg` only.
 Under `torchrun` the images are sharded over the ranks (`index % world == rank`), each written exactly once; rank 0 writes
@@ -16,7 +17,7 @@ import sys
 from . import args as cosa_args
 from .utils.export_io import MAX_WRITERS
 
-PRODUCTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux")
+PRODUCTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "pseudo_par", "pseudo_aux_par")
 SPLITS = ("val", "test", "train", "train_aug")
 
 
@@ -49,7 +50,9 @@ def parse(argv=None):
     if not 1 <= args.writers <= MAX_WRITERS:
         parser.error(f"--writers must be in 1..{MAX_WRITERS} (got {args.writers})")
     if args.usepar:
-        parser.error("--usepar true: PAR-refined export is not built (the fused cam2mask kernel refines square S x S maps only)")
+        parser.error("--usepar true does not select an export product: ask for the PAR-refined labels with --what pseudo_par[,pseudo_aux_par]")
+    if any(w.endswith("_par") for w in what) and args.par_downscale not in (0, 2):
+        parser.error(f"--par_downscale must be 2 or 0 for --what pseudo_par / pseudo_aux_par (got {args.par_downscale})")
     if args.eval_group < 1:
         parser.error("--eval_group must be >= 1")
     if args.dataset == "COCO" and args.split in ("test", "train_aug"):

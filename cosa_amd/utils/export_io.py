@@ -3,7 +3,8 @@
 Pure numpy / PIL: nothing here touches the GPU.  `evaluation_engine.export_predictions` hands finished host records to a
 `PredictionWriter`; its threads encode and write
 
-    <out_dir>/seg|seg_crf|pseudo|pseudo_aux/<name>.png      palette PNGs (mode P) with the PASCAL VOC colour map
+    <out_dir>/seg|seg_crf|pseudo|pseudo_aux|pseudo_par|pseudo_aux_par/<name>.png
+                                                            palette PNGs (mode P) with the PASCAL VOC colour map
     <out_dir>/camraw|camraw_aux/<name>.npy                  a pickled dict {0-based class index: float32 [H,W]} (np.load(...,
                                                             allow_pickle=True).item()), as the reference's save_cam_npv2 writes it;
                                                             an image without any present class gets no file
@@ -19,7 +20,7 @@ import numpy as np
 from PIL import Image
 
 MAX_WRITERS = 8                      # a GPU job has 16 CPUs: loader workers and the main thread need the rest
-PNG_PRODUCTS = ("seg", "seg_crf", "pseudo", "pseudo_aux")
+PNG_PRODUCTS = ("seg", "seg_crf", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par")
 NPY_DIRS = {"rawcam": "camraw", "rawcam_aux": "camraw_aux"}
 
 

@@ -230,8 +230,13 @@ def eval_label_maps(cam, seg, cls_label, size, bkg_thre):
     return lc, lp, lv
 
 
-EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16}          # COSA_EXPORT_* of include/cosa_hip.h
-_EXPORT_SLOTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "rawcam_idx", "rawcam_aux_idx")
+EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16,          # COSA_EXPORT_* of include/cosa_hip.h
+               "pseudo_par": 32, "pseudo_aux_par": 64}
+_EXPORT_SLOTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "rawcam_idx", "rawcam_aux_idx", "pseudo_par", "pseudo_aux_par")
+EXPORT_MAPS_MASK = 31                                    # the products cosa_export_maps writes; cosa_export_refine writes the PAR ones
+EXPORT_PAR_MASK = EXPORT_BITS["pseudo_par"] | EXPORT_BITS["pseudo_aux_par"]
+EXPORT_REFINE_MIN_SIDE = 16                              # COSA_EXPORT_REFINE_MIN_SIDE
+PAR_DILATIONS, PAR_NUM_ITER = (1, 2, 4, 8, 12, 24), 10   # the refine model CoSA trains with (main.py: PAR(num_iter=10, dilations=[1,2,4,8,12,24]))
 
 
 def export_what_mask(what):
@@ -278,9 +283,12 @@ def export_maps(cam, cam_aux, seg, cls_label, size, what, high_thre, low_thre, i
     None (no image-level labels: "seg" only, the plain argmax).  `what`: names out of seg, pseudo, pseudo_aux, rawcam, rawcam_aux.
     `out`: a caller-owned uint8 device record to write into (at least the layout's size); `k_live`: the number of present classes when the
     caller knows it on the host -- without it the label row is counted here, which waits for the device.
-    Returns views into the record (export_record_views): uint8 [H,W] maps, rawcam* float32 [k_live,H,W], rawcam*_idx int32 [k_live]."""
+    Returns views into the record (export_record_views): uint8 [H,W] maps, rawcam* float32 [k_live,H,W], rawcam*_idx int32 [k_live].
+    The PAR-refined products are export_refine's, not this function's."""
     H, W = int(size[0]), int(size[1])
     mask = export_what_mask(what)
+    if mask & EXPORT_PAR_MASK:
+        raise ValueError("export_maps: pseudo_par / pseudo_aux_par are written by export_refine")
     ref = seg if seg is not None else (cam if cam is not None else cam_aux)
     if ref is None:
         raise ValueError("export_maps: no input maps")
@@ -306,6 +314,50 @@ def export_maps(cam, cam_aux, seg, cls_label, size, what, high_thre, low_thre, i
                                        float(high_thre if high_thre is not None else 0.0), float(low_thre if low_thre is not None else 0.0),
                                        int(ignore_index), _C.ptr(out), out.numel(), _C.stream_ptr()), "cosa_export_maps")
     return export_record_views(out, C, H, W, k_live, mask)
+
+
+def export_refine(image, cam, cam_aux, cls_label, what, high_thre, low_thre, ignore_index=255, downscale=2, dilations=PAR_DILATIONS,
+                  num_iter=PAR_NUM_ITER, out=None, k_live=None):
+    """The PAR-refined pseudo labels of ONE image at its own size (cosa_export_refine): the reference's
+    `cam2mask(image, [[0,H,0,W]], cls * resize(cam, (H,W)), cls, high, low, refine_model=PAR(num_iter, dilations), downscale)` for the
+    main and / or the auxiliary CAMs in one pass -- one affinity tensor, one stream of it per propagation step.
+    image [1,3,H,W] / [3,H,W] in [0,1] (torch_helper.denormalize_img), cam / cam_aux [1,C,S,S] or [C,S,S], cls_label [1,C] / [C].
+    `what`: the products of the record (`out`, as export_maps lays it out), at least one of pseudo_par, pseudo_aux_par; only those two
+    slots are written.  downscale 2 or 0; H, W >= EXPORT_REFINE_MIN_SIDE.  Returns {product: uint8 [H,W] view} of the PAR products."""
+    mask = export_what_mask(what)
+    if not mask & EXPORT_PAR_MASK:
+        raise ValueError(f"export_refine: `what` names neither pseudo_par nor pseudo_aux_par (got {what})")
+    if image is None or cls_label is None:
+        raise _C.CosaError("export_refine: the image and the image-level label row are needed")
+    _C.require_cuda(image, cam, cam_aux, cls_label, out)
+    if image.dim() not in (3, 4) or image.numel() != 3 * image.shape[-2] * image.shape[-1] or image.shape[-3] != 3:
+        raise ValueError(f"export_refine: image must be one image's [3,H,W], got {tuple(image.shape)}")
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    prep = lambda t: t.contiguous().float() if t is not None else None
+    image, cam, cam_aux, cls = prep(image), prep(cam), prep(cam_aux), prep(cls_label)
+    C = cls.numel()
+    ref = cam if cam is not None else cam_aux
+    if ref is None:
+        raise _C.CosaError("export_refine: no CAM given")
+    S = ref.shape[-1]
+    for t, nm in ((cam, "cam"), (cam_aux, "cam_aux")):
+        if t is not None and (t.numel() != C * S * S or tuple(t.shape[-3:]) != (C, S, S)):
+            raise ValueError(f"export_refine: {nm} must be one image's [{C},{S},{S}], got {tuple(t.shape)}")
+    if k_live is None:
+        k_live = int((cls != 0).sum())
+    offs, nbytes = export_record_layout(C, H, W, k_live, mask)
+    if out is None:
+        out = torch.empty(nbytes, device=image.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes:
+        raise ValueError(f"export_refine: `out` must be a contiguous uint8 record of at least {nbytes} bytes")
+    L = _C.lib()
+    dil = [int(d) for d in dilations]
+    need = L.cosa_export_refine_workspace_bytes(H, W, int(k_live), mask, int(downscale or 0), len(dil))
+    ws = _C.workspace(need, image.device, "export_par")        # need == 0: arguments the entry itself refuses, with its own message
+    _C.check(L.cosa_export_refine(_C.ptr(image), _C.ptr(cam), _C.ptr(cam_aux), _C.ptr(cls), C, S, H, W, int(k_live), mask, float(high_thre),
+                                  float(low_thre), int(ignore_index), int(downscale or 0), _C.int_array(dil), len(dil), int(num_iter),
+                                  _C.ptr(out), out.numel(), _C.ptr(ws), ws.numel(), _C.stream_ptr()), "cosa_export_refine")
+    return {k: out[o:o + H * W].reshape(H, W) for k, o in offs.items() if k in ("pseudo_par", "pseudo_aux_par")}
 
 
 # --------------------------------------------------------------------------------------------

@@ -541,9 +541,11 @@ int cosa_confusion_hist(const uint8_t *gt, const uint8_t *pred, size_t n, int nu
  *   PSEUDO(_AUX) uint8 [H,W]  v = cls * resized CAM; m = max over present classes: m > high_thre -> class + 1, else
  *                             m > low_thre -> ignore_index, else 0 (cam2mask without refine model, whole image box)
  *   RAWCAM(_AUX) fp32 [K_live,H,W] + int32 [K_live]: the planes v of the present classes in class order and their indices
+ *   PSEUDO_PAR / PSEUDO_AUX_PAR uint8 [H,W]  the PAR-refined labels CoSA trains on, written by cosa_export_refine (below)
  * K_live = number of non-zero entries of cls_label (the host knows it: it sizes the record).
  * cosa_export_record_layout: offsets[COSA_EXPORT_SLOTS] (bytes from the record's start, each 16-byte aligned; (size_t)-1
- * when not asked for) in the order seg, pseudo, pseudo_aux, rawcam, rawcam_aux, rawcam indices, rawcam_aux indices;
+ * when not asked for) in the order seg, pseudo, pseudo_aux, rawcam, rawcam_aux, rawcam indices, rawcam_aux indices,
+ * pseudo_par, pseudo_aux_par (the PAR slots come last: a record without them is laid out as if they did not exist);
  * returns the record's size in bytes, 0 on bad arguments.  Host and device use this one definition.
  * ------------------------------------------------------------------------------------- */
 #define COSA_EXPORT_SEG 1u
@@ -551,12 +553,35 @@ int cosa_confusion_hist(const uint8_t *gt, const uint8_t *pred, size_t n, int nu
 #define COSA_EXPORT_PSEUDO_AUX 4u
 #define COSA_EXPORT_RAWCAM 8u
 #define COSA_EXPORT_RAWCAM_AUX 16u
-#define COSA_EXPORT_ALL 31u
-#define COSA_EXPORT_SLOTS 7
+#define COSA_EXPORT_ALL 31u               /* what cosa_export_maps writes */
+#define COSA_EXPORT_PSEUDO_PAR 32u
+#define COSA_EXPORT_PSEUDO_AUX_PAR 64u
+#define COSA_EXPORT_EVERY 127u
+#define COSA_EXPORT_SLOTS 9
+#define COSA_EXPORT_REFINE_MIN_SIDE 16    /* smallest H and W cosa_export_refine takes */
 size_t cosa_export_record_layout(int C, int H, int W, int K_live, unsigned what, size_t *offsets);
 int cosa_export_maps(const float *cam, const float *cam_aux, const float *seg, const float *cls_label, int C, int S, int H, int W,
                      int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, void *record,
                      size_t record_bytes, void *stream);
+
+/* PAR-refined pseudo labels of ONE image at its own H x W into the record's PSEUDO_PAR / PSEUDO_AUX_PAR slots (nothing else is
+ * written; `what` is the mask the record was laid out with and must name at least one of the two).  The reference's
+ *   cam2mask(images=image, img_boxes=[[0,H,0,W]], cams=cls * resize(cam, (H,W)), cls_labels, high, low,
+ *            refine_model=PAR(par_iters, dilations), ignore_index, downscale)
+ * (utils/seg_helper.py:721-797) read literally at H != W: PAR grid (H/2, W/2) (integer division; downscale 0: (H, W)), the
+ * threshold plane is key 0, softmax over the present classes, every resize bilinear align_corners=False by spec R, exp by spec E,
+ * first maximum wins, m = hi; m[hi == 0] = ignore; m[hi + lo == 0] = 0.  image: [3,H,W] in [0,1] (cosa_denormalize_img);
+ * cls_label must hold exactly K_live non-zero entries; K_live == 0 gives all-zero maps.  downscale: 0 or 2; 1..8 dilations;
+ * H, W >= COSA_EXPORT_REFINE_MIN_SIDE (smaller sizes are refused, nothing is clamped).  The affinity tensor is built once and
+ * streamed once per step for the hi and lo stacks of both CAM sets.  Workspace: cosa_export_refine_workspace_bytes (0 on bad
+ * arguments); too small a workspace is COSA_ENOMEM. */
+size_t cosa_export_refine_workspace_bytes(int H, int W, int K_live, unsigned what, int downscale, int n_dil);
+int cosa_export_refine(const float *image, const float *cam, const float *cam_aux, const float *cls_label, int C, int S, int H, int W,
+                       int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, int downscale,
+                       const int *dilations, int n_dil, int par_iters, void *record, size_t record_bytes, void *workspace,
+                       size_t workspace_bytes, void *stream);
+/* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
+int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
 #ifdef __cplusplus
 }

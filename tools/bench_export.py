@@ -1,11 +1,15 @@
 """Rate of prediction export next to evaluate() on the same loader.
 
-    python tools/bench_export.py --mode evaluate|seg|all_crf [--writers N] [--items 200] [--out profiles/r08_export.json]
+    python tools/bench_export.py --mode evaluate|seg|all_crf|pseudo|pseudo_par|refine_time [--writers N] [--items 200] [--out FILE]
 
 One mode per process (run each under its own time limit); the result is merged into the JSON file under the key `evaluate` or
 `<mode>_w<writers>`.  The loader is synthetic: `--items` images of VOC-like sizes (around 375 x 500, both orientations) with two
 present classes each, a seeded ViT-B/16 CoSA network at crop_size 448.  evaluate() is the comparison point: the same forward, the label
-maps folded into confusion matrices on the device instead of being copied out and encoded."""
+maps folded into confusion matrices on the device instead of being copied out and encoded.
+`pseudo` (seg,pseudo,pseudo_aux) and `pseudo_par` (seg,pseudo_par,pseudo_aux_par) are the pair that shows what PAR refinement costs an
+export run.  `refine_time` is no export run: the device time per image of `seg_helper.export_refine` (both CAM sets) against the generic
+way to the same two maps -- two `_cam2mask_generic(..., refine_model=PAR(...))` calls on resized, validated CAMs -- interleaved in one
+process after warm-up, HIP events around each call, median over `--reps` repetitions per size."""
 import argparse
 import json
 import os
@@ -35,9 +39,62 @@ def loader(n, C, seed=0):
     return [(f"item_{i:04d}",) + base[i % len(base)] for i in range(n)]
 
 
+def refine_time(reps, warmup=5):
+    """per size: median device ms of the fused path and of the generic path, same inputs, calls interleaved"""
+    import torch.nn.functional as F
+    from cosa_amd.models.PAR import PAR
+    from cosa_amd.utils import seg_helper, torch_helper
+    par = PAR(num_iter=seg_helper.PAR_NUM_ITER, dilations=list(seg_helper.PAR_DILATIONS))
+    C, S, hi, lo = 20, 448, 0.7, 0.25
+    rng = np.random.default_rng(0)
+    rows = []
+    for (H, W) in sorted(set(SIZES)):
+        img01 = torch_helper.denormalize_img(torch.from_numpy(rng.standard_normal((1, 3, H, W)).astype(np.float32)).cuda())
+        cam, aux = (torch.from_numpy(rng.random((C, S, S), dtype=np.float32)).cuda() for _ in range(2))
+        cls = torch.zeros(C, device="cuda")
+        cls[[3, 11]] = 1
+        rec = torch.empty(seg_helper.export_record_layout(C, H, W, 2, PAR_WHAT)[1], device="cuda", dtype=torch.uint8)
+
+        def fused():
+            return seg_helper.export_refine(img01, cam, aux, cls, PAR_WHAT, hi, lo, out=rec, k_live=2)
+
+        def generic():
+            out = []
+            for c in (cam, aux):
+                v = cls[None, :, None, None] * F.interpolate(c[None], size=(H, W), mode="bilinear", align_corners=False)
+                out.append(seg_helper._cam2mask_generic(img01, [[0, H, 0, W]], v, cls[None], hi, lo, par, 255, 2))
+            return out
+
+        times = {"fused": [], "generic": []}
+        for r in range(warmup + reps):
+            for name, fn in (("fused", fused), ("generic", generic)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                if r >= warmup:
+                    times[name].append(a.elapsed_time(b))
+        f, g = float(np.median(times["fused"])), float(np.median(times["generic"]))
+        rows.append({"H": H, "W": W, "fused_ms": f, "generic_ms": g, "ratio": g / f, "fused_ms_min_max": [min(times["fused"]), max(times["fused"])],
+                     "generic_ms_min_max": [min(times["generic"]), max(times["generic"])]})
+    return {"reps": reps, "warmup": warmup, "C": C, "S": S, "present": 2, "downscale": 2, "sizes": rows,
+            "fused_ms_mean_of_medians": float(np.mean([r["fused_ms"] for r in rows])),
+            "generic_ms_mean_of_medians": float(np.mean([r["generic_ms"] for r in rows])),
+            "ratio_of_means": float(np.mean([r["generic_ms"] for r in rows]) / np.mean([r["fused_ms"] for r in rows])),
+            "note": "device time between HIP events on the launch stream; the generic path's host-side Python (torch.nonzero, .tolist) "
+                    "waits for the device inside the interval, as it does in use"}
+
+
+PAR_WHAT = ("pseudo_par", "pseudo_aux_par")
+EXPORT_MODES = {"seg": (("seg",), False), "all_crf": (ALL, True), "pseudo": (("seg", "pseudo", "pseudo_aux"), False),
+                "pseudo_par": (("seg",) + PAR_WHAT, False)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("evaluate", "seg", "all_crf"), required=True)
+    ap.add_argument("--mode", choices=("evaluate",) + tuple(EXPORT_MODES) + ("refine_time",), required=True)
+    ap.add_argument("--reps", type=int, default=30, help="refine_time: timed repetitions per size")
     ap.add_argument("--writers", type=int, default=4)
     ap.add_argument("--items", type=int, default=200)
     ap.add_argument("--out", default=os.path.join("profiles", "r08_export.json"))
@@ -45,6 +102,11 @@ def main():
     from cosa_amd import evaluation_engine as ee
     from cosa_amd.models import build_model
     from cosa_amd.train_step import default_args
+    if opt.mode == "refine_time":
+        res = refine_time(opt.reps)
+        res["device"] = torch.cuda.get_device_name(0)
+        merge(opt.out, "refine_time", res)
+        return
     torch.manual_seed(0)
     args = default_args("VOC12", crop_size=448, batch_size=1)
     model = build_model(args).cuda().eval()
@@ -61,20 +123,24 @@ def main():
             dt = time.perf_counter() - t0
             res, key = {"images": len(items), "seconds": dt, "img_per_s": len(items) / dt}, "evaluate"
         else:
-            what, crf = (("seg",), False) if opt.mode == "seg" else (ALL, True)
+            what, crf = EXPORT_MODES[opt.mode]
             ee.export_predictions(model, warm, args, os.path.join(tmp, "warm"), what=what, getcrf=crf, writers=opt.writers)
             res = ee.export_predictions(model, items, args, os.path.join(tmp, "run"), what=what, getcrf=crf, writers=opt.writers)
             res["writers"], key = opt.writers, f"{opt.mode}_w{opt.writers}"
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     res["device"] = torch.cuda.get_device_name(0)
+    merge(opt.out, key, res)
+
+
+def merge(path, key, res):
     doc = {}
-    if os.path.exists(opt.out):
-        with open(opt.out) as f:
+    if os.path.exists(path):
+        with open(path) as f:
             doc = json.load(f)
     doc[key] = res
-    os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-    with open(opt.out, "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
     print(json.dumps({key: res}), flush=True)
