@@ -66,6 +66,11 @@ _SIGS = {
     "cosa_optim_record_bytes": (c_size_t, []),
     "cosa_optim_chunk_elems": (c_int, []),
     "cosa_fused_adamw_ema": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float, c_void_p]),
+    "cosa_state_record_bytes": (c_size_t, []),
+    "cosa_state_chunk_bytes": (c_size_t, []),
+    "cosa_state_layout": (c_size_t, [c_int, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+    "cosa_state_snapshot": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cosa_state_restore": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "cosa_add_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                        c_float, c_void_p]),
     "cosa_layernorm_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),

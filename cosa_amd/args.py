@@ -51,6 +51,10 @@ EXTRA = [
     ("teacher_precision", str, "auto"), # auto (fp16x3: train_step.resolve_teacher_precision) | bf16 | fp16 | bf16x3 | fp16x3 | fp16c8[-n[mk]|-xn[mk]] | fp16c4[...]: operand precision of the teacher's no-grad passes;
                                              # the default meets the 1e-3 / IoU 0.999 tolerance against the fp32 reference, bf16 (faster) does not
     ("log_iters", int, 20),
+    # full-state checkpoints (cosa_amd/checkpoint.py): bit-exact resumption
+    ("save_iters", int, 0),                  # write <output_dir>/state_<iteration>.cosa every N iterations; 0: never (nothing changes)
+    ("keep_states", int, 2),                 # complete state files kept; older ones go once a newer one is in place
+    ("resume", str, None),                   # a state file, or "auto": the newest complete state_*.cosa of the output directory, if any
 ]
 
 

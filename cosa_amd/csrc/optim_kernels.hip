@@ -97,6 +97,113 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorRec *__restr
     }
 }
 
+// ---- training-state snapshot / restore ---------------------------------------------------------------------
+// The same record-table + chunk-list pattern as above, over BYTES: every tensor that defines the future of a run (any dtype, contiguous)
+// is copied into its 16-byte-aligned, zero-padded slot of one contiguous arena (or back), and two 64-bit checksums per tensor are formed
+// over the slot's little-endian 32-bit words w_i: s0 = sum w_i, s1 = sum (i+1) w_i, both mod 2^64.  Integer addition commutes, so the
+// workgroup reduction + one atomicAdd pair per chunk gives the same bits in any order.
+// A tensor whose address is a multiple of 16 moves in 16-byte units, one that is only 4-byte aligned in 4-byte ones; any other address takes
+// sixteen single-byte accesses per unit for the WHOLE tensor.  Allocator-made tensors are always 16-byte aligned, so that path serves odd
+// views only; it is correct (tests/test_resume_gpu.py) and its throughput has not been measured.
+struct StateRec {
+    unsigned char *ptr;              // the tensor's bytes
+    unsigned long long nbytes;       // its size (slot = nbytes rounded up to 16, tail zero)
+    unsigned long long off;          // slot offset in the arena (cosa_state_layout)
+};
+
+constexpr unsigned long long kStateChunk = 262144;         // slot bytes per block
+constexpr int kStateMaxTensors = 4096;
+constexpr unsigned long long kStateMaxBytes = 1ull << 40;
+
+// MODE 0: tensor -> arena (snapshot); 1: arena -> checksums only (verify); 2: arena -> tensor (scatter)
+template <int MODE>
+__global__ __launch_bounds__(256) void state_kernel(const StateRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
+                                                    unsigned char *__restrict__ arena, unsigned long long *__restrict__ sums)
+{
+    const ChunkRec c = chunks[blockIdx.x];
+    const StateRec t = recs[c.tensor];
+    const unsigned long long slot = (t.nbytes + 15ull) & ~15ull;
+    const unsigned long long base = (unsigned long long)c.chunk * kStateChunk;
+    unsigned long long end = base + kStateChunk;
+    end = end < slot ? end : slot;
+    unsigned char *a = arena + t.off;                      // 16-byte aligned: the arena's base and every offset are
+    const unsigned mis = (unsigned)(reinterpret_cast<unsigned long long>(t.ptr) & 15ull);
+    unsigned long long s0 = 0, s1 = 0;
+    for (unsigned long long o = base + threadIdx.x * 16ull; o < end; o += 4096ull) {
+        const bool full = o + 16ull <= t.nbytes;
+        uint4 v;
+        if (MODE == 0) {
+            if (full && mis == 0) {
+                v = *reinterpret_cast<const uint4 *>(t.ptr + o);
+            } else if (full && (mis & 3u) == 0) {
+                const unsigned *s = reinterpret_cast<const unsigned *>(t.ptr + o);
+                v = make_uint4(s[0], s[1], s[2], s[3]);
+            } else {                                       // unaligned source or the slot's last, partly padded unit
+                unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int j = 0; j < 16; j++)
+                    if (o + j < t.nbytes) w[j >> 2] |= (unsigned)t.ptr[o + j] << (8 * (j & 3));
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            *reinterpret_cast<uint4 *>(a + o) = v;
+        } else {
+            v = *reinterpret_cast<const uint4 *>(a + o);
+            if (MODE == 2) {
+                if (full && mis == 0) {
+                    *reinterpret_cast<uint4 *>(t.ptr + o) = v;
+                } else if (full && (mis & 3u) == 0) {
+                    unsigned *d = reinterpret_cast<unsigned *>(t.ptr + o);
+                    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+                } else {
+                    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int j = 0; j < 16; j++)
+                        if (o + j < t.nbytes) t.ptr[o + j] = (unsigned char)(w[j >> 2] >> (8 * (j & 3)));
+                }
+            }
+        }
+        const unsigned long long i1 = (o >> 2) + 1ull;     // (index + 1) of the unit's first word
+        s0 += (unsigned long long)v.x + v.y + v.z + v.w;
+        s1 += i1 * v.x + (i1 + 1ull) * v.y + (i1 + 2ull) * v.z + (i1 + 3ull) * v.w;
+    }
+    __shared__ unsigned long long red[2][256];
+    red[0][threadIdx.x] = s0;
+    red[1][threadIdx.x] = s1;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        atomicAdd(&sums[2 * c.tensor], red[0][0]);
+        atomicAdd(&sums[2 * c.tensor + 1], red[1][0]);
+    }
+}
+
+template <int MODE>
+int launch_state(const void *records, const void *chunks, int n_tensors, int n_chunks, void *arena, void *sums, void *stream, const char *who)
+{
+    COSA_REQUIRE(n_tensors >= 0 && n_tensors <= kStateMaxTensors, "%s: %d tensors (at most %d)", who, n_tensors, kStateMaxTensors);
+    COSA_REQUIRE(n_chunks >= 0, "%s: negative chunk count", who);
+    if (n_tensors == 0) {
+        COSA_REQUIRE(n_chunks == 0, "%s: chunks without tensors", who);
+        return COSA_OK;
+    }
+    COSA_REQUIRE(records && sums, "%s: null record table or checksum buffer", who);
+    COSA_REQUIRE((reinterpret_cast<unsigned long long>(sums) & 7ull) == 0, "%s: the checksum buffer must be 8-byte aligned", who);
+    COSA_HIP_CHECK(hipMemsetAsync(sums, 0, (size_t)n_tensors * 16, as_stream(stream)));
+    if (n_chunks == 0) return COSA_OK;                      // zero-length tensors only
+    COSA_REQUIRE(chunks && arena, "%s: null chunk list or arena", who);
+    COSA_REQUIRE((reinterpret_cast<unsigned long long>(arena) & 15ull) == 0, "%s: the arena must be 16-byte aligned", who);
+    hipLaunchKernelGGL(state_kernel<MODE>, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const StateRec *>(records),
+                       static_cast<const ChunkRec *>(chunks), static_cast<unsigned char *>(arena), static_cast<unsigned long long *>(sums));
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
 }  // namespace
 }  // namespace cosa
 
@@ -117,4 +224,39 @@ extern "C" int cosa_fused_adamw_ema(const void *records, const void *chunks, int
                        static_cast<const ChunkRec *>(chunks), beta1, beta2, eps, bc1, bc2_sqrt, ema_momentum);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
+}
+
+/* ---- training-state arena (include/cosa_hip.h) ---- */
+extern "C" size_t cosa_state_record_bytes(void) { return sizeof(StateRec); }
+extern "C" size_t cosa_state_chunk_bytes(void) { return (size_t)kStateChunk; }
+
+extern "C" size_t cosa_state_layout(int n, const unsigned long long *nbytes, unsigned long long *offsets_out)
+{
+    if (n < 0 || n > kStateMaxTensors || (n > 0 && (!nbytes || !offsets_out))) {
+        set_error("cosa_state_layout: %d tensors (0..%d, with size and offset arrays)", n, kStateMaxTensors);
+        return (size_t)-1;
+    }
+    unsigned long long off = 0;
+    for (int i = 0; i < n; i++) {
+        if (nbytes[i] > kStateMaxBytes) {
+            set_error("cosa_state_layout: tensor %d has %llu bytes (at most 2^40)", i, nbytes[i]);
+            return (size_t)-1;
+        }
+        offsets_out[i] = off;
+        off += (nbytes[i] + 15ull) & ~15ull;
+    }
+    return (size_t)off;
+}
+
+extern "C" int cosa_state_snapshot(const void *records, const void *chunks, int n_tensors, int n_chunks, void *arena, void *sums, void *stream)
+{
+    return launch_state<0>(records, chunks, n_tensors, n_chunks, arena, sums, stream, "cosa_state_snapshot");
+}
+
+extern "C" int cosa_state_restore(const void *records, const void *chunks, int n_tensors, int n_chunks, const void *arena, void *sums,
+                                  int scatter, void *stream)
+{
+    if (scatter)
+        return launch_state<2>(records, chunks, n_tensors, n_chunks, const_cast<void *>(arena), sums, stream, "cosa_state_restore");
+    return launch_state<1>(records, chunks, n_tensors, n_chunks, const_cast<void *>(arena), sums, stream, "cosa_state_restore");
 }

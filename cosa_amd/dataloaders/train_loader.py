@@ -88,7 +88,18 @@ class DeviceTrainLoader:
         return len(self.loader)
 
     def __iter__(self):
-        for names, images, params, labels in self.loader:
+        return self.iter_from(0)
+
+    def iter_from(self, skip):
+        """an iterator whose first `skip` batches have been drawn and dropped already (resumption: cosa_amd/checkpoint.py): the sampler,
+        the decode and the augmentation draws run exactly as they did, in the same processes, and nothing of them reaches the device"""
+        inner = iter(self.loader)
+        for _ in range(skip):
+            next(inner)
+        return self._augmented(inner)
+
+    def _augmented(self, inner):
+        for names, images, params, labels in inner:
             wimg, simg, img_box = self.augment(images, params)
             yield names, wimg, simg, labels, img_box
 

@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from . import args as cosa_args
+from . import checkpoint
 from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
@@ -97,25 +98,53 @@ def main(args):
     n_parameters = sum(p.numel() for p in trainer.student.parameters() if p.requires_grad)
     log('Number of trainable params for Network: {}M'.format(n_parameters // 1000000))
 
-    def new_iter():
-        if getattr(train_loader, "sampler", None) is not None and hasattr(train_loader.sampler, "set_epoch"):
-            train_loader.sampler.set_epoch(np.random.randint(args.max_iters))       # main.py:74,111
-        return iter(train_loader)
+    # the loader position (cosa_amd/checkpoint.py): the RNG states just before the current new_iter(), the sampler epoch it drew and the
+    # number of batches taken since -- enough to make a new process draw batch k+1 exactly as this one would have
+    saving = args.save_iters > 0
+    pos = {"rng": None, "epoch": None, "consumed": 0}
 
-    it = new_iter()
+    def new_iter(skip=0):
+        if saving:
+            pos["rng"] = checkpoint.pack_rng(device)
+        pos["epoch"], pos["consumed"] = None, skip
+        if getattr(train_loader, "sampler", None) is not None and hasattr(train_loader.sampler, "set_epoch"):
+            pos["epoch"] = int(np.random.randint(args.max_iters))                    # main.py:74,111
+            train_loader.sampler.set_epoch(pos["epoch"])
+        return train_loader.iter_from(skip) if skip else iter(train_loader)
+
+    keys = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
+    acc = torch.zeros(len(keys), device=device, dtype=torch.float64)           # running sums of the interval, on the device
+    trainer.extra_state = {"launcher.acc": acc}                                # ... and part of a state file: saved and restored in place, no sync
+    resume = args.resume
+    if resume == "auto":
+        resume = checkpoint.newest_state(output_dir)                                # none: a fresh start
+    resumed = None
+    if resume:
+        resumed = trainer.load_state(resume)
+        checkpoint.unpack_rng(resumed["loader"]["rng"], device)                     # 1. the states the interrupted run built its iterator from
+        it = new_iter(skip=int(resumed["loader"]["consumed"]))                      # 2./3. same sampler epoch, the consumed batches drawn and dropped
+        assert pos["epoch"] == resumed["loader"]["epoch"], "the sampler epoch of the resumed iterator differs from the saved one"
+        checkpoint.unpack_rng(resumed["rng_at_save"], device)                       # 4. the states of the save point
+        log(f"Resumed from {resume}: continuing at iteration {int(resumed['n_iter']) + 1}")
+    else:
+        it = new_iter()
     log("Start training")
     start_time, time0, tick = time.time(), datetime.datetime.now().replace(microsecond=0), time.time()
-    keys = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
     loss_df = {k: [] for k in keys + ('iters',)}
-    acc = torch.zeros(len(keys), device=device, dtype=torch.float64)           # running sums of the interval, on the device
     best_seg = best_cam = -1
     df = None
-    for n_iter in range(args.max_iters):
+    first_iter = 0
+    if resumed is not None:
+        first_iter = int(resumed["n_iter"]) + 1
+        best_seg, best_cam, df = resumed["best_seg"], resumed["best_cam"], resumed["df"]
+        loss_df = {k: list(resumed["loss_df"][k]) for k in loss_df}
+    for n_iter in range(first_iter, args.max_iters):
         try:
             img_name, wimg, simg, cls_label, img_box = next(it)
         except StopIteration:
             it = new_iter()
             img_name, wimg, simg, cls_label, img_box = next(it)
+        pos["consumed"] += 1
         cls_label = cls_label.to(device, non_blocking=True)
         logs = trainer.step(wimg, simg, cls_label, img_box, n_iter)
         with torch.no_grad():                                                     # main.py:257-268, without the per-iteration .item() syncs
@@ -165,6 +194,10 @@ def main(args):
                     f.write(f'iters:{n_iter}\n')
                     f.write(f'ON model: cls:{aps[0]}, clsaux: {aps[1]}\n{tab}\n')
                     f.write(f'AN model: cls:{aps_a[0]}, clsaux: {aps_a[1]}\n{tab_a}\n')
+        if saving and (n_iter + 1) % args.save_iters == 0:                        # after this iteration's evaluation and save_best bookkeeping
+            trainer.save_state(checkpoint.state_path(output_dir, n_iter + 1), n_iter=n_iter, best_seg=best_seg, best_cam=best_cam,
+                               loss_df=loss_df, df=df, loader=dict(pos))
+    trainer.wait_state()
     torch.cuda.synchronize()
     if is_main:
         total = str(datetime.timedelta(seconds=int(time.time() - start_time)))

@@ -346,6 +346,31 @@ class CoSATrainer:
             self._student_shadows.refresh()              # W^T, and the 16-bit copies unless the fused kernel has just written them
         return logs
 
+    # -- full-state checkpoints (cosa_amd/checkpoint.py) --
+    def train_state(self):
+        """the TrainState of the networks and moments (in a world of one: of everything)"""
+        from . import checkpoint
+        return checkpoint.trainer_state(self)
+
+    def save_state(self, path, **extra):
+        """Write everything that defines the future of this run to `path` (one snapshot launch now; copy and file write run behind the
+        loop).  `extra`: the launcher's own bookkeeping, returned by load_state; tensors the launcher keeps on the device travel through
+        `self.extra_state` {name: tensor} (set before the first save or load).  Under a process group rank 0 writes `path`, every rank
+        `path.rank<r>`.  Older complete state files next to `path` are pruned to args.keep_states (default 2)."""
+        from . import checkpoint
+        return checkpoint.save_trainer(self, path, extra, keep=int(getattr(self.args, "keep_states", 2)))
+
+    def wait_state(self):
+        """until every state file asked for is written"""
+        from . import checkpoint
+        checkpoint.wait_trainer(self, keep=int(getattr(self.args, "keep_states", 2)))
+
+    def load_state(self, path):
+        """Restore a file written by save_state (verified before anything is overwritten), rebuild everything derived from the masters,
+        drop the captured teacher graph; -> extra (plus `rng_at_save`, the RNG states this call has just restored)."""
+        from . import checkpoint
+        return checkpoint.load_trainer(self, path)
+
 
 # ---- synthetic batches (SURVEY §8 d-2) --------------------------------------------------------------------
 def synthetic_batch(b, S, C, device, seed=1234, dataset="VOC12"):

@@ -488,6 +488,29 @@ int cosa_fused_adamw_ema(const void *records, const void *chunks, int n_chunks, 
                          int step, float ema_momentum, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training-state arena: every tensor that defines the future of a run, gathered into ONE contiguous
+ * device arena by one launch (and scattered back by one), with two 64-bit checksums per tensor.
+ * cosa_state_layout: THE definition of the arena for host and device: tensor i (nbytes[i] bytes, any dtype, contiguous)
+ *   occupies [offsets_out[i], offsets_out[i] + nbytes[i]) of a slot rounded up to 16 bytes whose tail is zero; slots follow
+ *   each other in table order.  Returns the arena's size; (size_t)-1 (message in cosa_last_error()) for n outside 0..4096 or a
+ *   tensor above 2^40 bytes.  Zero-length tensors are accepted (empty slot, checksums 0).
+ * `records`: device array of n_tensors { void *ptr; uint64 nbytes; uint64 off } (cosa_state_record_bytes() each); `chunks`:
+ *   device array of n_chunks {int tensor, int chunk} covering every SLOT in pieces of cosa_state_chunk_bytes().
+ * `sums`: device uint64 [n_tensors][2], zeroed by the call itself on `stream`: over the little-endian 32-bit words w_i of the
+ *   zero-padded slot, s0 = sum w_i and s1 = sum (i+1) w_i, both mod 2^64 (order-independent: bit-identical from run to run).
+ * cosa_state_snapshot: tensors -> arena (+ checksums of what was written).  The arena must be 16-byte aligned; sources of any
+ *   alignment and odd byte counts are taken (16-byte accesses where the pointer allows).
+ * cosa_state_restore: scatter == 0 only recomputes the checksums of the arena's slots (nothing is written but `sums`): the host
+ *   compares them with the recorded ones BEFORE it calls again with scatter == 1, which copies the slots back into the tensors.
+ * ------------------------------------------------------------------------------------- */
+size_t cosa_state_record_bytes(void);
+size_t cosa_state_chunk_bytes(void);
+size_t cosa_state_layout(int n, const unsigned long long *nbytes, unsigned long long *offsets_out);
+int cosa_state_snapshot(const void *records, const void *chunks, int n_tensors, int n_chunks, void *arena, void *sums, void *stream);
+int cosa_state_restore(const void *records, const void *chunks, int n_tensors, int n_chunks, const void *arena, void *sums, int scatter,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * models/vit/vit.py:154-158  the student's pre-LN residual blocks (training, bf16 stream), element-wise side:
  *   cosa_add_layernorm_fwd: x_out = bf16(x + delta) (delta may be NULL: x_out optional), y = LayerNorm(x_out; gamma, beta, eps),
  *     mean / rstd [rows] kept for the backward.  All tensors bf16 [rows, 768] except mean / rstd (fp32).
