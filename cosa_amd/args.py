@@ -55,6 +55,9 @@ EXTRA = [
     ("save_iters", int, 0),                  # write <output_dir>/state_<iteration>.cosa every N iterations; 0: never (nothing changes)
     ("keep_states", int, 2),                 # complete state files kept; older ones go once a newer one is in place
     ("resume", str, None),                   # a state file, or "auto": the newest complete state_*.cosa of the output directory, if any
+    # the gradient guard, decided on the device by the optimizer's own kernels; both off: nothing changes
+    ("clip_grad_norm", float, 0.0),          # clip the gradients by their global L2 norm to this bound (clip_grad_norm_'s formula); 0: off
+    ("skip_nonfinite", str2bool, False),     # refuse a step whose gradients hold an inf / NaN: weights, moments and the EMA teacher stay
 ]
 
 

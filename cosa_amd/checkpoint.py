@@ -2,7 +2,7 @@
 interrupted.
 
 `TrainState(trainer)` names every tensor that defines the future of a run -- parameters and buffers of both networks, the AdamW moments,
-with --usegmm the queues and threshold trackers -- and moves them as ONE byte arena: on the GPU with one launch of the gather / scatter
+with --usegmm the queues and threshold trackers, with the gradient guard its record (the arena's last, optional tensor) -- and moves them as ONE byte arena: on the GPU with one launch of the gather / scatter
 kernel of csrc/optim_kernels.hip (cosa_state_snapshot / cosa_state_restore, two 64-bit checksums per tensor), on a host-device trainer
 with torch copies and the same checksums from numpy.  Everything derived (16-bit shadows, W^T copies, split rows, CAM buffers, the
 captured teacher graph) is NOT state: load() rebuilds it.
@@ -302,6 +302,7 @@ class TrainState:
     """Every tensor that defines the future of `trainer`'s run, by stable name, and its arena."""
 
     TRACKERS = ("ema_lowthre", "ema_highthre", "ema_auxlowthre", "ema_auxhighthre")
+    GUARD = "guard.state"
 
     def __init__(self, trainer, part="all"):
         """part: "all" (a world of one), or under a process group "shared" (networks and moments: identical on every rank, written by
@@ -343,6 +344,10 @@ class TrainState:
             # tensors the launcher keeps on the device between iterations (CoSATrainer.extra_state: its running loss sums)
             for n, t in sorted(getattr(tr, "extra_state", {}).items()):
                 entries.append((f"aux.{n}", t))
+        if part != "local" and getattr(tr, "guard_state", None) is not None:
+            # the gradient guard's record (its counters; identical on every rank).  LAST, so that a file differs from one written without a
+            # guard by its tail only: load() reconciles the two (_reconcile_guard), and with the guard off nothing here changes
+            entries.append((self.GUARD, tr.guard_state))
         for n, t in entries:
             if not t.is_contiguous():
                 raise ValueError(f"TrainState: {n} is not contiguous")
@@ -519,11 +524,31 @@ class TrainState:
                 if t[k] != m[k]:
                     raise ValueError(f"{path}: tensor {t['name']}: {k} differs: the file has {t[k]!r}, this run {m[k]!r}")
 
+    def _reconcile_guard(self, header, a_len, path):
+        """The guard record is the one optional tensor, and the arena's last: -> (header as this run would have written it, its arena
+        bytes, the arena bytes to read from the file).  A file without it loads into a guarded run with the record zero (counters start at
+        zero); a file with it loads into a run without a guard, the entry ignored.  Each with a note."""
+        theirs = header["tensors"]
+        has = bool(theirs) and theirs[-1]["name"] == self.GUARD
+        mine = bool(self.names) and self.names[-1] == self.GUARD
+        if has == mine or self.part == "local":
+            return header, a_len, a_len
+        if has:
+            print(f"note: {path}: the file holds a gradient guard's counters and this run has no guard (--clip_grad_norm 0, --skip_nonfinite "
+                  f"false): the entry is ignored", flush=True)
+            keep = a_len - (int(theirs[-1]["nbytes"]) + 15) // 16 * 16
+            return dict(header, tensors=theirs[:-1]), keep, keep
+        print(f"note: {path}: written without a gradient guard: this run's guard counters start at zero", flush=True)
+        t, o, b = self.tensors[-1], self.offsets[-1], self.nbytes[-1]
+        entry = {"name": self.GUARD, "dtype": str(t.dtype), "shape": list(t.shape), "offset": o, "nbytes": b, "s0": 0, "s1": 0}
+        return dict(header, tensors=theirs + [entry]), a_len + (b + 15) // 16 * 16, a_len
+
     def load(self, path):
         """-> extra.  Verify, then restore: the checksums of what arrived on the device are compared with the file's BEFORE any tensor is
         overwritten; then counters, everything derived, and the RNG states last."""
         path = str(path)
         header, blobs, a_off, a_len = read_header(path)              # bad magic / truncation: nothing has been touched
+        header, a_len, f_len = self._reconcile_guard(header, a_len, path)
         self.check_header(header, path)
         if a_len != self.total:
             raise ValueError(f"{path}: arena size differs: the file has {a_len!r}, this run {self.total!r}")
@@ -533,9 +558,10 @@ class TrainState:
         host, arena, sums = self._hosts[0], self._arenas[0], self._sums[1]
         with open(path, "rb") as f:
             f.seek(a_off)
-            got = f.readinto(memoryview(host.numpy())[:a_len]) if a_len else 0
-        if got != a_len:
-            raise ValueError(f"{path}: truncated file ({got} arena bytes read, {a_len} announced)")
+            got = f.readinto(memoryview(host.numpy())[:f_len]) if f_len else 0
+        if got != f_len:
+            raise ValueError(f"{path}: truncated file ({got} arena bytes read, {f_len} announced)")
+        host[f_len:a_len].zero_()                                    # (a guard record the file does not have)
         if self.cuda:
             arena.copy_(host, non_blocking=True)
             self._table.restore(arena, sums, False)

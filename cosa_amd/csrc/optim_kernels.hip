@@ -40,8 +40,20 @@ __device__ __forceinline__ void store16(bf16 *dst, float v, int f16)
 }
 constexpr int kChunk = 65536;            // elements per block
 
-__global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
-                                                       float beta1, float beta2, float eps, float bc1, float bc2_sqrt, float ema)
+// The gradient guard: what grad_norm_finalize_kernel leaves for the guarded optimizer kernel, and the running
+// counters of a run.  40 bytes, 8-byte aligned (include/cosa_hip.h).
+struct GuardRec {
+    float norm;             // global L2 norm of all gradients of the step (non-finite exactly when some gradient element is)
+    float coef;             // min(1, max_norm / (norm + 1e-6)); 1 when clipping is off
+    int skip;               // 1: the step is refused (skip_nonfinite and a non-finite norm)
+    int pad;
+    long long applied, skipped, clipped;
+};
+
+// GUARDED: every gradient element is multiplied by `coef` first (exact for coef == 1: same bits as the unguarded kernel)
+template <bool GUARDED>
+__device__ __forceinline__ void adamw_ema_body(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks, float beta1, float beta2,
+                                               float eps, float bc1, float bc2_sqrt, float ema, float coef)
 {
     const ChunkRec c = chunks[blockIdx.x];
     const TensorRec t = recs[c.tensor];
@@ -60,6 +72,10 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorRec *__restr
                 const float4 g = *reinterpret_cast<const float4 *>(t.g + i);
                 float4 m = *reinterpret_cast<const float4 *>(t.m + i), v = *reinterpret_cast<const float4 *>(t.v + i);
                 float gv[4] = {g.x, g.y, g.z, g.w}, mv[4] = {m.x, m.y, m.z, m.w}, vv[4] = {v.x, v.y, v.z, v.w};
+                if (GUARDED) {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) gv[e] *= coef;
+                }
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
                     pv[e] *= decay;
@@ -82,7 +98,7 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorRec *__restr
         for (long long i = base + threadIdx.x; i < end; i += 256) {
             float p = t.p[i], tp = t.tp[i];
             if (t.g) {
-                const float g = t.g[i];
+                const float g = GUARDED ? t.g[i] * coef : t.g[i];
                 p *= decay;
                 const float m = beta1 * t.m[i] + (1.0f - beta1) * g;
                 const float v = beta2 * t.v[i] + (1.0f - beta2) * g * g;
@@ -93,6 +109,102 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorRec *__restr
             tp = ema * tp + (1.0f - ema) * p;
             t.tp[i] = tp;
             if (t.t16) store16(t.t16 + i, tp, t.t16_f16);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void adamw_ema_kernel(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
+                                                       float beta1, float beta2, float eps, float bc1, float bc2_sqrt, float ema)
+{
+    adamw_ema_body<false>(recs, chunks, beta1, beta2, eps, bc1, bc2_sqrt, ema, 1.0f);
+}
+
+// The same step behind the guard record of this iteration: refused as a whole (no block stores anything: masters, moments, teacher and
+// all 16-bit shadows keep their bytes, the EMA is not applied) or taken on g * coef.  The gradient buffers are only read.
+__global__ __launch_bounds__(256) void adamw_ema_guarded_kernel(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
+                                                               float beta1, float beta2, float eps, float bc1, float bc2_sqrt, float ema,
+                                                               const GuardRec *__restrict__ guard)
+{
+    if (guard->skip) return;
+    adamw_ema_body<true>(recs, chunks, beta1, beta2, eps, bc1, bc2_sqrt, ema, guard->coef);
+}
+
+// ---- global gradient norm ---------------------------------------------------------------------------------------
+// One block per chunk of the optimizer's own record table and chunk list; sum of g^2 in double (a finite fp32 squared and summed in double
+// cannot overflow: the norm is non-finite exactly when some gradient element is), one partial per chunk, every addition in a fixed order.
+__device__ __forceinline__ double block_sum_256(double s, double *red)
+{
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(256) void grad_norm_kernel(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
+                                                       double *__restrict__ partials)
+{
+    __shared__ double red[256];
+    const ChunkRec c = chunks[blockIdx.x];
+    const TensorRec t = recs[c.tensor];
+    if (!t.g) {                                             // frozen: contributes nothing (its chunk's partial is still written)
+        if (threadIdx.x == 0) partials[blockIdx.x] = 0.0;
+        return;
+    }
+    const long long base = (long long)c.chunk * kChunk;
+    long long end = base + kChunk;
+    end = end < t.n ? end : t.n;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if ((t.n & 3) == 0) {
+        for (long long i = base + threadIdx.x * 4; i < end; i += 1024) {
+            const float4 g = *reinterpret_cast<const float4 *>(t.g + i);
+            s0 += (double)g.x * (double)g.x;
+            s1 += (double)g.y * (double)g.y;
+            s2 += (double)g.z * (double)g.z;
+            s3 += (double)g.w * (double)g.w;
+        }
+    } else {
+        for (long long i = base + threadIdx.x; i < end; i += 256) {
+            const double g = (double)t.g[i];
+            s0 += g * g;
+        }
+    }
+    const double s = block_sum_256((s0 + s1) + (s2 + s3), red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// One block: thread k adds its contiguous run of partials in index order, the 256 runs are combined by the fixed tree above (no atomics:
+// the same bits from run to run); thread 0 writes this iteration's decision and advances the counters with ordinary stores.
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const double *__restrict__ partials, int n_chunks, float max_norm,
+                                                                int skip_nonfinite, GuardRec *__restrict__ guard)
+{
+    __shared__ double red[256];
+    const int per = (n_chunks + 255) / 256;
+    const int lo = (int)threadIdx.x * per;
+    int hi = lo + per;
+    hi = hi < n_chunks ? hi : n_chunks;
+    double s = 0.0;
+    for (int i = lo; i < hi; i++) s += partials[i];
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(s);
+        float coef = 1.0f;
+        if (max_norm > 0.0f) {                              // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1), NaN stays NaN
+            const float c = max_norm / (norm + 1e-6f);
+            coef = c > 1.0f ? 1.0f : c;
+        }
+        const int skip = (skip_nonfinite && !isfinite(s)) ? 1 : 0;    // on the double sum: an fp32 norm can round to inf from finite gradients
+        guard->norm = norm;
+        guard->coef = coef;
+        guard->skip = skip;
+        guard->pad = 0;
+        if (skip) {
+            guard->skipped += 1;
+        } else {
+            guard->applied += 1;
+            if (coef < 1.0f) guard->clipped += 1;
         }
     }
 }
@@ -222,6 +334,45 @@ extern "C" int cosa_fused_adamw_ema(const void *records, const void *chunks, int
     const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const TensorRec *>(records),
                        static_cast<const ChunkRec *>(chunks), beta1, beta2, eps, bc1, bc2_sqrt, ema_momentum);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+/* ---- the gradient guard (include/cosa_hip.h) ---- */
+extern "C" size_t cosa_grad_guard_bytes(void) { return sizeof(GuardRec); }
+extern "C" size_t cosa_grad_norm_workspace_bytes(int n_chunks) { return n_chunks > 0 ? (size_t)n_chunks * sizeof(double) : 0; }
+
+extern "C" int cosa_grad_norm(const void *records, const void *chunks, int n_chunks, float max_norm, int skip_nonfinite, void *workspace,
+                              size_t workspace_bytes, void *guard, void *stream)
+{
+    COSA_REQUIRE(records && chunks && n_chunks > 0, "cosa_grad_norm: null record table or chunk list, or no chunks");
+    COSA_REQUIRE(guard, "cosa_grad_norm: null guard record");
+    COSA_REQUIRE((reinterpret_cast<unsigned long long>(guard) & 7ull) == 0, "cosa_grad_norm: the guard record must be 8-byte aligned");
+    COSA_REQUIRE(max_norm >= 0.0f, "cosa_grad_norm: max_norm %g (0 = no clipping, or a positive bound)", (double)max_norm);
+    const size_t need = cosa_grad_norm_workspace_bytes(n_chunks);
+    COSA_REQUIRE(workspace && workspace_bytes >= need, "cosa_grad_norm: workspace of %zu bytes (%zu needed)", workspace ? workspace_bytes : (size_t)0,
+                 need);
+    COSA_REQUIRE((reinterpret_cast<unsigned long long>(workspace) & 7ull) == 0, "cosa_grad_norm: the workspace must be 8-byte aligned");
+    double *partials = static_cast<double *>(workspace);
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const TensorRec *>(records),
+                       static_cast<const ChunkRec *>(chunks), partials);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials, n_chunks, max_norm, skip_nonfinite ? 1 : 0,
+                       static_cast<GuardRec *>(guard));
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+extern "C" int cosa_fused_adamw_ema_guarded(const void *records, const void *chunks, int n_chunks, float beta1, float beta2, float eps,
+                                            int step, float ema_momentum, const void *guard, void *stream)
+{
+    COSA_REQUIRE(records && chunks && n_chunks > 0 && step >= 1, "cosa_fused_adamw_ema_guarded: bad arguments");
+    COSA_REQUIRE(guard, "cosa_fused_adamw_ema_guarded: null guard record");
+    COSA_REQUIRE((reinterpret_cast<unsigned long long>(guard) & 7ull) == 0, "cosa_fused_adamw_ema_guarded: the guard record must be 8-byte aligned");
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adamw_ema_guarded_kernel, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const TensorRec *>(records),
+                       static_cast<const ChunkRec *>(chunks), beta1, beta2, eps, bc1, bc2_sqrt, ema_momentum, static_cast<const GuardRec *>(guard));
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

@@ -154,7 +154,12 @@ def main(args):
                 logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
                 (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
-            vals = (acc / args.log_iters).tolist()                                # the one host sync of the interval
+            guard = trainer.guard_state                                           # None: no gradient guard, the line below as ever
+            if guard is None:
+                vals = (acc / args.log_iters).tolist()                            # the one host sync of the interval
+            else:      # the guard's own tensor rides along in the same sync: the last step's norm and the run's counters (`acc` keeps its length)
+                vals = torch.cat([acc / args.log_iters, torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]).tolist()
+                vals, gvals = vals[:len(keys)], vals[len(keys):]
             acc.zero_()
             now = time.time()
             itertime, tick = (now - tick) / args.log_iters, now
@@ -164,9 +169,12 @@ def main(args):
                 for k, v in zip(keys, vals):
                     loss_df[k].append(v)
                 loss_df['iters'].append(n_iter + 1)
-                log("Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  "
-                    "cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, reg_loss: %.4f ..."
-                    % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
+                line = ("Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  "
+                        "cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, reg_loss: %.4f ..."
+                        % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
+                if guard is not None:
+                    line += " grad_norm: %.4f, skipped: %d, clipped: %d" % (gvals[0], int(gvals[1]), int(gvals[2]))
+                log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,
                              threshold_filters=args.eval_threshold_filters)

@@ -37,7 +37,8 @@ def default_args(dataset="VOC12", **over):
              high_thre=0.7, high_thre_aux=0.7, low_thre=0.25, low_thre_aux=0.25, bkg_thre=0.5, par_downscale=2, usepar=False,
              aux_cam2seg=True, aux_cam2seg_alpha=0.5, aux_seg2cam=False, aux_seg2cam_alpha=0.5, after_softmax=False,
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
-             queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True)
+             queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
+             clip_grad_norm=0.0, skip_nonfinite=False)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -144,10 +145,21 @@ class CoSATrainer:
         self._student_shadows = nn_ops.ensure_shadows(self.student) if on else None
         # AdamW + EMA + shadow refresh as one multi-tensor kernel: it rewrites every shadow each step, so the no-grad entry points
         # need not refresh them (nn_ops.ensure_shadows); without it they do
+        # the gradient guard: off (None) unless --clip_grad_norm > 0 or --skip_nonfinite true
+        self._max_norm = float(getattr(args, "clip_grad_norm", 0.0) or 0.0)
+        self._skip_nonfinite = bool(getattr(args, "skip_nonfinite", False))
+        if not self._max_norm >= 0:
+            raise ValueError(f"clip_grad_norm {self._max_norm!r}: 0 (off) or a positive bound")
+        guard_on = self._max_norm > 0 or self._skip_nonfinite
         self._fused_step = None
         if on and getattr(args, "fused_optimizer", True):
             self._fused_step = torch_helper.FusedAdamWEMAStep(self.optimizer, self._ema_pairs[1], self._ema_pairs[0], args.momentum,
-                                                              shadow_of=nn_ops.shadow_of)
+                                                              shadow_of=nn_ops.shadow_of, max_norm=self._max_norm,
+                                                              skip_nonfinite=self._skip_nonfinite)
+        # the guard record: the fused step's (written by its kernels) or, on the torch path, one of the same layout written by torch
+        self.guard_state = None
+        if guard_on:
+            self.guard_state = self._fused_step.guard if self._fused_step is not None else torch_helper.new_guard_state(device)
         if on:
             self._teacher_shadows.optimizer_owned = self._student_shadows.optimizer_owned = self._fused_step is not None
             # bf16 W^T copies of the student's block projections (the input-gradient GEMMs run the forward kernel on them)
@@ -339,12 +351,22 @@ class CoSATrainer:
         loss.backward()
         if self._fused_step is not None:
             self._fused_step.step()
+        elif self.guard_state is not None:
+            torch_helper.guarded_torch_step(self.optimizer, self._ema_pairs[0], self._ema_pairs[1], self.args.momentum, self._max_norm,
+                                            self._skip_nonfinite, self.guard_state)
         else:
             self.optimizer.step()
             torch_helper.ema_update(self._ema_pairs[0], self._ema_pairs[1], self.args.momentum)
         if self._student_shadows is not None:
             self._student_shadows.refresh()              # W^T, and the 16-bit copies unless the fused kernel has just written them
+        if self.guard_state is not None:
+            logs["grad_norm"] = torch_helper.guard_norm(self.guard_state).clone()     # a device scalar: no sync
         return logs
+
+    def guard_counters(self):
+        """{applied, skipped, clipped} of the gradient guard over the run so far (synchronises: for tests and the log interval); None
+        when the guard is off"""
+        return torch_helper.guard_counters(self.guard_state) if self.guard_state is not None else None
 
     # -- full-state checkpoints (cosa_amd/checkpoint.py, DESIGN.md section 9) --
     def train_state(self):

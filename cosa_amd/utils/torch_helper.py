@@ -80,6 +80,26 @@ class PolyWarmupAdamW(torch.optim.AdamW):
         super().step(closure)
         self.global_step += 1
 
+    def skip_step(self):
+        """A refused iteration (the gradient guard): nothing is updated, but the schedule and the bias-correction count advance exactly as
+        in step(), because the fused path's host never learns that its kernel refused a step."""
+        mult = poly_warmup_lr_mult(self.global_step, self.warmup_iter, self.max_iter, self.warmup_ratio, self.power,
+                                   self.min_mult)
+        for i, g in enumerate(self.param_groups):
+            if mult is not None:
+                g["lr"] = self._init_lr[i] * mult
+            for p in g["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if "step" not in st:                        # as torch's AdamW creates them in its first step()
+                    on_dev = bool(g.get("fused")) or bool(g.get("capturable"))
+                    st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if on_dev else torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1
+        self.global_step += 1
+
 
 @torch.no_grad()
 def ema_update(teacher_params, student_params, momentum):
@@ -89,14 +109,87 @@ def ema_update(teacher_params, student_params, momentum):
     torch._foreach_add_(teacher_params, student_params, alpha=1 - momentum)
 
 
+# --------------------------------------------------------------------------------------------
+# the gradient guard: clip by the global norm, refuse a non-finite step
+# --------------------------------------------------------------------------------------------
+GUARD_WORDS = 5      # the guard record of include/cosa_hip.h as int64 words: {f32 norm, f32 coef | i32 skip, i32 pad | applied | skipped | clipped}
+
+
+def new_guard_state(device):
+    return torch.zeros(GUARD_WORDS, dtype=torch.int64, device=device)
+
+
+def guard_norm(state):
+    """the last step's global gradient norm: a 0-dim fp32 view of the guard record (no sync)"""
+    return state.view(torch.float32)[0]
+
+
+def guard_coef(state):
+    return state.view(torch.float32)[1]
+
+
+def guard_skip(state):
+    return state.view(torch.int32)[2]
+
+
+def guard_counters(state):
+    """{applied, skipped, clipped} of the run so far; synchronises"""
+    applied, skipped, clipped = state[2:5].tolist()
+    return {"applied": applied, "skipped": skipped, "clipped": clipped}
+
+
+@torch.no_grad()
+def guard_decision(grads, max_norm, skip_nonfinite, state):
+    """The guard's decision in plain torch, written into `state` the way cosa_grad_norm does: the global norm from a float64 sum of squares,
+    coef = clamp(max_norm / (norm + 1e-6), max=1) in fp32 (1 without clipping), skip = skip_nonfinite and a non-finite sum, the counters.
+    -> (coef as a 0-dim fp32 tensor, skip as a bool: this path, unlike the kernels, tells the host)."""
+    dev = state.device
+    if grads:
+        total = torch.stack([g.detach().double().square().sum() for g in grads]).sum()
+    else:
+        total = torch.zeros((), dtype=torch.float64, device=dev)
+    norm = total.sqrt().float()
+    coef = (float(max_norm) / (norm + 1e-6)).clamp(max=1.0) if max_norm > 0 else torch.ones((), dtype=torch.float32, device=dev)
+    skip = bool(skip_nonfinite) and not bool(torch.isfinite(total))
+    f32 = state.view(torch.float32)
+    f32[0], f32[1] = norm, coef
+    state.view(torch.int32)[2] = int(skip)
+    if skip:
+        state[3] += 1
+    else:
+        state[2] += 1
+        state[4] += (coef < 1).to(torch.int64)
+    return coef, skip
+
+
+@torch.no_grad()
+def guarded_torch_step(optimizer, teacher_params, student_params, momentum, max_norm, skip_nonfinite, state):
+    """optimizer.step() + ema_update behind the gradient guard, for the non-fused path and host trainers: the semantics of
+    cosa_grad_norm + cosa_fused_adamw_ema_guarded (a refused step changes nothing and still counts for the schedule and the bias
+    correction).  Clipping scales the gradients in place, as torch.nn.utils.clip_grad_norm_ does."""
+    grads = [p.grad for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
+    coef, skip = guard_decision(grads, max_norm, skip_nonfinite, state)
+    if skip:
+        optimizer.skip_step()
+        return
+    if max_norm > 0 and grads:
+        torch._foreach_mul_(grads, coef)
+    optimizer.step()
+    ema_update(teacher_params, student_params, momentum)
+
+
 class FusedAdamWEMAStep:
     """optimizer.step() + the teacher EMA (main.py:250-252) + refresh of the bf16 shadow weights as ONE HIP kernel.
 
     State lives where torch keeps it (optimizer.state[p]['exp_avg'|'exp_avg_sq'], optimizer.param_groups[i]['lr']) so the
     PolyWarmupAdamW object stays the source of truth (state_dict compatible); this class only replaces the sweeps over
-    memory.  The LR schedule is PolyWarmupAdamW's (utils/torch_helper.py:275-289)."""
+    memory.  The LR schedule is PolyWarmupAdamW's (utils/torch_helper.py:275-289).
 
-    def __init__(self, optimizer, student_params, teacher_params, momentum, shadow_of=None):
+    max_norm > 0 and / or skip_nonfinite: the gradient guard.  step() then launches the global-norm reduction and
+    the guarded kernel, which clips by `coef` or refuses the whole step on the device; `self.guard` is the guard record (GUARD_WORDS int64).
+    Without either, step() is the unguarded call."""
+
+    def __init__(self, optimizer, student_params, teacher_params, momentum, shadow_of=None, max_norm=0.0, skip_nonfinite=False):
         import numpy as np
         self.opt = optimizer
         self.momentum = float(momentum)
@@ -149,6 +242,14 @@ class FusedAdamWEMAStep:
         for r in self.recs[1:]:
             r[:] = self.recs[0]
         self.d_recs = [torch.empty(n * self.rec_dtype.itemsize, dtype=torch.uint8, device=dev) for _ in range(self.kRing)]
+        self.max_norm, self.skip_nonfinite = float(max_norm), bool(skip_nonfinite)
+        if not self.max_norm >= 0:
+            raise ValueError(f"max_norm {max_norm!r}: 0 (no clipping) or a positive bound")
+        self.guard = self.norm_ws = None
+        if self.max_norm > 0 or self.skip_nonfinite:
+            assert L.cosa_grad_guard_bytes() == GUARD_WORDS * 8
+            self.guard = new_guard_state(dev)
+            self.norm_ws = torch.empty(max(L.cosa_grad_norm_workspace_bytes(self.n_chunks), 8), dtype=torch.uint8, device=dev)
 
     def step(self):
         opt = self.opt
@@ -177,9 +278,20 @@ class FusedAdamWEMAStep:
         b1, b2 = groups[0]["betas"]
         opt.global_step += 1
         self._step_t.fill_(float(opt.global_step))
-        _C.check(_C.lib().cosa_fused_adamw_ema(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, float(b1), float(b2),
-                                               float(groups[0]["eps"]), int(opt.global_step), self.momentum, _C.stream_ptr()),
-                 "cosa_fused_adamw_ema")
+        if self.guard is None:
+            _C.check(_C.lib().cosa_fused_adamw_ema(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, float(b1), float(b2),
+                                                   float(groups[0]["eps"]), int(opt.global_step), self.momentum, _C.stream_ptr()),
+                     "cosa_fused_adamw_ema")
+            return
+        # behind loss.backward() (under DDP its hooks have all-reduced every gradient by now: each rank reduces the same values to the same
+        # decision, no further collective), on the stream of the optimizer kernel
+        with _C.profiled("grad_norm"):
+            _C.check(_C.lib().cosa_grad_norm(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, self.max_norm, int(self.skip_nonfinite),
+                                             _C.ptr(self.norm_ws), self.norm_ws.numel(), _C.ptr(self.guard), _C.stream_ptr()), "cosa_grad_norm")
+        with _C.profiled("adamw_ema_guarded"):
+            _C.check(_C.lib().cosa_fused_adamw_ema_guarded(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, float(b1), float(b2),
+                                                           float(groups[0]["eps"]), int(opt.global_step), self.momentum, _C.ptr(self.guard),
+                                                           _C.stream_ptr()), "cosa_fused_adamw_ema_guarded")
 
 
 # --------------------------------------------------------------------------------------------

@@ -488,6 +488,27 @@ int cosa_fused_adamw_ema(const void *records, const void *chunks, int n_chunks, 
                          int step, float ema_momentum, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The gradient guard: clip by the global norm and refuse a step with a non-finite gradient, decided
+ * on the device.  Both calls take the record table and chunk list of cosa_fused_adamw_ema and go on the same stream.
+ * `guard`: one device record of cosa_grad_guard_bytes() = 40 bytes, 8-byte aligned, zeroed once by the caller:
+ *   { float norm;  float coef;  int32 skip;  int32 pad;  int64 applied, skipped, clipped }
+ * cosa_grad_norm: norm = sqrt(sum g^2) over every record with g != NULL, summed in double in a fixed order (the same bits
+ *   from run to run; non-finite exactly when some gradient element is); coef = min(1, max_norm / (norm + 1e-6)), or 1 when
+ *   max_norm == 0 (no clipping); skip = skip_nonfinite && the double sum is not finite.  The counters advance by one call:
+ *   skipped on skip, else applied (and clipped when coef < 1).  `workspace`: cosa_grad_norm_workspace_bytes(n_chunks) bytes,
+ *   8-byte aligned.
+ * cosa_fused_adamw_ema_guarded: cosa_fused_adamw_ema on g * coef (the gradients are only read; with coef == 1 the bits of the
+ *   unguarded call), or, on skip, nothing at all: masters, moments, teacher and every 16-bit shadow keep their bytes.
+ *   `step` is the host's count and advances over a refused step too (nothing of the decision ever reaches the host).
+ * ------------------------------------------------------------------------------------- */
+size_t cosa_grad_guard_bytes(void);
+size_t cosa_grad_norm_workspace_bytes(int n_chunks);
+int cosa_grad_norm(const void *records, const void *chunks, int n_chunks, float max_norm, int skip_nonfinite, void *workspace,
+                   size_t workspace_bytes, void *guard, void *stream);
+int cosa_fused_adamw_ema_guarded(const void *records, const void *chunks, int n_chunks, float beta1, float beta2, float eps,
+                                 int step, float ema_momentum, const void *guard, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training-state arena: every tensor that defines the future of a run, gathered into ONE contiguous
  * device arena by one launch (and scattered back by one), with two 64-bit checksums per tensor.
  * cosa_state_layout: THE definition of the arena for host and device: tensor i (nbytes[i] bytes, any dtype, contiguous)
