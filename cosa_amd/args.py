@@ -58,6 +58,10 @@ EXTRA = [
     # the gradient guard, decided on the device by the optimizer's own kernels; both off: nothing changes
     ("clip_grad_norm", float, 0.0),          # clip the gradients by their global L2 norm to this bound (clip_grad_norm_'s formula); 0: off
     ("skip_nonfinite", str2bool, False),     # refuse a step whose gradients hold an inf / NaN: weights, moments and the EMA teacher stay
+    # per-step pseudo-label statistics and the teacher finite check; off: nothing changes
+    ("label_stats", str2bool, False),        # count ignore / bg / fg, main-aux agreement, the student's IoU and non-finite CAMs on the device;
+                                             # logged and written to <output_dir>/label_stats.jsonl every log_iters; with --skip_nonfinite a
+                                             # step whose teacher CAMs hold an inf / NaN is refused
 ]
 
 

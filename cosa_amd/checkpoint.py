@@ -2,9 +2,10 @@
 interrupted.
 
 `TrainState(trainer)` names every tensor that defines the future of a run -- parameters and buffers of both networks, the AdamW moments,
-with --usegmm the queues and threshold trackers, with the gradient guard its record (the arena's last, optional tensor) -- and moves them as ONE byte arena: on the GPU with one launch of the gather / scatter
-kernel of csrc/optim_kernels.hip (cosa_state_snapshot / cosa_state_restore, two 64-bit checksums per tensor), on a host-device trainer
-with torch copies and the same checksums from numpy.  Everything derived (16-bit shadows, W^T copies, split rows, CAM buffers, the
+with --usegmm the queues and threshold trackers, with the gradient guard its record (the arena's last, optional tensor), with
+--label_stats its counters (optional too) -- and moves them as ONE byte arena: on the GPU with one launch of the gather / scatter kernel
+of csrc/optim_kernels.hip (cosa_state_snapshot / cosa_state_restore, two 64-bit checksums per tensor), on a host-device trainer with
+torch copies and the same checksums from numpy.  Everything derived (16-bit shadows, W^T copies, split rows, CAM buffers, the
 captured teacher graph) is NOT state: load() rebuilds it.
 
 File:  MAGIC | u32 version | u64 header bytes | u64 host-section bytes | u64 arena bytes | JSON header | host section | arena.
@@ -303,6 +304,7 @@ class TrainState:
 
     TRACKERS = ("ema_lowthre", "ema_highthre", "ema_auxlowthre", "ema_auxhighthre")
     GUARD = "guard.state"
+    LABEL_STATS = "aux.label_stats.counters"         # CoSATrainer.extra_state["label_stats.counters"]
 
     def __init__(self, trainer, part="all"):
         """part: "all" (a world of one), or under a process group "shared" (networks and moments: identical on every rank, written by
@@ -346,7 +348,7 @@ class TrainState:
                 entries.append((f"aux.{n}", t))
         if part != "local" and getattr(tr, "guard_state", None) is not None:
             # the gradient guard's record (its counters; identical on every rank).  LAST, so that a file differs from one written without a
-            # guard by its tail only: load() reconciles the two (_reconcile_guard), and with the guard off nothing here changes
+            # guard by its tail only: load() reconciles the two (_reconcile_optional), and with the guard off nothing here changes
             entries.append((self.GUARD, tr.guard_state))
         for n, t in entries:
             if not t.is_contiguous():
@@ -524,31 +526,63 @@ class TrainState:
                 if t[k] != m[k]:
                     raise ValueError(f"{path}: tensor {t['name']}: {k} differs: the file has {t[k]!r}, this run {m[k]!r}")
 
-    def _reconcile_guard(self, header, a_len, path):
-        """The guard record is the one optional tensor, and the arena's last: -> (header as this run would have written it, its arena
-        bytes, the arena bytes to read from the file).  A file without it loads into a guarded run with the record zero (counters start at
-        zero); a file with it loads into a run without a guard, the entry ignored.  Each with a note."""
+    def _optional_notes(self):
+        """{name of an optional tensor: (note when the file has it and this run does not, note when only this run has it)}"""
+        return {
+            self.GUARD: ("the file holds a gradient guard's counters and this run has no guard (--clip_grad_norm 0, --skip_nonfinite "
+                         "false): the entry is ignored",
+                         "written without a gradient guard: this run's guard counters start at zero"),
+            self.LABEL_STATS: ("the file holds pseudo-label statistics and this run does not collect them (--label_stats false): the entry "
+                               "is ignored",
+                               "written without pseudo-label statistics: this run's label counters start at zero"),
+        }
+
+    def _reconcile_optional(self, header, a_len, path):
+        """Two tensors are optional: the guard record (the arena's last) and --label_stats' counters (among the launcher's tensors).  ->
+        (header as this run would have written it, its arena bytes, [(file offset, arena offset, bytes)] to read, [(arena offset,
+        bytes)] to zero).  A file without one of them loads into a run that has it with the tensor zero (counters start at zero); a
+        file with one loads into a run without it, the entry ignored.  Each with a note.  Any other difference is left as it is, for
+        check_header to refuse."""
+        notes = self._optional_notes()
         theirs = header["tensors"]
-        has = bool(theirs) and theirs[-1]["name"] == self.GUARD
-        mine = bool(self.names) and self.names[-1] == self.GUARD
-        if has == mine or self.part == "local":
-            return header, a_len, a_len
-        if has:
-            print(f"note: {path}: the file holds a gradient guard's counters and this run has no guard (--clip_grad_norm 0, --skip_nonfinite "
-                  f"false): the entry is ignored", flush=True)
-            keep = a_len - (int(theirs[-1]["nbytes"]) + 15) // 16 * 16
-            return dict(header, tensors=theirs[:-1]), keep, keep
-        print(f"note: {path}: written without a gradient guard: this run's guard counters start at zero", flush=True)
-        t, o, b = self.tensors[-1], self.offsets[-1], self.nbytes[-1]
-        entry = {"name": self.GUARD, "dtype": str(t.dtype), "shape": list(t.shape), "offset": o, "nbytes": b, "s0": 0, "s1": 0}
-        return dict(header, tensors=theirs + [entry]), a_len + (b + 15) // 16 * 16, a_len
+        their_names, my_names = {t["name"] for t in theirs}, set(self.names)
+        extra = [n for n in notes if n in their_names and n not in my_names]
+        missing = [n for n in notes if n in my_names and n not in their_names]
+        if not extra and not missing:
+            return header, a_len, [(0, 0, a_len)], []
+        slot = lambda nb: (int(nb) + 15) // 16 * 16
+        for n in extra:
+            print(f"note: {path}: {notes[n][0]}", flush=True)
+        for n in missing:
+            print(f"note: {path}: {notes[n][1]}", flush=True)
+        kept = [t for t in theirs if t["name"] not in extra]
+        out, segs, gaps, fi = [], [], [], 0
+        for n, t, o, b in zip(self.names, self.tensors, self.offsets, self.nbytes):
+            if n in missing:
+                out.append({"name": n, "dtype": str(t.dtype), "shape": list(t.shape), "offset": o, "nbytes": b, "s0": 0, "s1": 0})
+                gaps.append((o, slot(b)))
+                continue
+            if fi >= len(kept) or kept[fi]["name"] != n or int(kept[fi]["nbytes"]) != b:
+                return dict(header, tensors=kept), a_len, [], []            # another run's file: check_header names the difference
+            f_off, nb = int(kept[fi]["offset"]), slot(b)
+            if f_off < 0 or f_off + nb > a_len:
+                raise ValueError(f"{path}: tensor {n} lies outside the file's arena")
+            if segs and segs[-1][0] + segs[-1][2] == f_off and segs[-1][1] + segs[-1][2] == o:
+                segs[-1] = (segs[-1][0], segs[-1][1], segs[-1][2] + nb)
+            else:
+                segs.append((f_off, o, nb))
+            out.append(dict(kept[fi], offset=o))
+            fi += 1
+        if fi != len(kept):
+            return dict(header, tensors=kept), a_len, [], []
+        return dict(header, tensors=out), self.total, segs, gaps
 
     def load(self, path):
         """-> extra.  Verify, then restore: the checksums of what arrived on the device are compared with the file's BEFORE any tensor is
         overwritten; then counters, everything derived, and the RNG states last."""
         path = str(path)
         header, blobs, a_off, a_len = read_header(path)              # bad magic / truncation: nothing has been touched
-        header, a_len, f_len = self._reconcile_guard(header, a_len, path)
+        header, a_len, segs, gaps = self._reconcile_optional(header, a_len, path)
         self.check_header(header, path)
         if a_len != self.total:
             raise ValueError(f"{path}: arena size differs: the file has {a_len!r}, this run {self.total!r}")
@@ -556,12 +590,15 @@ class TrainState:
         self._ensure_buffers()
         tr, opt = self.trainer, self.trainer.optimizer
         host, arena, sums = self._hosts[0], self._arenas[0], self._sums[1]
+        f_len, got, view = sum(n for _, _, n in segs), 0, memoryview(host.numpy())
         with open(path, "rb") as f:
-            f.seek(a_off)
-            got = f.readinto(memoryview(host.numpy())[:f_len]) if f_len else 0
+            for f_off, h_off, n in segs:
+                f.seek(a_off + f_off)
+                got += f.readinto(view[h_off:h_off + n]) if n else 0
         if got != f_len:
             raise ValueError(f"{path}: truncated file ({got} arena bytes read, {f_len} announced)")
-        host[f_len:a_len].zero_()                                    # (a guard record the file does not have)
+        for h_off, n in gaps:
+            host[h_off:h_off + n].zero_()                            # (an optional tensor the file does not have)
         if self.cuda:
             arena.copy_(host, non_blocking=True)
             self._table.restore(arena, sums, False)

@@ -405,6 +405,178 @@ __global__ __launch_bounds__(256) void refine_merge_kernel(const RefineArgs a, c
     }
 }
 
+// ---- per-step pseudo-label statistics and the teacher finite check -----------------------------------------------
+// THE definition of the counter vector (uint64 elements) for the device and the host: off[i] of steps, pix, main[K+1], aux[K+1], agree,
+// inter[K], pred[K], bad_cam, bad_cam_aux; -> the number of elements
+constexpr int kStatsMaxK = 128;
+constexpr int kStatsSlots = 4 * kStatsMaxK + 7;
+constexpr unsigned kStatsMaxGroups = 1024;
+__host__ __device__ inline int label_stats_offsets(int K, int (&off)[COSA_LABEL_STATS_SLOTS])
+{
+    off[0] = 0;                  // steps
+    off[1] = 1;                  // pix
+    off[2] = 2;                  // main[K+1]
+    off[3] = off[2] + K + 1;     // aux[K+1]
+    off[4] = off[3] + K + 1;     // agree
+    off[5] = off[4] + 1;         // inter[K]
+    off[6] = off[5] + K;         // pred[K]
+    off[7] = off[6] + K;         // bad_cam
+    off[8] = off[7] + 1;         // bad_cam_aux
+    return off[8] + 1;
+}
+
+struct LabelStatsArgs {
+    const float *mask_main, *mask_aux, *seg, *cls, *cam, *cam_aux;
+    const int32_t *boxes;
+    unsigned long long *counters;
+    unsigned int *flag;                     // step-local: set when this call meets a non-finite CAM element
+    int B, K, S, h, w, vec;                 // vec: every full-resolution row may be read as float4 (S % 4 == 0, 16-byte aligned bases)
+    float sy, sx, ignore;
+};
+
+// ctr[slot] += 1 for every lane with `valid`, one LDS atomic per distinct slot of the wavefront (a crop holds a handful of labels: a
+// plain atomic per lane would serialise 64 deep on one address).  `todo` is wave-uniform, so every lane leaves the loop together.
+__device__ __forceinline__ void wave_count(unsigned long long *ctr, int slot, bool valid)
+{
+    unsigned long long todo = __ballot(valid);
+    while (todo) {
+        const int leader = __ffsll(todo) - 1;
+        const int s = __builtin_amdgcn_readlane(slot, leader);
+        const unsigned long long same = __ballot(valid && slot == s);
+        if ((int)__lane_id() == leader) atomicAdd(&ctr[s], (unsigned long long)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+__device__ __forceinline__ void load_f32x4(const float *__restrict__ p, int X, int S, int vec, float (&v)[4])
+{
+    if (vec) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = X + k < S ? p[k] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ bool nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// A thread owns four adjacent pixels of a row: the source rows and their weights once per thread, the source columns once per pixel,
+// the K low-resolution logit planes (L2-resident) through the same src_index_r / bilerp calls as eval_labels_kernel's lab_vd.  The two
+// masks and the CAM planes of the present classes are the only full-resolution streams, read once as float4.  A wavefront's 64 items
+// lie in one image (two or more only across an image boundary or at tiny S): the image's label row becomes a wave-uniform bit mask with
+// two loads and two ballots, so the class loops branch on scalars and an absent class costs no load at all.  Counts meet in
+// workgroup-private LDS counters and leave with one global integer atomic per non-zero slot: the same bits in any order.
+__global__ __launch_bounds__(256) void label_stats_kernel(const LabelStatsArgs a)
+{
+    __shared__ unsigned long long ctr[kStatsSlots];
+    int off[COSA_LABEL_STATS_SLOTS];
+    const int n = label_stats_offsets(a.K, off);
+    for (int i = threadIdx.x; i < n; i += 256) ctr[i] = 0;
+    __syncthreads();
+    const int S = a.S, K = a.K, S4 = (S + 3) >> 2;
+    const unsigned per_img = (unsigned)S * S4, total = per_img * a.B;          // < 2^31 (entry point)
+    const size_t ss = (size_t)S * S, hw = (size_t)a.h * a.w;
+    const int lane = (int)__lane_id();
+    const unsigned wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
+    unsigned n_pix = 0, n_agree = 0, n_bad[2] = {0, 0};
+    for (unsigned base = blockIdx.x * 256u + wave_off; base < total; base += gridDim.x * 256u) {          // (wave-uniform)
+        const unsigned item = base + lane;
+        const unsigned last = base + 63 < total - 1 ? base + 63 : total - 1;
+        const int b_lo = base / per_img, b_hi = last / per_img;
+        bool in[4] = {false, false, false, false};
+        float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f}, av[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        int iv[4] = {0, 0, 0, 0};
+        int b = -1, Y = 0, X = 0;
+        if (item < total) {
+            b = item / per_img;
+            const unsigned r = item - b * per_img;
+            Y = r / S4;
+            X = (r - Y * S4) * 4;
+            const int32_t *bx = a.boxes + 4 * b;
+            const bool row_in = Y >= bx[0] && Y < bx[1];
+#pragma unroll
+            for (int k = 0; k < 4; k++) in[k] = row_in && X + k >= bx[2] && X + k < bx[3] && X + k < S;
+        }
+        const bool any = in[0] || in[1] || in[2] || in[3];
+        if (any) {
+            const size_t o = ((size_t)b * S + Y) * S + X;
+            load_f32x4(a.mask_main + o, X, S, a.vec, mv);
+            if (a.mask_aux) load_f32x4(a.mask_aux + o, X, S, a.vec, av);
+        }
+        for (int bb = b_lo; bb <= b_hi; bb++) {
+            // present[0] bit i: class i + 1 is in image bb's label row (i < 64); present[1]: classes 65..128
+            const float *cl = a.cls + (size_t)bb * (K - 1);
+            const unsigned long long present[2] = {__ballot(lane < K - 1 && cl[lane < K - 1 ? lane : 0] != 0.0f),
+                                                   __ballot(lane + 64 < K - 1 && cl[lane + 64 < K - 1 ? lane + 64 : 0] != 0.0f)};
+            if (!(any && b == bb)) continue;
+            int y0, y1, x0[4], x1[4];
+            float ly0, ly1, lx0[4], lx1[4];
+            src_index_r(Y, a.h, a.sy, y0, y1, ly0, ly1);
+#pragma unroll
+            for (int k = 0; k < 4; k++) src_index_r(X + k < S ? X + k : S - 1, a.w, a.sx, x0[k], x1[k], lx0[k], lx1[k]);
+            const float *sb = a.seg + (size_t)bb * K * hw;
+            float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (int c = 0; c < K; c++) {
+                // seg_validation: an absent class is -1e5, its plane unread (a scalar branch: `present` is wave-uniform)
+                const bool live = c == 0 || ((present[(c - 1) >> 6] >> ((c - 1) & 63)) & 1ull);
+                const float *pl = sb + (size_t)c * hw;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float v = live ? bilerp(pl, a.w, y0, y1, x0[k], x1[k], ly0, ly1, lx0[k], lx1[k]) : -1e5f;
+                    if (c == 0 || v > bv[k]) { bv[k] = v; iv[k] = c; }
+                }
+            }
+            for (int g = 0; g < 2; g++) {
+                const float *cams = g ? a.cam_aux : a.cam;
+                if (!cams) continue;
+                const float *cb = cams + (size_t)bb * (K - 1) * ss + (size_t)Y * S + X;
+                for (int half = 0; half < 2; half++) {
+                    for (unsigned long long m = present[half]; m; m &= m - 1) {          // planes of absent classes are never read
+                        const int c = 64 * half + __ffsll(m) - 1;
+                        float v[4];
+                        load_f32x4(cb + (size_t)c * ss, X, S, a.vec, v);
+#pragma unroll
+                        for (int k = 0; k < 4; k++) n_bad[g] += (in[k] && nonfinite_bits(v[k])) ? 1u : 0u;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool m_ign = mv[k] == a.ignore, m_cls = mv[k] >= 0.0f && mv[k] < (float)K && mv[k] == (float)(int)mv[k];          // a label is an integer
+            const int m = m_ign ? K : (int)mv[k];
+            n_pix += in[k] ? 1u : 0u;
+            wave_count(ctr + off[2], m, in[k] && (m_ign || m_cls));
+            if (a.mask_aux) {
+                const bool a_ign = av[k] == a.ignore, a_cls = av[k] >= 0.0f && av[k] < (float)K && av[k] == (float)(int)av[k];
+                wave_count(ctr + off[3], a_ign ? K : (int)av[k], in[k] && (a_ign || a_cls));
+                n_agree += (in[k] && mv[k] == av[k]) ? 1u : 0u;
+            }
+            wave_count(ctr + off[6], iv[k], in[k] && m_cls && !m_ign);
+            wave_count(ctr + off[5], iv[k], in[k] && m_cls && !m_ign && iv[k] == m);
+        }
+    }
+    if (n_pix) atomicAdd(&ctr[off[1]], (unsigned long long)n_pix);
+    if (n_agree) atomicAdd(&ctr[off[4]], (unsigned long long)n_agree);
+    if (n_bad[0]) atomicAdd(&ctr[off[7]], (unsigned long long)n_bad[0]);
+    if (n_bad[1]) atomicAdd(&ctr[off[8]], (unsigned long long)n_bad[1]);
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += 256)
+        if (ctr[i]) atomicAdd(&a.counters[i], ctr[i]);
+    if (threadIdx.x == 0 && (ctr[off[7]] | ctr[off[8]])) atomicOr(a.flag, 1u);
+}
+
+// after label_stats_kernel on the same stream: the step count, and the factor the trainer multiplies its loss with
+__global__ void label_stats_finish_kernel(unsigned long long *__restrict__ counters, const unsigned int *__restrict__ flag,
+                                          float *__restrict__ step_scale)
+{
+    if (threadIdx.x == 0) {
+        counters[0] += 1;
+        *step_scale = *flag ? __uint_as_float(0x7fc00000u) : 1.0f;
+    }
+}
+
 __global__ __launch_bounds__(256) void spec_expf_kernel(const float *__restrict__ x, float *__restrict__ y, long long n)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -620,6 +792,51 @@ extern "C" int cosa_export_refine(const float *image, const float *cam, const fl
         Pfinal = src;
     }
     hipLaunchKernelGGL(refine_merge_kernel, gm, dim3(256), 0, st, a, Pfinal);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+// ---- per-step pseudo-label statistics ----------------------------------------------------------------------------
+extern "C" size_t cosa_label_stats_layout(int K, size_t *offsets)
+{
+    if (!offsets || K < 2 || K > kStatsMaxK) {
+        set_error("cosa_label_stats_layout: K must be in 2..%d (got %d) and offsets non-null", kStatsMaxK, K);
+        return 0;
+    }
+    int off[COSA_LABEL_STATS_SLOTS];
+    const int n = label_stats_offsets(K, off);
+    for (int i = 0; i < COSA_LABEL_STATS_SLOTS; i++) offsets[i] = (size_t)off[i];
+    return (size_t)n;
+}
+
+extern "C" int cosa_label_stats(const float *mask_main, const float *mask_aux, const float *seg_logits, const float *cls_label,
+                                const int32_t *boxes, const float *cam, const float *cam_aux, int B, int K, int S, int h, int w,
+                                int ignore_index, unsigned long long *counters, float *step_scale, void *workspace, void *stream)
+{
+    COSA_REQUIRE(mask_main && seg_logits && cls_label && boxes && counters && step_scale && workspace,
+                 "cosa_label_stats: null argument (only mask_aux, cam and cam_aux may be NULL)");
+    COSA_REQUIRE(K >= 2 && K <= kStatsMaxK, "cosa_label_stats: K must be in 2..%d (got %d)", kStatsMaxK, K);
+    COSA_REQUIRE(B > 0 && S > 0 && h > 0 && w > 0 && h <= S && w <= S,
+                 "cosa_label_stats: sizes outside the envelope (B %d, S %d, h %d, w %d: all > 0, h and w <= S)", B, S, h, w);
+    COSA_REQUIRE(ignore_index < 0 || ignore_index >= K, "cosa_label_stats: ignore_index %d is a class index (K %d)", ignore_index, K);
+    COSA_REQUIRE((size_t)B * S * ((S + 3) / 4) < 0x7fffffffull, "cosa_label_stats: maps too large (B %d, S %d)", B, S);
+    COSA_REQUIRE((((size_t)counters | (size_t)workspace) & 7) == 0, "cosa_label_stats: counters and workspace must be 8-byte aligned");
+    LabelStatsArgs a;
+    a.mask_main = mask_main; a.mask_aux = mask_aux; a.seg = seg_logits; a.cls = cls_label; a.cam = cam; a.cam_aux = cam_aux;
+    a.boxes = boxes; a.counters = counters; a.flag = (unsigned int *)workspace;
+    a.B = B; a.K = K; a.S = S; a.h = h; a.w = w;
+    a.sy = (float)h / (float)S; a.sx = (float)w / (float)S; a.ignore = (float)ignore_index;
+    a.vec = (S & 3) == 0 && ((((size_t)mask_main | (size_t)mask_aux | (size_t)cam | (size_t)cam_aux) & 15) == 0);
+    hipStream_t st = as_stream(stream);
+    COSA_HIP_CHECK(hipMemsetAsync(workspace, 0, COSA_LABEL_STATS_WORKSPACE_BYTES, st));
+    // at most kStatsMaxGroups workgroups (four per CU: one resident round, and few workgroups meeting at the global counters), the rest
+    // by grid stride with every workgroup making the same number of rounds
+    const unsigned groups = ((unsigned)B * S * ((S + 3) / 4) + 255u) / 256u;
+    const unsigned rounds = (groups + kStatsMaxGroups - 1) / kStatsMaxGroups;
+    const unsigned grid = (groups + rounds - 1) / rounds;
+    hipLaunchKernelGGL(label_stats_kernel, dim3(grid), dim3(256), 0, st, a);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(label_stats_finish_kernel, dim3(1), dim3(64), 0, st, counters, (const unsigned int *)workspace, step_scale);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

@@ -9,6 +9,7 @@ loss_dataframe.pt).  What differs is where the work runs: one process per GPU ov
 input pipeline, the fused training step (CoSATrainer.step: no per-iteration host sync -- the losses and the classification AP of an
 iteration stay on the device and are read back once per `log_iters`), device-resident evaluation.  `--usepar true` is live."""
 import datetime
+import json
 import os
 import random
 import sys
@@ -26,7 +27,7 @@ from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
 from .train_step import CoSATrainer, default_args
-from .utils import torch_helper
+from .utils import seg_helper, torch_helper
 
 
 def init_distributed_mode(args):
@@ -77,6 +78,43 @@ def check_supported(args):
         print("note:", n, flush=True)
 
 
+def label_stats_line(summary):
+    """what --label_stats adds to the interval's log line"""
+    return " ignore: %.3f, fg: %.3f, aux_agree: %.3f, student_miou: %.3f, teacher_nonfinite: %d" % (
+        summary["ignore_frac"], summary["fg_frac"], summary["aux_agree"], summary["student_miou"], summary["teacher_nonfinite"])
+
+
+def label_stats_record(summary, n_iter):
+    """one line of <output_dir>/label_stats.jsonl: the full summary of an interval, per-class lists included"""
+    return json.dumps(dict(summary, iters=int(n_iter)))
+
+
+def append_label_stats(output_dir, summary, n_iter):
+    with (Path(output_dir) / "label_stats.jsonl").open("a") as f:
+        f.write(label_stats_record(summary, n_iter) + "\n")
+
+
+def read_interval(acc, log_iters, guard, stats):
+    """The log interval's ONE host sync: -> (means of the running sums `acc`, [grad_norm, skipped, clipped] of the guard record or None,
+    the label counters as ints or None).  The guard's own tensor and the label counters ride along in the same transfer (`acc` keeps
+    its length; counts are exact in a double: an interval's stay far below 2^53).  `acc` and the label counters are an interval's:
+    both are zeroed on the device afterwards; the guard's counters are the run's and stay."""
+    parts = [acc / log_iters]
+    if guard is not None:
+        parts += [torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]
+    if stats is not None:
+        parts.append(stats.double())
+    vals = (torch.cat(parts) if len(parts) > 1 else parts[0]).tolist()
+    n = acc.numel()
+    vals, rest = vals[:n], vals[n:]
+    gvals, rest = (rest[:3], rest[3:]) if guard is not None else (None, rest)
+    svals = [int(v) for v in rest] if stats is not None else None
+    acc.zero_()
+    if stats is not None:
+        stats.zero_()
+    return vals, gvals, svals
+
+
 def main(args):
     check_supported(args)
     output_dir = Path(args.output_dir) if args.output_dir else Path(args.work_dir) / args.name
@@ -114,7 +152,8 @@ def main(args):
 
     keys = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
     acc = torch.zeros(len(keys), device=device, dtype=torch.float64)           # running sums of the interval, on the device
-    trainer.extra_state = {"launcher.acc": acc}                                # ... and part of a state file: saved and restored in place, no sync
+    # ... and part of a state file: saved and restored in place, no sync (next to what the trainer keeps there: --label_stats' counters)
+    trainer.extra_state = dict(getattr(trainer, "extra_state", {}), **{"launcher.acc": acc})
     resume = args.resume
     if resume == "auto":
         resume = checkpoint.newest_state(output_dir)                                # none: a fresh start
@@ -154,13 +193,8 @@ def main(args):
                 logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
                 (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
-            guard = trainer.guard_state                                           # None: no gradient guard, the line below as ever
-            if guard is None:
-                vals = (acc / args.log_iters).tolist()                            # the one host sync of the interval
-            else:      # the guard's own tensor rides along in the same sync: the last step's norm and the run's counters (`acc` keeps its length)
-                vals = torch.cat([acc / args.log_iters, torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]).tolist()
-                vals, gvals = vals[:len(keys)], vals[len(keys):]
-            acc.zero_()
+            guard, stats = trainer.guard_state, trainer.label_stats_state         # None: no gradient guard / no --label_stats, the line as ever
+            vals, gvals, svals = read_interval(acc, args.log_iters, guard, stats)   # the one host sync of the interval
             now = time.time()
             itertime, tick = (now - tick) / args.log_iters, now
             delta = datetime.datetime.now().replace(microsecond=0) - time0
@@ -174,6 +208,10 @@ def main(args):
                         % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
                 if guard is not None:
                     line += " grad_norm: %.4f, skipped: %d, clipped: %d" % (gvals[0], int(gvals[1]), int(gvals[2]))
+                if stats is not None:
+                    summary = seg_helper.label_stats_summary(svals, args.num_classes)
+                    line += label_stats_line(summary)
+                    append_label_stats(output_dir, summary, n_iter + 1)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,

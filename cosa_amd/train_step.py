@@ -38,7 +38,7 @@ def default_args(dataset="VOC12", **over):
              aux_cam2seg=True, aux_cam2seg_alpha=0.5, aux_seg2cam=False, aux_seg2cam_alpha=0.5, after_softmax=False,
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
-             clip_grad_norm=0.0, skip_nonfinite=False)
+             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -160,6 +160,13 @@ class CoSATrainer:
         self.guard_state = None
         if guard_on:
             self.guard_state = self._fused_step.guard if self._fused_step is not None else torch_helper.new_guard_state(device)
+        # pseudo-label statistics and the teacher finite check: off (None) unless --label_stats true.  The counters
+        # are state of the run: they travel in a state file as `label_stats.counters` of extra_state
+        self.label_stats_state = None
+        if bool(getattr(args, "label_stats", False)):
+            self.label_stats_state = seg_helper.new_label_stats(args.num_classes, device)
+            self._step_scale = torch.ones(1, device=device, dtype=torch.float32)
+            self.extra_state = {"label_stats.counters": self.label_stats_state}
         if on:
             self._teacher_shadows.optimizer_owned = self._student_shadows.optimizer_owned = self._fused_step is not None
             # bf16 W^T copies of the student's block projections (the input-gradient GEMMs run the forward kernel on them)
@@ -291,6 +298,9 @@ class CoSATrainer:
                 refine_mask_label = seg_helper.cam2mask(img_denorm, img_box, cam_ps, cls_label, threhigh, threlow,
                                                         refine_model=self.refine_model, downscale=args.par_downscale,
                                                         _fold_validation=True)
+            if self.label_stats_state is not None:
+                self.update_label_stats(refine_mask_label, refine_mask_label_aux if args.aux_cam2seg else None, seg_pred, cls_label, img_box,
+                                        cam_ps, cam_aux_ps if args.aux_cam2seg else None)
         if fused:
             # one forward + one backward kernel instead of ~10 full-resolution passes (same maths, main.py:167-212)
             seg_loss, reg_loss = seg_helper.fused_seg_and_energy_loss(seg_pred, refine_mask_label, refine_mask_label_aux, simg,
@@ -326,7 +336,12 @@ class CoSATrainer:
             wvec = self._loss_weights[wkey] = torch.tensor(wl, device=cls_loss.device, dtype=torch.float32)
         loss = torch.dot(torch.stack([cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(),
                                       reg_loss.reshape(()).float()]), wvec)
-        return loss, dict(overall_loss=loss.detach(), cls_loss=cls_loss.detach(), cls_aux_loss=cls_loss_aux.detach(),
+        overall = loss.detach()
+        if self.label_stats_state is not None and self._skip_nonfinite:
+            # teacher refusal: step_scale is 1.0f (an exact product: the bits of the step without it) or, when this step's CAMs held a
+            # non-finite element, NaN -- every gradient is then NaN and the gradient guard refuses the step (under DDP on every rank)
+            loss = loss * self._step_scale.reshape(())
+        return loss, dict(overall_loss=overall, cls_loss=cls_loss.detach(), cls_aux_loss=cls_loss_aux.detach(),
                           seg_loss=seg_loss.detach(), cam_loss=cam_loss.detach(), reg_loss=reg_loss.detach(),
                           mask=refine_mask_label, cls_logits=cls_final.detach(), cls_aux_logits=cls_aux.detach())
 
@@ -367,6 +382,22 @@ class CoSATrainer:
         """{applied, skipped, clipped} of the gradient guard over the run so far (synchronises: for tests and the log interval); None
         when the guard is off"""
         return torch_helper.guard_counters(self.guard_state) if self.guard_state is not None else None
+
+    # -- pseudo-label statistics (DESIGN.md section 11) --
+    @torch.no_grad()
+    def update_label_stats(self, mask_main, mask_aux, seg_logits, cls_label, img_box, cam, cam_aux):
+        """accumulate one step into the counters (the HIP reduction on the GPU, its torch restatement on a host trainer) and write
+        `_step_scale`; no sync"""
+        fn = seg_helper.label_stats if self.device.type == "cuda" else seg_helper.label_stats_torch
+        return fn(mask_main, mask_aux, seg_logits, cls_label, img_box, cam, cam_aux, self.label_stats_state,
+                  ignore_index=self.args.ignore_index, step_scale=self._step_scale)
+
+    def label_stats(self):
+        """the summary (seg_helper.label_stats_summary) of the counters accumulated since they were last zeroed (synchronises: for tests
+        and the log interval); None when --label_stats is off"""
+        if self.label_stats_state is None:
+            return None
+        return seg_helper.label_stats_summary(self.label_stats_state, self.args.num_classes)
 
     # -- full-state checkpoints (cosa_amd/checkpoint.py, DESIGN.md section 9) --
     def train_state(self):

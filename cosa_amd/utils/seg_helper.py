@@ -230,6 +230,136 @@ def eval_label_maps(cam, seg, cls_label, size, bkg_thre):
     return lc, lp, lv
 
 
+# --------------------------------------------------------------------------------------------
+# per-step pseudo-label statistics and the teacher finite check
+# --------------------------------------------------------------------------------------------
+LABEL_STATS_SLOTS = ("steps", "pix", "main", "aux", "agree", "inter", "pred", "bad_cam", "bad_cam_aux")     # cosa_label_stats_layout's order
+LABEL_STATS_MAX_K = 128
+
+
+def label_stats_layout(K):
+    """cosa_label_stats_layout: ({slot name: offset in elements}, number of elements) of the counter vector for K = num_classes
+    (background included).  Needs no device."""
+    off = (ctypes.c_size_t * len(LABEL_STATS_SLOTS))()
+    n = _C.lib().cosa_label_stats_layout(int(K), off)
+    if n == 0:
+        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
+    return {name: int(off[i]) for i, name in enumerate(LABEL_STATS_SLOTS)}, int(n)
+
+
+def new_label_stats(K, device):
+    """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay far below 2^63)"""
+    return torch.zeros(label_stats_layout(K)[1], dtype=torch.int64, device=device)
+
+
+def _label_stats_shapes(mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux, counters):
+    B, S = mask_main.shape[0], mask_main.shape[-1]
+    K = seg_logits.shape[1]
+    h, w = seg_logits.shape[-2:]
+    if mask_main.shape != (B, S, S) or (mask_aux is not None and mask_aux.shape != (B, S, S)) or seg_logits.shape != (B, K, h, w) or \
+            cls_label.shape != (B, K - 1) or any(c is not None and c.shape != (B, K - 1, S, S) for c in (cam, cam_aux)):
+        raise ValueError("label_stats: masks must be [B,S,S], seg_logits [B,K,h,w], cls_label [B,K-1] and the CAMs [B,K-1,S,S]")
+    if counters.dtype != torch.int64 or counters.shape != (4 * K + 7,) or not counters.is_contiguous():
+        raise ValueError(f"label_stats: counters must be a contiguous int64 vector of {4 * K + 7} elements (new_label_stats)")
+    return B, K, S, int(h), int(w)
+
+
+def label_stats(mask_main, mask_aux, seg_logits, cls_label, img_box, cam, cam_aux, counters, ignore_index=255, step_scale=None):
+    """One reduction (cosa_label_stats) over what a training step holds anyway, accumulated into `counters` on the device: label-map
+    histograms of the main and auxiliary pseudo labels inside the crop boxes, their agreement, the per-class intersection / count of
+    the student's own segmentation against the main labels, and the non-finite elements of the present classes' CAM planes.
+    mask_aux, cam, cam_aux may be None.  -> step_scale, a one-element fp32 device tensor: 1.0 when this call met only finite CAMs,
+    NaN otherwise.  No host sync."""
+    _C.require_cuda(mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux, counters)
+    f = lambda t: t.detach().contiguous().float() if t is not None else None
+    mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux = (f(t) for t in (mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux))
+    B, K, S, h, w = _label_stats_shapes(mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux, counters)
+    dev = mask_main.device
+    boxes = _boxes_to_device(img_box, dev)
+    if step_scale is None:
+        step_scale = torch.empty(1, device=dev, dtype=torch.float32)
+    ws = _C.workspace(8, dev, "label_stats")                         # COSA_LABEL_STATS_WORKSPACE_BYTES
+    _C.check(_C.lib().cosa_label_stats(_C.ptr(mask_main), _C.ptr(mask_aux), _C.ptr(seg_logits), _C.ptr(cls_label), _C.ptr(boxes), _C.ptr(cam),
+                                       _C.ptr(cam_aux), B, K, S, h, w, int(ignore_index), _C.ptr(counters), _C.ptr(step_scale), _C.ptr(ws),
+                                       _C.stream_ptr()), "cosa_label_stats")
+    return step_scale
+
+
+@torch.no_grad()
+def label_stats_torch(mask_main, mask_aux, seg_logits, cls_label, img_box, cam, cam_aux, counters, ignore_index=255, step_scale=None):
+    """label_stats in plain torch, for host trainers (the role guarded_torch_step plays for the gradient guard): F.interpolate + argmax
+    instead of the kernel's spec-R resize, the same counters in the same layout."""
+    f = lambda t: t.detach().float() if t is not None else None
+    mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux = (f(t) for t in (mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux))
+    B, K, S, h, w = _label_stats_shapes(mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux, counters)
+    if K > LABEL_STATS_MAX_K or h > S or w > S or 0 <= int(ignore_index) < K:
+        raise ValueError(f"label_stats: outside the envelope (K {K} <= {LABEL_STATS_MAX_K}, h {h} and w {w} <= S {S}, ignore_index no class)")
+    dev = mask_main.device
+    off, _ = label_stats_layout(K)
+    box = torch.as_tensor(img_box).to(device=dev, dtype=torch.int64)
+    ar = torch.arange(S, device=dev)
+    inside = ((ar[None, :, None] >= box[:, 0, None, None]) & (ar[None, :, None] < box[:, 1, None, None]) &
+              (ar[None, None, :] >= box[:, 2, None, None]) & (ar[None, None, :] < box[:, 3, None, None]))
+    add = torch.zeros_like(counters)
+    add[off["steps"]] = 1
+    add[off["pix"]] = inside.sum()
+
+    def hist(mask, valid):
+        """[K+1] counts of the values 0..K-1 and (slot K) ignore_index"""
+        slot = torch.where(mask == ignore_index, torch.full_like(mask, K), mask)
+        ok = valid & (slot >= 0) & (slot <= K) & (slot == slot.floor())          # a value that is no label is not counted
+        return torch.bincount(slot[ok].long(), minlength=K + 1)
+
+    add[off["main"]:off["main"] + K + 1] = hist(mask_main, inside)
+    if mask_aux is not None:
+        add[off["aux"]:off["aux"] + K + 1] = hist(mask_aux, inside)
+        add[off["agree"]] = (inside & (mask_main == mask_aux)).sum()
+    student = seg_validation(F.interpolate(seg_logits, size=(S, S), mode="bilinear", align_corners=False), cls_label).argmax(dim=1)
+    labelled = inside & (mask_main >= 0) & (mask_main < K) & (mask_main == mask_main.floor())
+    add[off["pred"]:off["pred"] + K] = torch.bincount(student[labelled], minlength=K)
+    add[off["inter"]:off["inter"] + K] = torch.bincount(student[labelled & (student == mask_main.long())], minlength=K)
+    bad = torch.zeros((), dtype=torch.int64, device=dev)
+    for name, c in (("bad_cam", cam), ("bad_cam_aux", cam_aux)):
+        if c is not None:
+            n = (~torch.isfinite(c) & (cls_label != 0)[:, :, None, None] & inside[:, None]).sum()
+            add[off[name]] = n
+            bad = bad + n
+    counters += add
+    if step_scale is None:
+        step_scale = torch.empty(1, device=dev, dtype=torch.float32)
+    step_scale.copy_(torch.where(bad > 0, torch.full((), float("nan"), device=dev), torch.ones((), device=dev)).reshape(1))
+    return step_scale
+
+
+def label_stats_summary(counters, K):
+    """The counter vector (tensor, array or list; a device tensor synchronises) as the figures a log line shows: ignore / background /
+    foreground fractions of the main and auxiliary label maps inside the boxes, the share of pixels where the two agree, the student's
+    mIoU against the main labels (mean of inter / (pred + main - inter) over the classes with a non-zero union) with the per-class
+    list (None for an empty union), the non-finite CAM elements met, and the steps accumulated.  Zero pixels give zeros, not NaN."""
+    c = [int(v) for v in (counters.tolist() if hasattr(counters, "tolist") else counters)]
+    off, n = label_stats_layout(K)
+    if len(c) != n:
+        raise ValueError(f"label_stats_summary: {len(c)} counters, K = {K} has {n}")
+    pix = c[off["pix"]]
+    frac = lambda v: v / pix if pix else 0.0
+    out = {"steps": c[off["steps"]], "pix": pix}
+    for tag, name in (("", "main"), ("aux_", "aux")):
+        hist = c[off[name]:off[name] + K + 1]
+        out[tag + "ignore_frac"], out[tag + "bg_frac"], out[tag + "fg_frac"] = frac(hist[K]), frac(hist[0]), frac(sum(hist[1:K]))
+        out[tag + "class_pixels"] = hist
+    out["aux_agree"] = frac(c[off["agree"]])
+    main = c[off["main"]:off["main"] + K]
+    inter, pred = c[off["inter"]:off["inter"] + K], c[off["pred"]:off["pred"] + K]
+    union = [p + m - i for p, m, i in zip(pred, main, inter)]
+    iou = [i / u if u else None for i, u in zip(inter, union)]
+    live = [v for v in iou if v is not None]
+    out["student_iou"] = iou
+    out["student_miou"] = sum(live) / len(live) if live else 0.0
+    out["teacher_nonfinite"] = c[off["bad_cam"]] + c[off["bad_cam_aux"]]
+    out["teacher_nonfinite_main"], out["teacher_nonfinite_aux"] = c[off["bad_cam"]], c[off["bad_cam_aux"]]
+    return out
+
+
 EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16,          # COSA_EXPORT_* of include/cosa_hip.h
                "pseudo_par": 32, "pseudo_aux_par": 64}
 _EXPORT_SLOTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "rawcam_idx", "rawcam_aux_idx", "pseudo_par", "pseudo_aux_par")

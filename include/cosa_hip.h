@@ -624,6 +624,36 @@ int cosa_export_refine(const float *image, const float *cam, const float *cam_au
                        int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, int downscale,
                        const int *dilations, int n_dil, int par_iters, void *record, size_t record_bytes, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* ---------------------------------------------------------------------------------------
+ * Per-step pseudo-label statistics and the teacher finite check: one reduction over tensors the
+ * training step already holds, accumulated on the device in a vector of uint64 counters.
+ * cosa_label_stats_layout: THE definition of that vector for host and device.  K = num_classes (background included,
+ *   2..128).  offsets[COSA_LABEL_STATS_SLOTS] (in elements) of, in order: steps; pix (pixels inside the crop boxes);
+ *   main[K+1] (pixels of the main label map per value 0..K-1, slot K = ignore); aux[K+1]; agree (pixels where main and
+ *   auxiliary label are equal, ignore counted as a value); inter[K] and pred[K] (per class: student label == main label,
+ *   and student label, over the pixels whose main label is not ignore); bad_cam; bad_cam_aux (non-finite CAM elements).
+ *   Returns the number of elements (4K + 7), 0 on bad arguments.
+ * cosa_label_stats: mask_main / mask_aux fp32 [B,S,S] in {0..K-1, ignore_index} (cosa_cam2mask_multi's output);
+ *   seg_logits fp32 [B,K,h,w], the student's low-resolution logits; cls_label fp32 [B,K-1]; boxes int32 [B,4]
+ *   (y0,y1,x0,x1); cam / cam_aux fp32 [B,K-1,S,S].  mask_aux, cam and cam_aux may be NULL: their slots stay untouched and
+ *   agree is not advanced.  A mask value that is neither an integer in 0..K-1 nor ignore_index is counted in pix only.
+ *   Only pixels inside an image's box count, for every slot; an empty box contributes nothing.
+ *   Student label: the K planes resized to (S,S) by spec R (scale = (float)h / (float)S), classes absent from cls_label
+ *   replaced by -1e5 (background always live), first maximum in class order: the lab_vd rule of cosa_eval_labels.
+ *   bad_*: elements that are not finite, over the planes of PRESENT classes only (an absent class's plane is never read).
+ *   step_scale: one device fp32, written by every call: 1.0f when this call met no non-finite element, a quiet NaN
+ *   otherwise.  The counters accumulate from call to call (integer atomics: the same bits in any order) and steps
+ *   advances by one.  workspace: COSA_LABEL_STATS_WORKSPACE_BYTES of device memory, 8-byte aligned: the step-local flag
+ *   behind step_scale, cleared by the call itself on `stream`.  Envelope: K <= 128, S, h, w > 0, h and w <= S; anything
+ *   else is COSA_EINVAL, nothing is launched or clamped.  One memset node and two launches.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_LABEL_STATS_SLOTS 9
+#define COSA_LABEL_STATS_WORKSPACE_BYTES 8
+size_t cosa_label_stats_layout(int K, size_t *offsets);
+int cosa_label_stats(const float *mask_main, const float *mask_aux, const float *seg_logits, const float *cls_label,
+                     const int32_t *boxes, const float *cam, const float *cam_aux, int B, int K, int S, int h, int w,
+                     int ignore_index, unsigned long long *counters, float *step_scale, void *workspace, void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
