@@ -165,13 +165,16 @@ _SIGS.update({
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose
-# name is not `name + "_f16"` (fn16 resolves through it); the regular ones are listed for their signatures
+# name is not `name + "_f16"`, plus the attention backward's pair, which is regular but listed so that every 16-bit entry point a test picks
+# by dtype is named in one place (fn16 resolves through it); the other regular ones are listed below for their signatures
 _F16_TWIN = {"cosa_gemm_bf16": "cosa_gemm_f16", "cosa_gemm_wgrad_bf16": "cosa_gemm_wgrad_f16",
              # fp16x3 (round 6): the three-term GEMM / attention with fp16 halves
-             "cosa_gemm_bf16x3": "cosa_gemm_f16x3", "cosa_attn_fwd_bf16x3": "cosa_attn_fwd_f16x3"}
+             "cosa_gemm_bf16x3": "cosa_gemm_f16x3", "cosa_attn_fwd_bf16x3": "cosa_attn_fwd_f16x3",
+             # the student's attention backward: the fp16 build of the same three kernels
+             "cosa_attn_bwd": "cosa_attn_bwd_f16", "cosa_attn_bwd_workspace_bytes": "cosa_attn_bwd_workspace_bytes_f16"}
 for _bf in list(_F16_TWIN) + ["cosa_layernorm", "cosa_conv3x3_dilated_nhwc", "cosa_conv3x3_dilated_wgrad", "cosa_gemm_set_variant",
                               "cosa_gemm_set_stamp_slot", "cosa_attn_workspace_bytes", "cosa_attn_prepare_vt", "cosa_attn_fwd",
-                              "cosa_attn_bwd_workspace_bytes", "cosa_attn_bwd", "cosa_split_rows", "cosa_layernorm_split"]:
+                              "cosa_split_rows", "cosa_layernorm_split"]:
     _SIGS[_F16_TWIN.get(_bf, _bf + "_f16")] = _SIGS[_bf]
 
 # entry points added by later translation units register themselves here (vit / gemm / attention)
