@@ -1579,14 +1579,105 @@ using namespace cosa;
 #define cosa_conv3x3_dilated_nhwc cosa_conv3x3_dilated_nhwc_f16
 #endif
 
+#include <type_traits>
+
 static size_t cosa_c4_scale_bytes_(int rows, int K) { return (size_t)((rows + 255) / 256) * (size_t)(K / 128) * 2048; }
 static unsigned long long *g_gemm_stamp_slot = nullptr;
 extern "C" void cosa_gemm_set_stamp_slot(void *slot) { g_gemm_stamp_slot = static_cast<unsigned long long *>(slot); }
+namespace {
+struct ClearSlot { ~ClearSlot() { g_gemm_stamp_slot = nullptr; } };      // the stamp slot is one-shot whatever kernel ran
+}
 
 static int g_gemm_balanced_grid = 0;          // see launch_v6
 static int g_gemm_variant = 0;               // 0 = pick per shape (measured, tools/bench_gemm.py); 1 = the 128 x 128 kernel, 6 / 9 = the persistent kernel on 256- / 192-wide jobs (tests)
 extern "C" void cosa_gemm_set_variant(int v) { g_gemm_variant = v; }
 extern "C" void cosa_gemm_set_grid_policy(int balanced) { g_gemm_balanced_grid = balanced; }
+
+// ---- the launch layer of the projection entry points ----------------------------------------------------------------
+// Kernels that use more than 64 KB of dynamic LDS must be allowed to: once per process and kernel instantiation, before its first launch.
+template <auto Kernel>
+static int max_dynamic_lds_once(int bytes)
+{
+    static bool done = false;
+    if (!done) {
+        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done = true;
+    }
+    return COSA_OK;
+}
+
+// the runtime epilogue (validated: 0..2) as a compile-time constant: f(std::integral_constant<int, EPI_*>{})
+template <class F>
+static int with_epilogue(int epilogue, F &&f)
+{
+    if (epilogue == EPI_BIAS) return f(std::integral_constant<int, EPI_BIAS>{});
+    if (epilogue == EPI_GELU) return f(std::integral_constant<int, EPI_GELU>{});
+    return f(std::integral_constant<int, EPI_RESIDUAL>{});
+}
+
+// The rules the entry points share, in the order they are checked: operands, the entry's own shape rule (positive, N and K multiples of
+// its tile; `shape_fmt` and its arguments are that rule's message), epilogue range, the residual pointer.  `who` is spelled out by the
+// caller: the fp16 build reports under the bf16 names.
+template <class... A>
+static int check_gemm_args(const char *who, bool operands, const char *operands_what, int epilogue, const float *residual, bool shape_ok,
+                           const char *shape_fmt, A... shape_args)
+{
+    COSA_REQUIRE(operands, "%s: %s", who, operands_what);
+    COSA_REQUIRE(shape_ok, shape_fmt, shape_args...);
+    COSA_REQUIRE(epilogue >= 0 && epilogue <= 2, "%s: unknown epilogue", who);
+    COSA_REQUIRE(epilogue != EPI_RESIDUAL || residual, "%s: residual epilogue needs the residual pointer", who);
+    return COSA_OK;
+}
+
+// Operands within the 2-GiB reach of the kernels' buffer descriptors.  The bounds are the ones each entry point has always used: moving
+// one changes which kernel runs for some shape.
+constexpr size_t kReach = 0x7fffffffull;
+// the persistent kernel on whole operands: X [M (+ one 256-row job), ld] and W [N, ld], 16-bit elements
+static bool fits_persistent(int M, int N, int ld) { return (size_t)(M + 256) * ld * 2 < kReach && (size_t)N * ld * 2 < kReach; }
+// ... with three-term operands (* 8 on the X panel: kept as found)
+static bool fits_persistent_x3(int M, int N, int ld) { return (size_t)(M + 256) * ld * 2 < kReach * 8 && (size_t)N * ld * 2 < kReach; }
+// fp16c8 / fp16c4 operands: one 256-row X panel, all of W, one 256-row fp32 output panel
+static bool fits_panels(int N, int ld, int ldy) { return (size_t)256 * ld * 2 < kReach && (size_t)N * ld * 2 < kReach && (size_t)256 * ldy * 4 < kReach; }
+
+// dynamic LDS of the 128 x 128 kernel: the two operand stages or one epilogue tile (kLdsBytes); split (1) and dual (2) 16-bit outputs
+// stage TWO epilogue tiles, hi and lo or H and A: 2 x 128 x 272 B
+constexpr int small_lds_bytes(int split)
+{
+    return ((split == 1 || split == 2) && 2 * BM * CT_LD > (int)kLdsBytes) ? 2 * BM * CT_LD : (int)kLdsBytes;
+}
+
+
+// The one launcher of the 128 x 128 kernel.  first_job < 0: the whole output, one workgroup per 128 x 128 tile.  Otherwise the tail of
+// the persistent kernel's job list: its 256 x 256 jobs [first_job, first_job + njobs) as four workgroups each.  ld / ldy 0: K / N.
+template <int EPI, int SPLIT>
+static int launch_small(const op16 *x, const op16 *w, const op16 *b, const float *residual, void *Y, void *Y2, int M, int N, int K, int ld, int ldy,
+                        hipStream_t st, int first_job = -1, int njobs = 0)
+{
+    constexpr int lds_bytes = small_lds_bytes(SPLIT);
+    if (int rc = max_dynamic_lds_once<gemm_bf16_kernel<EPI, SPLIT>>(lds_bytes)) return rc;
+    const bool tail = first_job >= 0;
+    const int tiles_m = tail ? (M + 255) / 256 : (M + BM - 1) / BM, tiles_n = tail ? N / 256 : N / BN;
+    hipLaunchKernelGGL((gemm_bf16_kernel<EPI, SPLIT>), dim3(tail ? 4 * njobs : tiles_m * tiles_n), dim3(256), lds_bytes, st, x, w, b, residual, Y,
+                       M, N, K, tiles_m, tiles_n, ld ? ld : K, ldy ? ldy : N, Y2, first_job);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+// Round quantisation: 256 workgroups walk ntiles jobs, so ntiles = 4 * 256 + 8 (the N = 768 projections of a training step: 1032) costs
+// FIVE rounds, the last with 8 busy CUs.  When the remainder is small, the persistent kernel stops after the full rounds and the
+// leftover 256 x 256 jobs run as 128 x 128 quarters on the two-stage kernel (4 workgroups per job, 2 per CU): a few per cent of a
+// round instead of a whole one.  Same products, same fp32 accumulation order per output element (k ascending) as the jobs it replaces.
+// ... when it pays: the idle share of the last round must be a sizeable part of the whole launch (> 10 % of its rounds).  The teacher's
+// N = 768 projections (4.03 rounds) qualify; its 12.09- and 16.1-round launches do not -- measured in the step: tail for all three
+// 45.83 / 45.96 ms, for the 4.03-round launches only 45.66 / 45.65, none 46.05 / 46.22
+// Returns the number of jobs the persistent kernel runs; the rest is the tail.  (nn_ops.gemm_bf16 repeats this rule for the stamped flops.)
+static int persistent_jobs(int ntiles)
+{
+    constexpr int tail_max = 48;
+    const int rem = ntiles % 256, rounds_up = (ntiles + 255) / 256;
+    if (ntiles > 256 && rem != 0 && rem <= tail_max && (256 - rem) * 10 > 256 * rounds_up) return ntiles - rem;
+    return ntiles;
+}
 
 template <int EPI, int SPLIT = 0, int FR = 4>
 static int launch_v6(const op16 *x, const op16 *w, const op16 *b, const float *residual, void *Y, int M, int N, int K, hipStream_t st,
@@ -1594,30 +1685,16 @@ static int launch_v6(const op16 *x, const op16 *w, const op16 *b, const float *r
                      unsigned char *ysc = nullptr)
 {
     constexpr size_t lds_bytes = kLdsBytesV5 + (SPLIT == 4 ? kC4ScaleLds + kStageLdsC4 : kStageLds);      // ring [+ fp16c4: scale ring] + output staging rows = 160 KB
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_v6_kernel<EPI, SPLIT, FR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        attr_done = true;
-    }
+    if (int rc = max_dynamic_lds_once<gemm_bf16_v6_kernel<EPI, SPLIT, FR>>((int)lds_bytes)) return rc;
     const int tiles_m = (M + 255) / 256, tiles_n = N / (64 * FR);
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < 256 ? ntiles : 256;          // one persistent workgroup per CU
-    // Round quantisation: 256 workgroups walk ntiles jobs, so ntiles = 4 * 256 + 8 (the N = 768 projections of a training step: 1032) costs
-    // FIVE rounds, the last with 8 busy CUs.  When the remainder is small, the persistent kernel stops after the full rounds and the
-    // leftover 256 x 256 jobs run as 128 x 128 quarters on the two-stage kernel (4 workgroups per job, 2 per CU): a few per cent of a
-    // round instead of a whole one.  Same products, same fp32 accumulation order per output element (k ascending) as the jobs it replaces.
-    constexpr int tail_max = 48;
-    int run = ntiles;
-    // ... when it pays: the idle share of the last round must be a sizeable part of the whole launch (> 10 % of its rounds).  The teacher's
-    // N = 768 projections (4.03 rounds) qualify; its 12.09- and 16.1-round launches do not -- measured in the step: tail for all three
-    // 45.83 / 45.96 ms, for the 4.03-round launches only 45.66 / 45.65, none 46.05 / 46.22
-    const int rem = ntiles % 256, rounds_up = (ntiles + 255) / 256;
+    // the leftover jobs of a ragged last round go to the 128 x 128 kernel (persistent_jobs), where it knows the tile sequence:
     // (fp16c8 operands: the 128 x 128 kernel knows their tile sequence for the residual epilogue -- the output projection, N = 768)
     // (three-term operands, SPLIT == 1 -- the default teacher's projections since round 6: the 128 x 128 kernel walks the same 3 K / 64 + 1 tile
     // sequence, so its quarters are interchangeable with the persistent jobs bit for bit; N = 768: 1032 jobs = 4 x 256 + 8)
     constexpr bool can_tail = FR == 4 && (SPLIT == 0 || SPLIT == 1 || (SPLIT == 3 && EPI == EPI_RESIDUAL));
-    if (can_tail && ntiles > 256 && rem != 0 && rem <= tail_max && (256 - rem) * 10 > 256 * rounds_up)
-        run = ntiles - rem;
+    const int run = can_tail ? persistent_jobs(ntiles) : ntiles;
     // The persistent grid is balanced over the rounds it needs anyway: 600 jobs are three rounds on 256 workgroups and on 200, and 200
     // leave 56 CUs to whatever else is running (the other stream's kernels, RCCL's channels under DDP: a 256-workgroup launch that finds
     // only 224 free CUs runs its last 32 workgroups AFTER the others -- twice the time).  Multiples of 8 keep a workgroup on one XCD chunk.
@@ -1635,18 +1712,7 @@ static int launch_v6(const op16 *x, const op16 *w, const op16 *b, const float *r
     g_gemm_stamp_slot = nullptr;                            // one-shot
     COSA_LAUNCH_CHECK();
     if constexpr (can_tail) {
-        if (run < ntiles) {
-            // (split 16-bit outputs stage TWO epilogue tiles, hi and lo: 2 x 128 x 272 B, as cosa_gemm_bf16x3 sizes it)
-            constexpr int tail_lds = (SPLIT == 1 && 2 * BM * CT_LD > (int)kLdsBytes) ? 2 * BM * CT_LD : (int)kLdsBytes;
-            static bool tail_attr = false;
-            if (!tail_attr) {
-                COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, tail_lds));
-                tail_attr = true;
-            }
-            hipLaunchKernelGGL((gemm_bf16_kernel<EPI, SPLIT>), dim3(4 * (ntiles - run)), dim3(256), tail_lds, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n,
-                               ld ? ld : K, ldy ? ldy : N, static_cast<void *>(nullptr), run);
-            COSA_LAUNCH_CHECK();
-        }
+        if (run < ntiles) return launch_small<EPI, SPLIT>(x, w, b, residual, Y, nullptr, M, N, K, ld, ldy, st, run, ntiles - run);
     }
     return COSA_OK;
 }
@@ -1654,19 +1720,16 @@ static int launch_v6(const op16 *x, const op16 *w, const op16 *b, const float *r
 extern "C" int cosa_gemm_bf16(const void *X, const void *W, const void *bias, const float *residual, void *Y,
                               int M, int N, int K, int epilogue, void *stream)
 {
-    struct ClearSlot { ~ClearSlot() { g_gemm_stamp_slot = nullptr; } } clear_slot_;      // the stamp slot is one-shot whatever kernel ran
-    COSA_REQUIRE(X && W && bias && Y, "cosa_gemm_bf16: null pointer");
-    COSA_REQUIRE(M > 0 && N > 0 && K > 0, "cosa_gemm_bf16: bad shape");
-    COSA_REQUIRE(N % BN == 0 && K % BK == 0, "cosa_gemm_bf16: N must be a multiple of 128 and K of 64 (got N=%d K=%d)", N, K);
-    COSA_REQUIRE(epilogue >= 0 && epilogue <= 2, "cosa_gemm_bf16: unknown epilogue");
-    COSA_REQUIRE(epilogue != EPI_RESIDUAL || residual, "cosa_gemm_bf16: residual epilogue needs the residual pointer");
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
-    const dim3 grid(tiles_m * tiles_n), blk(256);
+    ClearSlot clear_slot_;
+    const bool positive = M > 0 && N > 0 && K > 0;
+    if (int rc = check_gemm_args("cosa_gemm_bf16", X && W && bias && Y, "null pointer", epilogue, residual, positive && N % BN == 0 && K % BK == 0,
+                                 positive ? "cosa_gemm_bf16: N must be a multiple of 128 and K of 64 (got N=%d K=%d)" : "cosa_gemm_bf16: bad shape", N, K))
+        return rc;
     hipStream_t st = as_stream(stream);
     const op16 *x = static_cast<const op16 *>(X), *w = static_cast<const op16 *>(W), *b = static_cast<const op16 *>(bias);
     // shape rule (measured, profiles/r01_gemm_variants.txt): the persistent 256-wide kernel from 4096 rows up, the 128 x 128 kernel (two
     // workgroups per CU) below that and for operands beyond the 2-GiB reach of its buffer descriptors
-    const bool fits_v5 = N % 256 == 0 && M >= 256 && (size_t)(M + 256) * K * 2 < 0x7fffffffull && (size_t)N * K * 2 < 0x7fffffffull;
+    const bool fits_v5 = N % 256 == 0 && M >= 256 && fits_persistent(M, N, K);
     constexpr int big_m = 4096;                                  // rows from which the 256 x 256 kernels are used
     const bool fits_v6 = fits_v5 && K >= 128 && (epilogue != EPI_RESIDUAL || g_gemm_variant == 6 || g_gemm_variant == 9 || g_gemm_variant == 0);
     // 192-wide tiles (FR = 3) when they quantise better on the 256 CUs: the student's N = 768 projections (M = 12 560) are 150 jobs of
@@ -1677,37 +1740,12 @@ extern "C" int cosa_gemm_bf16(const void *X, const void *W, const void *bias, co
         const long tm = (M + 255) / 256, n4 = tm * (N / 256), n3 = tm * (N / 192);
         const double r4 = (n4 > 256 && n4 % 256 != 0 && n4 % 256 <= wide_max) ? (double)(n4 / 256) + 0.1 : (double)((n4 + 255) / 256);
         const double r3 = 0.78 * (double)((n3 + 255) / 256);
-        if (g_gemm_variant == 9 || r3 < r4 - 0.05) {
-            if (epilogue == EPI_BIAS) return launch_v6<EPI_BIAS, 0, 3>(x, w, b, residual, Y, M, N, K, st);
-            if (epilogue == EPI_GELU) return launch_v6<EPI_GELU, 0, 3>(x, w, b, residual, Y, M, N, K, st);
-            return launch_v6<EPI_RESIDUAL, 0, 3>(x, w, b, residual, Y, M, N, K, st);
-        }
+        if (g_gemm_variant == 9 || r3 < r4 - 0.05)
+            return with_epilogue(epilogue, [&](auto e) { return launch_v6<decltype(e)::value, 0, 3>(x, w, b, residual, Y, M, N, K, st); });
     }
-    if (fits_v6 && (g_gemm_variant == 6 || (g_gemm_variant == 0 && M >= big_m))) {       // plain stores
-        if (epilogue == EPI_BIAS) return launch_v6<EPI_BIAS>(x, w, b, residual, Y, M, N, K, st);
-        if (epilogue == EPI_GELU) return launch_v6<EPI_GELU>(x, w, b, residual, Y, M, N, K, st);
-        return launch_v6<EPI_RESIDUAL>(x, w, b, residual, Y, M, N, K, st);
-    }
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_RESIDUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        attr_done = true;
-    }
-    switch (epilogue) {
-    case EPI_BIAS:
-        hipLaunchKernelGGL(gemm_bf16_kernel<EPI_BIAS>, grid, blk, kLdsBytes, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n, K, N, nullptr);
-        break;
-    case EPI_GELU:
-        hipLaunchKernelGGL(gemm_bf16_kernel<EPI_GELU>, grid, blk, kLdsBytes, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n, K, N, nullptr);
-        break;
-    default:
-        hipLaunchKernelGGL(gemm_bf16_kernel<EPI_RESIDUAL>, grid, blk, kLdsBytes, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n, K, N, nullptr);
-        break;
-    }
-    COSA_LAUNCH_CHECK();
-    return COSA_OK;
+    if (fits_v6 && (g_gemm_variant == 6 || (g_gemm_variant == 0 && M >= big_m)))       // plain stores
+        return with_epilogue(epilogue, [&](auto e) { return launch_v6<decltype(e)::value>(x, w, b, residual, Y, M, N, K, st); });
+    return with_epilogue(epilogue, [&](auto e) { return launch_small<decltype(e)::value, 0>(x, w, b, residual, Y, nullptr, M, N, K, K, N, st); });
 }
 
 // (both builds since round 6: the fp16 build exports it as cosa_gemm_f16x3 -- "fp16x3": hi + lo fp16 halves, 11 + 11 significant bits, the
@@ -1718,43 +1756,17 @@ extern "C" int cosa_gemm_bf16(const void *X, const void *W, const void *bias, co
 extern "C" int cosa_gemm_bf16x3(const void *Xs, const void *Ws, const void *zeros, const float *residual, void *Y,
                                 int M, int N, int K, int epilogue, int ldy, void *stream)
 {
-    struct ClearSlot { ~ClearSlot() { g_gemm_stamp_slot = nullptr; } } clear_slot_;
-    COSA_REQUIRE(Xs && Ws && zeros && Y, "cosa_gemm_bf16x3: null pointer");
-    COSA_REQUIRE(M > 0 && N > 0 && K > 0 && N % BN == 0 && K % BK == 0, "cosa_gemm_bf16x3: N %% 128 and K %% 64 must be 0 (got N=%d K=%d)", N, K);
-    COSA_REQUIRE(epilogue >= 0 && epilogue <= 2, "cosa_gemm_bf16x3: unknown epilogue");
-    COSA_REQUIRE(epilogue != EPI_RESIDUAL || residual, "cosa_gemm_bf16x3: residual epilogue needs the residual pointer");
+    ClearSlot clear_slot_;
+    if (int rc = check_gemm_args("cosa_gemm_bf16x3", Xs && Ws && zeros && Y, "null pointer", epilogue, residual, M > 0 && N > 0 && K > 0 && N % BN == 0 && K % BK == 0,
+                                 "cosa_gemm_bf16x3: N %% 128 and K %% 64 must be 0 (got N=%d K=%d)", N, K))
+        return rc;
     COSA_REQUIRE(epilogue == EPI_RESIDUAL ? ldy == N : (ldy >= 2 * N && ldy % 8 == 0), "cosa_gemm_bf16x3: ldy must be N (fp32 out) or >= 2N (split out)");
     const int ld = 2 * K + 64;
     hipStream_t st = as_stream(stream);
     const op16 *x = static_cast<const op16 *>(Xs), *w = static_cast<const op16 *>(Ws), *b = static_cast<const op16 *>(zeros);
-    if (N % 256 == 0 && M >= 4096 && (size_t)(M + 256) * ld * 2 < 0x7fffffffull * 8 && (size_t)N * ld * 2 < 0x7fffffffull) {
-        if (epilogue == EPI_BIAS) return launch_v6<EPI_BIAS, 1>(x, w, b, residual, Y, M, N, K, st, ld, ldy);
-        if (epilogue == EPI_GELU) return launch_v6<EPI_GELU, 1>(x, w, b, residual, Y, M, N, K, st, ld, ldy);
-        return launch_v6<EPI_RESIDUAL, 1>(x, w, b, residual, Y, M, N, K, st, ld, ldy);
-    }
-    constexpr int kLdsSplit = 2 * BM * CT_LD > (int)kLdsBytes ? 2 * BM * CT_LD : (int)kLdsBytes;
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_BIAS, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsSplit));
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_GELU, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsSplit));
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_RESIDUAL, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsSplit));
-        attr_done = true;
-    }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
-    const dim3 grid(tiles_m * tiles_n), blk(256);
-    switch (epilogue) {
-    case EPI_BIAS:
-        hipLaunchKernelGGL((gemm_bf16_kernel<EPI_BIAS, 1>), grid, blk, kLdsSplit, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n, ld, ldy, nullptr);
-        break;
-    case EPI_GELU:
-        hipLaunchKernelGGL((gemm_bf16_kernel<EPI_GELU, 1>), grid, blk, kLdsSplit, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n, ld, ldy, nullptr);
-        break;
-    default:
-        hipLaunchKernelGGL((gemm_bf16_kernel<EPI_RESIDUAL, 1>), grid, blk, kLdsSplit, st, x, w, b, residual, Y, M, N, K, tiles_m, tiles_n, ld, ldy, nullptr);
-        break;
-    }
-    COSA_LAUNCH_CHECK();
-    return COSA_OK;
+    if (N % 256 == 0 && M >= 4096 && fits_persistent_x3(M, N, ld))
+        return with_epilogue(epilogue, [&](auto e) { return launch_v6<decltype(e)::value, 1>(x, w, b, residual, Y, M, N, K, st, ld, ldy); });
+    return with_epilogue(epilogue, [&](auto e) { return launch_small<decltype(e)::value, 1>(x, w, b, residual, Y, nullptr, M, N, K, ld, ldy, st); });
 }
 
 #if COSA_OP_F16
@@ -1765,20 +1777,17 @@ extern "C" int cosa_gemm_bf16x3(const void *Xs, const void *Ws, const void *zero
 extern "C" int cosa_gemm_f16c8(const void *Xs, const void *Ws, const void *zeros, const float *residual, void *Y,
                                int M, int N, int K, int epilogue, int ldy, void *stream)
 {
-    struct ClearSlot { ~ClearSlot() { g_gemm_stamp_slot = nullptr; } } clear_slot_;
-    COSA_REQUIRE(Xs && Ws && zeros && Y, "cosa_gemm_f16c8: null pointer");
-    COSA_REQUIRE(M > 0 && N > 0 && K > 0 && N % 256 == 0 && K % 128 == 0, "cosa_gemm_f16c8: N %% 256 == 0 and K %% 128 == 0 required (got M=%d N=%d K=%d)", M, N, K);
-    COSA_REQUIRE(epilogue >= 0 && epilogue <= 2, "cosa_gemm_f16c8: unknown epilogue");
-    COSA_REQUIRE(epilogue != EPI_RESIDUAL || residual, "cosa_gemm_f16c8: residual epilogue needs the residual pointer");
+    ClearSlot clear_slot_;
+    if (int rc = check_gemm_args("cosa_gemm_f16c8", Xs && Ws && zeros && Y, "null pointer", epilogue, residual, M > 0 && N > 0 && K > 0 && N % 256 == 0 && K % 128 == 0,
+                                 "cosa_gemm_f16c8: N %% 256 == 0 and K %% 128 == 0 required (got M=%d N=%d K=%d)", M, N, K))
+        return rc;
     COSA_REQUIRE(epilogue == EPI_RESIDUAL ? ldy == N : (epilogue == EPI_GELU ? ldy == 2 * N + 64 : (ldy >= N && ldy % 8 == 0)),
                  "cosa_gemm_f16c8: ldy must be N (fp32 out), 2N + 64 (c8 rows out) or >= N (fp16 out)");
     const int ld = 2 * K + 64;
-    COSA_REQUIRE((size_t)256 * ld * 2 < 0x7fffffffull && (size_t)N * ld * 2 < 0x7fffffffull && (size_t)256 * ldy * 4 < 0x7fffffffull, "cosa_gemm_f16c8: panel beyond 2 GiB");
+    COSA_REQUIRE(fits_panels(N, ld, ldy), "cosa_gemm_f16c8: panel beyond 2 GiB");
     hipStream_t st = as_stream(stream);
     const op16 *x = static_cast<const op16 *>(Xs), *w = static_cast<const op16 *>(Ws), *b = static_cast<const op16 *>(zeros);
-    if (epilogue == EPI_BIAS) return launch_v6<EPI_BIAS, 3>(x, w, b, residual, Y, M, N, K, st, ld, ldy);
-    if (epilogue == EPI_GELU) return launch_v6<EPI_GELU, 3>(x, w, b, residual, Y, M, N, K, st, ld, ldy);
-    return launch_v6<EPI_RESIDUAL, 3>(x, w, b, residual, Y, M, N, K, st, ld, ldy);
+    return with_epilogue(epilogue, [&](auto e) { return launch_v6<decltype(e)::value, 3>(x, w, b, residual, Y, M, N, K, st, ld, ldy); });
 }
 #endif
 
@@ -1790,24 +1799,22 @@ extern "C" int cosa_gemm_f16c8(const void *Xs, const void *Ws, const void *zeros
 extern "C" int cosa_gemm_f16c4(const void *Xs, const void *Xscales, const void *Ws, const void *Wscales, const void *zeros, const float *residual,
                                void *Y, void *Yscales, int M, int N, int K, int epilogue, int ldy, void *stream)
 {
-    struct ClearSlot { ~ClearSlot() { g_gemm_stamp_slot = nullptr; } } clear_slot_;
-    COSA_REQUIRE(Xs && Xscales && Ws && Wscales && zeros && Y, "cosa_gemm_f16c4: null pointer");
-    COSA_REQUIRE(M > 0 && N > 0 && K >= 256 && N % 256 == 0 && K % 256 == 0, "cosa_gemm_f16c4: N %% 256 == 0 and K %% 256 == 0 required (got M=%d N=%d K=%d)", M, N, K);
-    COSA_REQUIRE(epilogue >= 0 && epilogue <= 2, "cosa_gemm_f16c4: unknown epilogue");
-    COSA_REQUIRE(epilogue != EPI_RESIDUAL || residual, "cosa_gemm_f16c4: residual epilogue needs the residual pointer");
+    ClearSlot clear_slot_;
+    if (int rc = check_gemm_args("cosa_gemm_f16c4", Xs && Xscales && Ws && Wscales && zeros && Y, "null pointer", epilogue, residual,
+                                 M > 0 && N > 0 && K >= 256 && N % 256 == 0 && K % 256 == 0,
+                                 "cosa_gemm_f16c4: N %% 256 == 0 and K %% 256 == 0 required (got M=%d N=%d K=%d)", M, N, K))
+        return rc;
     COSA_REQUIRE(epilogue != EPI_GELU || Yscales, "cosa_gemm_f16c4: the GELU epilogue writes c4 rows and needs their scale tensor");
     COSA_REQUIRE(epilogue == EPI_RESIDUAL ? ldy == N : (epilogue == EPI_GELU ? ldy == 2 * N + 64 : (ldy >= N && ldy % 8 == 0)),
                  "cosa_gemm_f16c4: ldy must be N (fp32 out), 2N + 64 (c4 rows out) or >= N (fp16 out)");
     const int ld = 2 * K + 64;
-    COSA_REQUIRE((size_t)256 * ld * 2 < 0x7fffffffull && (size_t)N * ld * 2 < 0x7fffffffull && (size_t)256 * ldy * 4 < 0x7fffffffull, "cosa_gemm_f16c4: panel beyond 2 GiB");
-    COSA_REQUIRE(cosa_c4_scale_bytes_(M, K) < 0x7fffffffull && cosa_c4_scale_bytes_(M, N) < 0x7fffffffull, "cosa_gemm_f16c4: scale tensor beyond 2 GiB");
+    COSA_REQUIRE(fits_panels(N, ld, ldy), "cosa_gemm_f16c4: panel beyond 2 GiB");
+    COSA_REQUIRE(cosa_c4_scale_bytes_(M, K) < kReach && cosa_c4_scale_bytes_(M, N) < kReach, "cosa_gemm_f16c4: scale tensor beyond 2 GiB");
     hipStream_t st = as_stream(stream);
     const op16 *x = static_cast<const op16 *>(Xs), *w = static_cast<const op16 *>(Ws), *b = static_cast<const op16 *>(zeros);
     const unsigned char *xs = static_cast<const unsigned char *>(Xscales), *ws = static_cast<const unsigned char *>(Wscales);
     unsigned char *ys = static_cast<unsigned char *>(Yscales);
-    if (epilogue == EPI_BIAS) return launch_v6<EPI_BIAS, 4>(x, w, b, residual, Y, M, N, K, st, ld, ldy, nullptr, xs, ws, ys);
-    if (epilogue == EPI_GELU) return launch_v6<EPI_GELU, 4>(x, w, b, residual, Y, M, N, K, st, ld, ldy, nullptr, xs, ws, ys);
-    return launch_v6<EPI_RESIDUAL, 4>(x, w, b, residual, Y, M, N, K, st, ld, ldy, nullptr, xs, ws, ys);
+    return with_epilogue(epilogue, [&](auto e) { return launch_v6<decltype(e)::value, 4>(x, w, b, residual, Y, M, N, K, st, ld, ldy, nullptr, xs, ws, ys); });
 }
 #endif
 
@@ -1816,24 +1823,16 @@ extern "C" int cosa_gemm_f16c4(const void *Xs, const void *Xscales, const void *
 // from ONE pass over the accumulators
 extern "C" int cosa_gemm_bf16_dual_gelu(const void *X, const void *W, const void *bias, void *H, void *A, int M, int N, int K, void *stream)
 {
-    struct ClearSlot { ~ClearSlot() { g_gemm_stamp_slot = nullptr; } } clear_slot_;
-    COSA_REQUIRE(X && W && bias && H && A && H != A, "cosa_gemm_bf16_dual_gelu: null pointer / aliased outputs");
-    COSA_REQUIRE(M > 0 && N > 0 && K > 0 && N % BN == 0 && K % BK == 0, "cosa_gemm_bf16_dual_gelu: N %% 128 and K %% 64 must be 0 (got N=%d K=%d)", N, K);
+    ClearSlot clear_slot_;
+    if (int rc = check_gemm_args("cosa_gemm_bf16_dual_gelu", X && W && bias && H && A && H != A, "null pointer / aliased outputs", EPI_GELU, nullptr,
+                                 M > 0 && N > 0 && K > 0 && N % BN == 0 && K % BK == 0,
+                                 "cosa_gemm_bf16_dual_gelu: N %% 128 and K %% 64 must be 0 (got N=%d K=%d)", N, K))
+        return rc;
     hipStream_t st = as_stream(stream);
     const op16 *x = static_cast<const op16 *>(X), *w = static_cast<const op16 *>(W), *b = static_cast<const op16 *>(bias);
-    if (N % 256 == 0 && M >= 4096 && K >= 128 && (size_t)(M + 256) * K * 2 < 0x7fffffffull && (size_t)N * K * 2 < 0x7fffffffull)
+    if (N % 256 == 0 && M >= 4096 && K >= 128 && fits_persistent(M, N, K))
         return launch_v6<EPI_GELU, 2>(x, w, b, nullptr, H, M, N, K, st, K, N, A);
-    constexpr int kLdsDual = 2 * BM * CT_LD > (int)kLdsBytes ? 2 * BM * CT_LD : (int)kLdsBytes;
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16_kernel<EPI_GELU, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsDual));
-        attr_done = true;
-    }
-    const int tiles_m = (M + BM - 1) / BM, tiles_n = N / BN;
-    hipLaunchKernelGGL((gemm_bf16_kernel<EPI_GELU, 2>), dim3(tiles_m * tiles_n), dim3(256), kLdsDual, st, x, w, b, static_cast<const float *>(nullptr), H,
-                       M, N, K, tiles_m, tiles_n, K, N, A);
-    COSA_LAUNCH_CHECK();
-    return COSA_OK;
+    return launch_small<EPI_GELU, 2>(x, w, b, nullptr, H, A, M, N, K, K, N, st);
 }
 #endif
 
@@ -1876,11 +1875,7 @@ template <bool CONV>
 static int launch_wgrad(const op16 *dY, const op16 *X, float *dW, float *db, int M, int N, int K, int zero_first, void *workspace,
                         size_t workspace_bytes, hipStream_t st, ConvGeom cg, int x_bytes, const char *who)
 {
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_wgrad_kernel<CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS));
-        attr_done = true;
-    }
+    if (int rc = max_dynamic_lds_once<gemm_wgrad_kernel<CONV>>(WG_LDS)) return rc;
     int per = 0;
     const int splits = wgrad_splits(M, N, K, &per);
     const int tiles = ((N + 255) / 256) * (K / 128);
@@ -1924,11 +1919,7 @@ extern "C" int cosa_gemm_wgrad_bf16(const void *dY, const void *X, float *dW, fl
 extern "C" int cosa_gemm_wgrad_batched(const CosaWgradItem *items, int n_items, int M, void *stream)
 {
     COSA_REQUIRE(items && n_items > 0 && M > 0, "cosa_gemm_wgrad_batched: bad arguments");
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_wgrad_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WW_LDS));
-        attr_done = true;
-    }
+    if (int rc = max_dynamic_lds_once<gemm_wgrad_batched_kernel>(WW_LDS)) return rc;
     for (int i0 = 0; i0 < n_items; i0 += kWgradBatchMax) {
         WgradBatch B;
         B.n = n_items - i0 < kWgradBatchMax ? n_items - i0 : kWgradBatchMax;
@@ -1977,11 +1968,7 @@ extern "C" int cosa_conv3x3_dilated_nhwc(const void *X, const void *Wt, void *Y,
     COSA_REQUIRE(img_rows >= h * w + row_off && ldx >= Cin, "cosa_conv3x3_dilated_nhwc: bad view geometry");
     const long long x_bytes = (long long)B * img_rows * ldx * 2;
     COSA_REQUIRE(x_bytes < 0x7ffffff0ll, "cosa_conv3x3_dilated_nhwc: activation view beyond 2 GiB");
-    static bool attr_done = false;
-    if (!attr_done) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)conv3x3_dil_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-        attr_done = true;
-    }
+    if (int rc = max_dynamic_lds_once<conv3x3_dil_kernel>((int)kLdsBytes)) return rc;
     const int M = B * h * w;
     const int tiles_m = (M + 127) / 128, tiles_n = Cout / 128;
     hipLaunchKernelGGL(conv3x3_dil_kernel, dim3(tiles_m * tiles_n), dim3(256), kLdsBytes, as_stream(stream), static_cast<const op16 *>(X),

@@ -184,6 +184,7 @@ def gemm_bf16(x, w, b, epilogue=EPI_BIAS, residual=None, out=None):
     if gemm_stamps is not None and M >= 4096:
         # the stamped span is the persistent kernel's; when the job count leaves a small remainder its tail runs as a second, tiny launch
         # (csrc/gemm_kernels.hip: launch_v6) whose share of the flops is not inside the span
+        # (the rule below is a copy of persistent_jobs() in that file: change the two together)
         nt = ((M + 255) // 256) * (N // 256) if N % 256 == 0 else 0
         rem, rounds_up = nt % 256, (nt + 255) // 256
         frac = (nt - rem) / nt if (nt > 256 and 0 < rem <= 48 and (256 - rem) * 10 > 256 * rounds_up) else 1.0
