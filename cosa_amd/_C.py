@@ -95,6 +95,10 @@ _SIGS = {
                                    c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "cosa_label_stats_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
     "cosa_label_stats": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cosa_tensor_stats_layout": (c_size_t, [ctypes.POINTER(c_size_t)]),
+    "cosa_tensor_stats_workspace_bytes": (c_size_t, [c_int]),
+    "cosa_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "cosa_grad_blame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cosa_spec_expf": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
     "cosa_attn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cosa_attn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -62,6 +62,10 @@ EXTRA = [
     ("label_stats", str2bool, False),        # count ignore / bg / fg, main-aux agreement, the student's IoU and non-finite CAMs on the device;
                                              # logged and written to <output_dir>/label_stats.jsonl every log_iters; with --skip_nonfinite a
                                              # step whose teacher CAMs hold an inf / NaN is refused
+    # per-tensor diagnostics; off: nothing changes
+    ("tensor_stats", str2bool, False),       # per-tensor gradient / weight norms and the EMA gap, sampled on the step that closes each log_iters
+                                             # interval, and -- behind the gradient guard -- which tensor held the inf / NaN of a refused step;
+                                             # logged and written to <output_dir>/tensor_stats.jsonl
 ]
 
 

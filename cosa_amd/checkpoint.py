@@ -3,7 +3,7 @@ interrupted.
 
 `TrainState(trainer)` names every tensor that defines the future of a run -- parameters and buffers of both networks, the AdamW moments,
 with --usegmm the queues and threshold trackers, with the gradient guard its record (the arena's last, optional tensor), with
---label_stats its counters (optional too) -- and moves them as ONE byte arena: on the GPU with one launch of the gather / scatter kernel
+--label_stats its counters and with --tensor_stats behind a guard its blame counters (optional too) -- and moves them as ONE byte arena: on the GPU with one launch of the gather / scatter kernel
 of csrc/optim_kernels.hip (cosa_state_snapshot / cosa_state_restore, two 64-bit checksums per tensor), on a host-device trainer with
 torch copies and the same checksums from numpy.  Everything derived (16-bit shadows, W^T copies, split rows, CAM buffers, the
 captured teacher graph) is NOT state: load() rebuilds it.
@@ -305,6 +305,7 @@ class TrainState:
     TRACKERS = ("ema_lowthre", "ema_highthre", "ema_auxlowthre", "ema_auxhighthre")
     GUARD = "guard.state"
     LABEL_STATS = "aux.label_stats.counters"         # CoSATrainer.extra_state["label_stats.counters"]
+    TENSOR_BLAME = "aux.tensor_stats.blame"          # CoSATrainer.tensor_stats_state (--tensor_stats behind a gradient guard)
 
     def __init__(self, trainer, part="all"):
         """part: "all" (a world of one), or under a process group "shared" (networks and moments: identical on every rank, written by
@@ -346,6 +347,10 @@ class TrainState:
             # tensors the launcher keeps on the device between iterations (CoSATrainer.extra_state: its running loss sums)
             for n, t in sorted(getattr(tr, "extra_state", {}).items()):
                 entries.append((f"aux.{n}", t))
+        if part != "local" and getattr(tr, "tensor_stats_state", None) is not None:
+            # --tensor_stats' blame counters: in the shared part, because the gradients they are derived from are identical on every rank
+            # behind the all-reduce.  Optional like the guard record that follows (_reconcile_optional)
+            entries.append((self.TENSOR_BLAME, tr.tensor_stats_state))
         if part != "local" and getattr(tr, "guard_state", None) is not None:
             # the gradient guard's record (its counters; identical on every rank).  LAST, so that a file differs from one written without a
             # guard by its tail only: load() reconciles the two (_reconcile_optional), and with the guard off nothing here changes
@@ -535,10 +540,14 @@ class TrainState:
             self.LABEL_STATS: ("the file holds pseudo-label statistics and this run does not collect them (--label_stats false): the entry "
                                "is ignored",
                                "written without pseudo-label statistics: this run's label counters start at zero"),
+            self.TENSOR_BLAME: ("the file holds per-tensor blame counters and this run does not keep them (--tensor_stats false, or no "
+                                "gradient guard): the entry is ignored",
+                                "written without per-tensor blame counters: this run's blame counters start at zero"),
         }
 
     def _reconcile_optional(self, header, a_len, path):
-        """Two tensors are optional: the guard record (the arena's last) and --label_stats' counters (among the launcher's tensors).  ->
+        """Three tensors are optional: the guard record (the arena's last), --tensor_stats' blame counters (in front of it) and
+        --label_stats' counters (among the launcher's tensors).  ->
         (header as this run would have written it, its arena bytes, [(file offset, arena offset, bytes)] to read, [(arena offset,
         bytes)] to zero).  A file without one of them loads into a run that has it with the tensor zero (counters start at zero); a
         file with one loads into a run without it, the entry ignored.  Each with a note.  Any other difference is left as it is, for

@@ -6,6 +6,10 @@
 // (p, m, v, teacher, 2 x bf16) instead of four separate sweeps (~72 B).  Frozen tensors (grad == NULL) only take the EMA.
 #include "kernels.hpp"
 
+#include <cstddef>
+#include <mutex>
+#include <vector>
+
 namespace cosa {
 namespace {
 
@@ -209,6 +213,154 @@ __global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const double *_
     }
 }
 
+// ---- per-tensor diagnostics -------------------------------------------------------------------------------------
+// The reduction above keeps one number; these keep the per-tensor structure.  One row per tensor (cosa_tensor_stats_layout): three sums in
+// double, the largest finite |g|, two counts of non-finite elements.  Everything the record table points at is only read.
+struct StatsRow {
+    double g_sq, w_sq, gap_sq, g_absmax;
+    unsigned long long g_nonfinite, w_nonfinite;
+};
+static_assert(sizeof(StatsRow) == 8 * COSA_TENSOR_STATS_SLOTS, "a row is six 8-byte slots");
+constexpr int kStatsMaxDevices = 64;      // read-back streams of cosa_tensor_stats, one per device
+
+__device__ __forceinline__ bool nonfinite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+struct StatsLane {          // one thread's running values
+    double g[4], w[4], d[4];
+    float gmax;
+    unsigned gbad, wbad;
+};
+
+template <int L>
+__device__ __forceinline__ void stats_grad(StatsLane &a, float g)
+{
+    const bool bad = nonfinite_f32(g);
+    a.g[L] += bad ? 0.0 : (double)g * (double)g;           // grad_norm_kernel's term, or 0 in place of a non-finite square
+    a.gmax = bad ? a.gmax : fmaxf(a.gmax, fabsf(g));
+    a.gbad += bad ? 1u : 0u;
+}
+
+template <int L>
+__device__ __forceinline__ void stats_weight(StatsLane &a, float p, float tp)
+{
+    const bool pbad = nonfinite_f32(p), bad = pbad || nonfinite_f32(tp);
+    const double d = (double)tp - (double)p;
+    a.w[L] += pbad ? 0.0 : (double)p * (double)p;
+    a.d[L] += bad ? 0.0 : d * d;
+    a.wbad += bad ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void tensor_stats_kernel(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
+                                                          StatsRow *__restrict__ partials)
+{
+    __shared__ double red_g[256], red_w[256], red_d[256];
+    __shared__ float red_m[256];
+    __shared__ unsigned red_c[2][256];
+    const ChunkRec c = chunks[blockIdx.x];
+    const TensorRec t = recs[c.tensor];
+    const long long base = (long long)c.chunk * kChunk;
+    long long end = base + kChunk;
+    end = end < t.n ? end : t.n;
+    StatsLane a;
+#pragma unroll
+    for (int e = 0; e < 4; e++) a.g[e] = a.w[e] = a.d[e] = 0.0;
+    a.gmax = 0.0f;
+    a.gbad = a.wbad = 0u;
+    if ((t.n & 3) == 0) {
+        for (long long i = base + threadIdx.x * 4; i < end; i += 1024) {
+            const float4 p = *reinterpret_cast<const float4 *>(t.p + i);
+            const float4 tp = *reinterpret_cast<const float4 *>(t.tp + i);
+            if (t.g) {
+                const float4 g = *reinterpret_cast<const float4 *>(t.g + i);
+                stats_grad<0>(a, g.x);
+                stats_grad<1>(a, g.y);
+                stats_grad<2>(a, g.z);
+                stats_grad<3>(a, g.w);
+            }
+            stats_weight<0>(a, p.x, tp.x);
+            stats_weight<1>(a, p.y, tp.y);
+            stats_weight<2>(a, p.z, tp.z);
+            stats_weight<3>(a, p.w, tp.w);
+        }
+    } else {
+        for (long long i = base + threadIdx.x; i < end; i += 256) {
+            if (t.g) stats_grad<0>(a, t.g[i]);
+            stats_weight<0>(a, t.p[i], t.tp[i]);
+        }
+    }
+    // the three sums through the guard's own tree (g_sq: the bits of grad_norm_kernel's partial on an all-finite chunk), each in its own array
+    const double g_sq = block_sum_256((a.g[0] + a.g[1]) + (a.g[2] + a.g[3]), red_g);
+    const double w_sq = block_sum_256((a.w[0] + a.w[1]) + (a.w[2] + a.w[3]), red_w);
+    const double gap_sq = block_sum_256((a.d[0] + a.d[1]) + (a.d[2] + a.d[3]), red_d);
+    red_m[threadIdx.x] = a.gmax;
+    red_c[0][threadIdx.x] = a.gbad;                         // at most 65536 per block
+    red_c[1][threadIdx.x] = a.wbad;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red_m[threadIdx.x] = fmaxf(red_m[threadIdx.x], red_m[threadIdx.x + w]);
+            red_c[0][threadIdx.x] += red_c[0][threadIdx.x + w];
+            red_c[1][threadIdx.x] += red_c[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        StatsRow r;
+        r.g_sq = g_sq; r.w_sq = w_sq; r.gap_sq = gap_sq;
+        r.g_absmax = (double)red_m[0];
+        r.g_nonfinite = red_c[0][0];
+        r.w_nonfinite = red_c[1][0];
+        partials[blockIdx.x] = r;
+    }
+}
+
+// tensor t's chunks, clamped to the list: a table the host did not check (cosa_grad_blame) cannot send a thread outside the partials
+__device__ __forceinline__ void chunk_range(const int *__restrict__ first_chunk, int t, int n_chunks, int &lo, int &hi)
+{
+    lo = first_chunk[t];
+    hi = first_chunk[t + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n_chunks ? n_chunks : hi;
+}
+
+// One thread per tensor: its chunks' partial rows in index order (sums added in that order, counts as integers, maxima as maxima); a tensor
+// without chunks gets a zero row.
+__global__ __launch_bounds__(256) void tensor_stats_finalize_kernel(const StatsRow *__restrict__ partials, const int *__restrict__ first_chunk,
+                                                                   int n_tensors, int n_chunks, StatsRow *__restrict__ out)
+{
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= n_tensors) return;
+    int lo, hi;
+    chunk_range(first_chunk, t, n_chunks, lo, hi);
+    StatsRow r;
+    r.g_sq = r.w_sq = r.gap_sq = r.g_absmax = 0.0;
+    r.g_nonfinite = r.w_nonfinite = 0ull;
+    for (int i = lo; i < hi; i++) {
+        const StatsRow q = partials[i];
+        r.g_sq += q.g_sq;
+        r.w_sq += q.w_sq;
+        r.gap_sq += q.gap_sq;
+        r.g_absmax = q.g_absmax > r.g_absmax ? q.g_absmax : r.g_absmax;
+        r.g_nonfinite += q.g_nonfinite;
+        r.w_nonfinite += q.w_nonfinite;
+    }
+    out[t] = r;
+}
+
+// Which tensor made the guard's sum non-finite: over the partials grad_norm_kernel has just written (a double sum of squared fp32 values is
+// non-finite exactly when an element is), one thread per tensor, ordinary loads and stores.
+__global__ __launch_bounds__(256) void grad_blame_kernel(const double *__restrict__ partials, const int *__restrict__ first_chunk, int n_tensors,
+                                                        int n_chunks, unsigned long long *__restrict__ blame)
+{
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= n_tensors) return;
+    int lo, hi;
+    chunk_range(first_chunk, t, n_chunks, lo, hi);
+    bool bad = false;
+    for (int i = lo; i < hi; i++) bad = bad || !isfinite(partials[i]);
+    if (bad) blame[t] += 1ull;
+}
+
 // ---- training-state snapshot / restore ---------------------------------------------------------------------
 // The same record-table + chunk-list pattern as above, over BYTES: every tensor that defines the future of a run (any dtype, contiguous)
 // is copied into its 16-byte-aligned, zero-padded slot of one contiguous arena (or back), and two 64-bit checksums per tensor are formed
@@ -373,6 +525,76 @@ extern "C" int cosa_fused_adamw_ema_guarded(const void *records, const void *chu
     const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adamw_ema_guarded_kernel, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const TensorRec *>(records),
                        static_cast<const ChunkRec *>(chunks), beta1, beta2, eps, bc1, bc2_sqrt, ema_momentum, static_cast<const GuardRec *>(guard));
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+/* ---- per-tensor diagnostics (include/cosa_hip.h) ---- */
+extern "C" size_t cosa_tensor_stats_layout(size_t *offsets)
+{
+    if (!offsets) {
+        set_error("cosa_tensor_stats_layout: offsets must be non-null");
+        return 0;
+    }
+    offsets[0] = offsetof(StatsRow, g_sq);
+    offsets[1] = offsetof(StatsRow, w_sq);
+    offsets[2] = offsetof(StatsRow, gap_sq);
+    offsets[3] = offsetof(StatsRow, g_absmax);
+    offsets[4] = offsetof(StatsRow, g_nonfinite);
+    offsets[5] = offsetof(StatsRow, w_nonfinite);
+    return sizeof(StatsRow);
+}
+
+extern "C" size_t cosa_tensor_stats_workspace_bytes(int n_chunks) { return n_chunks > 0 ? (size_t)n_chunks * sizeof(StatsRow) : 0; }
+
+extern "C" int cosa_tensor_stats(const void *records, const void *chunks, const int *first_chunk, int n_tensors, int n_chunks, void *workspace,
+                                 size_t workspace_bytes, void *out, void *stream)
+{
+    COSA_REQUIRE(records && chunks && first_chunk && out, "cosa_tensor_stats: null record table, chunk list, first_chunk or out");
+    COSA_REQUIRE(n_tensors > 0 && n_chunks > 0, "cosa_tensor_stats: %d tensors, %d chunks (both must be positive)", n_tensors, n_chunks);
+    const size_t need = cosa_tensor_stats_workspace_bytes(n_chunks);
+    COSA_REQUIRE(workspace && workspace_bytes >= need, "cosa_tensor_stats: workspace of %zu bytes (%zu needed)", workspace ? workspace_bytes : (size_t)0,
+                 need);
+    COSA_REQUIRE(((reinterpret_cast<unsigned long long>(workspace) | reinterpret_cast<unsigned long long>(out)) & 7ull) == 0,
+                 "cosa_tensor_stats: workspace and out must be 8-byte aligned");
+    // first_chunk decides which partials a tensor's thread reads: checked on the host before anything is launched.  The n_tensors + 1 ints
+    // come back on a stream of our own (non-blocking: the caller's stream, and the step in flight on it, are not waited for).
+    // The host does wait for that copy (tens of microseconds, once per sample; DESIGN.md section 12 has the measured figure).  One stream per
+    // device, created on first use under a lock and kept for the life of the process, like the library's other per-process state.
+    static std::mutex side_lock;
+    static hipStream_t side_of[kStatsMaxDevices] = {};
+    int device = -1;
+    COSA_HIP_CHECK(hipGetDevice(&device));
+    COSA_REQUIRE(device >= 0 && device < kStatsMaxDevices, "cosa_tensor_stats: device %d (at most %d devices per process)", device, kStatsMaxDevices);
+    std::vector<int> fc((size_t)n_tensors + 1);
+    {
+        std::lock_guard<std::mutex> hold(side_lock);       // (also serialises two threads' read-backs on the one stream)
+        if (!side_of[device]) COSA_HIP_CHECK(hipStreamCreateWithFlags(&side_of[device], hipStreamNonBlocking));
+        COSA_HIP_CHECK(hipMemcpyAsync(fc.data(), first_chunk, fc.size() * sizeof(int), hipMemcpyDeviceToHost, side_of[device]));
+        COSA_HIP_CHECK(hipStreamSynchronize(side_of[device]));
+    }
+    COSA_REQUIRE(fc[0] == 0, "cosa_tensor_stats: first_chunk[0] is %d (must be 0)", fc[0]);
+    for (int t = 0; t < n_tensors; t++)
+        COSA_REQUIRE(fc[t + 1] >= fc[t], "cosa_tensor_stats: first_chunk is not monotone at tensor %d (%d after %d)", t, fc[t + 1], fc[t]);
+    COSA_REQUIRE(fc[n_tensors] == n_chunks, "cosa_tensor_stats: first_chunk ends at %d, the chunk list has %d", fc[n_tensors], n_chunks);
+    StatsRow *partials = static_cast<StatsRow *>(workspace);
+    hipLaunchKernelGGL(tensor_stats_kernel, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const TensorRec *>(records),
+                       static_cast<const ChunkRec *>(chunks), partials);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tensor_stats_finalize_kernel, dim3((n_tensors + 255) / 256), dim3(256), 0, as_stream(stream), partials, first_chunk, n_tensors,
+                       n_chunks, static_cast<StatsRow *>(out));
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+extern "C" int cosa_grad_blame(const void *partials, const int *first_chunk, int n_tensors, int n_chunks, unsigned long long *blame, void *stream)
+{
+    COSA_REQUIRE(partials && first_chunk && blame, "cosa_grad_blame: null partials, first_chunk or blame");
+    COSA_REQUIRE(n_tensors > 0 && n_chunks > 0, "cosa_grad_blame: %d tensors, %d chunks (both must be positive)", n_tensors, n_chunks);
+    COSA_REQUIRE(((reinterpret_cast<unsigned long long>(partials) | reinterpret_cast<unsigned long long>(blame)) & 7ull) == 0,
+                 "cosa_grad_blame: partials and blame must be 8-byte aligned");
+    hipLaunchKernelGGL(grad_blame_kernel, dim3((n_tensors + 255) / 256), dim3(256), 0, as_stream(stream), static_cast<const double *>(partials),
+                       first_chunk, n_tensors, n_chunks, blame);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

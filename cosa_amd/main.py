@@ -94,25 +94,55 @@ def append_label_stats(output_dir, summary, n_iter):
         f.write(label_stats_record(summary, n_iter) + "\n")
 
 
-def read_interval(acc, log_iters, guard, stats):
+def tensor_stats_line(summary):
+    """what --tensor_stats adds to the interval's log line: the global relative EMA gap, and the blamed / non-finite tensor's name or -"""
+    return " ema_gap: %.3e, worst: %s" % (summary["global"]["ema_gap_rel"], summary["worst"] if summary["worst"] is not None else "-")
+
+
+def tensor_stats_record(summary, n_iter):
+    """one line of <output_dir>/tensor_stats.jsonl: the full summary of an interval's sample, every tensor included"""
+    return json.dumps(dict(summary, iters=int(n_iter)))
+
+
+def append_tensor_stats(output_dir, summary, n_iter):
+    with (Path(output_dir) / "tensor_stats.jsonl").open("a") as f:
+        f.write(tensor_stats_record(summary, n_iter) + "\n")
+
+
+def read_interval(acc, log_iters, guard, stats, tensor_stats=None):
     """The log interval's ONE host sync: -> (means of the running sums `acc`, [grad_norm, skipped, clipped] of the guard record or None,
     the label counters as ints or None).  The guard's own tensor and the label counters ride along in the same transfer (`acc` keeps
     its length; counts are exact in a double: an interval's stay far below 2^53).  `acc` and the label counters are an interval's:
-    both are zeroed on the device afterwards; the guard's counters are the run's and stay."""
+    both are zeroed on the device afterwards; the guard's counters are the run's and stay.
+    tensor_stats: (--tensor_stats' table, its blame counters or None); they ride along too and a fourth value is returned, (the table's
+    values as [T][6] floats, the blame counters as ints or None).  The table is the sample of the interval's last step and is not
+    accumulated; the blame counters are the run's: neither is zeroed."""
     parts = [acc / log_iters]
     if guard is not None:
         parts += [torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]
     if stats is not None:
         parts.append(stats.double())
+    if tensor_stats is not None:
+        table, blame = tensor_stats
+        parts.append(torch_helper.tensor_stats_values(table).reshape(-1))
+        if blame is not None:
+            parts.append(blame.double())
     vals = (torch.cat(parts) if len(parts) > 1 else parts[0]).tolist()
     n = acc.numel()
     vals, rest = vals[:n], vals[n:]
     gvals, rest = (rest[:3], rest[3:]) if guard is not None else (None, rest)
-    svals = [int(v) for v in rest] if stats is not None else None
+    svals = None
+    if stats is not None:
+        svals, rest = [int(v) for v in rest[:stats.numel()]], rest[stats.numel():]
     acc.zero_()
     if stats is not None:
         stats.zero_()
-    return vals, gvals, svals
+    if tensor_stats is None:
+        return vals, gvals, svals
+    T, W = table.shape
+    tvals = [rest[i * W:(i + 1) * W] for i in range(T)]
+    bvals = [int(v) for v in rest[T * W:]] if blame is not None else None
+    return vals, gvals, svals, (tvals, bvals)
 
 
 def main(args):
@@ -177,6 +207,7 @@ def main(args):
         first_iter = int(resumed["n_iter"]) + 1
         best_seg, best_cam, df = resumed["best_seg"], resumed["best_cam"], resumed["df"]
         loss_df = {k: list(resumed["loss_df"][k]) for k in loss_df}
+    tstats_on = bool(getattr(args, "tensor_stats", False))                        # per-tensor diagnostics
     for n_iter in range(first_iter, args.max_iters):
         try:
             img_name, wimg, simg, cls_label, img_box = next(it)
@@ -185,6 +216,8 @@ def main(args):
             img_name, wimg, simg, cls_label, img_box = next(it)
         pos["consumed"] += 1
         cls_label = cls_label.to(device, non_blocking=True)
+        if tstats_on and (n_iter + 1) % args.log_iters == 0:
+            trainer.request_tensor_stats()                                         # this step closes the interval: it samples the table
         logs = trainer.step(wimg, simg, cls_label, img_box, n_iter)
         with torch.no_grad():                                                     # main.py:257-268, without the per-iteration .item() syncs
             ap, ok = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_logits"].float()))
@@ -194,7 +227,11 @@ def main(args):
                 (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
             guard, stats = trainer.guard_state, trainer.label_stats_state         # None: no gradient guard / no --label_stats, the line as ever
-            vals, gvals, svals = read_interval(acc, args.log_iters, guard, stats)   # the one host sync of the interval
+            tvals = None
+            if tstats_on:
+                vals, gvals, svals, tvals = read_interval(acc, args.log_iters, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state))
+            else:
+                vals, gvals, svals = read_interval(acc, args.log_iters, guard, stats)   # the one host sync of the interval
             now = time.time()
             itertime, tick = (now - tick) / args.log_iters, now
             delta = datetime.datetime.now().replace(microsecond=0) - time0
@@ -212,6 +249,10 @@ def main(args):
                     summary = seg_helper.label_stats_summary(svals, args.num_classes)
                     line += label_stats_line(summary)
                     append_label_stats(output_dir, summary, n_iter + 1)
+                if tvals is not None:
+                    tsummary = trainer.tensor_stats(tvals)
+                    line += tensor_stats_line(tsummary)
+                    append_tensor_stats(output_dir, tsummary, n_iter + 1)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,

@@ -38,7 +38,7 @@ def default_args(dataset="VOC12", **over):
              aux_cam2seg=True, aux_cam2seg_alpha=0.5, aux_seg2cam=False, aux_seg2cam_alpha=0.5, after_softmax=False,
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
-             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False)
+             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -151,15 +151,39 @@ class CoSATrainer:
         if not self._max_norm >= 0:
             raise ValueError(f"clip_grad_norm {self._max_norm!r}: 0 (off) or a positive bound")
         guard_on = self._max_norm > 0 or self._skip_nonfinite
+        self._tensor_stats = bool(getattr(args, "tensor_stats", False))
         self._fused_step = None
         if on and getattr(args, "fused_optimizer", True):
+            stats_kw = {}
+            if self._tensor_stats:                       # (off: the constructor call as it always was)
+                name_of = {id(p): n for n, p in self.student.named_parameters()}
+                stats_kw = dict(tensor_stats=True, names=[name_of[id(p)] for p in self._ema_pairs[1]])
             self._fused_step = torch_helper.FusedAdamWEMAStep(self.optimizer, self._ema_pairs[1], self._ema_pairs[0], args.momentum,
                                                               shadow_of=nn_ops.shadow_of, max_norm=self._max_norm,
-                                                              skip_nonfinite=self._skip_nonfinite)
+                                                              skip_nonfinite=self._skip_nonfinite, **stats_kw)
         # the guard record: the fused step's (written by its kernels) or, on the torch path, one of the same layout written by torch
         self.guard_state = None
         if guard_on:
             self.guard_state = self._fused_step.guard if self._fused_step is not None else torch_helper.new_guard_state(device)
+        # per-tensor diagnostics: off unless --tensor_stats true.  The table is a sample of one step (the one after
+        # request_tensor_stats()); `tensor_stats_state`, the blame counters, exists only behind a gradient guard, is state of the run and
+        # travels in a state file as `aux.tensor_stats.blame`
+        self.tensor_stats_state = self.tensor_stats_table = None
+        if self._tensor_stats:
+            if self._fused_step is not None:
+                self._tensor_names, self._tensor_groups = self._fused_step.names, self._fused_step.group_idx
+                self._tensor_sizes = self._fused_step.sizes
+                self.tensor_stats_table = self._fused_step.stats_table
+                self.tensor_stats_state = self._fused_step.blame
+            else:
+                group_of = {id(p): gi for gi, g in enumerate(self.optimizer.param_groups) for p in g["params"]}
+                self._tensor_names = [n for n, _ in self.student.named_parameters()]
+                self._tensor_groups = [group_of.get(id(p), -1) for p in self._ema_pairs[1]]
+                self._tensor_sizes = [int(p.numel()) for p in self._ema_pairs[1]]
+                self.tensor_stats_table = torch_helper.new_tensor_stats(len(self._tensor_names), device)
+                if guard_on:
+                    self.tensor_stats_state = torch.zeros(len(self._tensor_names), dtype=torch.int64, device=device)
+            self._tensor_stats_armed = False
         # pseudo-label statistics and the teacher finite check: off (None) unless --label_stats true.  The counters
         # are state of the run: they travel in a state file as `label_stats.counters` of extra_state
         self.label_stats_state = None
@@ -364,6 +388,8 @@ class CoSATrainer:
         if self.device.type == "cuda" and self._student_shadows is not None:
             nn_ops.wgrad_arena_begin(self.device)        # one clear for all weight gradients of this step (they are consumed below)
         loss.backward()
+        if self._tensor_stats and self._fused_step is None:
+            self._tensor_stats_torch_step()
         if self._fused_step is not None:
             self._fused_step.step()
         elif self.guard_state is not None:
@@ -382,6 +408,35 @@ class CoSATrainer:
         """{applied, skipped, clipped} of the gradient guard over the run so far (synchronises: for tests and the log interval); None
         when the guard is off"""
         return torch_helper.guard_counters(self.guard_state) if self.guard_state is not None else None
+
+    # -- per-tensor diagnostics (DESIGN.md section 12) --
+    def request_tensor_stats(self):
+        """arm the next step's sample: that step fills the table from its gradients and its pre-step weights (no sync)"""
+        if not self._tensor_stats:
+            raise RuntimeError("request_tensor_stats: the trainer was built with tensor_stats=False")
+        if self._fused_step is not None:
+            self._fused_step.arm()
+        else:
+            self._tensor_stats_armed = True
+
+    @torch.no_grad()
+    def _tensor_stats_torch_step(self):
+        """the torch path's share of a step (fused_optimizer=False, host trainers): the armed sample and, behind a guard, the blame"""
+        grads = [p.grad if gi >= 0 else None for p, gi in zip(self._ema_pairs[1], self._tensor_groups)]
+        if self._tensor_stats_armed:
+            self._tensor_stats_armed = False
+            self.tensor_stats_table.copy_(torch_helper.tensor_stats_torch(self._ema_pairs[1], self._ema_pairs[0], grads))
+        if self.tensor_stats_state is not None:
+            torch_helper.grad_blame_torch(grads, self.tensor_stats_state)
+
+    def tensor_stats(self, values=None):
+        """the summary (torch_helper.tensor_stats_summary) of the last sample and of the run's blame counters (synchronises: for tests);
+        None when --tensor_stats is off.  values: (table values, blame counts or None) already on the host -- what the launcher's
+        read_interval returns -- are summarised instead, without a sync."""
+        if not self._tensor_stats:
+            return None
+        table, blame = (self.tensor_stats_table, self.tensor_stats_state) if values is None else values
+        return torch_helper.tensor_stats_summary(table, blame, self._tensor_names, self._tensor_groups, self._tensor_sizes)
 
     # -- pseudo-label statistics (DESIGN.md section 11) --
     @torch.no_grad()

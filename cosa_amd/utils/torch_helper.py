@@ -178,6 +178,118 @@ def guarded_torch_step(optimizer, teacher_params, student_params, momentum, max_
     ema_update(teacher_params, student_params, momentum)
 
 
+# --------------------------------------------------------------------------------------------
+# per-tensor diagnostics: norms, the EMA gap, the blame counters
+# --------------------------------------------------------------------------------------------
+TENSOR_STATS_SLOTS = ("g_sq", "w_sq", "gap_sq", "g_absmax", "g_nonfinite", "w_nonfinite")      # cosa_tensor_stats_layout's order
+TENSOR_STATS_F64 = 4         # the first four slots of a row hold float64 bits, the last two uint64 counts
+
+
+def tensor_stats_layout():
+    """cosa_tensor_stats_layout: ({slot name: offset in bytes}, bytes per row)"""
+    off = (_C.c_size_t * len(TENSOR_STATS_SLOTS))()
+    n = _C.lib().cosa_tensor_stats_layout(off)
+    return {k: int(off[i]) for i, k in enumerate(TENSOR_STATS_SLOTS)}, int(n)
+
+
+def new_tensor_stats(n_tensors, device):
+    """the table of n_tensors rows as int64 [n_tensors, 6]: float64 bits in the first four columns, counts in the last two"""
+    return torch.zeros((int(n_tensors), len(TENSOR_STATS_SLOTS)), dtype=torch.int64, device=device)
+
+
+def tensor_stats_values(table):
+    """the table's six columns as float64 [T, 6] (the sums and the maximum reinterpreted, the counts converted: exact below 2^53);
+    on the table's device, no sync"""
+    return torch.cat([table[:, :TENSOR_STATS_F64].contiguous().view(torch.float64), table[:, TENSOR_STATS_F64:].double()], dim=1)
+
+
+@torch.no_grad()
+def tensor_stats_torch(student, teacher, grads):
+    """cosa_tensor_stats in plain torch, for fused_optimizer=False and host trainers (the role guarded_torch_step plays for the gradient
+    guard): float64 sums, the same six slots, the same table layout.  student / teacher: the parameter lists of the fused step;
+    grads: one gradient or None (frozen) per tensor.  -> int64 [T, 6] on the parameters' device."""
+    student, teacher, grads = list(student), list(teacher), list(grads)
+    assert len(student) == len(teacher) == len(grads)
+    dev = student[0].device if student else "cpu"
+    vals = torch.zeros((len(student), len(TENSOR_STATS_SLOTS)), dtype=torch.float64, device=dev)
+    for i, (p, tp, g) in enumerate(zip(student, teacher, grads)):
+        p, tp = p.detach().reshape(-1), tp.detach().reshape(-1)
+        pf, tf = torch.isfinite(p), torch.isfinite(tp)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        vals[i, 1] = torch.where(pf, p.double().square(), zero).sum()
+        vals[i, 2] = torch.where(pf & tf, (tp.double() - p.double()).square(), zero).sum()
+        vals[i, 5] = (~(pf & tf)).sum()
+        if g is not None:
+            g = g.detach().reshape(-1)
+            gf = torch.isfinite(g)
+            vals[i, 0] = torch.where(gf, g.double().square(), zero).sum()
+            if g.numel():
+                vals[i, 3] = torch.where(gf, g.abs().double(), zero).max()
+            vals[i, 4] = (~gf).sum()
+    return torch.cat([vals[:, :TENSOR_STATS_F64].contiguous().view(torch.int64), vals[:, TENSOR_STATS_F64:].to(torch.int64)], dim=1)
+
+
+@torch.no_grad()
+def grad_blame_torch(grads, blame):
+    """cosa_grad_blame in plain torch: blame[t] advances by one when tensor t's gradient holds a non-finite element"""
+    for i, g in enumerate(grads):
+        if g is not None:
+            blame[i] += (~torch.isfinite(g.detach())).any().to(blame.dtype)
+    return blame
+
+
+def _pooled(rows, sizes, blamed):
+    """the figures of a set of rows (one tensor, a parameter group, all): square roots of the pooled sums"""
+    g_sq, w_sq, gap_sq = (float(sum(r[k] for r in rows)) for k in range(3))
+    weight_norm, ema_gap = w_sq ** 0.5, gap_sq ** 0.5
+    return {"n": int(sum(sizes)) if all(s is not None for s in sizes) else None,
+            "grad_norm": g_sq ** 0.5, "grad_absmax": float(max([r[3] for r in rows], default=0.0)),
+            "weight_norm": weight_norm, "ema_gap": ema_gap,
+            "ema_gap_rel": ema_gap / (weight_norm + 1e-12) if weight_norm > 0 else 0.0,          # an all-zero weight: zeros, not 1e12 or NaN
+            "g_nonfinite": int(sum(r[4] for r in rows)), "w_nonfinite": int(sum(r[5] for r in rows)), "blamed": int(sum(blamed))}
+
+
+def tensor_stats_summary(table, blame, names, group_idx, sizes=None):
+    """What a table says, as plain Python (JSON-serialisable).  table: [T, 6], either the int64 table itself (a tensor or an array: the
+    float64 bits are reinterpreted) or its values as floats (tensor_stats_values, a list out of the log interval's one sync); blame: [T]
+    counts or None (no gradient guard: zeros); names: [T]; group_idx: [T] optimizer parameter group of each tensor (-1: in none);
+    sizes: [T] element counts (None: `n` is None).  -> {"tensors": {name: figures}, "groups": {group: figures pooled, with square roots
+    of the pooled sums}, "global": the same over all tensors, "worst": the name of the tensor with the largest `blamed`, then
+    `g_nonfinite` (the first such; None when all are zero)}.  Figures: n, grad_norm, grad_absmax, weight_norm, ema_gap,
+    ema_gap_rel = ema_gap / (weight_norm + 1e-12) (0 for a zero weight_norm), g_nonfinite, w_nonfinite, blamed.  A tensor synchronises."""
+    if torch.is_tensor(table):
+        table = table.detach().cpu().numpy()
+    t = np.asarray(table)
+    if t.dtype.kind in "iu":
+        t = np.ascontiguousarray(t.astype(np.int64))
+        t = np.concatenate([t[:, :TENSOR_STATS_F64].copy().view(np.float64), t[:, TENSOR_STATS_F64:].astype(np.float64)], axis=1)
+    t = np.asarray(t, dtype=np.float64).reshape(-1, len(TENSOR_STATS_SLOTS))
+    T = t.shape[0]
+    names, group_idx = list(names), [int(g) for g in group_idx]
+    if len(names) != T or len(group_idx) != T:
+        raise ValueError(f"tensor_stats_summary: {T} rows, {len(names)} names, {len(group_idx)} group indices")
+    if blame is None:
+        blame = [0] * T
+    elif torch.is_tensor(blame):
+        blame = blame.detach().cpu().tolist()
+    blame = [int(b) for b in blame]
+    sizes = [None] * T if sizes is None else [int(s) for s in sizes]
+    if len(blame) != T or len(sizes) != T:
+        raise ValueError(f"tensor_stats_summary: {T} rows, {len(blame)} blame counters, {len(sizes)} sizes")
+    rows = [tuple(float(v) for v in r) for r in t]
+    tensors = {n: _pooled([rows[i]], [sizes[i]], [blame[i]]) for i, n in enumerate(names)}
+    groups = {}
+    for gi in sorted(set(group_idx)):
+        idx = [i for i in range(T) if group_idx[i] == gi]
+        groups[str(gi)] = _pooled([rows[i] for i in idx], [sizes[i] for i in idx], [blame[i] for i in idx])
+    worst, key = None, (0, 0)
+    for i, n in enumerate(names):
+        k = (blame[i], int(rows[i][4]))
+        if k > key:
+            worst, key = n, k
+    return {"tensors": tensors, "groups": groups, "global": _pooled(rows, sizes, blame), "worst": worst}
+
+
 class FusedAdamWEMAStep:
     """optimizer.step() + the teacher EMA (main.py:250-252) + refresh of the bf16 shadow weights as ONE HIP kernel.
 
@@ -187,9 +299,15 @@ class FusedAdamWEMAStep:
 
     max_norm > 0 and / or skip_nonfinite: the gradient guard.  step() then launches the global-norm reduction and
     the guarded kernel, which clips by `coef` or refuses the whole step on the device; `self.guard` is the guard record (GUARD_WORDS int64).
-    Without either, step() is the unguarded call."""
+    Without either, step() is the unguarded call.
 
-    def __init__(self, optimizer, student_params, teacher_params, momentum, shadow_of=None, max_norm=0.0, skip_nonfinite=False):
+    tensor_stats: per-tensor diagnostics.  The step then owns `first_chunk`, the table (`stats_table`, int64 [T, 6]),
+    its workspace and -- with a guard -- `blame` (int64 [T]; None without one).  arm() makes the next step() run sample() in front of the
+    optimizer kernel; with a guard every step() launches cosa_grad_blame behind cosa_grad_norm.  Without a guard and unarmed, step() does
+    nothing it did not do before.  `names`: one per tensor (the stable parameter names of checkpoint.TrainState)."""
+
+    def __init__(self, optimizer, student_params, teacher_params, momentum, shadow_of=None, max_norm=0.0, skip_nonfinite=False,
+                 tensor_stats=False, names=None):
         import numpy as np
         self.opt = optimizer
         self.momentum = float(momentum)
@@ -219,9 +337,10 @@ class FusedAdamWEMAStep:
         self.rec = self.recs[0]
         self._step_t = torch.tensor(0.0)
         chunk = L.cosa_optim_chunk_elems()
-        chunks = []
+        chunks, first_chunk = [], []
         for i, (p, tp) in enumerate(zip(self.student, self.teacher)):
             assert p.is_contiguous() and tp.is_contiguous() and p.dtype == torch.float32 and tp.dtype == torch.float32
+            first_chunk.append(len(chunks))               # a tensor's chunks are contiguous and ascending in the list
             r = self.rec[i]
             r["p"], r["tp"], r["n"] = p.data_ptr(), tp.data_ptr(), p.numel()
             sp, st = shadow_of(p), shadow_of(tp)
@@ -250,6 +369,42 @@ class FusedAdamWEMAStep:
             assert L.cosa_grad_guard_bytes() == GUARD_WORDS * 8
             self.guard = new_guard_state(dev)
             self.norm_ws = torch.empty(max(L.cosa_grad_norm_workspace_bytes(self.n_chunks), 8), dtype=torch.uint8, device=dev)
+        self.tensor_stats = bool(tensor_stats)
+        self.names = list(names) if names is not None else [f"param{i}" for i in range(n)]
+        assert len(self.names) == n
+        self.sizes = [int(p.numel()) for p in self.student]
+        self.d_first_chunk = self.stats_table = self.stats_ws = self.blame = None
+        self._armed = False
+        self._last_rec = None
+        if self.tensor_stats:
+            assert tensor_stats_layout()[1] == 8 * len(TENSOR_STATS_SLOTS)
+            self.d_first_chunk = torch.tensor(first_chunk + [len(chunks)], dtype=torch.int32, device=dev).contiguous()
+            self.stats_table = new_tensor_stats(n, dev)
+            self.stats_ws = torch.empty(max(L.cosa_tensor_stats_workspace_bytes(self.n_chunks), 8), dtype=torch.uint8, device=dev)
+            if self.guard is not None:
+                self.blame = torch.zeros(n, dtype=torch.int64, device=dev)
+
+    def arm(self):
+        """the next step() samples the table in front of its optimizer kernel"""
+        if not self.tensor_stats:
+            raise RuntimeError("FusedAdamWEMAStep was built with tensor_stats=False")
+        self._armed = True
+
+    def sample(self, d_rec=None):
+        """cosa_tensor_stats on a step's device record table (default: the last step's, whose gradient pointers hold until the next
+        zero_grad), on the optimizer kernel's stream, into `stats_table`.  The call does not wait for that stream; the host does wait, inside
+        the call, for a read-back of first_chunk (T + 1 ints on a stream of the library's own: what cosa_tensor_stats checks before it
+        launches), once per sample"""
+        if not self.tensor_stats:
+            raise RuntimeError("FusedAdamWEMAStep was built with tensor_stats=False")
+        d_rec = self._last_rec if d_rec is None else d_rec
+        if d_rec is None:
+            raise RuntimeError("FusedAdamWEMAStep.sample: no step has filled a record table yet")
+        with _C.profiled("tensor_stats"):
+            _C.check(_C.lib().cosa_tensor_stats(_C.ptr(d_rec), _C.ptr(self.d_chunks), _C.ptr(self.d_first_chunk), len(self.student), self.n_chunks,
+                                                _C.ptr(self.stats_ws), self.stats_ws.numel(), _C.ptr(self.stats_table), _C.stream_ptr()),
+                     "cosa_tensor_stats")
+        return self.stats_table
 
     def step(self):
         opt = self.opt
@@ -278,6 +433,10 @@ class FusedAdamWEMAStep:
         b1, b2 = groups[0]["betas"]
         opt.global_step += 1
         self._step_t.fill_(float(opt.global_step))
+        self._last_rec = d_rec
+        if self._armed:                                    # the weights are the pre-step ones, the gradients (under DDP) already reduced
+            self._armed = False
+            self.sample(d_rec)
         if self.guard is None:
             _C.check(_C.lib().cosa_fused_adamw_ema(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, float(b1), float(b2),
                                                    float(groups[0]["eps"]), int(opt.global_step), self.momentum, _C.stream_ptr()),
@@ -288,6 +447,10 @@ class FusedAdamWEMAStep:
         with _C.profiled("grad_norm"):
             _C.check(_C.lib().cosa_grad_norm(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, self.max_norm, int(self.skip_nonfinite),
                                              _C.ptr(self.norm_ws), self.norm_ws.numel(), _C.ptr(self.guard), _C.stream_ptr()), "cosa_grad_norm")
+        if self.blame is not None:                         # which tensor: one small launch over the partials the norm has just left
+            with _C.profiled("grad_blame"):
+                _C.check(_C.lib().cosa_grad_blame(_C.ptr(self.norm_ws), _C.ptr(self.d_first_chunk), len(self.student), self.n_chunks,
+                                                  _C.ptr(self.blame), _C.stream_ptr()), "cosa_grad_blame")
         with _C.profiled("adamw_ema_guarded"):
             _C.check(_C.lib().cosa_fused_adamw_ema_guarded(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, float(b1), float(b2),
                                                            float(groups[0]["eps"]), int(opt.global_step), self.momentum, _C.ptr(self.guard),

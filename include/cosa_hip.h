@@ -654,6 +654,43 @@ int cosa_label_stats(const float *mask_main, const float *mask_aux, const float 
                      const int32_t *boxes, const float *cam, const float *cam_aux, int B, int K, int S, int h, int w,
                      int ignore_index, unsigned long long *counters, float *step_scale, void *workspace, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Per-tensor training diagnostics: norms, the EMA gap and the blame counters, over the record table
+ * and chunk list of cosa_fused_adamw_ema.  Every buffer of the table (p, g, m, v, tp, the shadows) is only ever read.
+ * `first_chunk`: device int32 [n_tensors + 1]: tensor t owns the chunks first_chunk[t] .. first_chunk[t+1] - 1 of the chunk
+ *   list (contiguous and ascending; a tensor without elements owns none); first_chunk[0] == 0, first_chunk[n_tensors] ==
+ *   n_chunks.
+ * cosa_tensor_stats_layout: THE definition of a tensor's row for host and device: COSA_TENSOR_STATS_SLOTS 8-byte slots,
+ *   offsets[] in bytes from the row's start, in the order
+ *     g_sq        f64  sum of g^2 over the finite elements of the gradient; 0 for a frozen tensor (g == NULL)
+ *     w_sq        f64  sum of p^2 over the finite elements of the student master
+ *     gap_sq      f64  sum of (tp - p)^2 over the elements where both are finite
+ *     g_absmax    f64  max of finite |g| (an fp32 value held in an f64 slot); 0 for a frozen or empty tensor
+ *     g_nonfinite u64  elements of g with an all-ones exponent
+ *     w_nonfinite u64  elements where p or tp has an all-ones exponent
+ *   Returns the row's size in bytes (48), 0 when offsets is NULL.
+ * cosa_tensor_stats: out [n_tensors][6] (8-byte aligned) = the rows, written whole by the call (a tensor without chunks gets a
+ *   zero row).  One block per chunk leaves one partial row per chunk in `workspace` (cosa_tensor_stats_workspace_bytes,
+ *   8-byte aligned); one thread per tensor then adds its chunks in index order, counts as integers, maxima as maxima: no
+ *   float atomics, the same bits from run to run.  Sums are formed in double; the g_sq partial of a chunk is formed exactly
+ *   as cosa_grad_norm forms its partial, a non-finite element contributing 0: on an all-finite chunk the two have the same bits.
+ *   Refused with COSA_EINVAL, nothing launched and `out` untouched: a NULL pointer, n_tensors <= 0, n_chunks <= 0, a
+ *   workspace that is too small or misaligned, a first_chunk that does not start at 0, is not monotone or does not end at
+ *   n_chunks.  For that check the n_tensors + 1 ints are read back on a stream of the library's own (one per device, created
+ *   on first use, thread-safe): the host waits for that copy and for nothing else -- the caller's stream is not waited for --
+ *   and first_chunk must not be pending on another stream.  Two launches.
+ * cosa_grad_blame: one launch, one thread per tensor, over the per-chunk partials cosa_grad_norm has just left in ITS
+ *   workspace (`partials`: n_chunks doubles): blame[t] (uint64, caller-zeroed once, 8-byte aligned) advances by one when any
+ *   of tensor t's partials is non-finite -- which is exactly when some element of its gradient is.  Ordinary loads and stores.
+ *   first_chunk is not read back here (the call is made every step): the kernel clamps every range to 0 .. n_chunks.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_TENSOR_STATS_SLOTS 6
+size_t cosa_tensor_stats_layout(size_t *offsets);
+size_t cosa_tensor_stats_workspace_bytes(int n_chunks);
+int cosa_tensor_stats(const void *records, const void *chunks, const int *first_chunk, int n_tensors, int n_chunks, void *workspace,
+                      size_t workspace_bytes, void *out, void *stream);
+int cosa_grad_blame(const void *partials, const int *first_chunk, int n_tensors, int n_chunks, unsigned long long *blame, void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
