@@ -66,6 +66,7 @@ _SIGS = {
     "cosa_optim_record_bytes": (c_size_t, []),
     "cosa_optim_chunk_elems": (c_int, []),
     "cosa_fused_adamw_ema": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float, c_void_p]),
+    "cosa_grad_accumulate": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
     "cosa_grad_guard_bytes": (c_size_t, []),
     "cosa_grad_norm_workspace_bytes": (c_size_t, [c_int]),
     "cosa_grad_norm": (c_int, [c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

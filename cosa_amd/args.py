@@ -66,6 +66,9 @@ EXTRA = [
     ("tensor_stats", str2bool, False),       # per-tensor gradient / weight norms and the EMA gap, sampled on the step that closes each log_iters
                                              # interval, and -- behind the gradient guard -- which tensor held the inf / NaN of a refused step;
                                              # logged and written to <output_dir>/tensor_stats.jsonl
+    # gradient accumulation; 1: nothing changes
+    ("accum_steps", int, 1),                 # micro-batches of --batch_size per optimizer step: their mean gradient is applied once, so the
+                                             # effective batch is batch_size x accum_steps x world; all *_iters flags stay in optimizer steps
 ]
 
 

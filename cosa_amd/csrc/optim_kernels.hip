@@ -6,6 +6,7 @@
 // (p, m, v, teacher, 2 x bf16) instead of four separate sweeps (~72 B).  Frozen tensors (grad == NULL) only take the EMA.
 #include "kernels.hpp"
 
+#include <cmath>
 #include <cstddef>
 #include <mutex>
 #include <vector>
@@ -131,6 +132,47 @@ __global__ __launch_bounds__(256) void adamw_ema_guarded_kernel(const TensorRec 
 {
     if (guard->skip) return;
     adamw_ema_body<true>(recs, chunks, beta1, beta2, eps, bc1, bc2_sqrt, ema, guard->coef);
+}
+
+// ---- gradient accumulation over micro-batches -------------------------------------------------------------------
+// One block per chunk of the optimizer's own record table and chunk list, its loop shape (a pure stream: 8 B read + 4 B written per element,
+// mode 0: 4 + 4).  MODE 0: acc = g (the first micro-step: the accumulator is not read, so it needs no clear); 1: acc = acc + g;
+// 2: acc = (acc + g) * scale (the closing micro-step).  fp32, one rounding per operation (this file is built with -ffp-contract=off: the
+// closing add and multiply are not fused), non-finite values propagate.  A tensor with g == NULL, or without an accumulator, is skipped;
+// the gradient buffers are only read.
+template <int MODE>
+__device__ __forceinline__ float accum_one(float a, float g, float scale)
+{
+    if (MODE == 0) return g;
+    if (MODE == 1) return a + g;
+    return (a + g) * scale;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const TensorRec *__restrict__ recs, const ChunkRec *__restrict__ chunks,
+                                                             float *const *__restrict__ accs, float scale)
+{
+    const ChunkRec c = chunks[blockIdx.x];
+    const TensorRec t = recs[c.tensor];
+    float *acc = accs[c.tensor];
+    if (!t.g || !acc) return;
+    const long long base = (long long)c.chunk * kChunk;
+    long long end = base + kChunk;
+    end = end < t.n ? end : t.n;
+    if ((t.n & 3) == 0) {
+        for (long long i = base + threadIdx.x * 4; i < end; i += 1024) {
+            const float4 g = *reinterpret_cast<const float4 *>(t.g + i);
+            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (MODE != 0) a = *reinterpret_cast<const float4 *>(acc + i);
+            a.x = accum_one<MODE>(a.x, g.x, scale);
+            a.y = accum_one<MODE>(a.y, g.y, scale);
+            a.z = accum_one<MODE>(a.z, g.z, scale);
+            a.w = accum_one<MODE>(a.w, g.w, scale);
+            *reinterpret_cast<float4 *>(acc + i) = a;
+        }
+    } else {
+        for (long long i = base + threadIdx.x; i < end; i += 256) acc[i] = accum_one<MODE>(MODE != 0 ? acc[i] : 0.0f, t.g[i], scale);
+    }
 }
 
 // ---- global gradient norm ---------------------------------------------------------------------------------------
@@ -486,6 +528,27 @@ extern "C" int cosa_fused_adamw_ema(const void *records, const void *chunks, int
     const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(n_chunks), dim3(256), 0, as_stream(stream), static_cast<const TensorRec *>(records),
                        static_cast<const ChunkRec *>(chunks), beta1, beta2, eps, bc1, bc2_sqrt, ema_momentum);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+/* ---- gradient accumulation (include/cosa_hip.h) ---- */
+extern "C" int cosa_grad_accumulate(const void *records, const void *chunks, int n_chunks, const void *acc_ptrs, int mode, float scale,
+                                    void *stream)
+{
+    COSA_REQUIRE(records && chunks && acc_ptrs, "cosa_grad_accumulate: null record table, chunk list or accumulator pointer array");
+    COSA_REQUIRE(n_chunks > 0, "cosa_grad_accumulate: %d chunks (must be positive)", n_chunks);
+    COSA_REQUIRE(mode >= 0 && mode <= 2, "cosa_grad_accumulate: mode %d (0: acc = g, 1: acc += g, 2: acc = (acc + g) * scale)", mode);
+    COSA_REQUIRE(std::isfinite(scale), "cosa_grad_accumulate: scale %g is not finite", (double)scale);
+    const TensorRec *recs = static_cast<const TensorRec *>(records);
+    const ChunkRec *ch = static_cast<const ChunkRec *>(chunks);
+    float *const *accs = static_cast<float *const *>(acc_ptrs);
+    if (mode == 0)
+        hipLaunchKernelGGL(grad_accumulate_kernel<0>, dim3(n_chunks), dim3(256), 0, as_stream(stream), recs, ch, accs, scale);
+    else if (mode == 1)
+        hipLaunchKernelGGL(grad_accumulate_kernel<1>, dim3(n_chunks), dim3(256), 0, as_stream(stream), recs, ch, accs, scale);
+    else
+        hipLaunchKernelGGL(grad_accumulate_kernel<2>, dim3(n_chunks), dim3(256), 0, as_stream(stream), recs, ch, accs, scale);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

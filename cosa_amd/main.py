@@ -69,6 +69,8 @@ def check_supported(args):
     if args.model != 'vit' or args.decoder != 'LargeFOV':
         raise NotImplementedError("only --model vit --decoder LargeFOV (the run scripts' configuration) is built")
     get_backbone(args.backbone)                                   # NotImplementedError listing the built encoders
+    if getattr(args, "accum_steps", 1) < 1:
+        raise ValueError(f"--accum_steps {args.accum_steps}: a positive number of micro-batches per optimizer step")
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
@@ -145,6 +147,18 @@ def read_interval(acc, log_iters, guard, stats, tensor_stats=None):
     return vals, gvals, svals, (tvals, bvals)
 
 
+def next_batch(it, new_iter, pos):
+    """-> (iterator, batch): the next batch, from a new iterator (new_iter() resets `pos`) when this one is exhausted.  pos["consumed"]
+    counts BATCHES drawn from the current iterator -- with --accum_steps N an optimizer step draws N -- so --resume skips the right number."""
+    try:
+        batch = next(it)
+    except StopIteration:
+        it = new_iter()
+        batch = next(it)
+    pos["consumed"] += 1
+    return it, batch
+
+
 def main(args):
     check_supported(args)
     output_dir = Path(args.output_dir) if args.output_dir else Path(args.work_dir) / args.name
@@ -208,30 +222,27 @@ def main(args):
         best_seg, best_cam, df = resumed["best_seg"], resumed["best_cam"], resumed["df"]
         loss_df = {k: list(resumed["loss_df"][k]) for k in loss_df}
     tstats_on = bool(getattr(args, "tensor_stats", False))                        # per-tensor diagnostics
+    n_micro = int(getattr(args, "accum_steps", 1))                                # micro-batches per optimizer step
     for n_iter in range(first_iter, args.max_iters):
-        try:
-            img_name, wimg, simg, cls_label, img_box = next(it)
-        except StopIteration:
-            it = new_iter()
-            img_name, wimg, simg, cls_label, img_box = next(it)
-        pos["consumed"] += 1
-        cls_label = cls_label.to(device, non_blocking=True)
         if tstats_on and (n_iter + 1) % args.log_iters == 0:
             trainer.request_tensor_stats()                                         # this step closes the interval: it samples the table
-        logs = trainer.step(wimg, simg, cls_label, img_box, n_iter)
-        with torch.no_grad():                                                     # main.py:257-268, without the per-iteration .item() syncs
-            ap, ok = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_logits"].float()))
-            apa, oka = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_aux_logits"].float()))
-            acc += torch.stack([t.reshape(()).double() for t in (
-                logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
-                (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
+        for _micro in range(n_micro):                                             # the last call applies the mean gradient; `acc` sums over all
+            it, (img_name, wimg, simg, cls_label, img_box) = next_batch(it, new_iter, pos)
+            cls_label = cls_label.to(device, non_blocking=True)
+            logs = trainer.step(wimg, simg, cls_label, img_box, n_iter)
+            with torch.no_grad():                                                 # main.py:257-268, without the per-iteration .item() syncs
+                ap, ok = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_logits"].float()))
+                apa, oka = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_aux_logits"].float()))
+                acc += torch.stack([t.reshape(()).double() for t in (
+                    logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
+                    (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
             guard, stats = trainer.guard_state, trainer.label_stats_state         # None: no gradient guard / no --label_stats, the line as ever
             tvals = None
             if tstats_on:
-                vals, gvals, svals, tvals = read_interval(acc, args.log_iters, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state))
+                vals, gvals, svals, tvals = read_interval(acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state))
             else:
-                vals, gvals, svals = read_interval(acc, args.log_iters, guard, stats)   # the one host sync of the interval
+                vals, gvals, svals = read_interval(acc, args.log_iters * n_micro, guard, stats)   # the one host sync of the interval
             now = time.time()
             itertime, tick = (now - tick) / args.log_iters, now
             delta = datetime.datetime.now().replace(microsecond=0) - time0

@@ -38,7 +38,7 @@ def default_args(dataset="VOC12", **over):
              aux_cam2seg=True, aux_cam2seg_alpha=0.5, aux_seg2cam=False, aux_seg2cam_alpha=0.5, after_softmax=False,
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
-             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False)
+             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -152,12 +152,20 @@ class CoSATrainer:
             raise ValueError(f"clip_grad_norm {self._max_norm!r}: 0 (off) or a positive bound")
         guard_on = self._max_norm > 0 or self._skip_nonfinite
         self._tensor_stats = bool(getattr(args, "tensor_stats", False))
+        # gradient accumulation: step() consumes one micro-batch, every accum_steps-th call applies the mean gradient
+        self._accum_steps = int(getattr(args, "accum_steps", 1) or 1)
+        if self._accum_steps < 1:
+            raise ValueError(f"accum_steps {self._accum_steps!r}: a positive number of micro-batches per optimizer step")
+        self._micro_k = 0                    # the micro-step the next step() call is (0: between optimizer steps)
+        self._accum = None                   # the torch path's accumulator (fused_optimizer=False, host trainers)
         self._fused_step = None
         if on and getattr(args, "fused_optimizer", True):
             stats_kw = {}
             if self._tensor_stats:                       # (off: the constructor call as it always was)
                 name_of = {id(p): n for n, p in self.student.named_parameters()}
                 stats_kw = dict(tensor_stats=True, names=[name_of[id(p)] for p in self._ema_pairs[1]])
+            if self._accum_steps > 1:                    # (1: the constructor call as it always was)
+                stats_kw.update(accum_steps=self._accum_steps, names=[n for n, _ in self.student.named_parameters()])     # (_ema_pairs[1]'s order)
             self._fused_step = torch_helper.FusedAdamWEMAStep(self.optimizer, self._ema_pairs[1], self._ema_pairs[0], args.momentum,
                                                               shadow_of=nn_ops.shadow_of, max_norm=self._max_norm,
                                                               skip_nonfinite=self._skip_nonfinite, **stats_kw)
@@ -383,11 +391,17 @@ class CoSATrainer:
         self._ddp_pending = False
 
     def step(self, wimg, simg, cls_label, img_box, n_iter):
+        if self._accum_steps > 1:
+            return self._micro_step(wimg, simg, cls_label, img_box, n_iter)
         loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter)
         self.optimizer.zero_grad(set_to_none=True)
         if self.device.type == "cuda" and self._student_shadows is not None:
             nn_ops.wgrad_arena_begin(self.device)        # one clear for all weight gradients of this step (they are consumed below)
         loss.backward()
+        return self._apply_gradients(logs)
+
+    def _apply_gradients(self, logs):
+        """the optimizer's share of a step, on the gradients of one batch or on the mean left by the closing micro-step"""
         if self._tensor_stats and self._fused_step is None:
             self._tensor_stats_torch_step()
         if self._fused_step is not None:
@@ -403,6 +417,34 @@ class CoSATrainer:
         if self.guard_state is not None:
             logs["grad_norm"] = torch_helper.guard_norm(self.guard_state).clone()     # a device scalar: no sync
         return logs
+
+    def _micro_step(self, wimg, simg, cls_label, img_box, n_iter):
+        """--accum_steps N > 1: one micro-batch of the optimizer step `n_iter`.  Forward, losses and backward are
+        a step's own (so the teacher, the warm-up weights and the LR are those of `n_iter` for all N calls; the label counters add up;
+        with --usegmm the queues and trackers move on every call); the gradients go into the accumulator, and only the N-th call applies
+        their mean -- optimizer, EMA, shadows, guard, the armed --tensor_stats sample.  Under DDP every call's backward all-reduces and the
+        accumulator takes reduced gradients (correct by linearity; skipping the first N - 1 reductions is not built)."""
+        k, n = self._micro_k, self._accum_steps
+        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter)
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.device.type == "cuda" and self._student_shadows is not None:
+            nn_ops.wgrad_arena_begin(self.device)        # this micro-step's weight gradients: consumed by accumulate() below
+        loss.backward()
+        if self._fused_step is not None:
+            self._fused_step.accumulate(k)
+        else:
+            self._accum = torch_helper.accumulate_grads_torch(self._accum, [p.grad for p in self._ema_pairs[1]], k, n,
+                                                              [nm for nm, _ in self.student.named_parameters()])
+        self._micro_k = (k + 1) % n
+        if self._micro_k != 0:
+            return logs
+        if self._fused_step is None:                     # the torch path reads p.grad: leave the mean there
+            with torch.no_grad():
+                for p, a in zip(self._ema_pairs[1], self._accum):
+                    if a is not None:
+                        p.grad.copy_(a)
+            self._accum = None
+        return self._apply_gradients(logs)
 
     def guard_counters(self):
         """{applied, skipped, clipped} of the gradient guard over the run so far (synchronises: for tests and the log interval); None
@@ -466,6 +508,7 @@ class CoSATrainer:
         `self.extra_state` {name: tensor} (set before the first save or load).  Under a process group rank 0 writes `path`, every rank
         `path.rank<r>`.  Older complete state files next to `path` are pruned to args.keep_states (default 2)."""
         from . import checkpoint
+        assert self._micro_k == 0, f"save_state inside an optimizer step (micro-step {self._micro_k} of {self._accum_steps} is next)"
         return checkpoint.save_trainer(self, path, extra, keep=int(getattr(self.args, "keep_states", 2)))
 
     def wait_state(self):
@@ -477,7 +520,11 @@ class CoSATrainer:
         """Restore a file written by save_state (verified before anything is overwritten), rebuild everything derived from the masters,
         drop the captured teacher graph; -> extra (plus `rng_at_save`, the RNG states this call has just restored)."""
         from . import checkpoint
-        return checkpoint.load_trainer(self, path)
+        extra = checkpoint.load_trainer(self, path)
+        self._micro_k, self._accum = 0, None             # a state file is written between optimizer steps: the accumulator is dead there
+        if self._fused_step is not None:
+            self._fused_step._acc_next = 0
+        return extra
 
 
 # ---- synthetic batches (SURVEY §8 d-2) --------------------------------------------------------------------

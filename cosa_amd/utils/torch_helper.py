@@ -179,9 +179,54 @@ def guarded_torch_step(optimizer, teacher_params, student_params, momentum, max_
 
 
 # --------------------------------------------------------------------------------------------
+# gradient accumulation over micro-batches
+# --------------------------------------------------------------------------------------------
+def accum_mode(k, n):
+    """cosa_grad_accumulate's mode for micro-step k of n > 1: 0 (acc = g) first, 2 (acc = (acc + g) * fl(1/n)) last, 1 (acc += g) between"""
+    if not (n > 1 and 0 <= k < n):
+        raise ValueError(f"micro-step {k} of {n}: accumulation needs n > 1 and 0 <= k < n")
+    return 0 if k == 0 else (2 if k == n - 1 else 1)
+
+
+def accum_scale(n):
+    """fl(1/n) as a Python float: what the closing micro-step multiplies by, on the device and in torch"""
+    return float(np.float32(1.0) / np.float32(n))
+
+
+def check_same_grads(had, grads, names):
+    """a parameter must have a gradient in every micro-step of an optimizer step or in none (the host knows: no sync)"""
+    for i, (h, g) in enumerate(zip(had, grads)):
+        if h != (g is not None):
+            raise RuntimeError(f"{names[i]}: .grad is {'None' if g is None else 'set'} in this micro-step and was "
+                               f"{'set' if h else 'None'} in the step's first one; a step's micro-batches must reach the same parameters")
+
+
+@torch.no_grad()
+def accumulate_grads_torch(acc, grads, k, n, names=None):
+    """cosa_grad_accumulate in plain torch, for fused_optimizer=False and host trainers: the same fp32 sequence, one rounding per operation.
+    acc: the list micro-step 0 returned (ignored for k == 0); grads: one gradient or None per tensor.  -> acc, one fp32 tensor or None per
+    tensor: g1 after k = 0, fl(acc + g) in between, fl(fl(acc + g) * fl(1/n)) after k = n - 1.  RuntimeError (naming the tensor) when a
+    tensor has a gradient in one micro-step and none in another."""
+    mode = accum_mode(k, n)
+    grads = list(grads)
+    if mode == 0:
+        return [None if g is None else g.detach().clone() for g in grads]
+    names = names if names is not None else [f"param{i}" for i in range(len(grads))]
+    if acc is None or len(acc) != len(grads):
+        raise RuntimeError("accumulate_grads_torch: micro-step 0 has not run for this set of tensors")
+    check_same_grads([a is not None for a in acc], grads, names)
+    for a, g in zip(acc, grads):
+        if a is not None:
+            a.add_(g.detach())
+            if mode == 2:
+                a.mul_(accum_scale(n))
+    return acc
+
+
+# --------------------------------------------------------------------------------------------
 # per-tensor diagnostics (DESIGN.md section 12): norms, the EMA gap, the blame counters
 # --------------------------------------------------------------------------------------------
-TENSOR_STATS_SLOTS = ("g_sq", "w_sq", "gap_sq", "g_absmax", "g_nonfinite", "w_nonfinite")      # cosa_tensor_stats_layout's order
+TENSOR_STATS_SLOTS =("g_sq", "w_sq", "gap_sq", "g_absmax", "g_nonfinite", "w_nonfinite")      # cosa_tensor_stats_layout's order
 TENSOR_STATS_F64 = 4         # the first four slots of a row hold float64 bits, the last two uint64 counts
 
 
@@ -304,10 +349,15 @@ class FusedAdamWEMAStep:
     tensor_stats: per-tensor diagnostics.  The step then owns `first_chunk`, the table (`stats_table`, int64 [T, 6]),
     its workspace and -- with a guard -- `blame` (int64 [T]; None without one).  arm() makes the next step() run sample() in front of the
     optimizer kernel; with a guard every step() launches cosa_grad_blame behind cosa_grad_norm.  Without a guard and unarmed, step() does
-    nothing it did not do before.  `names`: one per tensor (the stable parameter names of checkpoint.TrainState)."""
+    nothing it did not do before.  `names`: one per tensor (the stable parameter names of checkpoint.TrainState).
+
+    accum_steps = N > 1: gradient accumulation.  The step then owns `acc`, one fp32 arena with a 16-byte-aligned
+    slice per trainable tensor, and `d_acc_ptrs`; accumulate(k) adds micro-step k's gradients into it, and step() -- after accumulate(N - 1)
+    -- reads the mean gradient from it instead of p.grad: norm, blame, the armed sample and the optimizer kernel are otherwise unchanged.
+    With N == 1 nothing is allocated (`acc is None`) and step() is what it was."""
 
     def __init__(self, optimizer, student_params, teacher_params, momentum, shadow_of=None, max_norm=0.0, skip_nonfinite=False,
-                 tensor_stats=False, names=None):
+                 tensor_stats=False, names=None, accum_steps=1):
         import numpy as np
         self.opt = optimizer
         self.momentum = float(momentum)
@@ -383,6 +433,64 @@ class FusedAdamWEMAStep:
             self.stats_ws = torch.empty(max(L.cosa_tensor_stats_workspace_bytes(self.n_chunks), 8), dtype=torch.uint8, device=dev)
             if self.guard is not None:
                 self.blame = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError(f"accum_steps {accum_steps!r}: a positive number of micro-steps")
+        self.acc = self.acc_slices = self.d_acc_ptrs = None
+        self._acc_next = 0                                 # the micro-step accumulate() expects; accum_steps: the mean is ready for step()
+        self._acc_has = None                               # which tensors had a gradient in the step's first micro-step
+        if self.accum_steps > 1:
+            offs, total = [], 0
+            for sz, gi in zip(self.sizes, self.group_idx):
+                offs.append(total if gi >= 0 else None)
+                if gi >= 0:
+                    total += (sz + 3) // 4 * 4             # every slice starts on a 16-byte boundary
+            self.acc = torch.empty(max(total, 4), dtype=torch.float32, device=dev)
+            assert self.acc.data_ptr() % 16 == 0
+            self.acc_slices = [None if o is None else self.acc[o:o + sz] for o, sz in zip(offs, self.sizes)]
+            self.d_acc_ptrs = torch.tensor([0 if a is None else a.data_ptr() for a in self.acc_slices], dtype=torch.int64, device=dev)
+
+    def _take_slot(self):
+        """the next slot of the record-table ring, once the copy that last read its host table has completed"""
+        slot = self.slot
+        self.slot = (slot + 1) % self.kRing
+        if self.copied[slot] is not None:
+            self.copied[slot].synchronize()            # the copy issued kRing steps ago; never waits in practice
+        return slot
+
+    def _upload(self, slot):
+        """host table -> device table of `slot`, and the event that guards the host table"""
+        self.d_recs[slot].copy_(self.hosts[slot], non_blocking=True)
+        if self.copied[slot] is None:
+            self.copied[slot] = torch.cuda.Event()
+        self.copied[slot].record()
+        return self.d_recs[slot]
+
+    def accumulate(self, k):
+        """micro-step k of accum_steps: the current p.grad of every trainable tensor into the accumulator (cosa_grad_accumulate: acc = g
+        for k == 0, acc += g, and acc = (acc + g) * fl(1/N) for the last), on the optimizer kernel's stream, no sync.  RuntimeError when a
+        parameter has a gradient in one micro-step of a step and none in another."""
+        n = self.accum_steps
+        if n <= 1:
+            raise RuntimeError("FusedAdamWEMAStep was built with accum_steps=1: there is no accumulator")
+        if k != self._acc_next:
+            raise RuntimeError(f"FusedAdamWEMAStep.accumulate({k}): micro-step {self._acc_next % n} of {n} is next"
+                               + (" (after step())" if self._acc_next == n else ""))
+        mode = accum_mode(k, n)
+        grads = [p.grad if gi >= 0 else None for p, gi in zip(self.student, self.group_idx)]
+        if k == 0:
+            self._acc_has = [g is not None for g in grads]
+        else:
+            check_same_grads(self._acc_has, grads, self.names)
+        slot = self._take_slot()
+        rec = self.recs[slot]
+        for i, g in enumerate(grads):
+            rec[i]["g"] = g.data_ptr() if g is not None else 0
+        d_rec = self._upload(slot)
+        with _C.profiled("grad_accumulate"):
+            _C.check(_C.lib().cosa_grad_accumulate(_C.ptr(d_rec), _C.ptr(self.d_chunks), self.n_chunks, _C.ptr(self.d_acc_ptrs), mode,
+                                                   accum_scale(n), _C.stream_ptr()), "cosa_grad_accumulate")
+        self._acc_next = k + 1
 
     def arm(self):
         """the next step() samples the table in front of its optimizer kernel"""
@@ -408,28 +516,27 @@ class FusedAdamWEMAStep:
 
     def step(self):
         opt = self.opt
+        acc = self.acc_slices                              # None without accumulation: the gradients are p.grad
+        if acc is not None:
+            if self._acc_next != self.accum_steps:
+                raise RuntimeError(f"FusedAdamWEMAStep.step(): {self._acc_next} of {self.accum_steps} micro-steps accumulated")
+            self._acc_next = 0
         mult = poly_warmup_lr_mult(opt.global_step, opt.warmup_iter, opt.max_iter, opt.warmup_ratio, opt.power, opt.min_mult)
         if mult is not None:
             for i, g in enumerate(opt.param_groups):
                 g["lr"] = opt._init_lr[i] * mult
         groups = opt.param_groups
-        slot = self.slot
-        self.slot = (slot + 1) % self.kRing
-        if self.copied[slot] is not None:
-            self.copied[slot].synchronize()            # the copy issued kRing steps ago; never waits in practice
-        rec, d_rec = self.recs[slot], self.d_recs[slot]
+        slot = self._take_slot()
+        rec = self.recs[slot]
         for i, p in enumerate(self.student):
             gi = self.group_idx[i]
-            if gi >= 0 and p.grad is not None:
-                rec[i]["g"] = p.grad.data_ptr()
+            if gi >= 0 and (p.grad is not None if acc is None else self._acc_has[i]):
+                rec[i]["g"] = p.grad.data_ptr() if acc is None else acc[i].data_ptr()
                 rec[i]["lr"] = groups[gi]["lr"]
                 rec[i]["wd"] = groups[gi]["weight_decay"]
             else:
                 rec[i]["g"] = 0
-        d_rec.copy_(self.hosts[slot], non_blocking=True)
-        if self.copied[slot] is None:
-            self.copied[slot] = torch.cuda.Event()
-        self.copied[slot].record()
+        d_rec = self._upload(slot)
         b1, b2 = groups[0]["betas"]
         opt.global_step += 1
         self._step_t.fill_(float(opt.global_step))

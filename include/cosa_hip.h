@@ -509,6 +509,22 @@ int cosa_fused_adamw_ema_guarded(const void *records, const void *chunks, int n_
                                  int step, float ema_momentum, const void *guard, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Gradient accumulation over micro-batches, over the record table and chunk list of
+ * cosa_fused_adamw_ema: one block per chunk, one launch.  `acc_ptrs`: device array of one float* per record (NULL: no
+ * accumulator, the tensor is skipped; so is a record with g == NULL, whose accumulator keeps its bytes).  An accumulator
+ * holds the record's n floats and, when n % 4 == 0, is 16-byte aligned (as g is).
+ *   mode 0: acc = g                    (first micro-step: acc is not read, it needs no clear)
+ *   mode 1: acc = acc + g
+ *   mode 2: acc = (acc + g) * scale    (closing micro-step, scale = fl(1/N))
+ * fp32, one rounding per operation, so N micro-steps leave fl(fl(...fl(g1 + g2)... + gN) * scale) -- what the same torch
+ * expression gives bit for bit.  Non-finite values propagate.  The gradient buffers are only read.
+ * Refused with COSA_EINVAL, nothing launched: a NULL table, chunk list or pointer array, n_chunks <= 0, a mode outside
+ * 0..2, a non-finite scale (whatever the mode).
+ * ------------------------------------------------------------------------------------- */
+int cosa_grad_accumulate(const void *records, const void *chunks, int n_chunks, const void *acc_ptrs, int mode, float scale,
+                         void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training-state arena: every tensor that defines the future of a run, gathered into ONE contiguous
  * device arena by one launch (and scattered back by one), with two 64-bit checksums per tensor.
  * cosa_state_layout: THE definition of the arena for host and device: tensor i (nbytes[i] bytes, any dtype, contiguous)
