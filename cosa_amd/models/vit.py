@@ -11,6 +11,7 @@ Execution differs from the reference on purpose:
   * the bicubic position-embedding resize is cached per token grid (pos_embed is frozen)
   * bf16 compute with fp32 master weights (compute_dtype=torch.float32 is the parity mode)
 """
+import typing
 from functools import partial
 
 import torch
@@ -29,6 +30,52 @@ class FP32Tokens:
 
     def __init__(self, final, aux):
         self.final, self.aux = final, aux
+
+
+class OperandMap(typing.NamedTuple):
+    """operand formats of a no-grad pass (VisionTransformer._operand_map): of the patch projection -- the family that assembles the tokens and
+    closes with its LayerNorm -- and per block of the attention half and the MLP half: "plain", "x3", "c8" or "c4" (qkv / fc1 / fc2 on fp16c4
+    operands in an otherwise fp16c8 half)"""
+    patch: str
+    attn: tuple
+    mlp: tuple
+    plain_qkv: bool            # the qkv projections of the c8 / c4 halves on plain fp16 operands (the output projection keeps its terms)
+    c4_proj: bool              # the output projections of the c4 halves on fp16c4 operands too (default: fp16c8)
+    dt16: object               # type of the plain operands
+    hdt: object                # type of the hi / lo halves of the x3 operands
+
+    def of(self, i, name):
+        """operand format of projection `name` ("qkv", "proj", "fc1", "fc2") of block i"""
+        half = (self.attn if name in ("qkv", "proj") else self.mlp)[i]
+        if half in ("c8", "c4") and name == "qkv" and self.plain_qkv:
+            return "plain"
+        if half == "c4" and name == "proj" and not self.c4_proj:
+            return "c8"
+        return half
+
+    def uses(self, fmt):
+        return fmt in self.attn or fmt in self.mlp
+
+
+class TokenPack(typing.NamedTuple):
+    """the token rows of several image batches in one [M, D] buffer: batch i is `shapes[i]` = (images, tokens per image) at rows offs[i]:offs[i+1]"""
+    shapes: tuple
+    offs: tuple
+    M: int
+    Kp: int                    # width of an im2col row
+    nf: int                    # 2: every batch stands for cat(x, x.flip(-1))
+    dev: object
+
+    def scales(self):
+        return [(B, N, o0, o1) for (B, N), o0, o1 in zip(self.shapes, self.offs[:-1], self.offs[1:])]
+
+    def cut(self, a16, xn32, aux, D):
+        """per batch (cls fp32, 16-bit tokens, aux tokens, fp32 tokens); a16 may be operand rows whose first D columns are the tokens"""
+        outs = []
+        for B, N, o0, o1 in self.scales():
+            t16, a32, ax = a16[o0:o1].view(B, N, -1)[:, :, :D], xn32[o0:o1].view(B, N, D), aux[o0:o1].view(B, N, D)
+            outs.append((a32[:, 0], t16[:, 1:], ax[:, 1:], a32[:, 1:]))
+        return outs
 
 
 class Mlp(nn.Module):
@@ -207,95 +254,59 @@ class VisionTransformer(nn.Module):
         y = nn_ops.linear(y, blk.mlp.fc1.weight, blk.mlp.fc1.bias, dt, act=True)
         return x_in, x, nn_ops.linear(y, blk.mlp.fc2.weight, blk.mlp.fc2.bias, dt)
 
-    # -- fused no-grad path (the teacher's 6 passes): fp32 residual stream, HIP GEMM/LN/attention kernels -------
-    def _forward_features_fused(self, x):
-        return self._forward_features_fused_multi([x])[0]
+    # -- fused no-grad path (the teacher's 6 passes, evaluation): fp32 residual stream, HIP GEMM / LN / attention kernels ----------------
+    #    Operand formats of a projection: "plain" (bf16 or fp16), "x3" (hi + lo 16-bit halves, three MFMA terms: bf16x3 / fp16x3), "c8" (fp16 +
+    #    8-bit correction terms, csrc/c8.hpp; attention on plain fp16 q, k, v, its OUTPUT leaves as c8 rows) and "c4" (fp16 + FP4 MX-block
+    #    correction terms, csrc/c4.hpp).  tools/sim_precision_map.py is the sensitivity study behind the mixed maps.
+    def _plain_from(self):
+        """(first block whose attention half, first block whose MLP half) runs on plain fp16 operands in the fp16c8 / fp16c4 modes"""
+        a = self.c8_plain_from if self.c8_plain_from is not None else len(self.blocks)
+        return a, (self.c8_plain_mlp_from if self.c8_plain_mlp_from is not None else a)
 
-    def _forward_features_fused_multi(self, xs, flip_pairs=False):
-        """Several image batches (the teacher's three scales) through the encoder TOGETHER: LayerNorm and the four
-        projections are token-wise, so all tokens of all scales go through one launch each per block (M = sum B_i N_i:
-        better tile quantisation on 256 CUs, a third of the launches); only attention runs per scale, on its slice of
-        the packed qkv buffer."""
-        if self.precision == "bf16x3":
-            return self._forward_features_x3_multi(xs, flip_pairs)
-        if self.precision in ("fp16c8", "fp16c4"):
-            return self._forward_features_c8_multi(xs, flip_pairs)
-        dt16 = self.compute_dtype                                # bf16, or fp16 (no-grad passes only: same kernels, fp16 operands)
-        c = lambda p_: nn_ops.cast_param(p_, dt16)
-        D = self.embed_dim
-        p = self.patch_size
-        nf = 2 if flip_pairs else 1                              # flip_pairs: every batch stands for cat(x, x.flip(-1)) (the teacher's passes)
-        shapes = [(nf * x.shape[0], (x.shape[2] // p) * (x.shape[3] // p) + 1) for x in xs]
-        offs = [0]
-        for B, N in shapes:
-            offs.append(offs[-1] + B * N)
-        Mtot = offs[-1]
-        if all(x.is_cuda for x in xs) and D % 128 == 0 and (3 * p * p) % 64 == 0 and p % 8 == 0:
-            # patch projection on the own GEMM, then ONE pass per scale that adds the class token and the position rows and writes the fp32
-            # residual stream in place (cosa_embed_finish) -- instead of cat(cls, tok) + pos, .float() and the concatenation of the scales
-            from .. import _C
-            xr = torch.empty((Mtot, D), device=xs[0].device, dtype=torch.float32)
-            wgt = c(self.patch_embed.proj.weight).reshape(D, -1).contiguous()
-            bias, cls = c(self.patch_embed.proj.bias).contiguous(), c(self.cls_token).reshape(-1).contiguous()
-            for x, (B, N), o0 in zip(xs, shapes, offs[:-1]):
-                h, w = x.shape[2] // p, x.shape[3] // p
-                xf = x.float().contiguous()
-                cols = torch.empty((B * h * w, x.shape[1] * p * p), device=x.device, dtype=dt16)
-                _C.check(_C.lib().cosa_im2col_flip(_C.ptr(xf), _C.ptr(cols), x.shape[0], x.shape[1], x.shape[2], x.shape[3], p, nf,
-                                                   1 if dt16 == torch.bfloat16 else 2, _C.stream_ptr()), "cosa_im2col_flip")
-                tok = nn_ops.gemm_bf16(cols, wgt, bias, nn_ops.EPI_BIAS)
-                pos = self._pos_for_grid(h, w, dt16).reshape(N, D).contiguous()
-                _C.check(_C.lib().cosa_embed_finish(_C.ptr(tok), _C.ptr(cls), _C.ptr(pos), _C.ptr(xr[o0:o0 + B * N]), B, N - 1, D,
-                                                    1 if dt16 == torch.bfloat16 else 2, _C.stream_ptr()), "cosa_embed_finish")
-        else:
-            toks = []
-            for x in ([torch.cat([x, x.flip(-1)], dim=0) for x in xs] if flip_pairs else xs):
-                tok, h, w = self.prepare_tokens(x)                   # 16-bit [B,N,768]
-                toks.append(tok.float().reshape(-1, tok.shape[-1]))
-            xr = toks[0].contiguous() if len(toks) == 1 else torch.cat(toks, 0)     # fp32 residual stream [sum M_i, 768]
+    def _x3_until(self):
+        """(xa, xm): the attention halves of blocks < xa and the MLP halves of blocks < xm of an fp16c8 / fp16c4 pass run on bf16x3 operands
+        (16 significant bits: "fp16c8-x6", "fp16c8-x6m4") -- the early blocks, whose rounding passes through the most layers"""
+        xa = self.x3_until if getattr(self, "x3_until", None) is not None else 0
+        return xa, (self.x3_mlp_until if getattr(self, "x3_mlp_until", None) is not None else xa)
+
+    def _is_c4(self, i):
+        """does block i take its qkv / fc1 / fc2 projections on fp16c4 operands?  (every block in the fp16c4 modes; blocks >= c4_from in the mixed
+        fp16c8 maps: the late blocks, whose rounding passes through the fewest layers)"""
+        return self.precision == "fp16c4" or (self.precision == "fp16c8" and self.c4_from is not None and i >= self.c4_from)
+
+    def _operand_map(self):
+        """which projection of which block runs on which operand format, from the fields `set_nograd_precision` sets: the ONE place that
+        decides it (weight sets, buffers and the block loop all read the result).  Reads no tensor, launches nothing."""
         depth = len(self.blocks)
-        aux_idx = self.aux_layer % depth
-        aux = None
-        o = torch.empty((Mtot, D), device=xr.device, dtype=dt16)
-        for i, blk in enumerate(self.blocks):
-            y, _ = nn_ops.layernorm_f32(xr, c(blk.norm1.weight), c(blk.norm1.bias), blk.norm1.eps)
-            qkv = nn_ops.gemm_bf16(y, c(blk.attn.qkv.weight), c(blk.attn.qkv.bias), nn_ops.EPI_BIAS)
-            for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-                nn_ops._attn_fwd(qkv[o0:o1].view(B, N, 3 * D), B, N, self.num_heads, out=o[o0:o1].view(B, N, D), nograd=True)
-            # the stream is updated in place, except right after the auxiliary layer: its output stays where it is (it IS the aux
-            # feature) and the next residual GEMM writes the stream to a fresh buffer -- no 270-MB clone
-            xn = torch.empty_like(xr) if aux is xr else xr
-            nn_ops.gemm_bf16(o, c(blk.attn.proj.weight), c(blk.attn.proj.bias), nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
-            xr = xn
-            y, _ = nn_ops.layernorm_f32(xr, c(blk.norm2.weight), c(blk.norm2.bias), blk.norm2.eps)
-            hmid = nn_ops.gemm_bf16(y, c(blk.mlp.fc1.weight), c(blk.mlp.fc1.bias), nn_ops.EPI_GELU)
-            nn_ops.gemm_bf16(hmid, c(blk.mlp.fc2.weight), c(blk.mlp.fc2.bias), nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
-            if i == aux_idx and aux_idx != depth - 1:
-                aux = xr
-        xn16, xn32 = nn_ops.layernorm_f32(xr, c(self.norm.weight), c(self.norm.bias), self.norm.eps, True, True)
-        if aux is None:
-            aux = xn32
-        outs = []
-        for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-            a16, a32, ax = xn16[o0:o1].view(B, N, D), xn32[o0:o1].view(B, N, D), aux[o0:o1].view(B, N, D)
-            outs.append((a32[:, 0], a16[:, 1:], ax[:, 1:], a32[:, 1:]))
-        return outs
+        if self.precision not in ("bf16x3", "fp16c8", "fp16c4"):
+            return OperandMap("plain", ("plain",) * depth, ("plain",) * depth, False, False, self.compute_dtype, None)
+        if self.precision == "bf16x3":                # (hi / lo halves of x3_dtype: "bf16x3" or "fp16x3")
+            return OperandMap("x3", ("x3",) * depth, ("x3",) * depth, False, False, None, self.x3_dtype)
+        (pa, pm), (xa, xm) = self._plain_from(), self._x3_until()
+        # the early blocks on bf16x3 operands (the bf16 build's split-row kernels on the same fp32 stream); the last blocks on plain fp16
+        # operands (the fused 1x path): rounding injected there passes through the fewest layers and never reaches the auxiliary CAM
+        half = lambda i, x, p_: "x3" if i < x else "plain" if i >= p_ else "c4" if self._is_c4(i) else "c8"
+        return OperandMap("c8", tuple(half(i, xa, pa) for i in range(depth)), tuple(half(i, xm, pm) for i in range(depth)),
+                          bool(self.c8_plain_qkv), bool(self.c4_proj), torch.float16, torch.bfloat16)
 
-    # -- parity-grade no-grad path: every MFMA operand as hi + lo bf16 halves (bf16x3), fp32 residual / LayerNorm / CAM heads ----------
-    def _split_weights(self, until=None, dtype=torch.bfloat16):
-        """split rows [N, 2K+64] (bias in the augmentation block) of the patch projection and the 48 block projections, rebuilt from
-        the fp32 masters on every pass (the teacher's masters move every step; ~0.5 GB of traffic, part of the captured graph).
-        until = (xa, xm): only the attention projections of blocks < xa and the MLP projections of blocks < xm (the mixed fp16c8-xN maps;
-        the patch projection then stays with the fp16c8 path)"""
+    def _operand_items(self, fmap, fmt):
+        """(name, weight, bias) of every projection that `fmap` puts on operand format `fmt`, the patch projection first"""
+        items = [("patch", self.patch_embed.proj.weight.reshape(self.embed_dim, -1), self.patch_embed.proj.bias)] if fmap.patch == fmt else []
+        for i, blk in enumerate(self.blocks):
+            for n, m in (("qkv", blk.attn.qkv), ("proj", blk.attn.proj), ("fc1", blk.mlp.fc1), ("fc2", blk.mlp.fc2)):
+                if fmap.of(i, n) == fmt:
+                    items.append((f"{i}.{n}", m.weight, m.bias))
+        return items
+
+    def _operand_rows(self, fmap, fmt):
+        """{name: weight operand} of format `fmt` ("x3", "c8" or "c4"), rebuilt from the fp32 masters on every pass (the teacher's masters move
+        every step; ~0.5 GB of traffic, part of the captured graph)"""
+        items = self._operand_items(fmap, fmt)
+        return self._split_weights(items, fmap.hdt) if fmt == "x3" else self._batched_rows(fmt, items)
+
+    def _split_weights(self, items, dtype):
+        """split rows [N, 2K+64] (bias in the augmentation block), one launch per tensor"""
         ws = self.__dict__.setdefault("_x3_w", {}).setdefault(dtype, {})          # (bf16 halves: bf16x3 and the early blocks of fp16c8-xN; fp16: fp16x3)
-        depth = len(self.blocks)
-        xa, xm = until if until is not None else (depth, depth)
-        items = [("patch", self.patch_embed.proj.weight.reshape(self.embed_dim, -1), self.patch_embed.proj.bias)] if until is None else []
-        for i, blk in enumerate(self.blocks):
-            if i < xa:
-                items += [(f"{i}.qkv", blk.attn.qkv.weight, blk.attn.qkv.bias), (f"{i}.proj", blk.attn.proj.weight, blk.attn.proj.bias)]
-            if i < xm:
-                items += [(f"{i}.fc1", blk.mlp.fc1.weight, blk.mlp.fc1.bias), (f"{i}.fc2", blk.mlp.fc2.weight, blk.mlp.fc2.bias)]
         for name, w, b in items:
             buf = ws.get(name)
             if buf is None or buf.device != w.device:
@@ -303,329 +314,266 @@ class VisionTransformer(nn.Module):
             nn_ops.split_rows(w.detach(), bias=b.detach(), out=buf)
         return ws
 
-    def _x3_buffers(self, M, dev, dtype=torch.bfloat16):
-        """persistent split-row activations for M token rows; the (1, 1, 0, ...) augmentation block of the fc1 output is set once here
-        (the GEMM epilogue writes the hi | lo halves only), the other buffers get theirs from their producing kernels"""
-        bufs = self.__dict__.setdefault("_x3_bufs", {})
-        ent = bufs.get((M, dev, dtype))
-        if ent is None:
-            D, Hd = self.embed_dim, self.blocks[0].mlp.fc1.weight.shape[0]
-            mk = lambda cols: torch.zeros((M, cols), device=dev, dtype=dtype)
-            ent = {"y": mk(nn_ops.split_ld(D)), "qkv": mk(2 * 3 * D), "o": mk(nn_ops.split_ld(D)), "h": mk(nn_ops.split_ld(Hd))}
-            ent["h"][:, 2 * Hd:2 * Hd + 2] = 1
-            bufs[(M, dev, dtype)] = ent
-        return ent
-
-    def _forward_features_x3_multi(self, xs, flip_pairs=False):
-        from .. import _C
-        D, H = self.embed_dim, self.num_heads
-        p = self.patch_size
-        hdt = self.x3_dtype                      # bf16 halves ("bf16x3") or fp16 halves ("fp16x3", round 6: 11 + 11 significant bits at the same cost)
-        W = self._split_weights(dtype=hdt)
-        nf = 2 if flip_pairs else 1              # flip_pairs: every batch stands for cat(x, x.flip(-1)) (the teacher's passes)
-        # token assembly without ATen passes (as the fp16c8 path has it): the residual stream xr [sum_i B_i (n_i + 1), D] starts as
-        # (cls + pos_0 | pos rows) per image, the im2col kernel writes the split rows of the patches (images and their mirror images) into a
-        # token-shaped operand whose class-token rows stay zero (augmentation block included: no bias there), and the patch projection of
-        # a scale adds into xr in place through its fp32 residual epilogue.  One launch per scale, as before: cosa_gemm_bf16x3 picks its kernel by
-        # M (the 128 x 128 kernel below 4096 rows: another summation order than the persistent one), so per token row the same products are
-        # summed in the same order as with one projection per scale on materialised im2col rows (the form up to round 6): bit-identical CAMs.
-        shapes = [(nf * x.shape[0], (x.shape[2] // p) * (x.shape[3] // p) + 1) for x in xs]
-        offs = [0]
-        for B, N in shapes:
-            offs.append(offs[-1] + B * N)
-        M = offs[-1]
-        dev = xs[0].device
-        Kp = xs[0].shape[1] * p * p
-        bf = self._x3_buffers(M, dev, dtype=hdt)
-        ckey = ("cols", tuple(shapes), Kp)
-        cols = bf.get(ckey)
-        if cols is None:
-            for k in [k for k in bf if isinstance(k, tuple) and k[0] == "cols"]:
-                del bf[k]                                                                 # (another token geometry at the same M: its zero rows are elsewhere)
-            cols = bf[ckey] = torch.zeros((M, nn_ops.split_ld(Kp)), device=dev, dtype=hdt)      # (class-token rows: zero for good)
-        xr = torch.empty((M, D), device=dev, dtype=torch.float32)
-        cls = self.cls_token.detach().float().reshape(1, 1, D)
-        for x, (B, N), o0, o1 in zip(xs, shapes, offs[:-1], offs[1:]):
-            h, w = x.shape[2] // p, x.shape[3] // p
-            pos = self._pos_for_grid(h, w, torch.float32)                              # [1, n+1, D]
-            first = torch.cat((cls + pos[:, :1], pos[:, 1:]), dim=1).contiguous()       # (a [n+1, D] tensor: small)
-            _C.check(_C.lib().cosa_broadcast_rows(_C.ptr(first), _C.ptr(xr[o0:o1]), B, N * D, _C.stream_ptr()), "cosa_broadcast_rows")
-            xf = x.float().contiguous()
-            _C.check(nn_ops._x3_fn("cosa_im2col_flip_split_tokens", hdt)(_C.ptr(xf), _C.ptr(cols[o0:o1]), x.shape[0], x.shape[1], x.shape[2], x.shape[3],
-                                                                       p, nf, 1, _C.stream_ptr()), "cosa_im2col_flip_split_tokens")
-            nn_ops.gemm_x3(cols[o0:o1], W["patch"], B * N, D, Kp, nn_ops.EPI_RESIDUAL, residual=xr[o0:o1], out=xr[o0:o1])
-        depth = len(self.blocks)
-        aux_idx = self.aux_layer % depth
-        aux = None
-        f = lambda t: t.detach()
-        for i, blk in enumerate(self.blocks):
-            nn_ops.layernorm_split(xr, f(blk.norm1.weight), f(blk.norm1.bias), blk.norm1.eps, out=bf["y"])
-            nn_ops.gemm_x3(bf["y"], W[f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"], ldy=2 * 3 * D)
-            for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-                nn_ops.attn_fwd_x3(bf["qkv"][o0:o1], B, N, H, bf["o"][o0:o1])
-            xn = torch.empty_like(xr) if aux is xr else xr              # right after the auxiliary layer: keep its output, no clone
-            nn_ops.gemm_x3(bf["o"], W[f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
-            xr = xn
-            nn_ops.layernorm_split(xr, f(blk.norm2.weight), f(blk.norm2.bias), blk.norm2.eps, out=bf["y"])
-            nn_ops.gemm_x3(bf["y"], W[f"{i}.fc1"], M, bf["h"].shape[1] // 2 - 32, D, nn_ops.EPI_GELU, out=bf["h"], ldy=bf["h"].shape[1])
-            nn_ops.gemm_x3(bf["h"], W[f"{i}.fc2"], M, D, bf["h"].shape[1] // 2 - 32, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
-            if i == aux_idx and aux_idx != depth - 1:
-                aux = xr
-        yfin = torch.empty_like(bf["y"])
-        _, xn32 = nn_ops.layernorm_split(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps, out=yfin, want_f32=True)
-        if aux is None:
-            aux = xn32
-        outs = []
-        for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-            a16 = yfin[o0:o1].view(B, N, -1)[:, :, :D]                      # the hi halves: bf16 tokens for the decoder convs (strided view)
-            a32, ax = xn32[o0:o1].view(B, N, D), aux[o0:o1].view(B, N, D)
-            outs.append((a32[:, 0], a16[:, 1:], ax[:, 1:], a32[:, 1:]))
-        return outs
-
-    # -- parity-grade no-grad path at 2x: fp16 operands + 8-bit correction terms (fp16c8; csrc/c8.hpp), fp32 residual / LayerNorm / CAM heads;
-    #    attention on plain fp16 q, k, v (its OUTPUT leaves as c8 rows): tools/sim_precision_map.py is the sensitivity study behind this map
-    def _plain_from(self):
-        """(first block whose attention half, first block whose MLP half) runs on plain fp16 operands in the fp16c8 / fp16c4 modes"""
-        depth = len(self.blocks)
-        a = self.c8_plain_from if self.c8_plain_from is not None else depth
-        m = self.c8_plain_mlp_from if self.c8_plain_mlp_from is not None else a
-        return a, m
-
-    def _x3_until(self):
-        """(xa, xm): the attention halves of blocks < xa and the MLP halves of blocks < xm of an fp16c8 / fp16c4 pass run on bf16x3 operands
-        (16 significant bits: "fp16c8-x6", "fp16c8-x6m4") -- the early blocks, whose rounding passes through the most layers"""
-        xa = self.x3_until if getattr(self, "x3_until", None) is not None else 0
-        xm = self.x3_mlp_until if getattr(self, "x3_mlp_until", None) is not None else xa
-        return xa, xm
-
-    def _is_c4(self, i):
-        """does block i take its qkv / fc1 / fc2 projections on fp16c4 operands?  (every block in the fp16c4 modes; blocks >= c4_from in the mixed
-        fp16c8 maps: the late blocks, whose rounding passes through the fewest layers)"""
-        return self.precision == "fp16c4" or (self.precision == "fp16c8" and self.c4_from is not None and i >= self.c4_from)
-
-    def _any_c4(self):
-        return any(self._is_c4(i) for i in range(len(self.blocks)))
-
-    def _c8_weights(self):
-        """c8 rows [N, 2K+64 fp16 units] (bias in the augmentation block) of the patch projection and the block projections, rebuilt from the
-        fp32 masters on every pass (the teacher's masters move every step; part of the captured graph) by ONE batched launch"""
+    def _batched_rows(self, fmt, items):
+        """c8 rows [N, 2K+64 fp16 units] (bias in the augmentation block), or fp16c4 rows + their scale tensors (csrc/c4.hpp; the patch
+        projection never: its operand comes out of the im2col kernel as c8 rows), by ONE batched launch"""
         import numpy as np
         from .. import _C
-        items = [("patch", self.patch_embed.proj.weight.reshape(self.embed_dim, -1), self.patch_embed.proj.bias)]
-        pa, pm = self._plain_from()
-        xa, xm = self._x3_until()
-        for i, blk in enumerate(self.blocks):
-            if self._is_c4(i):                      # qkv / fc1 / fc2 (and proj with c4_proj) run on fp16c4 operands (_c4_weights)
-                if not self.c4_proj and xa <= i < pa:
-                    items += [(f"{i}.proj", blk.attn.proj.weight, blk.attn.proj.bias)]
-                continue
-            if xa <= i < pa:
-                items += ([] if self.c8_plain_qkv else [(f"{i}.qkv", blk.attn.qkv.weight, blk.attn.qkv.bias)]) + \
-                         [(f"{i}.proj", blk.attn.proj.weight, blk.attn.proj.bias)]
-            if xm <= i < pm:
-                items += [(f"{i}.fc1", blk.mlp.fc1.weight, blk.mlp.fc1.bias), (f"{i}.fc2", blk.mlp.fc2.weight, blk.mlp.fc2.bias)]
-        ent = self.__dict__.get("_c8_w")
+        c4 = fmt == "c4"
+        ent = self.__dict__.get(f"_{fmt}_w")
         key = tuple((n, w.data_ptr(), b.data_ptr()) for n, w, b in items)
         if ent is None or ent["key"] != key:
             dev = items[0][1].device
-            bufs = {n: torch.empty((w.shape[0], nn_ops.split_ld(w.shape[1])), device=dev, dtype=torch.float16) for n, w, _ in items}
-            rec_dt = np.dtype([("src", "u8"), ("bias", "u8"), ("dst", "u8"), ("rows", "i4"), ("K", "i4"), ("row0", "i4"), ("qrows", "i4")])
-            assert rec_dt.itemsize == _C.lib().cosa_c8_record_bytes()
+            rows = lambda w: (torch.zeros if c4 else torch.empty)((w.shape[0], nn_ops.split_ld(w.shape[1])), device=dev, dtype=torch.float16)
+            bufs = {n: (rows(w), nn_ops.c4_scales(w.shape[0], w.shape[1], dev)) if c4 else rows(w) for n, w, _ in items}
+            rec_dt = np.dtype([("src", "u8"), ("bias", "u8"), ("dst", "u8")] + ([("sc", "u8")] if c4 else []) +
+                              [("rows", "i4"), ("K", "i4"), ("row0", "i4"), ("qrows", "i4")])
+            assert rec_dt.itemsize == (_C.lib().cosa_c4_record_bytes() if c4 else _C.lib().cosa_c8_record_bytes())
             rec, row0 = np.zeros(len(items), rec_dt), 0
             for j, (n, w, b) in enumerate(items):
-                assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[1] % 128 == 0
+                assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[1] % (256 if c4 else 128) == 0 and (not c4 or w.shape[0] % 256 == 0)
+                dst = tuple(t.data_ptr() for t in bufs[n]) if c4 else (bufs[n].data_ptr(),)
                 # (qkv: the attention scale is folded into the q rows -- the attention kernel is then called with scale = ln 2, nn_ops.LN2)
-                rec[j] = (w.data_ptr(), b.data_ptr(), bufs[n].data_ptr(), w.shape[0], w.shape[1], row0, w.shape[0] // 3 if n.endswith(".qkv") else 0)
+                rec[j] = (w.data_ptr(), b.data_ptr()) + dst + (w.shape[0], w.shape[1], row0, w.shape[0] // 3 if n.endswith(".qkv") else 0)
                 row0 += w.shape[0]
-            ent = self.__dict__["_c8_w"] = {"key": key, "bufs": bufs, "rec": torch.from_numpy(rec.view(np.uint8).copy()).to(dev),
-                                            "n": len(items), "rows": row0}
-        _C.check(_C.lib().cosa_c8_rows_batched(_C.ptr(ent["rec"]), ent["n"], ent["rows"], _C.stream_ptr()), "cosa_c8_rows_batched")
+            ent = self.__dict__[f"_{fmt}_w"] = {"key": key, "bufs": bufs, "rec": torch.from_numpy(rec.view(np.uint8).copy()).to(dev),
+                                                "n": len(items), "rows": row0}
+        fn = "cosa_c4_rows_batched" if c4 else "cosa_c8_rows_batched"
+        _C.check(getattr(_C.lib(), fn)(_C.ptr(ent["rec"]), ent["n"], ent["rows"], _C.stream_ptr()), fn)
         return ent["bufs"]
 
-    def _c4_weights(self):
-        """fp16c4 weight rows + scale tensors (csrc/c4.hpp) of the projections that run on fp16c4 operands -- qkv, fc1, fc2 of the corrected
-        blocks (and proj with `c4_proj`); the patch projection stays fp16c8 (its operand comes out of the im2col kernel as c8 rows) --
-        rebuilt from the fp32 masters on every pass by ONE batched launch"""
-        import numpy as np
-        from .. import _C
-        items = []
-        pa, pm = self._plain_from()
-        xa, xm = self._x3_until()
-        for i, blk in enumerate(self.blocks):
-            if not self._is_c4(i):
-                continue
-            if xa <= i < pa:
-                if not self.c8_plain_qkv:
-                    items.append((f"{i}.qkv", blk.attn.qkv.weight, blk.attn.qkv.bias))
-                if self.c4_proj:
-                    items.append((f"{i}.proj", blk.attn.proj.weight, blk.attn.proj.bias))
-            if xm <= i < pm:
-                items += [(f"{i}.fc1", blk.mlp.fc1.weight, blk.mlp.fc1.bias), (f"{i}.fc2", blk.mlp.fc2.weight, blk.mlp.fc2.bias)]
-        ent = self.__dict__.get("_c4_w")
-        key = tuple((n, w.data_ptr(), b.data_ptr()) for n, w, b in items)
-        if ent is None or ent["key"] != key:
-            dev = items[0][1].device
-            bufs = {n: (torch.zeros((w.shape[0], nn_ops.split_ld(w.shape[1])), device=dev, dtype=torch.float16),
-                        nn_ops.c4_scales(w.shape[0], w.shape[1], dev)) for n, w, _ in items}
-            rec_dt = np.dtype([("src", "u8"), ("bias", "u8"), ("dst", "u8"), ("sc", "u8"), ("rows", "i4"), ("K", "i4"), ("row0", "i4"), ("qrows", "i4")])
-            assert rec_dt.itemsize == _C.lib().cosa_c4_record_bytes()
-            rec, row0 = np.zeros(len(items), rec_dt), 0
-            for j, (n, w, b) in enumerate(items):
-                assert w.dtype == torch.float32 and w.is_contiguous() and w.shape[1] % 256 == 0 and w.shape[0] % 256 == 0
-                rec[j] = (w.data_ptr(), b.data_ptr(), bufs[n][0].data_ptr(), bufs[n][1].data_ptr(), w.shape[0], w.shape[1], row0,
-                          w.shape[0] // 3 if n.endswith(".qkv") else 0)          # (q rows pre-scaled: see _c8_weights)
-                row0 += w.shape[0]
-            ent = self.__dict__["_c4_w"] = {"key": key, "bufs": bufs, "rec": torch.from_numpy(rec.view(np.uint8).copy()).to(dev),
-                                            "n": len(items), "rows": row0}
-        _C.check(_C.lib().cosa_c4_rows_batched(_C.ptr(ent["rec"]), ent["n"], ent["rows"], _C.stream_ptr()), "cosa_c4_rows_batched")
-        return ent["bufs"]
+    _BUFS_MAX = 8          # cached geometries (each holds ~M x 7 KB of activations): evaluation over many image sizes must not pin them all
 
-    _C8_BUFS_MAX = 8          # cached geometries (each holds ~M x 7 KB of activations): evaluation over many image sizes must not pin them all
-
-    def _c8_buffers(self, M, dev, geom=None):
-        """persistent activations for M token rows; the (1, 1, 0, ...) augmentation block of the fc1 output is set once here (the GEMM
-        epilogue writes hi | lo8 | hi8 only), the other c8 buffers get theirs from their producing kernels.  Keyed on the FULL token geometry
-        (the (images, tokens) split per scale and the patch width), not on M alone: the token-shaped patch operand `cols` relies on its
-        class-token rows staying zero, and another split of the same M puts class tokens where stale patch rows sit.  Least
-        recently used geometries are dropped beyond _C8_BUFS_MAX, except those a captured hipGraph replays into."""
-        bufs = self.__dict__.setdefault("_c8_bufs", {})
-        key = (M, dev, geom)
+    def _operand_buffers(self, fmt, dtype, pk, cols=False):
+        """persistent "x3" / "c8" activations for the token rows of `pk`; the (1, 1, 0, ...) augmentation block of the fc1 output is set once
+        here (the GEMM epilogues write the operand halves only), the other buffers get theirs from their producing kernels.  Keyed on the FULL
+        token geometry (the (images, tokens) split per scale and the patch width), not on M alone: the token-shaped patch operand `cols`
+        relies on its class-token rows staying zero, and another split of the same M puts class tokens where stale patch rows sit (ADVICE
+        r4).  Least recently used entries are dropped beyond _BUFS_MAX, except those a captured hipGraph replays into."""
+        bufs = self.__dict__.setdefault("_operand_bufs", {})
+        key = (fmt, dtype, pk.M, pk.dev, (pk.shapes, pk.Kp))
         ent = bufs.pop(key, None)
+        mk = lambda n: torch.zeros((pk.M, n), device=pk.dev, dtype=dtype)
         if ent is None:
             D, Hd = self.embed_dim, self.blocks[0].mlp.fc1.weight.shape[0]
-            mk = lambda cols: torch.zeros((M, cols), device=dev, dtype=torch.float16)
-            ent = {"y": mk(nn_ops.split_ld(D)), "qkv": mk(3 * D), "o": mk(nn_ops.split_ld(D)), "h": mk(nn_ops.split_ld(Hd))}
+            ent = {"y": mk(nn_ops.split_ld(D)), "qkv": mk((2 if fmt == "x3" else 1) * 3 * D), "o": mk(nn_ops.split_ld(D)), "h": mk(nn_ops.split_ld(Hd))}
             ent["h"][:, 2 * Hd:2 * Hd + 2] = 1
-            if self._any_c4():                      # the scale tensors of the c4 activation operands (LayerNorm, attention and GELU outputs)
-                ent["y_sc"], ent["o_sc"], ent["h_sc"] = nn_ops.c4_scales(M, D, dev), nn_ops.c4_scales(M, D, dev), nn_ops.c4_scales(M, Hd, dev)
+        if cols and "cols" not in ent:
+            ent["cols"] = mk(nn_ops.split_ld(pk.Kp))      # (class-token rows: zero for good)
         bufs[key] = ent                             # (re-inserted last: the dict is the LRU order)
         if torch.cuda.is_current_stream_capturing():
             ent["pinned"] = True
-        elif len(bufs) > self._C8_BUFS_MAX:
-            for k in [k for k, e in bufs.items() if not e.get("pinned") and k != key][:len(bufs) - self._C8_BUFS_MAX]:
+        elif len(bufs) > self._BUFS_MAX:
+            for k in [k for k, e in bufs.items() if not e.get("pinned") and k != key][:len(bufs) - self._BUFS_MAX]:
                 del bufs[k]
         return ent
 
-    def _forward_features_c8_multi(self, xs, flip_pairs=False):
-        from .. import _C
-        D, H = self.embed_dim, self.num_heads
+    def _token_pack(self, xs, flip_pairs):
         p = self.patch_size
-        W = self._c8_weights()
-        any_c4 = self._any_c4()
-        W4 = self._c4_weights() if any_c4 else None
-        nf = 2 if flip_pairs else 1                                                     # flip_pairs: every batch stands for cat(x, x.flip(-1))
-        # token assembly without concatenations: the residual stream xr [sum_i B_i (n_i + 1), D] starts as (cls + pos_0 | pos rows) per image, the
-        # im2col kernel writes the c8 rows of the patches (images and their mirror images) into a token-shaped operand whose class-token rows
-        # stay zero (augmentation block included: no bias there), and the patch projection of ALL scales -- one launch, token-wise like the
-        # block projections -- adds into xr in place through its fp32 residual epilogue
+        nf = 2 if flip_pairs else 1                  # flip_pairs: every batch stands for cat(x, x.flip(-1)) (the teacher's passes)
         shapes = [(nf * x.shape[0], (x.shape[2] // p) * (x.shape[3] // p) + 1) for x in xs]
         offs = [0]
         for B, N in shapes:
             offs.append(offs[-1] + B * N)
-        M = offs[-1]
-        dev = xs[0].device
-        Kp = xs[0].shape[1] * p * p
-        bf = self._c8_buffers(M, dev, geom=(tuple(shapes), Kp))
-        cols = bf.get("cols")
-        if cols is None or cols.shape[1] != nn_ops.split_ld(Kp):
-            cols = bf["cols"] = torch.zeros((M, nn_ops.split_ld(Kp)), device=dev, dtype=torch.float16)      # (class-token rows: zero for good)
-        xr = torch.empty((M, D), device=dev, dtype=torch.float32)
-        cls = self.cls_token.detach().float().reshape(1, 1, D)
-        for x, (B, N), o0, o1 in zip(xs, shapes, offs[:-1], offs[1:]):
+        return TokenPack(tuple(shapes), tuple(offs), offs[-1], xs[0].shape[1] * p * p, nf, xs[0].device)
+
+    def _forward_features_fused(self, x):
+        return self._forward_features_fused_multi([x])[0]
+
+    def _forward_features_fused_multi(self, xs, flip_pairs=False):
+        """Several image batches (the teacher's three scales) through the encoder TOGETHER: LayerNorm and the four
+        projections are token-wise, so all tokens of all scales go through one launch each per block (M = sum B_i N_i:
+        better tile quantisation on 256 CUs, a third of the launches); only attention runs per scale, on its slice of
+        the packed qkv buffer.  Token assembly and the closing LayerNorm belong to the operand family of the patch projection."""
+        fmap, pk = self._operand_map(), self._token_pack(xs, flip_pairs)
+        D = self.embed_dim
+        f = lambda t: t.detach()
+        if fmap.patch == "x3":
+            W = {"x3": self._operand_rows(fmap, "x3")}
+            bufs = {"x3": self._operand_buffers("x3", fmap.hdt, pk, cols=True)}
+            xr, aux = self._blocks_nograd(self._tokens_x3(xs, pk, bufs["x3"], W["x3"]["patch"], fmap.hdt), pk, fmap, W, bufs)
+            a16 = torch.empty_like(bufs["x3"]["y"])      # (its hi halves: 16-bit tokens for the decoder convs, a strided view)
+            _, xn32 = nn_ops.layernorm_split(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps, out=a16, want_f32=True)
+        elif fmap.patch == "c8":
+            W = {"c8": self._operand_rows(fmap, "c8")}
+            if fmap.uses("c4"):
+                W["c4"] = self._operand_rows(fmap, "c4")
+            bufs = {"c8": self._operand_buffers("c8", torch.float16, pk, cols=True)}
+            xr = self._tokens_c8(xs, pk, bufs["c8"], W["c8"]["patch"])
+            if "c4" in W and "y_sc" not in bufs["c8"]:
+                # the scale tensors of the c4 activation operands (LayerNorm, attention and GELU outputs), created when first needed: the
+                # buffers may stem from another precision setting
+                M, Hd = pk.M, self.blocks[0].mlp.fc1.weight.shape[0]
+                bufs["c8"].update(y_sc=nn_ops.c4_scales(M, D, pk.dev), o_sc=nn_ops.c4_scales(M, D, pk.dev), h_sc=nn_ops.c4_scales(M, Hd, pk.dev))
+            if fmap.uses("x3"):
+                W["x3"], bufs["x3"] = self._operand_rows(fmap, "x3"), self._operand_buffers("x3", fmap.hdt, pk)
+            xr, aux = self._blocks_nograd(xr, pk, fmap, W, bufs)
+            a16 = torch.empty_like(bufs["c8"]["y"])      # (its hi parts: fp16 tokens for the decoder convs, a strided view)
+            _, xn32 = nn_ops.layernorm_c8(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps, out=a16, want_f32=True)
+        else:
+            c = lambda p_: nn_ops.cast_param(p_, fmap.dt16)
+            xr, aux = self._blocks_nograd(self._tokens_plain(xs, pk, fmap.dt16, flip_pairs), pk, fmap, {}, {})
+            a16, xn32 = nn_ops.layernorm_f32(xr, c(self.norm.weight), c(self.norm.bias), self.norm.eps, True, True)
+        return pk.cut(a16, xn32, xn32 if aux is None else aux, D)
+
+    def _tokens_plain(self, xs, pk, dt16, flip_pairs):
+        """fp32 residual stream [sum M_i, 768] of the plain 16-bit family (dt16: bf16, or fp16 -- no-grad passes only: same kernels)"""
+        c = lambda p_: nn_ops.cast_param(p_, dt16)
+        D, p = self.embed_dim, self.patch_size
+        if not (all(x.is_cuda for x in xs) and D % 128 == 0 and (3 * p * p) % 64 == 0 and p % 8 == 0):
+            toks = []
+            for x in ([torch.cat([x, x.flip(-1)], dim=0) for x in xs] if flip_pairs else xs):
+                tok, h, w = self.prepare_tokens(x)                   # 16-bit [B,N,768]
+                toks.append(tok.float().reshape(-1, tok.shape[-1]))
+            return toks[0].contiguous() if len(toks) == 1 else torch.cat(toks, 0)
+        # patch projection on the own GEMM, then ONE pass per scale that adds the class token and the position rows and writes the fp32
+        # residual stream in place (cosa_embed_finish) -- instead of cat(cls, tok) + pos, .float() and the concatenation of the scales
+        from .. import _C
+        xr = torch.empty((pk.M, D), device=pk.dev, dtype=torch.float32)
+        wgt = c(self.patch_embed.proj.weight).reshape(D, -1).contiguous()
+        bias, cls = c(self.patch_embed.proj.bias).contiguous(), c(self.cls_token).reshape(-1).contiguous()
+        code = 1 if dt16 == torch.bfloat16 else 2
+        for x, (B, N, o0, o1) in zip(xs, pk.scales()):
             h, w = x.shape[2] // p, x.shape[3] // p
-            pos = self._pos_for_grid(h, w, torch.float32)                              # [1, n+1, D]
-            first = torch.cat((pos[:, :1] + cls, pos[:, 1:]), dim=1).contiguous()       # (a [n+1, D] tensor: small)
+            xf = x.float().contiguous()
+            cols = torch.empty((B * h * w, x.shape[1] * p * p), device=x.device, dtype=dt16)
+            _C.check(_C.lib().cosa_im2col_flip(_C.ptr(xf), _C.ptr(cols), x.shape[0], x.shape[1], x.shape[2], x.shape[3], p, pk.nf, code,
+                                               _C.stream_ptr()), "cosa_im2col_flip")
+            tok = nn_ops.gemm_bf16(cols, wgt, bias, nn_ops.EPI_BIAS)
+            pos = self._pos_for_grid(h, w, dt16).reshape(N, D).contiguous()
+            _C.check(_C.lib().cosa_embed_finish(_C.ptr(tok), _C.ptr(cls), _C.ptr(pos), _C.ptr(xr[o0:o1]), B, N - 1, D, code, _C.stream_ptr()),
+                     "cosa_embed_finish")
+        return xr
+
+    def _stream_and_cols(self, xs, pk, cols, im2col, name):
+        """token assembly without ATen passes or concatenations: the residual stream xr [sum_i B_i (n_i + 1), D] starts as (cls + pos_0 | pos rows)
+        per image, and the im2col kernel writes the operand rows of the patches (images and their mirror images) into the token-shaped `cols`,
+        whose class-token rows stay zero (augmentation block included: no bias there) -- the patch projection then adds into xr in place
+        through its fp32 residual epilogue"""
+        from .. import _C
+        D, p = self.embed_dim, self.patch_size
+        xr = torch.empty((pk.M, D), device=pk.dev, dtype=torch.float32)
+        cls = self.cls_token.detach().float().reshape(1, 1, D)
+        for x, (B, N, o0, o1) in zip(xs, pk.scales()):
+            pos = self._pos_for_grid(x.shape[2] // p, x.shape[3] // p, torch.float32)   # [1, n+1, D]
+            first = torch.cat((cls + pos[:, :1], pos[:, 1:]), dim=1).contiguous()       # (a [n+1, D] tensor: small)
             _C.check(_C.lib().cosa_broadcast_rows(_C.ptr(first), _C.ptr(xr[o0:o1]), B, N * D, _C.stream_ptr()), "cosa_broadcast_rows")
             xf = x.float().contiguous()
-            _C.check(_C.lib().cosa_im2col_flip_c8_tokens(_C.ptr(xf), _C.ptr(cols[o0:o1]), x.shape[0], x.shape[1], x.shape[2], x.shape[3], p, nf, 1,
-                                                         _C.stream_ptr()), "cosa_im2col_flip_c8_tokens")
-        nn_ops.gemm_c8(cols, W["patch"], M, D, Kp, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
-        Hd = self.blocks[0].mlp.fc1.weight.shape[0]
-        if any_c4 and "y_sc" not in bf:              # (the buffers were created under another precision setting)
-            bf["y_sc"], bf["o_sc"], bf["h_sc"] = nn_ops.c4_scales(M, D, dev), nn_ops.c4_scales(M, D, dev), nn_ops.c4_scales(M, Hd, dev)
+            _C.check(im2col(_C.ptr(xf), _C.ptr(cols[o0:o1]), x.shape[0], x.shape[1], x.shape[2], x.shape[3], p, pk.nf, 1, _C.stream_ptr()), name)
+        return xr
+
+    def _tokens_x3(self, xs, pk, bf, w_patch, hdt):
+        xr = self._stream_and_cols(xs, pk, bf["cols"], nn_ops._x3_fn("cosa_im2col_flip_split_tokens", hdt), "cosa_im2col_flip_split_tokens")
+        # One launch per scale: cosa_gemm_bf16x3 picks its kernel by M (the 128 x 128 kernel below 4096 rows: another summation order than the
+        # persistent one), so per token row the same products are summed in the same order as with one projection per scale on materialised
+        # im2col rows: bit-identical CAMs.
+        for B, N, o0, o1 in pk.scales():
+            nn_ops.gemm_x3(bf["cols"][o0:o1], w_patch, B * N, self.embed_dim, pk.Kp, nn_ops.EPI_RESIDUAL, residual=xr[o0:o1], out=xr[o0:o1])
+        return xr
+
+    def _tokens_c8(self, xs, pk, bf, w_patch):
+        from .. import _C
+        xr = self._stream_and_cols(xs, pk, bf["cols"], _C.lib().cosa_im2col_flip_c8_tokens, "cosa_im2col_flip_c8_tokens")
+        # the patch projection of ALL scales in one launch, token-wise like the block projections
+        nn_ops.gemm_c8(bf["cols"], w_patch, pk.M, self.embed_dim, pk.Kp, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+        return xr
+
+    def _blocks_nograd(self, xr, pk, fmap, W, bufs):
+        """the blocks on the fp32 stream xr, each half on the operand format `fmap` gives it -> (stream, aux-layer output or None)"""
         depth = len(self.blocks)
         aux_idx = self.aux_layer % depth
         aux = None
-        f = lambda t: t.detach()
-        c16 = lambda p_: nn_ops.cast_param(p_, torch.float16)
-        pa, pm = self._plain_from()
-        xa, xm = self._x3_until()
-        # mixed maps ("fp16c8-x6"): the early blocks on bf16x3 operands -- the bf16 build's split-row kernels on the same fp32 stream
-        W3 = self._split_weights(until=(xa, xm)) if max(xa, xm) > 0 else None
-        b3 = self._x3_buffers(M, dev) if W3 is not None else None
-        o16 = torch.empty((M, D), device=xr.device, dtype=torch.float16) if pa < depth else None
+        o16 = torch.empty((pk.M, self.embed_dim), device=xr.device, dtype=fmap.dt16) if "plain" in fmap.attn else None
         for i, blk in enumerate(self.blocks):
-            c4 = self._is_c4(i)
-            # ---- attention half ----
-            xn = torch.empty_like(xr) if aux is xr else xr              # right after the auxiliary layer: keep its output, no clone
-            if i < xa:
-                nn_ops.layernorm_split(xr, f(blk.norm1.weight), f(blk.norm1.bias), blk.norm1.eps, out=b3["y"])
-                nn_ops.gemm_x3(b3["y"], W3[f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=b3["qkv"], ldy=2 * 3 * D)
-                for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-                    nn_ops.attn_fwd_x3(b3["qkv"][o0:o1], B, N, H, b3["o"][o0:o1])
-                nn_ops.gemm_x3(b3["o"], W3[f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
-            elif i >= pa:
-                # the last blocks on plain fp16 operands (the fused 1x path on the same fp32 stream): rounding injected here passes through
-                # the fewest layers and never reaches the auxiliary CAM (tools/sim_precision_map.py, `from:` maps)
-                y, _ = nn_ops.layernorm_f32(xr, c16(blk.norm1.weight), c16(blk.norm1.bias), blk.norm1.eps)
-                qkv = nn_ops.gemm_bf16(y, c16(blk.attn.qkv.weight), c16(blk.attn.qkv.bias), nn_ops.EPI_BIAS)
-                for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-                    nn_ops._attn_fwd(qkv[o0:o1].view(B, N, 3 * D), B, N, H, out=o16[o0:o1].view(B, N, D), nograd=True)
-                nn_ops.gemm_bf16(o16, c16(blk.attn.proj.weight), c16(blk.attn.proj.bias), nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+            # the stream is updated in place, except right after the auxiliary layer: its output stays where it is (it IS the aux
+            # feature) and the next residual GEMM writes the stream to a fresh buffer -- no 270-MB clone
+            xn = torch.empty_like(xr) if aux is xr else xr
+            if fmap.attn[i] == "plain":
+                self._attn_plain(xr, xn, blk, pk, o16, fmap.dt16)
+            elif fmap.attn[i] == "x3":
+                self._attn_x3(xr, xn, blk, pk, bufs["x3"], W["x3"], i)
             else:
-                pre = True
-                if self.c8_plain_qkv:
-                    y, _ = nn_ops.layernorm_f32(xr, c16(blk.norm1.weight), c16(blk.norm1.bias), blk.norm1.eps)
-                    nn_ops.gemm_bf16(y, c16(blk.attn.qkv.weight), c16(blk.attn.qkv.bias), nn_ops.EPI_BIAS, out=bf["qkv"])
-                    pre = False
-                elif c4:
-                    # fp16c4: LayerNorm and the GELU epilogue (and, with c4_proj, the attention kernel) write c4 rows + scale bytes; qkv / fc1 /
-                    # fc2 run on the FP4 block-scaled MFMA, the output projection on fp16c8 operands unless c4_proj
-                    nn_ops.layernorm_c4(xr, f(blk.norm1.weight), f(blk.norm1.bias), blk.norm1.eps, out=bf["y"], scales=bf["y_sc"])
-                    nn_ops.gemm_c4(bf["y"], bf["y_sc"], *W4[f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"], ldy=3 * D)
-                else:
-                    nn_ops.layernorm_c8(xr, f(blk.norm1.weight), f(blk.norm1.bias), blk.norm1.eps, out=bf["y"])
-                    nn_ops.gemm_c8(bf["y"], W[f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"], ldy=3 * D)
-                for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-                    if c4 and self.c4_proj:
-                        nn_ops.attn_fwd_c4(bf["qkv"][o0:o1].view(B, N, 3 * D), B, N, H, bf["o"][o0:o1], bf["o_sc"], o0, q_prescaled=pre)
-                    else:
-                        nn_ops.attn_fwd_c8(bf["qkv"][o0:o1].view(B, N, 3 * D), B, N, H, bf["o"][o0:o1], q_prescaled=pre)
-                if c4 and self.c4_proj:
-                    nn_ops.gemm_c4(bf["o"], bf["o_sc"], *W4[f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
-                else:
-                    nn_ops.gemm_c8(bf["o"], W[f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+                self._attn_c8(xr, xn, blk, pk, bufs["c8"], W, i, fmap)
             xr = xn
-            # ---- MLP half ----
-            if i < xm:
-                nn_ops.layernorm_split(xr, f(blk.norm2.weight), f(blk.norm2.bias), blk.norm2.eps, out=b3["y"])
-                nn_ops.gemm_x3(b3["y"], W3[f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=b3["h"], ldy=b3["h"].shape[1])
-                nn_ops.gemm_x3(b3["h"], W3[f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
-            elif i >= pm:
-                y, _ = nn_ops.layernorm_f32(xr, c16(blk.norm2.weight), c16(blk.norm2.bias), blk.norm2.eps)
-                hmid = nn_ops.gemm_bf16(y, c16(blk.mlp.fc1.weight), c16(blk.mlp.fc1.bias), nn_ops.EPI_GELU)
-                nn_ops.gemm_bf16(hmid, c16(blk.mlp.fc2.weight), c16(blk.mlp.fc2.bias), nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
-            elif c4:
-                nn_ops.layernorm_c4(xr, f(blk.norm2.weight), f(blk.norm2.bias), blk.norm2.eps, out=bf["y"], scales=bf["y_sc"])
-                nn_ops.gemm_c4(bf["y"], bf["y_sc"], *W4[f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], out_scales=bf["h_sc"],
-                               ldy=nn_ops.split_ld(Hd))
-                nn_ops.gemm_c4(bf["h"], bf["h_sc"], *W4[f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+            if fmap.mlp[i] == "plain":
+                self._mlp_plain(xr, blk, fmap.dt16)
+            elif fmap.mlp[i] == "x3":
+                self._mlp_x3(xr, blk, pk, bufs["x3"], W["x3"], i)
             else:
-                nn_ops.layernorm_c8(xr, f(blk.norm2.weight), f(blk.norm2.bias), blk.norm2.eps, out=bf["y"])
-                nn_ops.gemm_c8(bf["y"], W[f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], ldy=nn_ops.split_ld(Hd))
-                nn_ops.gemm_c8(bf["h"], W[f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+                self._mlp_c8(xr, blk, pk, bufs["c8"], W, i, fmap.mlp[i] == "c4")
             if i == aux_idx and aux_idx != depth - 1:
                 aux = xr
-        yfin = torch.empty_like(bf["y"])
-        _, xn32 = nn_ops.layernorm_c8(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps, out=yfin, want_f32=True)
-        if aux is None:
-            aux = xn32
-        outs = []
-        for (B, N), o0, o1 in zip(shapes, offs[:-1], offs[1:]):
-            a16 = yfin[o0:o1].view(B, N, -1)[:, :, :D]                      # the hi parts: fp16 tokens for the decoder convs (strided view)
-            a32, ax = xn32[o0:o1].view(B, N, D), aux[o0:o1].view(B, N, D)
-            outs.append((a32[:, 0], a16[:, 1:], ax[:, 1:], a32[:, 1:]))
-        return outs
+        return xr, aux
+
+    def _attn_plain(self, xr, xn, blk, pk, o16, dt16):
+        c = lambda p_: nn_ops.cast_param(p_, dt16)
+        D = self.embed_dim
+        y, _ = nn_ops.layernorm_f32(xr, c(blk.norm1.weight), c(blk.norm1.bias), blk.norm1.eps)
+        qkv = nn_ops.gemm_bf16(y, c(blk.attn.qkv.weight), c(blk.attn.qkv.bias), nn_ops.EPI_BIAS)
+        for B, N, o0, o1 in pk.scales():
+            nn_ops._attn_fwd(qkv[o0:o1].view(B, N, 3 * D), B, N, self.num_heads, out=o16[o0:o1].view(B, N, D), nograd=True)
+        nn_ops.gemm_bf16(o16, c(blk.attn.proj.weight), c(blk.attn.proj.bias), nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+
+    def _mlp_plain(self, xr, blk, dt16):
+        c = lambda p_: nn_ops.cast_param(p_, dt16)
+        y, _ = nn_ops.layernorm_f32(xr, c(blk.norm2.weight), c(blk.norm2.bias), blk.norm2.eps)
+        hmid = nn_ops.gemm_bf16(y, c(blk.mlp.fc1.weight), c(blk.mlp.fc1.bias), nn_ops.EPI_GELU)
+        nn_ops.gemm_bf16(hmid, c(blk.mlp.fc2.weight), c(blk.mlp.fc2.bias), nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+
+    def _attn_x3(self, xr, xn, blk, pk, bf, W, i):
+        M, D = pk.M, self.embed_dim
+        nn_ops.layernorm_split(xr, blk.norm1.weight.detach(), blk.norm1.bias.detach(), blk.norm1.eps, out=bf["y"])
+        nn_ops.gemm_x3(bf["y"], W[f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"], ldy=2 * 3 * D)
+        for B, N, o0, o1 in pk.scales():
+            nn_ops.attn_fwd_x3(bf["qkv"][o0:o1], B, N, self.num_heads, bf["o"][o0:o1])
+        nn_ops.gemm_x3(bf["o"], W[f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+
+    def _mlp_x3(self, xr, blk, pk, bf, W, i):
+        M, D, Hd = pk.M, self.embed_dim, blk.mlp.fc1.weight.shape[0]
+        nn_ops.layernorm_split(xr, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, out=bf["y"])
+        nn_ops.gemm_x3(bf["y"], W[f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], ldy=bf["h"].shape[1])
+        nn_ops.gemm_x3(bf["h"], W[f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+
+    def _attn_c8(self, xr, xn, blk, pk, bf, W, i, fmap):
+        """fp16c8 attention half; its qkv projection may run on plain fp16 (`c8_plain_qkv`) or fp16c4 operands, its output projection on
+        fp16c4 operands (`c4_proj`: the attention kernel then writes c4 rows + scale bytes)"""
+        M, D, H = pk.M, self.embed_dim, self.num_heads
+        n1w, n1b = blk.norm1.weight.detach(), blk.norm1.bias.detach()
+        fq, fp = fmap.of(i, "qkv"), fmap.of(i, "proj")
+        if fq == "plain":
+            c16 = lambda p_: nn_ops.cast_param(p_, torch.float16)
+            y, _ = nn_ops.layernorm_f32(xr, c16(blk.norm1.weight), c16(blk.norm1.bias), blk.norm1.eps)
+            nn_ops.gemm_bf16(y, c16(blk.attn.qkv.weight), c16(blk.attn.qkv.bias), nn_ops.EPI_BIAS, out=bf["qkv"])
+        elif fq == "c4":
+            # fp16c4: LayerNorm and the GELU epilogue write c4 rows + scale bytes; qkv / fc1 / fc2 run on the FP4 block-scaled MFMA
+            nn_ops.layernorm_c4(xr, n1w, n1b, blk.norm1.eps, out=bf["y"], scales=bf["y_sc"])
+            nn_ops.gemm_c4(bf["y"], bf["y_sc"], *W["c4"][f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"], ldy=3 * D)
+        else:
+            nn_ops.layernorm_c8(xr, n1w, n1b, blk.norm1.eps, out=bf["y"])
+            nn_ops.gemm_c8(bf["y"], W["c8"][f"{i}.qkv"], M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"], ldy=3 * D)
+        for B, N, o0, o1 in pk.scales():                 # (the q rows of the c8 / c4 weight operands are pre-scaled: _batched_rows)
+            if fp == "c4":
+                nn_ops.attn_fwd_c4(bf["qkv"][o0:o1].view(B, N, 3 * D), B, N, H, bf["o"][o0:o1], bf["o_sc"], o0, q_prescaled=fq != "plain")
+            else:
+                nn_ops.attn_fwd_c8(bf["qkv"][o0:o1].view(B, N, 3 * D), B, N, H, bf["o"][o0:o1], q_prescaled=fq != "plain")
+        if fp == "c4":
+            nn_ops.gemm_c4(bf["o"], bf["o_sc"], *W["c4"][f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+        else:
+            nn_ops.gemm_c8(bf["o"], W["c8"][f"{i}.proj"], M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+
+    def _mlp_c8(self, xr, blk, pk, bf, W, i, c4):
+        """fp16c8 MLP half, or (c4) the same on fp16c4 operands"""
+        M, D, Hd = pk.M, self.embed_dim, blk.mlp.fc1.weight.shape[0]
+        n2w, n2b = blk.norm2.weight.detach(), blk.norm2.bias.detach()
+        if c4:
+            nn_ops.layernorm_c4(xr, n2w, n2b, blk.norm2.eps, out=bf["y"], scales=bf["y_sc"])
+            nn_ops.gemm_c4(bf["y"], bf["y_sc"], *W["c4"][f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], out_scales=bf["h_sc"],
+                           ldy=nn_ops.split_ld(Hd))
+            nn_ops.gemm_c4(bf["h"], bf["h_sc"], *W["c4"][f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+        else:
+            nn_ops.layernorm_c8(xr, n2w, n2b, blk.norm2.eps, out=bf["y"])
+            nn_ops.gemm_c8(bf["y"], W["c8"][f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], ldy=nn_ops.split_ld(Hd))
+            nn_ops.gemm_c8(bf["h"], W["c8"][f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
 
     def _n_defer_groups(self):
         g = self.defer_groups

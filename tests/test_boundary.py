@@ -193,6 +193,57 @@ def test_teacher_precision_mode_strings():
             net.set_nograd_precision(bad)
 
 
+def test_operand_map_and_weight_sets_per_mode():
+    """`VisionTransformer._operand_map`: the operand format of both halves of every block, and the weight set of each format
+    (`_operand_items`), against expectations written out here by hand for each mode string; every projection of every block is in exactly one
+    weight set or runs on plain operands, and the patch projection is in the set of its family"""
+    import torch
+    from cosa_amd.models import build_model
+    from cosa_amd.train_step import default_args
+    net = build_model(default_args("VOC12", crop_size=64))
+    enc = net.encoder
+    ALL = ("qkv", "proj", "fc1", "fc2")
+    names = lambda blocks, projs=ALL: {f"{i}.{n}" for i in blocks for n in projs}
+    r = range
+    # mode: (attention halves, MLP halves, x3 set, c8 set, c4 set)
+    want = {
+        "bf16": (["plain"] * 12, ["plain"] * 12, set(), set(), set()),
+        "fp16x3": (["x3"] * 12, ["x3"] * 12, {"patch"} | names(r(12)), set(), set()),
+        "fp16c8": (["c8"] * 12, ["c8"] * 12, set(), {"patch"} | names(r(12)), set()),
+        "fp16c8-9": (["c8"] * 9 + ["plain"] * 3, ["c8"] * 9 + ["plain"] * 3, set(), {"patch"} | names(r(9)), set()),
+        "fp16c8-9m7q": (["c8"] * 9 + ["plain"] * 3, ["c8"] * 7 + ["plain"] * 5, set(),
+                        {"patch"} | names(r(9), ("proj",)) | names(r(7), ("fc1", "fc2")), set()),
+        "fp16c8-x2": (["x3"] * 2 + ["c8"] * 10, ["x3"] * 2 + ["c8"] * 10, names(r(2)), {"patch"} | names(r(2, 12)), set()),
+        "fp16c8-x6m4": (["x3"] * 6 + ["c8"] * 6, ["x3"] * 4 + ["c8"] * 8, names(r(6), ("qkv", "proj")) | names(r(4), ("fc1", "fc2")),
+                        {"patch"} | names(r(6, 12), ("qkv", "proj")) | names(r(4, 12), ("fc1", "fc2")), set()),
+        "fp16c8-x2c6": (["x3"] * 2 + ["c8"] * 4 + ["c4"] * 6, ["x3"] * 2 + ["c8"] * 4 + ["c4"] * 6, names(r(2)),
+                        {"patch"} | names(r(2, 6)) | names(r(6, 12), ("proj",)), names(r(6, 12), ("qkv", "fc1", "fc2"))),
+        "fp16c4": (["c4"] * 12, ["c4"] * 12, set(), {"patch"} | names(r(12), ("proj",)), names(r(12), ("qkv", "fc1", "fc2"))),
+        "fp16c4-12m9": (["c4"] * 12, ["c4"] * 9 + ["plain"] * 3, set(), {"patch"} | names(r(12), ("proj",)),
+                        names(r(12), ("qkv",)) | names(r(9), ("fc1", "fc2"))),
+        "fp16c4 c4_proj": (["c4"] * 12, ["c4"] * 12, set(), {"patch"}, names(r(12))),
+    }
+    family = {"bf16": "plain", "fp16x3": "x3"}
+    for mode, (attn, mlp, x3, c8, c4) in want.items():
+        net.set_nograd_precision(mode.split()[0])
+        enc.c4_proj = mode.endswith("c4_proj")
+        fmap = enc._operand_map()
+        assert list(fmap.attn) == attn and list(fmap.mlp) == mlp, mode
+        assert fmap.patch == family.get(mode, "c8") and fmap.plain_qkv == mode.endswith("q") and fmap.c4_proj == enc.c4_proj, mode
+        got = {fmt: [n for n, _, _ in enc._operand_items(fmap, fmt)] for fmt in ("x3", "c8", "c4")}
+        assert {k: set(v) for k, v in got.items()} == {"x3": x3, "c8": c8, "c4": c4}, mode
+        listed = got["x3"] + got["c8"] + got["c4"]
+        assert len(listed) == len(set(listed)), mode                                     # in at most one set ...
+        for i in r(12):
+            for n in ALL:                                                                # ... and in one exactly unless plain
+                assert (f"{i}.{n}" in listed) == (fmap.of(i, n) != "plain"), (mode, i, n)
+        plain = {f"{i}.{n}" for i in r(12) for n in ALL} - set(listed)
+        want_plain = names([i for i in r(12) if attn[i] == "plain"], ("qkv", "proj")) | names([i for i in r(12) if mlp[i] == "plain"], ("fc1", "fc2")) | \
+            (names([i for i in r(12) if attn[i] != "plain"], ("qkv",)) if mode.endswith("q") else set())
+        assert plain == want_plain, mode
+        assert fmap.hdt == {"plain": None, "x3": torch.float16, "c8": torch.bfloat16}[fmap.patch], mode
+
+
 def test_auto_teacher_precision_is_backed_by_the_committed_accuracy_record():
     """`resolve_teacher_precision("auto", ...)` may only name a mode whose every line in the newest committed accuracy record
     (profiles/rNN_accuracy_teacher.txt: fused HIP teacher vs the fp32 CPU oracle, written on the GPU by tests/test_precision_gpu.py) keeps

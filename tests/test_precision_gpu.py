@@ -314,7 +314,7 @@ def test_im2col_c8_and_batched_weight_rows_equal_the_row_producer():
     with torch.no_grad():
         for q in net.parameters():
             q.add_(torch.randn_like(q) * 0.01)                                        # (biases are zero-initialised)
-    ws = net.encoder._c8_weights()
+    ws = net.encoder._operand_rows(net.encoder._operand_map(), "c8")
     assert len(ws) == 1 + 4 * 9 and "9.qkv" not in ws
     blk = net.encoder.blocks[3]
     for name, wgt, b in (("patch", net.encoder.patch_embed.proj.weight.reshape(768, -1), net.encoder.patch_embed.proj.bias),
@@ -825,7 +825,7 @@ def test_teacher_masks_through_par_vs_fp32_cpu_oracle(seed):
 
 
 def test_c8_operand_buffers_are_keyed_on_the_token_geometry():
-    """the token-shaped patch operand of the fp16c8 / fp16c4 passes keeps its class-token rows zero "for good", so its cache must
+    """the token-shaped patch operand of the fp16c8 / fp16c4 / x3 passes keeps its class-token rows zero "for good", so its cache must
     be keyed on the (images, tokens) split and not on the row count M alone: two batches with the SAME M and another split (2 images of 4 x 4
     patches, then 1 image of 3 x 11: 34 token rows each) must give what a fresh model gives, and the cache stays bounded"""
     from cosa_amd.models import build_model
@@ -835,7 +835,7 @@ def test_c8_operand_buffers_are_keyed_on_the_token_geometry():
     net = build_model(a).cuda().eval()
     sd = {k: v.clone() for k, v in net.state_dict().items()}
     xa, xb = torch.randn(2, 3, 64, 64, device="cuda"), torch.randn(1, 3, 48, 176, device="cuda")
-    for mode in ("fp16c4", "fp16c8"):
+    for mode in ("fp16c4", "fp16c8", "fp16x3", "bf16x3", "fp16c8-x2"):
         net.set_nograd_precision(mode)
         with torch.no_grad():
             net.forward_multi([xa])
@@ -848,6 +848,6 @@ def test_c8_operand_buffers_are_keyed_on_the_token_geometry():
         for g, w in zip(got, want):
             assert torch.equal(g, w), mode
     with torch.no_grad():
-        for wd in range(1, 14):                      # 13 more geometries: the cache holds at most _C8_BUFS_MAX of them
+        for wd in range(1, 14):                      # 13 more geometries: the cache holds at most _BUFS_MAX of them
             net.forward_multi([torch.randn(1, 3, 16, 16 * wd, device="cuda")])
-    assert len(net.encoder._c8_bufs) <= net.encoder._C8_BUFS_MAX
+    assert net.encoder._BUFS_MAX == 8 and len(net.encoder._operand_bufs) <= net.encoder._BUFS_MAX

@@ -195,7 +195,7 @@ def test_shapes_outside_the_hip_path_raise_instead_of_falling_back():
         nn_ops.attention(qkv32, 2)
 
 
-@pytest.mark.parametrize("S,mode,use_act", [(64, "fp16c8-x2", True), (64, "bf16", False), (224, "fp16c8-x2", True)])
+@pytest.mark.parametrize("S,mode,use_act", [(64, "fp16c8-x2", True), (64, "bf16", False), (224, "fp16c8-x2", True), (64, "fp16x3", True)])
 def test_teacher_graph_every_replay_equals_the_eager_pass(S, mode, use_act):
     """Round 6: the captured teacher pass must give the eager pass's bits on EVERY replay, not only on the first.  It did not: the min-max
     normalisation initialised its per-plane keys with hipMemsetAsync, and inside a captured hipGraph those memset nodes were not ordered with the
@@ -229,6 +229,35 @@ def test_teacher_graph_every_replay_equals_the_eager_pass(S, mode, use_act):
             torch.cuda.synchronize()
             for name, c, r in zip(("cam", "cam_aux", "seg0", "seg1", "seg2"), [out[0], out[1]] + list(out[2]), ref):
                 assert torch.equal(c, r), (rep + 1, name, float((c - r).abs().max()))
+
+
+def test_captured_teacher_keeps_its_operand_buffers_through_evictions():
+    """the activation-buffer cache pins what a captured graph replays into: a captured fp16x3 pass (the trainer's mode), then nine other
+    token geometries eagerly -- more than the cache's bound, one of them with the SAME row count and another (images, tokens) split, whose
+    token-shaped patch operand has its zero class-token rows elsewhere -- and the replay still gives the eager pass's bits"""
+    from cosa_amd.models import build_model
+    from cosa_amd.train_step import default_args
+    torch.manual_seed(0)
+    net = build_model(default_args("VOC12", crop_size=64)).cuda().eval()
+    net.set_nograd_precision("fp16x3")
+    xa, xb = torch.randn(2, 3, 64, 64, device="cuda"), torch.randn(1, 3, 48, 176, device="cuda")       # 34 token rows each
+    others = [xb] + [torch.randn(1, 3, 16, 16 * wd, device="cuda") for wd in range(1, 9)]
+    with torch.no_grad():
+        for _ in range(2):
+            e = net.forward_multi([xa], need_cls=False)[0]
+        torch.cuda.synchronize()
+        ref = [t.clone() for t in e if t is not None]
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            out = [t for t in net.forward_multi([xa], need_cls=False)[0] if t is not None]
+        for x in others:
+            net.forward_multi([x], need_cls=False)
+        assert len(net.encoder._operand_bufs) <= net.encoder._BUFS_MAX
+        g.replay()
+        torch.cuda.synchronize()
+    assert len(out) == len(ref) == 4                       # feature map, seg, cam, cam_aux
+    for j, (c, r) in enumerate(zip(out, ref)):
+        assert torch.equal(c, r), j
 
 
 def test_trainer_with_the_captured_teacher_trains_the_same_weights_as_with_the_eager_one():
