@@ -108,9 +108,12 @@ __device__ __forceinline__ bool attn_block_map(int nblk, int ngroups, int H, int
 // one is computed, one barrier per tile, no staging registers.  (The first version staged them through 32 registers that the compiler
 // kept in scratch: every tile waited for its global loads to store them, 1.02 ms per launch of the teacher's mix against 0.14 ms for
 // the bf16 kernel.)
-__global__ __launch_bounds__(256) void attn_fwd_x3_kernel(const op16 *__restrict__ qkv, op16 *__restrict__ out, float *__restrict__ lse,
-                                                         int N, int H, int nblk, int ngroups, float scale_log2e, int ldq, int ldo,
-                                                         unsigned long long *__restrict__ stamps)
+// The second bound (64 KB of LDS: two workgroups per CU anyway) is what keeps the MFMA accumulators in VGPRs: with a 512-register budget the
+// compiler put them into AGPRs and copied 64 of them per key tile to VGPRs for the softmax and the (hoisted) rescale, draining the matrix
+// pipe at every tile.  Same bits; fp16 launch at B = 32: 969 -> 913 us (N = 1765), 251 -> 232 us (N = 785) (profiles/attn_x3_vgpr_ab.txt).
+__global__ __launch_bounds__(256, 2) void attn_fwd_x3_kernel(const op16 *__restrict__ qkv, op16 *__restrict__ out, float *__restrict__ lse,
+                                                            int N, int H, int nblk, int ngroups, float scale_log2e, int ldq, int ldo,
+                                                            unsigned long long *__restrict__ stamps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];          // [2 stages][Kh | Kl | Vh | Vl][64 * 128]
     if (stamps && threadIdx.x == 0) atomicMin(&stamps[2 * (blockIdx.x & 63)], __builtin_amdgcn_s_memrealtime());     // device-clock span of the launch, as attn_fwd2_kernel
@@ -164,7 +167,12 @@ __global__ __launch_bounds__(256) void attn_fwd_x3_kernel(const op16 *__restrict
     };
     int ring = 0;
     dma_tile(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // The Q fragments are operands of this wait so that the compiler counts them as arrived HERE.  It does not read the wait inside the asm:
+    // with two of their loads scheduled behind the DMA it kept them pending around the loop and put vmcnt(1) / vmcnt(0) in front of the score
+    // MFMAs that use them -- on every tile, where those counts wait for the NEXT tile's DMA in the middle of the score block.
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(qh[0]), "+v"(qh[1]), "+v"(qh[2]), "+v"(qh[3]), "+v"(ql[0]), "+v"(ql[1]), "+v"(ql[2]), "+v"(ql[3])
+                 :: "memory");
     __syncthreads();
     const float NEG_INF = -INFINITY;
     auto tile = [&](int k0, auto tail_tag) {
@@ -749,9 +757,12 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const op16 *__restri
     }
 }
 
-__global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const op16 *__restrict__ qkv, const op16 *__restrict__ dO,
-                                                         const float *__restrict__ lse, const float *__restrict__ delta,
-                                                         op16 *__restrict__ dqkv, int N, int H, int nblk, int ngroups, float scale)
+// The second bound (32 KB of LDS and ~190 registers: two workgroups per CU) keeps the MFMA accumulators in VGPRs, as in attn_fwd_x3_kernel:
+// without it s0, s1, p0, p1 and g0, g1 lived in 96 AGPRs and every key tile moved 128 of them through v_accvgpr reads and writes.
+// Same bits; the kernel in the training step 86.4 -> 75.2 us, the whole backward at B = 16, N = 785 181.9 -> 171.2 us (profiles/attn_x3_vgpr_ab.txt).
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const op16 *__restrict__ qkv, const op16 *__restrict__ dO,
+                                                            const float *__restrict__ lse, const float *__restrict__ delta,
+                                                            op16 *__restrict__ dqkv, int N, int H, int nblk, int ngroups, float scale)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[4 * BK * 128];        // 2-deep ring of (K tile | V tile)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hh = lane >> 5;
