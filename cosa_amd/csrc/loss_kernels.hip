@@ -94,9 +94,15 @@ __device__ __forceinline__ float wave_sum(float v)
 // wrapping -- contributes nothing and sets a sticky flag word instead; the kernels that convert the sums back to fp32 then write NaN, as the
 // float atomics of round 2 would have.  Ranges: forward sums |v| < 2^31.  Gradient cells: a cell of the low-resolution logits receives at most
 // (2 S / h)^2 = 1024 adds at the configured 16x up-sampling (one per full-resolution pixel whose bilinear taps touch it; fewer when a wave or a
-// quad pre-sums its pixels), and one add is at most 0.5 g (the per-pixel gradient is 0.25 g / count per class group, summed over at most `count`
-// pixels of each of the two groups): |v| < 16 keeps 1024 adds inside 48 + 15 bits for every loss weight g < 32 (round 4 bounded |v| < 1 at 52
-// fractional bits, which a weight g >= 2 with few foreground pixels could trip: ADVICE r4).
+// quad pre-sums its pixels).  One add: a pixel of label map M in class group c (background / foreground) carries w_Mc g / count_Mc on
+// |p_k - [k == label]| <= 1 and bilinear weights <= 1; an add pre-sums any subset of the pixels, at most count_Mc of each group, so it is at most
+// W g with W = wA_bg + wA_fg + wB_bg + wB_fg (the sum, not the larger of each pair: for a class k that is nobody's label every term is +p_k; the
+// regulariser's share, weight 1e-7, is out of sight).  The trainer's table has W = (1-b)(1-a) + (1-b)a + b(1-a) + ba = 1 for every fg_alpha a and
+// aux blend b -- the defaults' 4 x 0.25 included --, so |v| < 16 carries every add for every loss weight g < 16; the entry point admits
+// weights in [0, 1] each, W <= 4, so g < 4 there.  The cell total is bounded by the same W g (all pixels once), far inside the 15 integer bits that
+// 1024 adds below 16 could fill (48 + 15 bits + sign).  A larger g may trip the check: the sticky flag then gives NaN, never a wrapped sum.
+// (Round 4 bounded |v| < 1 at 52 fractional bits, which a weight g >= 2 with few foreground pixels could trip: ADVICE r4.  This comment used
+// to give 0.5 g per add and g < 32 for the defaults; summed over all four groups it is g, hence g < 16.)
 __device__ __forceinline__ unsigned long long fix32(float v, unsigned long long *flag)
 {
     if (!(__builtin_fabsf(v) < 2147483648.0f)) { atomicOr(flag, 1ull); return 0ull; }
@@ -111,6 +117,8 @@ __device__ __forceinline__ unsigned long long fix52(float v, unsigned long long 
 
 // ---- forward ---------------------------------------------------------------------------------------------------
 // sums[8] = {bgA_sum, bgA_cnt, fgA_sum, fgA_cnt, bgB_sum, bgB_cnt, fgB_sum, fgB_cnt}
+// HAS_B = false: no second label map -- nothing of it is loaded and sums[4..7] stay zero (--aux_cam2seg false)
+template <bool HAS_B>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restrict__ seg_lr, const float *__restrict__ maskA,
                                                           const float *__restrict__ maskB, const float *__restrict__ simg,
                                                           const int32_t *__restrict__ boxes, unsigned long long *__restrict__ sums,
@@ -138,11 +146,13 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restri
             inv[p] = 1.0f / se;
             const float lse = mx + __logf(se);
             const size_t pix = (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1);
-            const int la = (int)maskA[(size_t)b * SS + pix], lb = (int)maskB[(size_t)b * SS + pix];
+            const int la = (int)maskA[(size_t)b * SS + pix], lb = HAS_B ? (int)maskB[(size_t)b * SS + pix] : 255;
             if (la == 0) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
             else if (la != 255) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
-            if (lb == 0) { acc[4] += lse - tap(tile, c.t[p]); acc[5] += 1.f; }
-            else if (lb != 255) { acc[6] += lse - tap(tile + lb * TC * TC, c.t[p]); acc[7] += 1.f; }
+            if (HAS_B) {
+                if (lb == 0) { acc[4] += lse - tap(tile, c.t[p]); acc[5] += 1.f; }
+                else if (lb != 255) { acc[6] += lse - tap(tile + lb * TC * TC, c.t[p]); acc[7] += 1.f; }
+            }
         }
         // pass 3: probabilities, 2x2 mean (the exact x0.5 bilinear), energy-grid outputs
         const int qy = c.Y >> 1, qx = c.X >> 1;
@@ -186,12 +196,17 @@ __global__ void seg_loss_sums_kernel(const unsigned long long *__restrict__ fix,
 // ---- backward ---------------------------------------------------------------------------------------------------
 // d/dz_k(pixel) = g_seg * [cA(pix) (p_k - [k==lA]) + cB(pix) (p_k - [k==lB])] + p_k (dP_k - sum_j p_j dP_j),
 //   dP_k = 0.25 * G_k(quad),  G = -2 * g_regw * AS / N * roi   (utils/seg_helper.py:899-902 + the x0.5 mean's adjoint)
+//   cM(pix) = w_M,bg / (count_M,bg + 1e-6) on a background pixel of map M, w_M,fg / (count_M,fg + 1e-6) on a foreground one, 0 on ignore
+// SegWeights: the four blend weights of main.py:200-203 x seg_helper.py:813 (fg_alpha a, aux blend b): A = ((1-b)(1-a), (1-b)a), B = (b(1-a), ba)
+struct SegWeights { float a_bg, a_fg, b_bg, b_fg; };
+
+template <bool HAS_B>
 __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restrict__ seg_lr, const float *__restrict__ maskA,
                                                           const float *__restrict__ maskB, const float *__restrict__ sums,
                                                           const float *__restrict__ AS, const float *__restrict__ roi,
                                                           const float *__restrict__ g_seg, const float *__restrict__ g_regw,
                                                           unsigned long long *__restrict__ grad, unsigned long long *__restrict__ flag,
-                                                          int B, int K, int hs, int ws, int S, float sy, float sx)
+                                                          SegWeights wt, int B, int K, int hs, int ws, int S, float sy, float sx)
 {
     extern __shared__ __attribute__((aligned(16))) float tile[];       // [K][TC][TC] logits, then [K][TC][TC] gradient cells (64-bit fixed point)
     const int b = blockIdx.z;
@@ -215,9 +230,9 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
         const int Sq = S >> 1;
         const size_t QQ = (size_t)Sq * Sq, q = (size_t)(c.Y >> 1) * Sq + (c.X >> 1);
         const float gs = g_seg[0];
-        // fg_alpha = 0.5 and aux blend 0.5 (main.py:200-203, seg_helper.py:813): each of the four terms carries 0.25
-        const float cbgA = 0.25f * gs / (sums[1] + 1e-6f), cfgA = 0.25f * gs / (sums[3] + 1e-6f);
-        const float cbgB = 0.25f * gs / (sums[5] + 1e-6f), cfgB = 0.25f * gs / (sums[7] + 1e-6f);
+        // main.py:200-203, seg_helper.py:813: with fg_alpha = 0.5 and aux blend 0.5 each of the four terms carries 0.25 (w * gs / count, in this order)
+        const float cbgA = wt.a_bg * gs / (sums[1] + 1e-6f), cfgA = wt.a_fg * gs / (sums[3] + 1e-6f);
+        const float cbgB = HAS_B ? wt.b_bg * gs / (sums[5] + 1e-6f) : 0.f, cfgB = HAS_B ? wt.b_fg * gs / (sums[7] + 1e-6f) : 0.f;
         const float ge = -2.0f * g_regw[0] / (float)B * roi[(size_t)b * QQ + q] * 0.25f;
         float m[4], inv[4], dot[4], ca[4], cb[4];
         int la[4], lb[4];
@@ -231,7 +246,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
             inv[p] = 1.0f / se;
             const size_t pix = (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1);
             la[p] = (int)maskA[(size_t)b * SS + pix];
-            lb[p] = (int)maskB[(size_t)b * SS + pix];
+            lb[p] = HAS_B ? (int)maskB[(size_t)b * SS + pix] : 255;
             ca[p] = la[p] == 0 ? cbgA : (la[p] != 255 ? cfgA : 0.f);
             cb[p] = lb[p] == 0 ? cbgB : (lb[p] != 255 ? cfgB : 0.f);
             dot[p] = 0.f;
@@ -252,7 +267,8 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
 #pragma unroll
             for (int p = 0; p < 4; p++) {
                 const float pk = __expf(tap(pl, c.t[p]) - m[p]) * inv[p];
-                dz[p] = ca[p] * (pk - (la[p] == k ? 1.f : 0.f)) + cb[p] * (pk - (lb[p] == k ? 1.f : 0.f)) + pk * (dP - dot[p]);
+                if (HAS_B) dz[p] = ca[p] * (pk - (la[p] == k ? 1.f : 0.f)) + cb[p] * (pk - (lb[p] == k ? 1.f : 0.f)) + pk * (dP - dot[p]);
+                else dz[p] = ca[p] * (pk - (la[p] == k ? 1.f : 0.f)) + pk * (dP - dot[p]);
             }
             unsigned long long *gp = gt + k * TC * TC;
             if (grouped) {    // 4 x 4 quads (lanes differing in bits 0, 1, 4, 5) share their four cells: one lane adds the sum of all sixteen
@@ -375,6 +391,10 @@ __device__ __forceinline__ float bilerp_fma(const float *pl, int w, int y0, int 
 
 // One WAVE per output cell, the class index on the lane (k = lane, lane + 64): every summed logit is evaluated once (the serial version
 // recomputed it in three passes and ran 12 544 threads in total), max / sum are wave reductions.
+// AFTER = true is the reference's other branch (seg_helper.py:558-561, --after_softmax true): the softmax runs over all K channels of
+// sum_scales / T, then the channels of absent classes are set to zero.  The {0,1} label factor commutes exactly with the bilinear blend
+// (0 * x = 0 and 1 * x = x in every term), so it is applied once, to the blended cell.
+template <bool AFTER>
 __global__ __launch_bounds__(256) void cam_target_kernel(SegScales sc, const float *__restrict__ labels, float *__restrict__ out,
                                                         int B, int K, int S, int oh, int ow, float inv_temp)
 {
@@ -390,12 +410,14 @@ __global__ __launch_bounds__(256) void cam_target_kernel(SegScales sc, const flo
     const int C = K - 1;
     constexpr int KR = 2;                           // classes per lane: K <= 128
     float z[KR][4];
+    bool pres[KR];
     float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
     for (int kr = 0; kr < KR; kr++) {
         const int k = lane + 64 * kr;
         const bool live = k < K;
         const bool present = live && (k == 0 || labels[(size_t)b * C + k - 1] != 0.0f);
+        pres[kr] = present;
 #pragma unroll
         for (int p = 0; p < 4; p++) {
             float zz = -INFINITY;
@@ -414,7 +436,7 @@ __global__ __launch_bounds__(256) void cam_target_kernel(SegScales sc, const flo
                     const float v = bilerp_fma(a, w, y0, y1, x0, x1, ly0, ly1, lx0, lx1) + bilerp_fma(f, w, y0, y1, f0, f1, ly0, ly1, fl0, fl1);
                     acc = s2 == 0 ? v : acc + v;
                 }
-                zz = (present ? acc : -1e5f) * inv_temp;
+                zz = ((AFTER || present) ? acc : -1e5f) * inv_temp;
             }
             z[kr][p] = zz;
             m[p] = fmaxf(m[p], zz);
@@ -442,7 +464,7 @@ __global__ __launch_bounds__(256) void cam_target_kernel(SegScales sc, const flo
             float acc_out = 0.f;
 #pragma unroll
             for (int p = 0; p < 4; p++) acc_out += wy[p >> 1] * wx[p & 1] * (z[kr][p] / se[p]);
-            out[(((size_t)b * C + k - 1) * oh + oy) * ow + ox] = acc_out;
+            out[(((size_t)b * C + k - 1) * oh + oy) * ow + ox] = (AFTER && !pres[kr]) ? 0.f : acc_out;
         }
     }
 }
@@ -628,11 +650,12 @@ extern "C" size_t cosa_seg_loss_workspace_bytes(int B, int K, int hs, int ws)
     return align_up((size_t)B * K * hs * ws * sizeof(unsigned long long) + (64 * 8 + 1) * sizeof(unsigned long long), 256);
 }
 
-extern "C" int cosa_seg_loss_forward(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
-                                     const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
-                                     int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+/* the general forms: maskB may be NULL (no second label map), four blend weights; the entry points without a suffix are these with both maps and 0.25 x 4 */
+extern "C" int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
+                                       const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                                       int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
 {
-    COSA_REQUIRE(seg_lr && maskA && maskB && simg && boxes && sums && s_seg && s_img && roi && unlabel && workspace, "cosa_seg_loss_forward: null pointer");
+    COSA_REQUIRE(seg_lr && maskA && simg && boxes && sums && s_seg && s_img && roi && unlabel && workspace, "cosa_seg_loss_forward: null pointer");
     int rc = check_shapes(B, K, hs, ws, S);
     if (rc) return rc;
     if (workspace_bytes < cosa_seg_loss_workspace_bytes(B, K, hs, ws)) {
@@ -646,19 +669,37 @@ extern "C" int cosa_seg_loss_forward(const float *seg_lr, const float *maskA, co
     COSA_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned long long), st));
     const dim3 grid((S + 31) / 32, (S + 31) / 32, B), blk(16, 16);
     const size_t lds = (size_t)K * TC * TC * sizeof(float);
-    hipLaunchKernelGGL(seg_loss_fwd_kernel, grid, blk, lds, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K,
-                       hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
+    if (maskB)
+        hipLaunchKernelGGL(seg_loss_fwd_kernel<true>, grid, blk, lds, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K,
+                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
+    else
+        hipLaunchKernelGGL(seg_loss_fwd_kernel<false>, grid, blk, lds, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K,
+                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_loss_sums_kernel, dim3(1), dim3(64), 0, st, fix, flag, sums);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }
 
-extern "C" int cosa_seg_loss_backward(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
-                                      const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
-                                      int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+extern "C" int cosa_seg_loss_forward(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
+                                     const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                                     int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
 {
-    COSA_REQUIRE(seg_lr && maskA && maskB && sums && AS && roi && g_seg && g_regw && grad_seg_lr && workspace, "cosa_seg_loss_backward: null pointer");
+    COSA_REQUIRE(maskB, "cosa_seg_loss_forward: null pointer");
+    return cosa_seg_loss_forward_w(seg_lr, maskA, maskB, simg, boxes, sums, s_seg, s_img, roi, unlabel, B, K, hs, ws, S, workspace, workspace_bytes,
+                                   stream);
+}
+
+extern "C" int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
+                                        const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
+                                        float wA_bg, float wA_fg, float wB_bg, float wB_fg,
+                                        int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+{
+    COSA_REQUIRE(seg_lr && maskA && sums && AS && roi && g_seg && g_regw && grad_seg_lr && workspace, "cosa_seg_loss_backward: null pointer");
+    // (a NaN fails every comparison: refused here as well)
+    COSA_REQUIRE(wA_bg >= 0.f && wA_bg <= 1.f && wA_fg >= 0.f && wA_fg <= 1.f && wB_bg >= 0.f && wB_bg <= 1.f && wB_fg >= 0.f && wB_fg <= 1.f,
+                 "cosa_seg_loss_backward: blend weights must lie in [0, 1] (got %g %g %g %g)", (double)wA_bg, (double)wA_fg, (double)wB_bg,
+                 (double)wB_fg);
     int rc = check_shapes(B, K, hs, ws, S);
     if (rc) return rc;
     const size_t n = (size_t)B * K * hs * ws;
@@ -672,17 +713,33 @@ extern "C" int cosa_seg_loss_backward(const float *seg_lr, const float *maskA, c
     COSA_HIP_CHECK(hipMemsetAsync(fix, 0, n * sizeof(unsigned long long), st));
     const dim3 grid((S + 31) / 32, (S + 31) / 32, B), blk(16, 16);
     const size_t lds = (size_t)((K * TC * TC + 1) & ~1) * sizeof(float) + (size_t)K * TC * TC * sizeof(unsigned long long);
-    static size_t lds_set = 0;
-    if (lds > 65536 && lds > lds_set) {
-        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)seg_loss_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
+    static size_t lds_set[2] = {0, 0};
+    const int hb = maskB ? 1 : 0;
+    if (lds > 65536 && lds > lds_set[hb]) {
+        const void *fn = hb ? (const void *)seg_loss_bwd_kernel<true> : (const void *)seg_loss_bwd_kernel<false>;
+        COSA_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set[hb] = lds;
     }
-    hipLaunchKernelGGL(seg_loss_bwd_kernel, grid, blk, lds, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, B, K, hs,
-                       ws, S, (float)hs / (float)S, (float)ws / (float)S);
+    const SegWeights wt = {wA_bg, wA_fg, wB_bg, wB_fg};
+    if (hb)
+        hipLaunchKernelGGL(seg_loss_bwd_kernel<true>, grid, blk, lds, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K,
+                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
+    else
+        hipLaunchKernelGGL(seg_loss_bwd_kernel<false>, grid, blk, lds, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K,
+                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_loss_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fix, flag, grad_seg_lr, n);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
+}
+
+extern "C" int cosa_seg_loss_backward(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
+                                      const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
+                                      int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+{
+    COSA_REQUIRE(maskB, "cosa_seg_loss_backward: null pointer");
+    return cosa_seg_loss_backward_w(seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, grad_seg_lr, 0.25f, 0.25f, 0.25f, 0.25f, B, K, hs, ws, S,
+                                    workspace, workspace_bytes, stream);
 }
 
 // multilabel_soft_margin_loss(v, y) with v = x or relu(x), and its gradient w.r.t. x for a unit upstream gradient (F.multilabel_soft_margin_loss,
@@ -700,11 +757,14 @@ extern "C" int cosa_msm_loss(const float *x, const float *y, float *grad, float 
     return COSA_OK;
 }
 
-extern "C" int cosa_cam_loss_targets(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
-                                     float *out, int B, int K, int S, int oh, int ow, float temperature, void *stream)
+/* after_softmax: 0 -- absent classes masked with -1e5 before the softmax (the reference's default); 1 -- softmax over all K channels, absent
+ * classes zeroed afterwards (seg_helper.py:558-561) */
+extern "C" int cosa_cam_loss_targets_m(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
+                                       float *out, int B, int K, int S, int oh, int ow, float temperature, int after_softmax, void *stream)
 {
     COSA_REQUIRE(seg_scales && hs && ws && labels && out && n_scales >= 1 && n_scales <= 4, "cosa_cam_loss_targets: bad arguments");
     COSA_REQUIRE(B > 0 && K > 1 && S > 0 && oh > 0 && ow > 0 && temperature > 0.f, "cosa_cam_loss_targets: bad shape");
+    COSA_REQUIRE(after_softmax == 0 || after_softmax == 1, "cosa_cam_loss_targets: after_softmax must be 0 or 1 (got %d)", after_softmax);
     SegScales sc;
     sc.n = n_scales;
     for (int i = 0; i < 4; i++) {
@@ -714,10 +774,20 @@ extern "C" int cosa_cam_loss_targets(const float *const *seg_scales, const int *
     }
     COSA_REQUIRE(K <= 128, "cosa_cam_loss_targets: at most 128 classes (got %d)", K);
     const int total = B * oh * ow;
-    hipLaunchKernelGGL(cam_target_kernel, dim3((total + 3) / 4), dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, oh, ow,
-                       1.0f / temperature);
+    if (after_softmax)
+        hipLaunchKernelGGL(cam_target_kernel<true>, dim3((total + 3) / 4), dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, oh, ow,
+                           1.0f / temperature);
+    else
+        hipLaunchKernelGGL(cam_target_kernel<false>, dim3((total + 3) / 4), dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, oh, ow,
+                           1.0f / temperature);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
+}
+
+extern "C" int cosa_cam_loss_targets(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
+                                     float *out, int B, int K, int S, int oh, int ow, float temperature, void *stream)
+{
+    return cosa_cam_loss_targets_m(seg_scales, hs, ws, n_scales, labels, out, B, K, S, oh, ow, temperature, 0, stream);
 }
 
 /* softmax over the classes of full-resolution logits [B,K,H,W] followed by DenseEnergyLoss's resize by 0.5 (H, W even), and its backward */

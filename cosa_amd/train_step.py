@@ -209,7 +209,11 @@ class CoSATrainer:
         # COSA_TEACHER_GRAPH=0 / COSA_TEACHER_SYNC=1: fallbacks reachable from any launcher's command line (first multi-GPU runs)
         self.use_graph = bool(getattr(args, "teacher_graph", True)) and on and os.environ.get("COSA_TEACHER_GRAPH", "1") != "0"
         self.graph_error = None              # why the capture was abandoned, if it was (the teacher then runs eagerly)
-        self.fused_losses = bool(getattr(args, "fused_losses", True)) and device.type == "cuda" and not args.after_softmax
+        # fused_losses: the dense losses on the HIP kernels, for every setting of --segfg_alpha / --aux_cam2seg_alpha / --aux_cam2seg /
+        # --after_softmax.  False selects the op-by-op torch path (host trainers; the A/B partner of the fused one)
+        self.fused_losses = bool(getattr(args, "fused_losses", True)) and device.type == "cuda"
+        if self.fused_losses:               # (refuses an alpha outside [0, 1] here, not in the first step past warm-up)
+            seg_helper.seg_blend_weights(args.segfg_alpha, args.aux_cam2seg_alpha, bool(args.aux_cam2seg))
         self._graph = None
         self._loss_weights = {}
         self._graph_calls = 0
@@ -298,7 +302,7 @@ class CoSATrainer:
     def forward_losses(self, wimg, simg, cls_label, img_box, n_iter):
         args = self.args
         img_denorm = torch_helper.denormalize_img(simg) if self.refine_model is not None else simg
-        fused = self.fused_losses and args.aux_cam2seg and args.segfg_alpha == 0.5 and args.aux_cam2seg_alpha == 0.5
+        fused = self.fused_losses
         if fused and self._lattice is not None:
             self._lattice.start(simg, args.num_classes)
         if self._ddp_pending:
@@ -327,16 +331,18 @@ class CoSATrainer:
                     img_denorm, img_box, [cam_ps, cam_aux_ps], cls_label, [threhigh, auxthrehigh], [threlow, auxthrelow],
                     refine_model=self.refine_model, downscale=args.par_downscale, _fold_validation=True)
             else:
+                refine_mask_label_aux = None
                 refine_mask_label = seg_helper.cam2mask(img_denorm, img_box, cam_ps, cls_label, threhigh, threlow,
                                                         refine_model=self.refine_model, downscale=args.par_downscale,
                                                         _fold_validation=True)
             if self.label_stats_state is not None:
-                self.update_label_stats(refine_mask_label, refine_mask_label_aux if args.aux_cam2seg else None, seg_pred, cls_label, img_box,
+                self.update_label_stats(refine_mask_label, refine_mask_label_aux, seg_pred, cls_label, img_box,
                                         cam_ps, cam_aux_ps if args.aux_cam2seg else None)
         if fused:
             # one forward + one backward kernel instead of ~10 full-resolution passes (same maths, main.py:167-212)
             seg_loss, reg_loss = seg_helper.fused_seg_and_energy_loss(seg_pred, refine_mask_label, refine_mask_label_aux, simg,
-                                                                      img_box, self.reg_layer, prepared=self._lattice)
+                                                                      img_box, self.reg_layer, prepared=self._lattice,
+                                                                      fg_alpha=args.segfg_alpha, aux_alpha=args.aux_cam2seg_alpha)
         else:
             seg_pred = F.interpolate(seg_pred, size=refine_mask_label.shape[1:], mode='bilinear', align_corners=False)
             seg_loss = seg_helper.seg_loss(seg_pred, refine_mask_label, fg_alpha=args.segfg_alpha)
@@ -347,7 +353,8 @@ class CoSATrainer:
                                                   loss_layer=self.reg_layer)
         if self.fused_losses:
             with torch.no_grad():      # seg_ps is the list of per-scale low-res teacher segs here
-                tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:], args.seg_softmaxtemp)
+                tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:], args.seg_softmaxtemp,
+                                                  after_softmax=args.after_softmax)
             cam_loss = seg_helper.cam_loss_from_targets(cam_pred, tgt)
             if args.aux_seg2cam:
                 cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + \

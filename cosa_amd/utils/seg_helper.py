@@ -772,16 +772,46 @@ class DenseEnergyLoss(torch.nn.Module):
             self.sigma_rgb, self.sigma_xy, self.weight, self.scale_factor)
 
 
+def seg_blend_weights(fg_alpha=0.5, aux_alpha=0.5, has_aux=True):
+    """(wA_bg, wA_fg, wB_bg, wB_fg): the weights of the four class-balanced terms of main.py:200-203 x seg_helper.py:813,
+    (1-b) ((1-a) bgA + a fgA) + b ((1-a) bgB + a fgB) with a = fg_alpha (--segfg_alpha), b = aux_alpha (--aux_cam2seg_alpha); without an
+    auxiliary label map (--aux_cam2seg false) b = 0.  The reference asserts a in [0, 1] (seg_helper.py:803); b outside [0, 1] would make a
+    weight negative, which the kernels' fixed-point range argument does not cover: refused here, as the entry point would."""
+    a, b = float(fg_alpha), (float(aux_alpha) if has_aux else 0.0)
+    if not (0.0 <= a <= 1.0):
+        raise ValueError(f"fg_alpha {fg_alpha!r} should be in [0,1]")
+    if not (0.0 <= b <= 1.0):
+        raise ValueError(f"aux_alpha {aux_alpha!r} should be in [0,1]")
+    return ((1 - b) * (1 - a), (1 - b) * a, b * (1 - a), b * a)
+
+
+_DEFAULT_BLEND = (0.25, 0.25, 0.25, 0.25)
+_blend_vecs = {}
+
+
+def _blend_vec(weights, device):
+    """the four weights as a device vector, made once per (setting, device)"""
+    key = (weights, str(device))
+    v = _blend_vecs.get(key)
+    if v is None:
+        v = _blend_vecs[key] = torch.tensor(weights, device=device, dtype=torch.float32)
+    return v
+
+
 class FusedSegRegLoss(Function):
     """seg_loss(main) / seg_loss(aux) blend + dense-energy regulariser of the SAME low-res logits in two launches.
 
-    Equivalent to main.py:167-212 (F.interpolate -> seg_loss x2 -> get_energy_loss) with fg_alpha = 0.5 and
-    aux_cam2seg_alpha = 0.5 (the reference defaults), but nothing of size [b,K,S,S] is ever written: the kernels
-    re-derive the per-pixel softmax from an LDS tile of the low-res logits.  Returns (seg_loss, reg_loss)."""
+    Equivalent to main.py:167-212 (F.interpolate -> seg_loss x2 -> get_energy_loss), but nothing of size [b,K,S,S] is ever written: the
+    kernels re-derive the per-pixel softmax from an LDS tile of the low-res logits.  Returns (seg_loss, reg_loss).
+    `weights` = None: fg_alpha = 0.5 and aux_cam2seg_alpha = 0.5 (the reference defaults) through the entry points that have these built in
+    (maskB required).  `weights` = seg_blend_weights(...): the general entry points (cosa_seg_loss_*_w); maskB may then be None (no auxiliary
+    label map).  Both give the same bits for the defaults (tests/test_loss_flags_gpu.py)."""
 
     @staticmethod
-    def forward(ctx, seg_lr, maskA, maskB, simg, boxes, weight, sigma_rgb, sigma_xy, prepared=None):
+    def forward(ctx, seg_lr, maskA, maskB, simg, boxes, weight, sigma_rgb, sigma_xy, prepared=None, weights=None):
         _C.require_cuda(seg_lr, maskA, maskB, simg, boxes)
+        if maskB is None and (weights is None or weights[2] != 0 or weights[3] != 0):
+            raise ValueError("FusedSegRegLoss: no auxiliary label map needs weights with wB_bg = wB_fg = 0")
         seg_lr = seg_lr.contiguous().float()
         B, K, hs, ws = seg_lr.shape
         S = maskA.shape[-1]
@@ -793,11 +823,14 @@ class FusedSegRegLoss(Function):
         roi = torch.empty((B, Sq, Sq), device=dev)
         unl = torch.empty((B, Sq, Sq), device=dev, dtype=torch.uint8)
         L = _C.lib()
-        maskA, maskB, simg = maskA.contiguous().float(), maskB.contiguous().float(), simg.contiguous().float()
+        maskA, simg = maskA.contiguous().float(), simg.contiguous().float()
+        maskB = maskB.contiguous().float() if maskB is not None else None
         wsl = _C.workspace(L.cosa_seg_loss_workspace_bytes(B, K, hs, ws), dev, "seg_loss")
-        _C.check(L.cosa_seg_loss_forward(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(simg), _C.ptr(boxes), _C.ptr(sums),
-                                         _C.ptr(s_seg), _C.ptr(s_img), _C.ptr(roi), _C.ptr(unl), B, K, hs, ws, S, _C.ptr(wsl), wsl.numel(),
-                                         _C.stream_ptr()), "cosa_seg_loss_forward")
+        fwd, fwd_name = (L.cosa_seg_loss_forward, "cosa_seg_loss_forward") if weights is None else \
+            (L.cosa_seg_loss_forward_w, "cosa_seg_loss_forward_w")
+        _C.check(fwd(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(simg), _C.ptr(boxes), _C.ptr(sums),
+                     _C.ptr(s_seg), _C.ptr(s_img), _C.ptr(roi), _C.ptr(unl), B, K, hs, ws, S, _C.ptr(wsl), wsl.numel(),
+                     _C.stream_ptr()), fwd_name)
         AS = torch.empty_like(s_seg)
         energy = torch.empty(1, device=dev)
         if prepared is not None and prepared.matches(B, K, Sq, sigma_rgb, sigma_xy):
@@ -814,8 +847,12 @@ class FusedSegRegLoss(Function):
         # 0.5 * (0.5 bgA + 0.5 fgA) + 0.5 * (0.5 bgB + 0.5 fgB), each term sum / (count + 1e-6)  (seg_helper.py:800-813, main.py:200-203):
         # four vector ops instead of eighteen scalar ones
         pairs = sums.view(4, 2)
-        seg_l = (pairs[:, 0] / (pairs[:, 1] + 1e-6)).sum() * 0.25
+        if weights is None or tuple(weights) == _DEFAULT_BLEND:
+            seg_l = (pairs[:, 0] / (pairs[:, 1] + 1e-6)).sum() * 0.25
+        else:       # sum_i w_i sums_i / (cnt_i + 1e-6); a group without a pixel (and all of B without a second map) is 0 / 1e-6 = 0
+            seg_l = ((pairs[:, 0] / (pairs[:, 1] + 1e-6)) * _blend_vec(tuple(weights), dev)).sum()
         ctx.save_for_backward(seg_lr, maskA, maskB, sums, AS, roi)
+        ctx.weights = None if weights is None else tuple(float(w) for w in weights)
         ctx.weight = float(weight)
         ctx.S = S
         return seg_l, energy * float(weight)
@@ -828,10 +865,15 @@ class FusedSegRegLoss(Function):
         gs = g_seg.reshape(1).float().contiguous()
         gr = (g_reg.reshape(1).float() * ctx.weight).contiguous()
         wsl = _C.workspace(_C.lib().cosa_seg_loss_workspace_bytes(B, K, hs, ws), seg_lr.device, "seg_loss")
-        _C.check(_C.lib().cosa_seg_loss_backward(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(sums), _C.ptr(AS), _C.ptr(roi),
-                                                 _C.ptr(gs), _C.ptr(gr), _C.ptr(grad), B, K, hs, ws, ctx.S, _C.ptr(wsl), wsl.numel(),
-                                                 _C.stream_ptr()), "cosa_seg_loss_backward")
-        return grad, None, None, None, None, None, None, None, None
+        if ctx.weights is None:
+            _C.check(_C.lib().cosa_seg_loss_backward(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(sums), _C.ptr(AS), _C.ptr(roi),
+                                                     _C.ptr(gs), _C.ptr(gr), _C.ptr(grad), B, K, hs, ws, ctx.S, _C.ptr(wsl), wsl.numel(),
+                                                     _C.stream_ptr()), "cosa_seg_loss_backward")
+        else:
+            _C.check(_C.lib().cosa_seg_loss_backward_w(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(sums), _C.ptr(AS), _C.ptr(roi),
+                                                       _C.ptr(gs), _C.ptr(gr), _C.ptr(grad), *ctx.weights, B, K, hs, ws, ctx.S, _C.ptr(wsl),
+                                                       wsl.numel(), _C.stream_ptr()), "cosa_seg_loss_backward_w")
+        return grad, None, None, None, None, None, None, None, None, None
 
 
 class PreparedLattice:
@@ -876,14 +918,24 @@ class PreparedLattice:
         self.key = None                                  # one filter pass per prepared lattice in the training step
 
 
-def fused_seg_and_energy_loss(seg_pred_lr, mask_main, mask_aux, img, img_box, loss_layer, prepared=None):
-    """(seg_loss, reg_loss) of main.py:167-212 for the reference defaults (fg_alpha 0.5, aux blend 0.5, scale_factor 0.5).
-    `prepared`: a PreparedLattice started on this step's `img` (optional; otherwise the lattice is built here)."""
+def fused_seg_and_energy_loss(seg_pred_lr, mask_main, mask_aux, img, img_box, loss_layer, prepared=None, fg_alpha=0.5, aux_alpha=0.5,
+                              _builtin_defaults=False):
+    """(seg_loss, reg_loss) of main.py:167-212 for DenseEnergyLoss(scale_factor=0.5):
+    (1 - aux_alpha) seg_loss(main, fg_alpha) + aux_alpha seg_loss(aux, fg_alpha), or seg_loss(main, fg_alpha) alone with `mask_aux` = None
+    (--aux_cam2seg false), and the regulariser on the main labels.
+    `prepared`: a PreparedLattice started on this step's `img` (optional; otherwise the lattice is built here).
+    `_builtin_defaults`: the entry points with fg_alpha = aux_alpha = 0.5 built in instead of the weighted ones (same bits; kept for the
+    test of exactly that)."""
     if loss_layer.scale_factor != 0.5:
         raise NotImplementedError("fused losses are built for DenseEnergyLoss(scale_factor=0.5) (main.py:77)")
     boxes = _boxes_to_device(img_box, seg_pred_lr.device)
+    weights = seg_blend_weights(fg_alpha, aux_alpha, mask_aux is not None)
+    if _builtin_defaults:
+        if weights != _DEFAULT_BLEND:
+            raise ValueError("_builtin_defaults: the built-in entry points are fg_alpha = aux_alpha = 0.5 with an auxiliary label map")
+        weights = None
     return FusedSegRegLoss.apply(seg_pred_lr, mask_main, mask_aux, img, boxes, loss_layer.weight, loss_layer.sigma_rgb,
-                                 loss_layer.sigma_xy * loss_layer.scale_factor, prepared)
+                                 loss_layer.sigma_xy * loss_layer.scale_factor, prepared, weights)
 
 
 def _crop_mask_from_boxes(img_box, b, h, w, device):
@@ -954,8 +1006,8 @@ def seg_refine_by_label(seg, cls_label, softmaxtemp, after_softmax=False):
     return F.softmax(valid_seg / softmaxtemp, dim=1)
 
 
-def cam_loss_targets(seg_scales, cls_label, S, out_hw, softmaxtemp):
-    """seg_refine_by_label(sum_scales seg, T)[:, 1:] bilinearly resized to `out_hw` (main.py:227-228, seg_helper.py:553-568,
+def cam_loss_targets(seg_scales, cls_label, S, out_hw, softmaxtemp, after_softmax=False):
+    """seg_refine_by_label(sum_scales seg, T, after_softmax)[:, 1:] bilinearly resized to `out_hw` (main.py:227-228, seg_helper.py:553-568,
     595-597), computed from the per-scale low-res teacher segs without building the [b,K,S,S] tensor."""
     b2, K = seg_scales[0].shape[:2]
     B = b2 // 2
@@ -966,8 +1018,8 @@ def cam_loss_targets(seg_scales, cls_label, S, out_hw, softmaxtemp):
     hs = _C.int_array([t.shape[2] for t in seg_scales])
     ws = _C.int_array([t.shape[3] for t in seg_scales])
     lab = cls_label.contiguous().float()
-    _C.check(_C.lib().cosa_cam_loss_targets(ptrs, hs, ws, n, _C.ptr(lab), _C.ptr(out), B, K, int(S), oh, ow, float(softmaxtemp),
-                                            _C.stream_ptr()), "cosa_cam_loss_targets")
+    _C.check(_C.lib().cosa_cam_loss_targets_m(ptrs, hs, ws, n, _C.ptr(lab), _C.ptr(out), B, K, int(S), oh, ow, float(softmaxtemp),
+                                              int(bool(after_softmax)), _C.stream_ptr()), "cosa_cam_loss_targets_m")
     return out
 
 

@@ -457,6 +457,22 @@ int cosa_seg_loss_forward(const float *seg_lr, const float *maskA, const float *
 int cosa_seg_loss_backward(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
                            const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
                            int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream);
+/* The same two for every setting of --segfg_alpha a, --aux_cam2seg_alpha b, --aux_cam2seg (main.py:200-203, seg_helper.py:813):
+ *   loss = wA_bg bgA + wA_fg fgA + wB_bg bgB + wB_fg fgB, each term sum / (count + 1e-6), with
+ *   wA_bg = (1-b)(1-a), wA_fg = (1-b) a, wB_bg = b (1-a), wB_fg = b a;  --aux_cam2seg false: b = 0 and maskB = NULL.
+ *   maskB == NULL: nothing of a second label map is read, sums[4..7] come back 0 and the B terms add nothing to the gradient.
+ *   The forward emits the sums (the weights enter on the host: sum_i w_i sums_i / (cnt_i + 1e-6)); the backward takes the weights.  Each
+ *   weight must lie in [0, 1] (non-finite ones are refused too): COSA_EINVAL, nothing is launched.  The entry points above are these with
+ *   both maps and 0.25 x 4 -- same kernels, same bits.  Fixed-point range of the gradient cells: every value is carried while
+ *   g_seg (wA_bg + wA_fg + wB_bg + wB_fg) < 16, i.e. g_seg < 16 for the table above; beyond it the result may be NaN (sticky flag), never a
+ *   wrapped sum. */
+int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
+                            const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                            int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream);
+int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
+                             const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
+                             float wA_bg, float wA_fg, float wB_bg, float wB_fg,
+                             int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream);
 
 /* F.multilabel_soft_margin_loss (main.py:127-128 on the classification logits; seg_helper.py:593-602 on relu(cam) against the resized teacher
  * probabilities) and its gradient in one pass: loss[0] = mean_r mean_c -(y log s(v) + (1-y) log s(-v)), v = relu ? max(x,0) : x;
@@ -469,6 +485,10 @@ int cosa_msm_loss(const float *x, const float *y, float *grad, float *loss, void
  *   out [B, K-1, oh, ow]                                                                                                      */
 int cosa_cam_loss_targets(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
                           float *out, int B, int K, int S, int oh, int ow, float temperature, void *stream);
+/* ... with the reference's other branch (seg_helper.py:558-561, --after_softmax true) selectable: after_softmax = 1 takes the softmax of
+ * sum_scales / T over all K channels and sets the channels of absent classes to zero afterwards; 0 is the call above, bit for bit.      */
+int cosa_cam_loss_targets_m(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
+                            float *out, int B, int K, int S, int oh, int ow, float temperature, int after_softmax, void *stream);
 /* utils/seg_helper.py:210-230 (get_energy_loss: F.softmax over the classes of the full-resolution logits) + :199-203 (DenseEnergyLoss.forward:
  * bilinear resize of the probabilities by 0.5 = the mean of each 2x2 quad) in one pass, and the backward of the pair:
  *   logit [B,K,H,W] (H, W even)   out / grad_out [B,K,H/2,W/2]   grad_logit [B,K,H,W]                                                     */
