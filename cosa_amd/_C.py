@@ -100,6 +100,9 @@ _SIGS = {
                                    c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "cosa_label_stats_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
     "cosa_label_stats": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cosa_teacher_check_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
+    "cosa_teacher_check_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cosa_teacher_check": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cosa_tensor_stats_layout": (c_size_t, [ctypes.POINTER(c_size_t)]),
     "cosa_tensor_stats_workspace_bytes": (c_size_t, [c_int]),
     "cosa_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
@@ -245,11 +248,31 @@ def require_cuda(*tensors):
 
 
 _ws_cache = {}
+_ws_scope = ""
+
+
+class workspace_scope:
+    """`with workspace_scope("name"):` -- workspace() calls inside take slots of their own ("name/<tag>").  For a second network that runs
+    between the steps of a trainer whose captured graph holds the addresses of the default slots (the --teacher_check pass): a larger request
+    of its own can then never replace, and so free, a buffer that graph replays into.  Outside a scope the keys are what they always were."""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __enter__(self):
+        global _ws_scope
+        self.prev, _ws_scope = _ws_scope, self.name + "/"
+        return self
+
+    def __exit__(self, *exc):
+        global _ws_scope
+        _ws_scope = self.prev
+        return False
 
 
 def workspace(nbytes, device, tag="default"):
     """Grow-only per-(device,tag) byte workspace (never freed inside the step: graph-safe)."""
-    key = (str(device), tag)
+    key = (str(device), _ws_scope + tag)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)

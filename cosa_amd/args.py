@@ -69,6 +69,12 @@ EXTRA = [
     # gradient accumulation; 1: nothing changes
     ("accum_steps", int, 1),                 # micro-batches of --batch_size per optimizer step: their mean gradient is applied once, so the
                                              # effective batch is batch_size x accum_steps x world; all *_iters flags stay in optimizer steps
+    # the teacher-precision monitor; 0: nothing changes
+    ("teacher_check_iters", int, 0),         # every N-th optimizer step runs the teacher's pass a second time on --teacher_check_mode operands and
+                                             # scores the two passes against each other on the device (literal 1e-3 bar, label agreement, mask
+                                             # mIoU); logged and written to <output_dir>/teacher_check.jsonl every log_iters; training is untouched
+    ("teacher_check_mode", str, "auto"),     # any --teacher_precision value; auto: bf16x3 against an fp16x3 teacher (the same kernels with fp32's
+                                             # exponent range: an fp16 overflow shows), fp16x3 against every other teacher mode
 ]
 
 

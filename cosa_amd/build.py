@@ -42,6 +42,7 @@ SOURCES = {
     # the lattice file once more with a 2-D lattice: the position-only Gaussian kernel of the dense-CRF post-processing
     "permuto_kernels.hip@d2": EXACT + ["-DCOSA_PD=2"],
     "optim_kernels.hip": ["-ffp-contract=off"],
+    "teacher_check_kernels.hip": EXACT,
 }
 
 

@@ -71,6 +71,8 @@ def check_supported(args):
     get_backbone(args.backbone)                                   # NotImplementedError listing the built encoders
     if getattr(args, "accum_steps", 1) < 1:
         raise ValueError(f"--accum_steps {args.accum_steps}: a positive number of micro-batches per optimizer step")
+    if getattr(args, "teacher_check_iters", 0) < 0:
+        raise ValueError(f"--teacher_check_iters {args.teacher_check_iters}: 0 (off) or a positive number of optimizer steps")
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
@@ -111,14 +113,33 @@ def append_tensor_stats(output_dir, summary, n_iter):
         f.write(tensor_stats_record(summary, n_iter) + "\n")
 
 
-def read_interval(acc, log_iters, guard, stats, tensor_stats=None):
+def teacher_check_line(summary, check_mode):
+    """what --teacher_check_iters adds to the log line of an interval that held a check: the worst figure over the map sets, the planes
+    over the literal bar, the lowest agreement and mIoU over the label pairs"""
+    w = seg_helper.teacher_check_worst(summary)
+    return " tcheck[%s]: worst %.1e, over %d/%d, agree %.5f, miou %.5f" % (check_mode, w["worst"], w["over"], w["planes"], w["agree"], w["miou"])
+
+
+def teacher_check_record(summary, n_iter, mode, check_mode):
+    """one line of <output_dir>/teacher_check.jsonl: the full summary of an interval's checks and the two operand modes compared"""
+    return json.dumps(dict(summary, iters=int(n_iter), mode=mode, check_mode=check_mode))
+
+
+def append_teacher_check(output_dir, summary, n_iter, mode, check_mode):
+    with (Path(output_dir) / "teacher_check.jsonl").open("a") as f:
+        f.write(teacher_check_record(summary, n_iter, mode, check_mode) + "\n")
+
+
+def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check=None):
     """The log interval's ONE host sync: -> (means of the running sums `acc`, [grad_norm, skipped, clipped] of the guard record or None,
     the label counters as ints or None).  The guard's own tensor and the label counters ride along in the same transfer (`acc` keeps
     its length; counts are exact in a double: an interval's stay far below 2^53).  `acc` and the label counters are an interval's:
     both are zeroed on the device afterwards; the guard's counters are the run's and stay.
     tensor_stats: (--tensor_stats' table, its blame counters or None); they ride along too and a fourth value is returned, (the table's
     values as [T][6] floats, the blame counters as ints or None).  The table is the sample of the interval's last step and is not
-    accumulated; the blame counters are the run's: neither is zeroed."""
+    accumulated; the blame counters are the run's: neither is zeroed.
+    teacher_check: --teacher_check_iters' counters; they ride along too, are an interval's (zeroed afterwards), and FIVE values are
+    returned: the three, the tensor_stats pair or None, and the counters as ints."""
     parts = [acc / log_iters]
     if guard is not None:
         parts += [torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]
@@ -129,6 +150,8 @@ def read_interval(acc, log_iters, guard, stats, tensor_stats=None):
         parts.append(torch_helper.tensor_stats_values(table).reshape(-1))
         if blame is not None:
             parts.append(blame.double())
+    if teacher_check is not None:
+        parts.append(teacher_check.double())               # (the largest value, a bit pattern below 2^32, is exact in a double too)
     vals = (torch.cat(parts) if len(parts) > 1 else parts[0]).tolist()
     n = acc.numel()
     vals, rest = vals[:n], vals[n:]
@@ -139,12 +162,16 @@ def read_interval(acc, log_iters, guard, stats, tensor_stats=None):
     acc.zero_()
     if stats is not None:
         stats.zero_()
+    cvals = None
+    if teacher_check is not None:
+        rest, cvals = rest[:len(rest) - teacher_check.numel()], [int(v) for v in rest[len(rest) - teacher_check.numel():]]
+        teacher_check.zero_()
     if tensor_stats is None:
-        return vals, gvals, svals
+        return (vals, gvals, svals) if teacher_check is None else (vals, gvals, svals, None, cvals)
     T, W = table.shape
     tvals = [rest[i * W:(i + 1) * W] for i in range(T)]
     bvals = [int(v) for v in rest[T * W:]] if blame is not None else None
-    return vals, gvals, svals, (tvals, bvals)
+    return (vals, gvals, svals, (tvals, bvals)) if teacher_check is None else (vals, gvals, svals, (tvals, bvals), cvals)
 
 
 def next_batch(it, new_iter, pos):
@@ -238,8 +265,12 @@ def main(args):
                     (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
             guard, stats = trainer.guard_state, trainer.label_stats_state         # None: no gradient guard / no --label_stats, the line as ever
-            tvals = None
-            if tstats_on:
+            tvals = cvals = None
+            if trainer.teacher_check_state is not None:                           # (--teacher_check_iters: its counters in the same transfer)
+                vals, gvals, svals, tvals, cvals = read_interval(
+                    acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state) if tstats_on else None,
+                    teacher_check=trainer.teacher_check_state)
+            elif tstats_on:
                 vals, gvals, svals, tvals = read_interval(acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state))
             else:
                 vals, gvals, svals = read_interval(acc, args.log_iters * n_micro, guard, stats)   # the one host sync of the interval
@@ -264,6 +295,11 @@ def main(args):
                     tsummary = trainer.tensor_stats(tvals)
                     line += tensor_stats_line(tsummary)
                     append_tensor_stats(output_dir, tsummary, n_iter + 1)
+                if cvals is not None:
+                    csummary = seg_helper.teacher_check_summary(cvals, args.num_classes)
+                    if csummary["checks"] > 0:                                    # (an interval without a check step: the line as ever)
+                        line += teacher_check_line(csummary, targs.teacher_check_mode)
+                        append_teacher_check(output_dir, csummary, n_iter + 1, targs.teacher_precision, targs.teacher_check_mode)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,

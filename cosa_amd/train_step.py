@@ -38,7 +38,8 @@ def default_args(dataset="VOC12", **over):
              aux_cam2seg=True, aux_cam2seg_alpha=0.5, aux_seg2cam=False, aux_seg2cam_alpha=0.5, after_softmax=False,
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
-             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1)
+             clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
+             teacher_check_iters=0, teacher_check_mode="auto")
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -74,6 +75,39 @@ def resolve_teacher_precision(mode, crop_size, usepar=False):
     if mode != "auto":
         return mode
     return "fp16x3"
+
+
+def resolve_teacher_check_mode(mode, teacher_precision):
+    """--teacher_check_mode: "auto" -> "bf16x3" against an "fp16x3" teacher -- the same three-term kernels on halves
+    with fp32's exponent range, so an fp16 split that overflows (|t| > 65504: hi = inf) shows as a difference --, "fp16x3", the conforming
+    default, against every other teacher mode.  Any other value is taken as it is (VITNetwork.set_nograd_precision's names)."""
+    if mode != "auto":
+        return mode
+    return "bf16x3" if teacher_precision == "fp16x3" else "fp16x3"
+
+
+@torch.no_grad()
+def teacher_products(model, args, wimg, img_denorm, img_box, cls_label, thresholds, seg_scales, tgt_hw, buffers, refine_model=None):
+    """What a training step derives from ONE teacher pass of `model` over `wimg`, by the step's own calls: -> ((cam, cam_aux) as cam2mask
+    reads them, (main label map, auxiliary label map | None), cam-loss targets | None).  thresholds = ((high, low), (aux high, aux low)),
+    floats or device scalars; tgt_hw: the targets' size, None for none (they need seg_scales); buffers: the caller's CAM-buffer dict for
+    this model.  The --teacher_check pass (CoSATrainer._teacher_check) and tools/teacher_check.py; no host sync, no RNG."""
+    cam, aux, seg = seg_helper.multi_scale_camseg(model, wimg, args.pseudo_scales, _active_labels=None if args.use_cammix else cls_label,
+                                                  _seg_scales=seg_scales, _buffers=buffers)
+    if args.use_cammix:
+        cam = (cam + aux) / 2
+    (hi, lo), (hi_aux, lo_aux) = thresholds
+    if args.aux_cam2seg:
+        mask, mask_aux = seg_helper.cam2mask_multi(img_denorm, img_box, [cam, aux], cls_label, [hi, hi_aux], [lo, lo_aux],
+                                                   refine_model=refine_model, downscale=args.par_downscale, _fold_validation=True)
+    else:
+        mask_aux = None
+        mask = seg_helper.cam2mask(img_denorm, img_box, cam, cls_label, hi, lo, refine_model=refine_model, downscale=args.par_downscale,
+                                   _fold_validation=True)
+    tgt = None
+    if tgt_hw is not None:
+        tgt = seg_helper.cam_loss_targets(seg, cls_label, wimg.shape[-1], tuple(tgt_hw), args.seg_softmaxtemp, after_softmax=args.after_softmax)
+    return (cam, aux), (mask, mask_aux), tgt
 
 
 class CoSATrainer:
@@ -199,6 +233,25 @@ class CoSATrainer:
             self.label_stats_state = seg_helper.new_label_stats(args.num_classes, device)
             self._step_scale = torch.ones(1, device=device, dtype=torch.float32)
             self.extra_state = {"label_stats.counters": self.label_stats_state}
+        # the teacher-precision monitor: off (None) unless --teacher_check_iters N > 0.  Every N-th optimizer step runs
+        # the teacher's pass once more on `model_CK`, a third network on --teacher_check_mode operands that takes the teacher's weights at
+        # that moment, and scores the two passes against each other.  The counters are state of the run (`teacher_check.counters` of
+        # extra_state); model_CK is not: every check overwrites it
+        self.teacher_check_state = self.model_CK = None
+        self._check_iters = int(getattr(args, "teacher_check_iters", 0) or 0)
+        if self._check_iters < 0:
+            raise ValueError(f"teacher_check_iters {self._check_iters!r}: 0 (off) or a positive number of optimizer steps")
+        if self._check_iters > 0:
+            cm = resolve_teacher_check_mode(getattr(args, "teacher_check_mode", "auto"), tp)
+            args.teacher_check_mode = cm
+            self.model_AN.check_nograd_precision(cm)      # (on the host too: a mode the encoder is not built for fails here, not in a step)
+            if device.type == "cuda" and not on:
+                raise NotImplementedError("teacher_check_iters: the check compares 16-bit operand modes of the teacher's no-grad passes; "
+                                          "this trainer's compute dtype has none")
+            self.teacher_check_state = seg_helper.new_teacher_check(args.num_classes, device)
+            self.extra_state = dict(getattr(self, "extra_state", {}), **{"teacher_check.counters": self.teacher_check_state})
+            if on:
+                self._build_check_model(cm)
         if on:
             self._teacher_shadows.optimizer_owned = self._student_shadows.optimizer_owned = self._fused_step is not None
             # bf16 W^T copies of the student's block projections (the input-gradient GEMMs run the forward kernel on them)
@@ -280,6 +333,62 @@ class CoSATrainer:
             st.begin_eager()
         return self._s_out
 
+    def _build_check_model(self, mode):
+        """model_CK: a network of its own (parameters, 16-bit shadows, operand and CAM buffers: nn_ops._owner_of is keyed by parameter), built
+        without drawing from any RNG the run reads: the network is initialised on the host and the host generators' states are put back.
+        Its initial weights never matter -- every check begins by copying the teacher's"""
+        import random
+        states = torch.get_rng_state(), np.random.get_state(), random.getstate()
+        try:
+            ck = build_model(SimpleNamespace(**dict(vars(self.args), pretrained=False)))
+        finally:
+            torch.set_rng_state(states[0])
+            np.random.set_state(states[1])
+            random.setstate(states[2])
+        ck = ck.to(self.device)
+        for p in ck.parameters():
+            p.requires_grad = False
+        ck.set_nograd_precision(mode)
+        self.model_CK = ck
+        self._ck_params = list(ck.parameters())
+        assert len(self._ck_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ck_params, self._ema_pairs[0]))
+        self._ck_shadows = nn_ops.ensure_shadows(ck, ck.compute_dtype)        # not optimizer-owned: refreshed at the entry of every pass
+        self._ck_buffers = {}                                                 # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
+
+    def _is_check_step(self, n_iter):
+        """the step that closes every N-th optimizer iteration; with --accum_steps its last micro-batch"""
+        return self.teacher_check_state is not None and (n_iter + 1) % self._check_iters == 0 and self._micro_k == self._accum_steps - 1
+
+    @torch.no_grad()
+    def _teacher_check(self, wimg, img_denorm, img_box, cls_label, cams, masks, thresholds, tgt):
+        """One check, eagerly on the current stream after the teacher's pass has been joined: the teacher's weights of
+        THIS step (the EMA update comes later) into model_CK, its pass over the same images, the same cam2mask call on the threshold
+        VALUES this step used (the queues and trackers of --usegmm are the run's: not touched), the cam-loss targets, and the reduction.
+        cams = (cam, cam_aux) as cam2mask read them, masks = (main, aux | None), thresholds = ((high, low), (aux high, aux low)).
+        No host sync, no RNG, and nothing the training path reads is written: model_CK's weights, shadows, operand and CAM buffers are
+        its own, the library workspaces it needs are slots of their own (_C.workspace_scope)."""
+        args = self.args
+        torch._foreach_copy_(self._ck_params, self._ema_pairs[0])
+        held = nn_ops.stamps, nn_ops.gemm_stamps           # (a benchmark's kernel-span slots are the training kernels')
+        nn_ops.stamps = nn_ops.gemm_stamps = None
+        try:
+            with _C.workspace_scope("teacher_check"):
+                (cam_b, aux_b), (mask_b, mask_aux_b), tgt_b = teacher_products(
+                    self.model_CK, args, wimg, img_denorm, img_box, cls_label, thresholds, self.fused_losses,
+                    tgt.shape[-2:] if tgt is not None else None, self._ck_buffers, self.refine_model)
+        finally:
+            nn_ops.stamps, nn_ops.gemm_stamps = held
+        seg_helper.teacher_check((cams[0], cam_b), (cams[1], aux_b), (tgt, tgt_b) if tgt is not None else None, (masks[0], mask_b),
+                                 (masks[1], mask_aux_b) if masks[1] is not None else None, None if args.use_cammix else cls_label, img_box,
+                                 self.teacher_check_state, ignore_index=args.ignore_index, bar=seg_helper.TEACHER_CHECK_BAR)
+
+    def teacher_check(self):
+        """the summary (seg_helper.teacher_check_summary) of the checks accumulated since the counters were last zeroed (synchronises: for
+        tests and the log interval); None when --teacher_check_iters is 0"""
+        if self.teacher_check_state is None:
+            return None
+        return seg_helper.teacher_check_summary(self.teacher_check_state, self.args.num_classes)
+
     def _join_teacher(self):
         if self._teacher_pending:
             torch.cuda.current_stream().wait_stream(self._side)
@@ -351,11 +460,13 @@ class CoSATrainer:
                 seg_loss = (1 - args.aux_cam2seg_alpha) * seg_loss + args.aux_cam2seg_alpha * seg_loss_aux
             reg_loss = seg_helper.get_energy_loss(img=simg, logit=seg_pred, label=refine_mask_label, img_box=img_box,
                                                   loss_layer=self.reg_layer)
+        check_tgt = None
         if self.fused_losses:
             with torch.no_grad():      # seg_ps is the list of per-scale low-res teacher segs here
                 tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:], args.seg_softmaxtemp,
                                                   after_softmax=args.after_softmax)
             cam_loss = seg_helper.cam_loss_from_targets(cam_pred, tgt)
+            check_tgt = tgt
             if args.aux_seg2cam:
                 cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + \
                     args.aux_seg2cam_alpha * seg_helper.cam_loss_from_targets(cam_aux_pred, tgt)
@@ -367,6 +478,9 @@ class CoSATrainer:
             if args.aux_seg2cam:
                 cam_aux_loss = seg_helper.cam_loss(cam_aux_pred, valid_seg_ps)
                 cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + args.aux_seg2cam_alpha * cam_aux_loss
+        if self.model_CK is not None and self._is_check_step(n_iter):
+            self._teacher_check(wimg, img_denorm, img_box, cls_label, (cam_ps, cam_aux_ps), (refine_mask_label, refine_mask_label_aux),
+                                ((threhigh, threlow), (auxthrehigh, auxthrelow)), check_tgt)
         # main.py:230-236: the weighted sum of the five losses (warm-up: classification losses only) as one dot product
         wkey = n_iter <= args.warmup_iters
         wvec = self._loss_weights.get(wkey)

@@ -4,6 +4,7 @@ Same names, arguments and error behaviour as the reference (utils/seg_helper.py)
 cites the lines it replaces.  All tensors live on the GPU; nothing here falls back to the CPU.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -358,6 +359,190 @@ def label_stats_summary(counters, K):
     out["teacher_nonfinite"] = c[off["bad_cam"]] + c[off["bad_cam_aux"]]
     out["teacher_nonfinite_main"], out["teacher_nonfinite_aux"] = c[off["bad_cam"]], c[off["bad_cam_aux"]]
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# the --teacher_check monitor: two teacher passes on two operand modes, scored against each other
+# --------------------------------------------------------------------------------------------
+TEACHER_CHECK_SETS = ("cam", "aux", "tgt")                       # map sets, then label pairs: cosa_teacher_check_layout's order
+TEACHER_CHECK_PAIRS = ("main", "aux_label")
+_TC_SET_FIELDS = ("planes", "over", "worst", "hist", "nonfinite_a", "nonfinite_b")
+_TC_PAIR_FIELDS = ("pix", "agree", "ign_a", "ign_b", "cnt_a", "cnt_b", "inter")
+TEACHER_CHECK_SLOTS = ("checks",) + tuple(f"{s}.{f}" for s in TEACHER_CHECK_SETS for f in _TC_SET_FIELDS) + \
+    tuple(f"{p}.{f}" for p in TEACHER_CHECK_PAIRS for f in _TC_PAIR_FIELDS)
+TEACHER_CHECK_EDGES = (1e-6, 1e-5, 1e-4, 3e-4, 1e-3, 3e-3, 1e-2, float("inf"))      # upper edges of hist (as fp32), a plane in the first bin with fig <= edge
+TEACHER_CHECK_BAR = 1e-3                                          # the literal bar of tests/test_precision_gpu.py: normalised-CAM |delta| per plane
+TEACHER_CHECK_AGREE, TEACHER_CHECK_MIOU = 0.999, 0.999            # ... its label agreement and mask mIoU
+TEACHER_CHECK_MAX_K = 256
+
+
+def teacher_check_layout(K):
+    """cosa_teacher_check_layout: ({slot name: offset in elements}, number of elements) of the counter vector for K = num_classes
+    (background included).  Slot names are "checks", "<set>.<field>" for the map sets cam / aux / tgt and "<pair>.<field>" for the label
+    pairs main / aux_label.  Needs no device."""
+    off = (ctypes.c_size_t * len(TEACHER_CHECK_SLOTS))()
+    n = _C.lib().cosa_teacher_check_layout(int(K), off)
+    if n == 0:
+        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
+    return {name: int(off[i]) for i, name in enumerate(TEACHER_CHECK_SLOTS)}, int(n)
+
+
+def new_teacher_check(K, device):
+    """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay far below 2^63)"""
+    return torch.zeros(teacher_check_layout(K)[1], dtype=torch.int64, device=device)
+
+
+def _teacher_check_shapes(cams, auxs, tgts, labels, aux_labels, cls_label, counters):
+    B, C, S = cams[0].shape[0], cams[0].shape[1], cams[0].shape[-1]
+    h = w = 0
+    ok = all(t.shape == (B, C, S, S) for t in tuple(cams) + tuple(auxs)) and all(t.shape == (B, S, S) for t in labels)
+    if tgts is not None:
+        h, w = (int(v) for v in tgts[0].shape[-2:])
+        ok = ok and all(t.shape == (B, C, h, w) for t in tgts)
+    if aux_labels is not None:
+        ok = ok and all(t.shape == (B, S, S) for t in aux_labels)
+    if cls_label is not None:
+        ok = ok and cls_label.shape == (B, C)
+    if not ok:
+        raise ValueError("teacher_check: CAM pairs must be [B,C,S,S], the target pair [B,C,h,w], label maps [B,S,S] and cls_label [B,C]")
+    K = C + 1
+    if K > TEACHER_CHECK_MAX_K or h > S or w > S:
+        raise ValueError(f"teacher_check: outside the envelope (C {C} <= {TEACHER_CHECK_MAX_K - 1}, h {h} and w {w} <= S {S})")
+    if counters.dtype != torch.int64 or counters.shape != (48 + 6 * K,) or not counters.is_contiguous():
+        raise ValueError(f"teacher_check: counters must be a contiguous int64 vector of {48 + 6 * K} elements (new_teacher_check)")
+    return B, C, K, S, h, w
+
+
+def teacher_check(cams, auxs, tgts, labels, aux_labels, cls_label, img_box, counters, ignore_index=255, bar=TEACHER_CHECK_BAR):
+    """One reduction (cosa_teacher_check) that scores two teacher passes A and B against each other, accumulated into `counters` on the
+    device.  cams / auxs: (A, B) pairs of min-max normalised CAMs [B,C,S,S]; tgts: the (A, B) cam-loss targets [B,C,h,w] or None; labels:
+    the (A, B) main label maps [B,S,S]; aux_labels: the auxiliary pair or None; cls_label [B,C], or None: every plane is active.  Per
+    map set the active planes' figure max |a - b| against `bar`, its histogram and worst value, the non-finite elements; per label pair
+    agreement and per-class counts / intersections inside the boxes.  Every counter is an integer.  No host sync."""
+    f = lambda t: t.detach().contiguous().float() if t is not None else None
+    pair = lambda p: tuple(f(t) for t in p) if p is not None else None
+    cams, auxs, tgts, labels, aux_labels, cls_label = pair(cams), pair(auxs), pair(tgts), pair(labels), pair(aux_labels), f(cls_label)
+    _C.require_cuda(*cams, *auxs, *(tgts or ()), *labels, *(aux_labels or ()), cls_label, counters)
+    B, C, K, S, h, w = _teacher_check_shapes(cams, auxs, tgts, labels, aux_labels, cls_label, counters)
+    dev = cams[0].device
+    boxes = _boxes_to_device(img_box, dev)
+    if boxes.shape != (B, 4):
+        raise ValueError("teacher_check: img_box must be [B,4]")
+    L = _C.lib()
+    ws = _C.workspace(L.cosa_teacher_check_workspace_bytes(B, C), dev, "teacher_check")
+    none = (None, None)
+    _C.check(L.cosa_teacher_check(*[_C.ptr(t) for t in cams + auxs + (tgts or none) + labels + (aux_labels or none)], _C.ptr(cls_label),
+                                  _C.ptr(boxes), B, C, K, S, h, w, int(ignore_index), float(bar), _C.ptr(counters), _C.ptr(ws), ws.numel(),
+                                  _C.stream_ptr()), "cosa_teacher_check")
+    return counters
+
+
+@torch.no_grad()
+def teacher_check_torch(cams, auxs, tgts, labels, aux_labels, cls_label, img_box, counters, ignore_index=255, bar=TEACHER_CHECK_BAR):
+    """teacher_check in plain torch, for host trainers and as the kernel's partner in the tests (the role label_stats_torch plays): the
+    same counters in the same layout"""
+    f = lambda t: t.detach().float() if t is not None else None
+    pair = lambda p: tuple(f(t) for t in p) if p is not None else None
+    cams, auxs, tgts, labels, aux_labels, cls_label = pair(cams), pair(auxs), pair(tgts), pair(labels), pair(aux_labels), f(cls_label)
+    B, C, K, S, h, w = _teacher_check_shapes(cams, auxs, tgts, labels, aux_labels, cls_label, counters)
+    if 0 <= int(ignore_index) < K or not float(bar) >= 0:
+        raise ValueError("teacher_check: ignore_index must be no class and the bar a non-negative number")
+    dev = cams[0].device
+    off, _ = teacher_check_layout(K)
+    add = torch.zeros_like(counters)
+    add[off["checks"]] = 1
+    active = (cls_label != 0) if cls_label is not None else torch.ones((B, C), dtype=torch.bool, device=dev)
+    edges = torch.tensor(TEACHER_CHECK_EDGES, dtype=torch.float32, device=dev)
+    bar32 = torch.tensor(float(bar), dtype=torch.float32, device=dev)
+    worst = {}
+    for name, ab in zip(TEACHER_CHECK_SETS, (cams, auxs, tgts)):
+        if ab is None:
+            continue
+        a, b = ab
+        bad_a, bad_b = ~torch.isfinite(a), ~torch.isfinite(b)
+        d = torch.where(bad_a | bad_b, torch.full_like(a, float("inf")), (a - b).abs())          # (finite a - b: finite or inf, never NaN)
+        fig = d.flatten(2).amax(dim=2)[active]                                                   # the active planes' figures, fp32
+        add[off[name + ".planes"]] = fig.numel()
+        add[off[name + ".over"]] = (fig > bar32).sum()
+        add[off[name + ".hist"]:off[name + ".hist"] + len(TEACHER_CHECK_EDGES)] = \
+            torch.bincount(torch.bucketize(fig, edges), minlength=len(TEACHER_CHECK_EDGES))        # first bin with fig <= edge
+        add[off[name + ".nonfinite_a"]] = (bad_a & active[:, :, None, None]).sum()
+        add[off[name + ".nonfinite_b"]] = (bad_b & active[:, :, None, None]).sum()
+        worst[name] = fig.contiguous().view(torch.int32).max().long() if fig.numel() else torch.zeros((), dtype=torch.int64, device=dev)
+    box = torch.as_tensor(img_box).to(device=dev, dtype=torch.int64)
+    ar = torch.arange(S, device=dev)
+    inside = ((ar[None, :, None] >= box[:, 0, None, None]) & (ar[None, :, None] < box[:, 1, None, None]) &
+              (ar[None, None, :] >= box[:, 2, None, None]) & (ar[None, None, :] < box[:, 3, None, None]))
+    for name, ab in zip(TEACHER_CHECK_PAIRS, (labels, aux_labels)):
+        if ab is None:
+            continue
+        a, b = ab
+        is_cls = lambda m: inside & (m >= 0) & (m < K) & (m == m.floor())                         # a value that is no label is counted nowhere
+        add[off[name + ".pix"]] = inside.sum()
+        add[off[name + ".agree"]] = (inside & (a == b)).sum()
+        add[off[name + ".ign_a"]] = (inside & (a == ignore_index)).sum()
+        add[off[name + ".ign_b"]] = (inside & (b == ignore_index)).sum()
+        add[off[name + ".cnt_a"]:off[name + ".cnt_a"] + K] = torch.bincount(a[is_cls(a)].long(), minlength=K)
+        add[off[name + ".cnt_b"]:off[name + ".cnt_b"] + K] = torch.bincount(b[is_cls(b)].long(), minlength=K)
+        add[off[name + ".inter"]:off[name + ".inter"] + K] = torch.bincount(a[is_cls(a) & (a == b)].long(), minlength=K)
+    counters += add
+    for name, v in worst.items():                  # a maximum, not a sum: fp32 bit patterns of non-negative values order as integers
+        o = off[name + ".worst"]
+        counters[o] = torch.maximum(counters[o], v)
+    return counters
+
+
+def teacher_check_summary(counters, K):
+    """The counter vector (tensor, array or list; a device tensor synchronises) as figures: per map set `worst` (a float), `over`,
+    `planes`, `hist`, `nonfinite_a` / `nonfinite_b`; per label pair `agree` = agree / pix and `miou`, the mean of inter / (cnt_a + cnt_b -
+    inter) over the classes with a non-zero union (`iou` the per-class list, None for an empty union); `checks`; and `conforms`: every over
+    == 0, every agree >= 0.999 and every miou >= 0.999 over the sets and pairs that were counted -- the LITERAL leg of the criterion of
+    tests/test_precision_gpu.py.  Its float64-bounded exemption for planes of conditioning > 50 is not evaluated (`exemption_evaluated`
+    is False, `criterion` says so): a plane that the full criterion would exempt counts as over here.  `conforms_without_tgt` is the same
+    verdict without the `tgt` set: the record's criterion speaks of the normalised CAMs and the masks only, and the cam-loss targets, a
+    softmax at temperature --seg_softmaxtemp, magnify a logit difference up to 0.25 / T-fold where two classes tie.  Zero
+    pixels or zero checks give agree = miou = 1.0 for an absent pair and both verdicts None when nothing was checked."""
+    import struct
+    c = [int(v) for v in (counters.tolist() if hasattr(counters, "tolist") else counters)]
+    off, n = teacher_check_layout(K)
+    if len(c) != n:
+        raise ValueError(f"teacher_check_summary: {len(c)} counters, K = {K} has {n}")
+    nb = len(TEACHER_CHECK_EDGES)
+    out = {"checks": c[off["checks"]], "bar": TEACHER_CHECK_BAR, "hist_edges": [float(np.float32(e)) for e in TEACHER_CHECK_EDGES[:-1]] + ["inf"],
+           "criterion": "literal bar only: max |a - b| per active plane <= bar, label agreement >= 0.999, mask mIoU >= 0.999; the "
+                        "float64-bounded exemption for planes of conditioning > 50 is NOT evaluated",
+           "exemption_evaluated": False}
+    ok = ok_cams = True
+    for s in TEACHER_CHECK_SETS:
+        bits = c[off[s + ".worst"]]
+        worst = struct.unpack("<f", struct.pack("<I", bits & 0xffffffff))[0]
+        out[s] = {"planes": c[off[s + ".planes"]], "over": c[off[s + ".over"]], "worst": worst if math.isfinite(worst) else "inf",
+                  "worst_bits": bits, "hist": c[off[s + ".hist"]:off[s + ".hist"] + nb],
+                  "nonfinite_a": c[off[s + ".nonfinite_a"]], "nonfinite_b": c[off[s + ".nonfinite_b"]]}
+        ok = ok and out[s]["over"] == 0
+        ok_cams = ok_cams and (s == "tgt" or out[s]["over"] == 0)
+    for p in TEACHER_CHECK_PAIRS:
+        pix = c[off[p + ".pix"]]
+        ca, cb, it = (c[off[f"{p}.{f}"]:off[f"{p}.{f}"] + K] for f in ("cnt_a", "cnt_b", "inter"))
+        union = [a + b - i for a, b, i in zip(ca, cb, it)]
+        iou = [i / u if u else None for i, u in zip(it, union)]
+        live = [v for v in iou if v is not None]
+        out[p] = {"pix": pix, "agree": c[off[p + ".agree"]] / pix if pix else 1.0, "miou": sum(live) / len(live) if live else 1.0,
+                  "iou": iou, "ign_a": c[off[p + ".ign_a"]], "ign_b": c[off[p + ".ign_b"]]}
+        pair_ok = out[p]["agree"] >= TEACHER_CHECK_AGREE and out[p]["miou"] >= TEACHER_CHECK_MIOU
+        ok, ok_cams = ok and pair_ok, ok_cams and pair_ok
+    out["conforms"] = bool(ok) if out["checks"] else None
+    out["conforms_without_tgt"] = bool(ok_cams) if out["checks"] else None
+    return out
+
+
+def teacher_check_worst(summary):
+    """the figures of a summary that a log line shows: the worst over the map sets and over the label pairs that were counted"""
+    sets = [summary[s] for s in TEACHER_CHECK_SETS if summary[s]["planes"]]
+    pairs = [summary[p] for p in TEACHER_CHECK_PAIRS if summary[p]["pix"]]
+    worst = max([float(s["worst"]) for s in sets], default=0.0)
+    return {"worst": worst, "over": sum(s["over"] for s in sets), "planes": sum(s["planes"] for s in sets),
+            "agree": min([p["agree"] for p in pairs], default=1.0), "miou": min([p["miou"] for p in pairs], default=1.0)}
 
 
 EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16,          # COSA_EXPORT_* of include/cosa_hip.h

@@ -727,6 +727,42 @@ int cosa_tensor_stats(const void *records, const void *chunks, const int *first_
                       size_t workspace_bytes, void *out, void *stream);
 int cosa_grad_blame(const void *partials, const int *first_chunk, int n_tensors, int n_chunks, unsigned long long *blame, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The --teacher_check monitor: two teacher passes over the same weights and images, on two operand
+ * modes (A, B), scored against each other by one reduction, accumulated on the device in a vector of uint64 counters.
+ * cosa_teacher_check_layout: THE definition of that vector for host and device.  K = num_classes (background included,
+ *   2..256).  offsets[COSA_TEACHER_CHECK_SLOTS] (in elements) of, in order: checks (calls accumulated); then for each map
+ *   set (cam, aux, tgt): planes, over, worst, hist[COSA_TEACHER_CHECK_BINS], nonfinite_a, nonfinite_b; then for each label
+ *   pair (main, aux): pix, agree, ign_a, ign_b, cnt_a[K], cnt_b[K], inter[K].  Returns the number of elements (48 + 6K), 0 on
+ *   bad arguments.
+ * cosa_teacher_check: camA/camB and auxA/auxB fp32 [B,C,S,S] (the min-max normalised CAMs of the two passes); tgtA/tgtB fp32
+ *   [B,C,h,w] (the cam-loss targets; the pair may be NULL); mainA/mainB and lauxA/lauxB fp32 [B,S,S] label maps in {0..K-1,
+ *   ignore_index} (the auxiliary pair may be NULL); cls_label fp32 [B,C] or NULL (every plane active); boxes int32 [B,4]
+ *   (y0,y1,x0,x1).  An absent pair leaves its slots untouched.
+ *   Per map set, over the ACTIVE planes (cls_label != 0; a plane of an absent class is never read): a plane's figure is the
+ *   maximum of |a - b| over its elements, +inf (bits 0x7f800000) when either pass holds a non-finite element in it.  planes
+ *   counts the active planes; over those with figure > bar (a figure equal to the bar is not over); worst is the largest
+ *   figure met so far as its fp32 bit pattern (non-negative floats order as unsigned integers); hist[i] counts the planes in
+ *   the first bin with figure <= edge, edges 1e-6, 1e-5, 1e-4, 3e-4, 1e-3, 3e-3, 1e-2, +inf as fp32; nonfinite_a /
+ *   nonfinite_b count the non-finite elements of the active planes of each pass.
+ *   Per label pair, over the pixels inside an image's box only: pix; agree (a == b, ignore counted as a value); ign_a,
+ *   ign_b; per class k < K cnt_a[k], cnt_b[k] and inter[k] (a == b == k).  A value that is neither an integer in 0..K-1
+ *   nor ignore_index is counted in pix (and, where the two maps hold the same value, in agree) only.
+ *   Every sum is an integer atomic, every maximum an integer maximum of bit patterns of exactly computed fp32 values: the
+ *   same bits in any order.  workspace: cosa_teacher_check_workspace_bytes(B, C) of device memory (0 on bad arguments),
+ *   8-byte aligned, cleared by the call itself on `stream`.  Envelope: C <= 255, K == C + 1, B, S > 0, with a tgt pair h, w
+ *   > 0 and <= S, ignore_index no class, bar >= 0; anything else is COSA_EINVAL, nothing is launched or clamped.  One
+ *   memset node and two launches.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_TEACHER_CHECK_SLOTS 33
+#define COSA_TEACHER_CHECK_BINS 8
+size_t cosa_teacher_check_layout(int K, size_t *offsets);
+size_t cosa_teacher_check_workspace_bytes(int B, int C);
+int cosa_teacher_check(const float *camA, const float *camB, const float *auxA, const float *auxB, const float *tgtA,
+                       const float *tgtB, const float *mainA, const float *mainB, const float *lauxA, const float *lauxB,
+                       const float *cls_label, const int32_t *boxes, int B, int C, int K, int S, int h, int w, int ignore_index,
+                       float bar, unsigned long long *counters, void *workspace, size_t workspace_bytes, void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
