@@ -174,6 +174,12 @@ _SIGS.update({
     "cosa_attn_fwd_f16c4": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "cosa_gemm_f16c4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                 c_int, c_void_p]),
+    # the "f32" operand family (csrc/f32_kernels.hip; teacher mode "fp32")
+    "cosa_gemm_f32": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
+    "cosa_conv3x3_dilated_f32": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_void_p]),
+    "cosa_attn_fwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "cosa_layernorm_f32out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "cosa_im2col_flip_f32_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

@@ -48,7 +48,7 @@ COCO_DEFAULTS = dict(eval_iters=6000, dataset='COCO', num_classes=81, batch_size
 EXTRA = [
     ("pretrained_path", str, None),          # local timm ViT-B/16 checkpoint for --pretrained true (no network here)
     ("name_list_dir", str, None),            # split lists / cls_labels_onehot.npy (default: ./dataloaders/<dataset>/ as the reference)
-    ("teacher_precision", str, "auto"), # auto (fp16x3: train_step.resolve_teacher_precision) | bf16 | fp16 | bf16x3 | fp16x3 | fp16c8[-n[mk]|-xn[mk]] | fp16c4[...]: operand precision of the teacher's no-grad passes;
+    ("teacher_precision", str, "auto"), # auto (fp16x3: train_step.resolve_teacher_precision) | bf16 | fp16 | bf16x3 | fp16x3 | fp16c8[-n[mk]|-xn[mk]] | fp16c4[...] | fp32 (fp32 operands on the f32-input MFMA: the reference's arithmetic, several times the default's teacher time): operand precision of the teacher's no-grad passes;
                                              # the default meets the 1e-3 / IoU 0.999 tolerance against the fp32 reference, bf16 (faster) does not
     ("log_iters", int, 20),
     # full-state checkpoints (cosa_amd/checkpoint.py): bit-exact resumption
@@ -74,7 +74,8 @@ EXTRA = [
                                              # scores the two passes against each other on the device (literal 1e-3 bar, label agreement, mask
                                              # mIoU); logged and written to <output_dir>/teacher_check.jsonl every log_iters; training is untouched
     ("teacher_check_mode", str, "auto"),     # any --teacher_precision value; auto: bf16x3 against an fp16x3 teacher (the same kernels with fp32's
-                                             # exponent range: an fp16 overflow shows), fp16x3 against every other teacher mode
+                                             # exponent range: an fp16 overflow shows), fp16x3 against every other teacher mode; fp32: the teacher's mode against
+                                             # the reference's arithmetic -- the figure is then the conformance criterion's own
 ]
 
 

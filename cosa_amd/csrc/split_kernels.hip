@@ -542,6 +542,14 @@ extern "C" int cosa_layernorm_split_f16(const float *x, const float *gamma, cons
     return layernorm_split_launch<_Float16>(x, gamma, beta, y_split, y_f32, rows, dim, eps, stream);
 }
 
+/* the fp32 output alone (the "f32" operand family, f32_kernels.hip): the same kernel without its split rows, so the same bits as the
+ * y_f32 by-product above */
+extern "C" int cosa_layernorm_f32out(const float *x, const float *gamma, const float *beta, float *y_f32, int rows, int dim, float eps, void *stream)
+{
+    COSA_REQUIRE(y_f32, "cosa_layernorm_f32out: null output");
+    return layernorm_split_launch<bf16>(x, gamma, beta, nullptr, y_f32, rows, dim, eps, stream);
+}
+
 // ---- fp16c8 producers (c8.hpp; include/cosa_hip.h) ---------------------------------------------------------------------------------
 extern "C" int cosa_c8_rows(const float *src, const float *bias, void *dst, int R, int K, long long src_ld, int ones, void *stream)
 {

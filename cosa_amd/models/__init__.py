@@ -41,6 +41,17 @@ class LargeFOV(nn.Module):
             seg = nn_ops.reference_op("linear", f"LargeFOV.conv8 ({tuple(w8.shape)}, {dt})", y, w8, None).float()
         return seg.view(B, h, w, -1).permute(0, 3, 1, 2).contiguous()
 
+    def forward_tokens_f32(self, tok, B, h, w):
+        """no-grad fp32 path (teacher mode "fp32"): conv6 / conv7 as implicit GEMMs on the f32-input MFMA over the fp32 tokens and the fp32 master
+        weights, conv8 on the exact-fp32 narrow-head kernel.  tok [B, h*w, 768] fp32 (may be the strided view) -> seg [B, classes, h, w] fp32"""
+        y = nn_ops.conv3x3_dilated_f32(tok, self.conv6.weight, B, h, w, self.dilation, relu=True)
+        y = nn_ops.conv3x3_dilated_f32(y.view(B, h * w, -1), self.conv7.weight, B, h, w, self.dilation, relu=True)
+        w8 = self.conv8.weight.detach().reshape(self.conv8.weight.shape[0], -1)
+        seg = nn_ops.head_linear(y.view(B, h * w, -1), w8.contiguous())
+        if seg is None:
+            seg = nn_ops.reference_op("linear", f"LargeFOV.conv8 ({tuple(w8.shape)}, fp32)", y, w8, None).float()
+        return seg.view(B, h, w, -1).permute(0, 3, 1, 2).contiguous()
+
     def forward_tokens_train(self, tok, B, h, w):
         """bf16 training path (autograd): conv6 / conv7 forward, input- and weight-gradient on our MFMA kernels
         (nn_ops.DilatedConvReluFn), conv8 (1x1) as a GEMM over the tokens.  tok [B, h*w, 768] bf16 -> seg [B, classes, h, w] fp32"""
@@ -102,7 +113,8 @@ class VITNetwork(nn.Module):
 
     def set_nograd_precision(self, mode):
         """operand precision of the no-grad passes (teacher pseudo-labels, evaluation): "bf16" (8 significant bits), "fp16" (11; the
-        same kernels built for fp16 operands), "bf16x3" (16; hi + lo bf16 halves, three MFMA terms), "fp16x3" (22: hi + lo fp16 halves, the same three
+        same kernels built for fp16 operands), "fp32" (the reference's arithmetic: fp32 operands from the fp32 masters on the f32-input MFMA, fp32
+        decoder; no suffix, no 16-bit copy of anything), "bf16x3" (16; hi + lo bf16 halves, three MFMA terms), "fp16x3" (22: hi + lo fp16 halves, the same three
         terms at the same cost), "fp16c8" (fp16 + 8-bit correction
         terms on the block-scaled MFMA, ~14 bits at twice the 16-bit work; attention operands plain fp16) or "fp16c4" (the same with FP4 MX-block
         correction terms at 4x the fp16 rate: ~1.6x the 16-bit work); "-n" suffix: blocks from index n on plain fp16, "-nmk": their MLP halves (fc1, fc2) from
@@ -113,12 +125,12 @@ class VITNetwork(nn.Module):
         mx = re.fullmatch(r"(?:x(\d+)(?:m(\d+))?)?(?:c(\d+))?", tail) if tail and not m else None     # "fp16c8-x6": the blocks BELOW index 6 on bf16x3
         #                       operands (round 5); "fp16c8-x6m4": their attention halves below 6, their MLP halves below 4; "fp16c8-x2c6" / "fp16c8-c6":
         #                       the blocks from index 6 on take qkv / fc1 / fc2 on fp16c4 operands (fp16c8 base only)
-        assert base in ("bf16", "fp16", "bf16x3", "fp16x3", "fp16c8", "fp16c4") and (bool(tail) == bool(sep)) and \
+        assert base in ("bf16", "fp16", "fp32", "bf16x3", "fp16x3", "fp16c8", "fp16c4") and (bool(tail) == bool(sep)) and \
             (not tail or (base in ("fp16c8", "fp16c4") and (m or mx))), mode
         self.check_nograd_precision(mode)
-        self.set_compute_dtype(torch.float16 if base in ("fp16", "fp16x3", "fp16c8", "fp16c4") else torch.bfloat16)
+        self.set_compute_dtype(torch.float32 if base == "fp32" else torch.float16 if base in ("fp16", "fp16x3", "fp16c8", "fp16c4") else torch.bfloat16)
         # "fp16x3" (round 6): the three-term path with fp16 halves (hi + lo: 11 + 11 significant bits; bf16x3: 8 + 8) -- same kernels, same cost
-        self.encoder.precision = "bf16x3" if base == "fp16x3" else (base if base in ("bf16x3", "fp16c8", "fp16c4") else None)
+        self.encoder.precision = "bf16x3" if base == "fp16x3" else "f32" if base == "fp32" else (base if base in ("bf16x3", "fp16c8", "fp16c4") else None)
         self.encoder.x3_dtype = torch.float16 if base == "fp16x3" else torch.bfloat16
         self.encoder.c8_plain_from = int(m.group(1)) if m else None
         self.encoder.c8_plain_mlp_from = int(m.group(2)) if m and m.group(2) else None
@@ -242,6 +254,8 @@ class VITNetwork(nn.Module):
         x4 = (tok if tok32 is None else tok32).reshape(B, h, w, -1).permute(0, 3, 1, 2)
         if tok32 is not None and tok.dtype in vitencoder._OP16 and self.decoder.conv6.weight.shape[1] % 64 == 0:
             seg = self.decoder.forward_tokens(tok, B, h, w)            # fused no-grad path: own implicit-GEMM convs
+        elif tok32 is not None and self.encoder.precision == "f32" and self.decoder.conv6.weight.shape[1] % 16 == 0:
+            seg = self.decoder.forward_tokens_f32(tok32, B, h, w)      # ... of the fp32 family (an fp32 network WITHOUT that mode set: below, raises)
         elif tok.dtype == torch.bfloat16 and tok.is_cuda and self.decoder.conv6.weight.shape[1] % 128 == 0 \
                 and torch.is_grad_enabled():
             seg = self.decoder.forward_tokens_train(tok, B, h, w)      # training: forward + both gradients on own kernels

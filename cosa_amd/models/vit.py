@@ -34,8 +34,8 @@ class FP32Tokens:
 
 class OperandMap(typing.NamedTuple):
     """operand formats of a no-grad pass (VisionTransformer._operand_map): of the patch projection -- the family that assembles the tokens and
-    closes with its LayerNorm -- and per block of the attention half and the MLP half: "plain", "x3", "c8" or "c4" (qkv / fc1 / fc2 on fp16c4
-    operands in an otherwise fp16c8 half)"""
+    closes with its LayerNorm -- and per block of the attention half and the MLP half: "plain", "x3", "c8", "c4" (qkv / fc1 / fc2 on fp16c4
+    operands in an otherwise fp16c8 half) or "f32" (fp32 operands read from the fp32 masters: all of the pass or none of it)"""
     patch: str
     attn: tuple
     mlp: tuple
@@ -137,7 +137,8 @@ class VisionTransformer(nn.Module):
         self.norm = nn.LayerNorm(embed_dim, eps=eps)
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()   # unused by the path (vit.py:257,325)
         self.compute_dtype = compute_dtype
-        self.precision = None          # "bf16x3" / "fp16c8" / "fp16c4": parity-grade operand representations of the no-grad passes
+        self.precision = None          # "bf16x3" / "fp16c8" / "fp16c4": parity-grade operand representations of the no-grad passes;
+        #                                "f32": fp32 operands on the f32-input MFMA (mode string "fp32")
         # residual stream of the TRAINING path: "fp32" (default since round 4: the reference trains in fp32, main.py:124-246 -- the sums
         # x + attn(..), x + mlp(..) and the gradient sums of the skip connections are formed and kept in fp32; MFMA operands stay bf16) or
         # "bf16" (rounds 1-3: the stream itself rounded to 8 significant bits after every add; kept for A/B measurements)
@@ -278,6 +279,8 @@ class VisionTransformer(nn.Module):
         """which projection of which block runs on which operand format, from the fields `set_nograd_precision` sets: the ONE place that
         decides it (weight sets, buffers and the block loop all read the result).  Reads no tensor, launches nothing."""
         depth = len(self.blocks)
+        if self.precision == "f32":                   # (no 16-bit type anywhere: weights are the masters, activations fp32 buffers)
+            return OperandMap("f32", ("f32",) * depth, ("f32",) * depth, False, False, None, None)
         if self.precision not in ("bf16x3", "fp16c8", "fp16c4"):
             return OperandMap("plain", ("plain",) * depth, ("plain",) * depth, False, False, self.compute_dtype, None)
         if self.precision == "bf16x3":                # (hi / lo halves of x3_dtype: "bf16x3" or "fp16x3")
@@ -345,7 +348,7 @@ class VisionTransformer(nn.Module):
     _BUFS_MAX = 8          # cached geometries (each holds ~M x 7 KB of activations): evaluation over many image sizes must not pin them all
 
     def _operand_buffers(self, fmt, dtype, pk, cols=False):
-        """persistent "x3" / "c8" activations for the token rows of `pk`; the (1, 1, 0, ...) augmentation block of the fc1 output is set once
+        """persistent "x3" / "c8" / "f32" activations for the token rows of `pk` ("f32": plain fp32 rows, no augmentation block); the (1, 1, 0, ...) augmentation block of the fc1 output is set once
         here (the GEMM epilogues write the operand halves only), the other buffers get theirs from their producing kernels.  Keyed on the FULL
         token geometry (the (images, tokens) split per scale and the patch width), not on M alone: the token-shaped patch operand `cols`
         relies on its class-token rows staying zero, and another split of the same M puts class tokens where stale patch rows sit (ADVICE
@@ -356,10 +359,13 @@ class VisionTransformer(nn.Module):
         mk = lambda n: torch.zeros((pk.M, n), device=pk.dev, dtype=dtype)
         if ent is None:
             D, Hd = self.embed_dim, self.blocks[0].mlp.fc1.weight.shape[0]
-            ent = {"y": mk(nn_ops.split_ld(D)), "qkv": mk((2 if fmt == "x3" else 1) * 3 * D), "o": mk(nn_ops.split_ld(D)), "h": mk(nn_ops.split_ld(Hd))}
-            ent["h"][:, 2 * Hd:2 * Hd + 2] = 1
+            if fmt == "f32":
+                ent = {"y": mk(D), "qkv": mk(3 * D), "o": mk(D), "h": mk(Hd)}
+            else:
+                ent = {"y": mk(nn_ops.split_ld(D)), "qkv": mk((2 if fmt == "x3" else 1) * 3 * D), "o": mk(nn_ops.split_ld(D)), "h": mk(nn_ops.split_ld(Hd))}
+                ent["h"][:, 2 * Hd:2 * Hd + 2] = 1
         if cols and "cols" not in ent:
-            ent["cols"] = mk(nn_ops.split_ld(pk.Kp))      # (class-token rows: zero for good)
+            ent["cols"] = mk(pk.Kp if fmt == "f32" else nn_ops.split_ld(pk.Kp))      # (class-token rows: zero for good)
         bufs[key] = ent                             # (re-inserted last: the dict is the LRU order)
         if torch.cuda.is_current_stream_capturing():
             ent["pinned"] = True
@@ -410,6 +416,10 @@ class VisionTransformer(nn.Module):
             xr, aux = self._blocks_nograd(xr, pk, fmap, W, bufs)
             a16 = torch.empty_like(bufs["c8"]["y"])      # (its hi parts: fp16 tokens for the decoder convs, a strided view)
             _, xn32 = nn_ops.layernorm_c8(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps, out=a16, want_f32=True)
+        elif fmap.patch == "f32":
+            bufs = {"f32": self._operand_buffers("f32", torch.float32, pk, cols=True)}
+            xr, aux = self._blocks_nograd(self._tokens_f32(xs, pk, bufs["f32"]), pk, fmap, {}, bufs)
+            a16 = xn32 = nn_ops.layernorm_f32out(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps)      # (no 16-bit tokens: the decoder runs fp32 too)
         else:
             c = lambda p_: nn_ops.cast_param(p_, fmap.dt16)
             xr, aux = self._blocks_nograd(self._tokens_plain(xs, pk, fmap.dt16, flip_pairs), pk, fmap, {}, {})
@@ -471,6 +481,20 @@ class VisionTransformer(nn.Module):
             nn_ops.gemm_x3(bf["cols"][o0:o1], w_patch, B * N, self.embed_dim, pk.Kp, nn_ops.EPI_RESIDUAL, residual=xr[o0:o1], out=xr[o0:o1])
         return xr
 
+    def _tokens_f32(self, xs, pk, bf):
+        """the fp32 family's token assembly: fp32 im2col rows, the patch projection on the fp32 master weight through the residual epilogue into
+        the stream in place, all scales in one launch (a row's chain does not depend on M).  The bias is an epilogue operand here, not an
+        augmentation column, so the class-token rows (zero operand rows) receive it too: they are written again afterwards as cls + pos_0"""
+        from .. import _C
+        D = self.embed_dim
+        xr = self._stream_and_cols(xs, pk, bf["cols"], _C.lib().cosa_im2col_flip_f32_tokens, "cosa_im2col_flip_f32_tokens")
+        first = [xr[o0].clone() for _, _, o0, _ in pk.scales()]             # cls + pos_0 of each scale ([D]: small)
+        pe = self.patch_embed.proj
+        nn_ops.gemm_f32(bf["cols"], pe.weight.detach().reshape(D, -1), pe.bias.detach(), pk.M, D, pk.Kp, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+        for row, (B, N, o0, o1) in zip(first, pk.scales()):
+            xr[o0:o1].view(B, N, D)[:, 0] = row
+        return xr
+
     def _tokens_c8(self, xs, pk, bf, w_patch):
         from .. import _C
         xr = self._stream_and_cols(xs, pk, bf["cols"], _C.lib().cosa_im2col_flip_c8_tokens, "cosa_im2col_flip_c8_tokens")
@@ -492,6 +516,8 @@ class VisionTransformer(nn.Module):
                 self._attn_plain(xr, xn, blk, pk, o16, fmap.dt16)
             elif fmap.attn[i] == "x3":
                 self._attn_x3(xr, xn, blk, pk, bufs["x3"], W["x3"], i)
+            elif fmap.attn[i] == "f32":
+                self._attn_f32(xr, xn, blk, pk, bufs["f32"])
             else:
                 self._attn_c8(xr, xn, blk, pk, bufs["c8"], W, i, fmap)
             xr = xn
@@ -499,6 +525,8 @@ class VisionTransformer(nn.Module):
                 self._mlp_plain(xr, blk, fmap.dt16)
             elif fmap.mlp[i] == "x3":
                 self._mlp_x3(xr, blk, pk, bufs["x3"], W["x3"], i)
+            elif fmap.mlp[i] == "f32":
+                self._mlp_f32(xr, blk, pk, bufs["f32"])
             else:
                 self._mlp_c8(xr, blk, pk, bufs["c8"], W, i, fmap.mlp[i] == "c4")
             if i == aux_idx and aux_idx != depth - 1:
@@ -533,6 +561,23 @@ class VisionTransformer(nn.Module):
         nn_ops.layernorm_split(xr, blk.norm2.weight.detach(), blk.norm2.bias.detach(), blk.norm2.eps, out=bf["y"])
         nn_ops.gemm_x3(bf["y"], W[f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], ldy=bf["h"].shape[1])
         nn_ops.gemm_x3(bf["h"], W[f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+
+    def _attn_f32(self, xr, xn, blk, pk, bf):
+        """fp32 attention half: the projections read the fp32 master weights and biases themselves -- no weight set, nothing rebuilt per pass"""
+        M, D = pk.M, self.embed_dim
+        d = lambda p_: None if p_ is None else p_.detach()
+        nn_ops.layernorm_f32out(xr, d(blk.norm1.weight), d(blk.norm1.bias), blk.norm1.eps, out=bf["y"])
+        nn_ops.gemm_f32(bf["y"], d(blk.attn.qkv.weight), d(blk.attn.qkv.bias), M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"])
+        for B, N, o0, o1 in pk.scales():
+            nn_ops.attn_fwd_f32(bf["qkv"][o0:o1], B, N, self.num_heads, bf["o"][o0:o1])
+        nn_ops.gemm_f32(bf["o"], d(blk.attn.proj.weight), d(blk.attn.proj.bias), M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+
+    def _mlp_f32(self, xr, blk, pk, bf):
+        M, D, Hd = pk.M, self.embed_dim, blk.mlp.fc1.weight.shape[0]
+        d = lambda p_: p_.detach()
+        nn_ops.layernorm_f32out(xr, d(blk.norm2.weight), d(blk.norm2.bias), blk.norm2.eps, out=bf["y"])
+        nn_ops.gemm_f32(bf["y"], d(blk.mlp.fc1.weight), d(blk.mlp.fc1.bias), M, Hd, D, nn_ops.EPI_GELU, out=bf["h"])
+        nn_ops.gemm_f32(bf["h"], d(blk.mlp.fc2.weight), d(blk.mlp.fc2.bias), M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
 
     def _attn_c8(self, xr, xn, blk, pk, bf, W, i, fmap):
         """fp16c8 attention half; its qkv projection may run on plain fp16 (`c8_plain_qkv`) or fp16c4 operands, its output projection on
@@ -628,7 +673,7 @@ class VisionTransformer(nn.Module):
         return FP32Tokens(xn, aux)                              # their gradients are summed in fp32; aux = block aux_idx's output, pre-norm
 
     def use_fused(self, x):
-        return (not torch.is_grad_enabled()) and self.compute_dtype in _OP16 and x.is_cuda and self.embed_dim == 768
+        return (not torch.is_grad_enabled()) and (self.compute_dtype in _OP16 or self.precision == "f32") and x.is_cuda and self.embed_dim == 768
 
     # -- vit.py:302-321: returns cls token, final tokens, aux-layer tokens (pre final norm unless aux is the last) --
     def forward_features(self, x):

@@ -422,6 +422,72 @@ def attn_fwd_x3(qkv_s, B, N, H, out_s, lse=None):
 
 
 # --------------------------------------------------------------------------------------------
+# "f32" operands: the no-grad passes in the reference's own arithmetic (include/cosa_hip.h; csrc/f32_kernels.hip).  Every operand fp32 (the
+#   weights are the fp32 masters themselves), every product on the exact f32-input MFMA; teacher mode string "fp32" 
+# --------------------------------------------------------------------------------------------
+def _f32_rows(t, what):
+    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+        raise _C.CosaError(f"{what}: fp32 rows of unit column stride, got {t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def gemm_f32(x, w, b, M, N, K, epilogue=EPI_BIAS, residual=None, out=None):
+    """x [M, >= K], w [N, >= K] fp32 rows (any row stride), b [N] fp32 or None -> fp32 [M, N] (out: rows of any stride >= N) = x w^T + b, then
+    GELU (epilogue 1) or + residual (epilogue 2: fp32 rows, in place allowed); one fma chain over ascending k per element"""
+    _f32_rows(x, "gemm_f32 x"), _f32_rows(w, "gemm_f32 w")
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32)
+    _f32_rows(out, "gemm_f32 out")
+    if residual is not None:
+        _f32_rows(residual, "gemm_f32 residual")
+    assert x.shape[0] >= M and w.shape[0] >= N and out.shape[0] >= M and out.shape[1] >= N and (b is None or (b.dtype == torch.float32 and b.is_contiguous()))
+    with _C.profiled("gemm_f32"):
+        _C.check(_C.lib().cosa_gemm_f32(_C.ptr(x), _C.ptr(w), _C.ptr(b), _C.ptr(residual), _C.ptr(out), M, N, K, x.stride(0), w.stride(0),
+                                        residual.stride(0) if residual is not None else 0, out.stride(0), epilogue, _C.stream_ptr()), "cosa_gemm_f32")
+    _flops["gemm_f32"] = _flops.get("gemm_f32", 0) + 2.0 * M * N * K
+    return out
+
+
+def attn_fwd_f32(qkv, B, N, H, out):
+    """attention on fp32 qkv rows [B*N, >= 3*H*64] (the projection's own [3, H, 64] layout) -> fp32 rows out [B*N, >= H*64]"""
+    _f32_rows(qkv, "attn_fwd_f32 qkv"), _f32_rows(out, "attn_fwd_f32 out")
+    assert qkv.shape[0] >= B * N and out.shape[0] >= B * N and qkv.shape[1] >= 3 * H * 64 and out.shape[1] >= H * 64
+    with _C.profiled("attn_f32"):
+        _C.check(_C.lib().cosa_attn_fwd_f32(_C.ptr(qkv), _C.ptr(out), B, N, H, 64, 0.125, qkv.stride(0), out.stride(0), _C.stream_ptr()),
+                 "cosa_attn_fwd_f32")
+    _flops["attn_f32"] = _flops.get("attn_f32", 0) + 4.0 * B * H * N * N * 64
+    return out
+
+
+def layernorm_f32out(x, g, b, eps, out=None):
+    """LayerNorm(768) over fp32 rows with fp32 gamma / beta -> fp32 [rows, 768]: layernorm_split's `want_f32` output alone, same bits"""
+    rows, D = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and g.dtype == torch.float32 and b.dtype == torch.float32
+    if out is None:
+        out = torch.empty((rows, D), device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape
+    _C.check(_C.lib().cosa_layernorm_f32out(_C.ptr(x), _C.ptr(g), _C.ptr(b), _C.ptr(out), rows, D, float(eps), _C.stream_ptr()), "cosa_layernorm_f32out")
+    return out
+
+
+def conv3x3_dilated_f32(tok, weight, B, h, w, dilation, relu=True):
+    """LargeFOV conv on fp32 NHWC tokens, an implicit GEMM on the f32 MFMA.  tok [B, h*w, Cin] fp32 (possibly the row-strided view without
+    the class-token rows); weight [Cout, Cin, 3, 3] fp32 (the master).  Returns fp32 [B*h*w, Cout]."""
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    assert tok.dtype == torch.float32 and weight.dtype == torch.float32 and tok.stride(2) == 1 and tok.shape[1] == h * w and tok.shape[2] == Cin
+    ldx = tok.stride(1)
+    img_rows = tok.stride(0) // ldx if B > 1 else h * w
+    assert B == 1 or tok.stride(0) == img_rows * ldx
+    wt = weight.detach().permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous()          # tap-major [Cout, (ky, kx, cin)]
+    y = torch.empty((B * h * w, Cout), device=tok.device, dtype=torch.float32)
+    with _C.profiled("conv3x3_f32"):
+        _C.check(_C.lib().cosa_conv3x3_dilated_f32(_C.ptr(tok), _C.ptr(wt), _C.ptr(y), B, h, w, Cin, Cout, int(dilation), img_rows, ldx, int(relu),
+                                                   _C.stream_ptr()), "cosa_conv3x3_dilated_f32")
+    _flops["conv3x3_f32"] = _flops.get("conv3x3_f32", 0) + 2.0 * B * h * w * Cout * Cin * 9
+    return y
+
+
+# --------------------------------------------------------------------------------------------
 # fp16c8 operands: parity-grade no-grad passes at 2x the 16-bit MFMA work (include/cosa_hip.h; csrc/c8.hpp)
 #   a c8 row of logical width K, in bytes: [hi fp16 (2K) | lo8 e5m2 (K) | hi8 e5m2 (K) | aug fp16 (128)]; held as fp16 tensors of
 #   2K + 64 columns (the same stride as a bf16x3 row)

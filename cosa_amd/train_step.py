@@ -80,7 +80,8 @@ def resolve_teacher_precision(mode, crop_size, usepar=False):
 def resolve_teacher_check_mode(mode, teacher_precision):
     """--teacher_check_mode: "auto" -> "bf16x3" against an "fp16x3" teacher -- the same three-term kernels on halves
     with fp32's exponent range, so an fp16 split that overflows (|t| > 65504: hi = inf) shows as a difference --, "fp16x3", the conforming
-    default, against every other teacher mode.  Any other value is taken as it is (VITNetwork.set_nograd_precision's names)."""
+    default, against every other teacher mode.  Any other value is taken as it is (VITNetwork.set_nograd_precision's names); "fp32" makes the
+    figure the criterion's own: the teacher's mode against the reference's arithmetic."""
     if mode != "auto":
         return mode
     return "bf16x3" if teacher_precision == "fp16x3" else "fp16x3"
@@ -175,7 +176,8 @@ class CoSATrainer:
         if on:
             self.model_AN.set_nograd_precision(tp)
         tdt = self.model_AN.compute_dtype if on else args.compute_dtype
-        self._teacher_shadows = nn_ops.ensure_shadows(self.model_AN, tdt) if on else None
+        # ("fp32": the teacher's passes read the fp32 masters themselves -- no 16-bit shadows exist, the fused optimizer step writes none)
+        self._teacher_shadows = nn_ops.ensure_shadows(self.model_AN, tdt) if on and tdt != torch.float32 else None
         self._student_shadows = nn_ops.ensure_shadows(self.student) if on else None
         # AdamW + EMA + shadow refresh as one multi-tensor kernel: it rewrites every shadow each step, so the no-grad entry points
         # need not refresh them (nn_ops.ensure_shadows); without it they do
@@ -253,7 +255,9 @@ class CoSATrainer:
             if on:
                 self._build_check_model(cm)
         if on:
-            self._teacher_shadows.optimizer_owned = self._student_shadows.optimizer_owned = self._fused_step is not None
+            for sh in (self._teacher_shadows, self._student_shadows):
+                if sh is not None:
+                    sh.optimizer_owned = self._fused_step is not None
             # bf16 W^T copies of the student's block projections (the input-gradient GEMMs run the forward kernel on them)
             ws = [self.student.encoder.patch_embed.proj.weight]
             for blk in self.student.encoder.blocks:
@@ -352,7 +356,8 @@ class CoSATrainer:
         self.model_CK = ck
         self._ck_params = list(ck.parameters())
         assert len(self._ck_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ck_params, self._ema_pairs[0]))
-        self._ck_shadows = nn_ops.ensure_shadows(ck, ck.compute_dtype)        # not optimizer-owned: refreshed at the entry of every pass
+        # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads model_CK's fp32 parameters)
+        self._ck_shadows = nn_ops.ensure_shadows(ck, ck.compute_dtype) if ck.compute_dtype != torch.float32 else None
         self._ck_buffers = {}                                                 # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
 
     def _is_check_step(self, n_iter):

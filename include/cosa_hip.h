@@ -367,6 +367,34 @@ int cosa_attn_fwd_f16x3(const void *qkv_split, void *out_split, float *lse, int 
                         int ldq, int ldo, uint64_t *stamps, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * "f32" operands (csrc/f32_kernels.hip; teacher mode string "fp32"): the no-grad passes in the reference's own
+ * arithmetic (models/vit/vit.py:96-137, models/decoder/conv_head.py:32-41 run fp32) -- every operand fp32, read from the fp32 masters, every
+ * product on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain).  1/16 of the 16-bit MFMA rate.
+ *   cosa_gemm_f32             Y[M, N] (row stride ldy) = X[M, K] (ldx) W[N, K]^T (ldw); epilogue 0: + bias, 1: + bias then erf-form GELU
+ *                             (erff), 2: + bias + residual (fp32, row stride ldr; may alias Y).  bias may be null (none).  Every output
+ *                             element is ONE fma chain over ascending k starting from zero, the epilogue applied afterwards in fp32: no
+ *                             split-K, no atomics, no dependence on M, on the row's position or on the other rows.  Envelope: M >= 1 (tail
+ *                             rows guarded), N % 64 == 0, K % 16 == 0, ldx / ldw % 4 == 0 on 16-byte aligned bases; anything else is
+ *                             COSA_EINVAL and nothing is launched.
+ *   cosa_conv3x3_dilated_f32  Y[B*h*w, Cout] = relu?(conv3x3(tokens, dilation d, zero padding d, no bias)) as an implicit GEMM on the same
+ *                             kernel: tokens NHWC, image b at tok + b * img_rows * ldx, pixel rows of stride ldx; Wt [Cout, 9 * Cin] tap-major
+ *                             (ky, kx, cin).  Per output element one chain over (tap, cin) ascending, a padded tap contributing exact zeros:
+ *                             independent of the batch.  Cin % 16 == 0, Cout % 64 == 0.
+ *   cosa_attn_fwd_f32         out [B, N, H*64] (token stride ldo) = softmax(q k^T * scale) v on fp32 qkv [B, N, 3, H, 64] (token stride ldq: a
+ *                             row slice of the packed buffer); scores, max-subtracted expf, row sums and P V in fp32 on the f32 MFMA, key
+ *                             tiles of 32 through LDS, tail keys masked; a (batch, head) slice's result depends on that slice alone.  N >= 1.
+ *   cosa_layernorm_f32out     nn.LayerNorm(768, eps), fp32 in / gamma / beta / out: cosa_layernorm_split's y_f32 by-product alone, same bits
+ *   cosa_im2col_flip_f32_tokens  cosa_im2col_flip_split_tokens with plain fp32 rows [flips * B * (h*w + cls_rows), C P P]; P % 4 == 0
+ * ------------------------------------------------------------------------------------- */
+int cosa_gemm_f32(const float *X, const float *W, const float *bias, const float *residual, float *Y, int M, int N, int K, int ldx, int ldw,
+                  int ldr, int ldy, int epilogue, void *stream);
+int cosa_conv3x3_dilated_f32(const float *tok, const float *Wt, float *Y, int B, int h, int w, int Cin, int Cout, int dilation, int img_rows,
+                             int ldx, int relu, void *stream);
+int cosa_attn_fwd_f32(const float *qkv, float *out, int B, int N, int H, int head_dim, float scale, int ldq, int ldo, void *stream);
+int cosa_layernorm_f32out(const float *x, const float *gamma, const float *beta, float *y_f32, int rows, int dim, float eps, void *stream);
+int cosa_im2col_flip_f32_tokens(const float *x, float *rows, int B, int C, int H, int W, int P, int flips, int cls_rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * utils/seg_helper.py:961-996 (DenseCRF / crf_inference_infv2, final evaluation only): the position-only Gaussian kernel of the dense
  * CRF -- pydensecrf's addPairwiseGaussian: features (x / sxy, y / sxy) -- as a permutohedral-lattice filter on a 2-D lattice (the lattice
  * kernels of the bilateral filter, csrc/permuto_kernels.hip, compiled a second time with -DCOSA_PD=2).  ins / outs [N, K, H, W] fp32.

@@ -1,7 +1,7 @@
 """Score two operand modes of the no-grad passes against each other on a CHECKPOINT, without training: the
 stand-alone form of --teacher_check_iters, for the day released weights are at hand.
 
-    python tools/teacher_check.py --checkpoint best_seg.pth [--mode fp16x3] [--check_mode fp16c8-x2] [--batches 8] \
+    python tools/teacher_check.py --checkpoint best_seg.pth [--mode fp16x3] [--check_mode fp16c8-x2 | fp32] [--batches 8] \
         (--synthetic | --dataset VOC12 --voc12_root ... | --dataset COCO --coco_root ...) [--crop_size 448] [--batch_size 16] [launcher flags]
 
 The checkpoint (best_seg.pth / best_cam.pth layout, read as cosa_amd.predict reads it: the restricted unpickler, --trust_checkpoint for the
@@ -23,7 +23,8 @@ def get_parser():
     p.description = "Compare two operand modes of the teacher's no-grad passes on a checkpoint"
     p.add_argument("--checkpoint", type=str, default=None, help="best_seg.pth / best_cam.pth of a run (reference key names)")
     p.add_argument("--mode", type=str, default="fp16x3", help="operand mode A (any --teacher_precision value)")
-    p.add_argument("--check_mode", type=str, default="auto", help="operand mode B; auto: bf16x3 against fp16x3, fp16x3 against anything else")
+    p.add_argument("--check_mode", type=str, default="auto", help="operand mode B; auto: bf16x3 against fp16x3, fp16x3 against anything else; fp32: the reference's arithmetic on the device "
+                   "(the figure is then the criterion's own: DESIGN.md section 16)")
     p.add_argument("--batches", type=int, default=4)
     p.add_argument("--synthetic", action="store_true", help="synthetic batches (train_step.synthetic_batch) instead of a dataset")
     p.add_argument("--trust_checkpoint", action="store_true",
