@@ -103,6 +103,8 @@ _SIGS = {
     "cosa_teacher_check_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
     "cosa_teacher_check_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cosa_teacher_check": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cosa_student_check_counters": (c_size_t, [c_int]),
+    "cosa_student_check": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_void_p]),
     "cosa_tensor_stats_layout": (c_size_t, [ctypes.POINTER(c_size_t)]),
     "cosa_tensor_stats_workspace_bytes": (c_size_t, [c_int]),
     "cosa_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

@@ -43,6 +43,7 @@ SOURCES = {
     "permuto_kernels.hip@d2": EXACT + ["-DCOSA_PD=2"],
     "optim_kernels.hip": ["-ffp-contract=off"],
     "teacher_check_kernels.hip": EXACT,
+    "student_check_kernels.hip": EXACT,
     # the "f32" operand family: fp32 operands on the f32-input MFMA.  No contraction: the MFMA's chain is the only fused arithmetic, what
     # else is an fma is written fmaf; no fast math (expf / erff at their full accuracy, infinities honoured by the tail-key mask)
     "f32_kernels.hip": EXACT,

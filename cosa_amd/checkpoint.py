@@ -307,6 +307,7 @@ class TrainState:
     LABEL_STATS = "aux.label_stats.counters"         # CoSATrainer.extra_state["label_stats.counters"]
     TENSOR_BLAME = "aux.tensor_stats.blame"          # CoSATrainer.tensor_stats_state (--tensor_stats behind a gradient guard)
     TEACHER_CHECK = "aux.teacher_check.counters"     # CoSATrainer.extra_state["teacher_check.counters"] (--teacher_check_iters N > 0)
+    STUDENT_CHECK = "aux.student_check.counters"     # CoSATrainer.extra_state["student_check.counters"] (--student_check_iters N > 0)
 
     def __init__(self, trainer, part="all"):
         """part: "all" (a world of one), or under a process group "shared" (networks and moments: identical on every rank, written by
@@ -547,11 +548,14 @@ class TrainState:
             self.TEACHER_CHECK: ("the file holds a teacher check's counters and this run makes no checks (--teacher_check_iters 0): the entry "
                                  "is ignored",
                                  "written without a teacher check: this run's check counters start at zero"),
+            self.STUDENT_CHECK: ("the file holds a student check's counters and this run makes no checks (--student_check_iters 0): the entry "
+                                 "is ignored",
+                                 "written without a student check: this run's check counters start at zero"),
         }
 
     def _reconcile_optional(self, header, a_len, path):
-        """Four tensors are optional: the guard record (the arena's last), --tensor_stats' blame counters (in front of it), and
-        --label_stats' and --teacher_check_iters' counters (among the launcher's tensors).  ->
+        """Five tensors are optional: the guard record (the arena's last), --tensor_stats' blame counters (in front of it), and
+        --label_stats', --teacher_check_iters' and --student_check_iters' counters (among the launcher's tensors).  ->
         (header as this run would have written it, its arena bytes, [(file offset, arena offset, bytes)] to read, [(arena offset,
         bytes)] to zero).  A file without one of them loads into a run that has it with the tensor zero (counters start at zero); a
         file with one loads into a run without it, the entry ignored.  Each with a note.  Any other difference is left as it is, for

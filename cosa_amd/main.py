@@ -73,6 +73,8 @@ def check_supported(args):
         raise ValueError(f"--accum_steps {args.accum_steps}: a positive number of micro-batches per optimizer step")
     if getattr(args, "teacher_check_iters", 0) < 0:
         raise ValueError(f"--teacher_check_iters {args.teacher_check_iters}: 0 (off) or a positive number of optimizer steps")
+    if getattr(args, "student_check_iters", 0) < 0:
+        raise ValueError(f"--student_check_iters {args.student_check_iters}: 0 (off) or a positive number of optimizer steps")
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
@@ -130,7 +132,27 @@ def append_teacher_check(output_dir, summary, n_iter, mode, check_mode):
         f.write(teacher_check_record(summary, n_iter, mode, check_mode) + "\n")
 
 
-def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check=None):
+def student_check_line(summary, check_mode):
+    """what --student_check_iters adds to the log line of an interval that held a check, exactly:
+    ` scheck[MODE]: seg rel 1.2e-03, agree 0.99987, flips>=1e-1 0, loss rel 3.1e-04` -- the seg logits' relative L2 difference, the share of
+    cells with the same argmax, the differing cells whose check-pass margin is at least 1e-1 (real flips, not near-ties), and the largest
+    relative difference over the four loss terms"""
+    return " scheck[%s]: seg rel %.1e, agree %.5f, flips>=1e-1 %d, loss rel %.1e" % (
+        check_mode, summary["seg"]["rel_l2"], summary["seg_agree"], summary["flip_hist"][3], summary["loss_rel"])
+
+
+def student_check_record(summary, n_iter, mode, check_mode):
+    """one line of <output_dir>/student_check.jsonl: the full summary of an interval's checks, the training forward's operand mode (`mode`)
+    and the check pass's (`check_mode`)"""
+    return json.dumps(dict(summary, iters=int(n_iter), mode=mode, check_mode=check_mode))
+
+
+def append_student_check(output_dir, summary, n_iter, mode, check_mode):
+    with (Path(output_dir) / "student_check.jsonl").open("a") as f:
+        f.write(student_check_record(summary, n_iter, mode, check_mode) + "\n")
+
+
+def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check=None, student_check=None):
     """The log interval's ONE host sync: -> (means of the running sums `acc`, [grad_norm, skipped, clipped] of the guard record or None,
     the label counters as ints or None).  The guard's own tensor and the label counters ride along in the same transfer (`acc` keeps
     its length; counts are exact in a double: an interval's stay far below 2^53).  `acc` and the label counters are an interval's:
@@ -139,7 +161,10 @@ def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check
     values as [T][6] floats, the blame counters as ints or None).  The table is the sample of the interval's last step and is not
     accumulated; the blame counters are the run's: neither is zeroed.
     teacher_check: --teacher_check_iters' counters; they ride along too, are an interval's (zeroed afterwards), and FIVE values are
-    returned: the three, the tensor_stats pair or None, and the counters as ints."""
+    returned: the three, the tensor_stats pair or None, and the counters as ints.
+    student_check: --student_check_iters' counters; they ride along too, are an interval's (zeroed afterwards), and SIX values are returned:
+    the five (None for what is off) and these counters as ints.  Their fixed-point sums may pass 2^53, so each travels as two doubles,
+    its high and its low 32 bits."""
     parts = [acc / log_iters]
     if guard is not None:
         parts += [torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]
@@ -152,9 +177,16 @@ def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check
             parts.append(blame.double())
     if teacher_check is not None:
         parts.append(teacher_check.double())               # (the largest value, a bit pattern below 2^32, is exact in a double too)
+    if student_check is not None:
+        parts += [(student_check >> 32).double(), (student_check & 0xffffffff).double()]
     vals = (torch.cat(parts) if len(parts) > 1 else parts[0]).tolist()
     n = acc.numel()
     vals, rest = vals[:n], vals[n:]
+    if student_check is not None:
+        m = student_check.numel()
+        rest, hi, lo = rest[:len(rest) - 2 * m], rest[len(rest) - 2 * m:len(rest) - m], rest[len(rest) - m:]
+        scvals = [(int(h) << 32) | int(l) for h, l in zip(hi, lo)]
+        student_check.zero_()
     gvals, rest = (rest[:3], rest[3:]) if guard is not None else (None, rest)
     svals = None
     if stats is not None:
@@ -166,12 +198,17 @@ def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check
     if teacher_check is not None:
         rest, cvals = rest[:len(rest) - teacher_check.numel()], [int(v) for v in rest[len(rest) - teacher_check.numel():]]
         teacher_check.zero_()
+    tpair = None
+    if tensor_stats is not None:
+        T, W = table.shape
+        tvals = [rest[i * W:(i + 1) * W] for i in range(T)]
+        bvals = [int(v) for v in rest[T * W:]] if blame is not None else None
+        tpair = (tvals, bvals)
+    if student_check is not None:
+        return vals, gvals, svals, tpair, cvals, scvals
     if tensor_stats is None:
         return (vals, gvals, svals) if teacher_check is None else (vals, gvals, svals, None, cvals)
-    T, W = table.shape
-    tvals = [rest[i * W:(i + 1) * W] for i in range(T)]
-    bvals = [int(v) for v in rest[T * W:]] if blame is not None else None
-    return (vals, gvals, svals, (tvals, bvals)) if teacher_check is None else (vals, gvals, svals, (tvals, bvals), cvals)
+    return (vals, gvals, svals, tpair) if teacher_check is None else (vals, gvals, svals, tpair, cvals)
 
 
 def next_batch(it, new_iter, pos):
@@ -265,8 +302,12 @@ def main(args):
                     (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
             guard, stats = trainer.guard_state, trainer.label_stats_state         # None: no gradient guard / no --label_stats, the line as ever
-            tvals = cvals = None
-            if trainer.teacher_check_state is not None:                           # (--teacher_check_iters: its counters in the same transfer)
+            tvals = cvals = scvals = None
+            if trainer.student_check_state is not None:                           # (--student_check_iters: its counters in the same transfer)
+                vals, gvals, svals, tvals, cvals, scvals = read_interval(
+                    acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state) if tstats_on else None,
+                    teacher_check=trainer.teacher_check_state, student_check=trainer.student_check_state)
+            elif trainer.teacher_check_state is not None:                           # (--teacher_check_iters: its counters in the same transfer)
                 vals, gvals, svals, tvals, cvals = read_interval(
                     acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state) if tstats_on else None,
                     teacher_check=trainer.teacher_check_state)
@@ -300,6 +341,11 @@ def main(args):
                     if csummary["checks"] > 0:                                    # (an interval without a check step: the line as ever)
                         line += teacher_check_line(csummary, targs.teacher_check_mode)
                         append_teacher_check(output_dir, csummary, n_iter + 1, targs.teacher_precision, targs.teacher_check_mode)
+                if scvals is not None:
+                    ssummary = seg_helper.student_check_summary(scvals, args.num_classes)
+                    if ssummary["checks"] > 0:                                    # (an interval without a check step: the line as ever)
+                        line += student_check_line(ssummary, targs.student_check_mode)
+                        append_student_check(output_dir, ssummary, n_iter + 1, "bf16", targs.student_check_mode)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,

@@ -39,7 +39,7 @@ def default_args(dataset="VOC12", **over):
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
              clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
-             teacher_check_iters=0, teacher_check_mode="auto")
+             teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32")
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -47,6 +47,9 @@ def default_args(dataset="VOC12", **over):
     a.update(over)
     a["dataset"] = dataset
     return SimpleNamespace(**a)
+
+
+NOGRAD_PRECISIONS = ("bf16", "fp16", "fp32", "bf16x3", "fp16x3", "fp16c8", "fp16c4")     # VITNetwork.set_nograd_precision's base names
 
 
 def wrap_ddp(module, device):
@@ -254,6 +257,27 @@ class CoSATrainer:
             self.extra_state = dict(getattr(self, "extra_state", {}), **{"teacher_check.counters": self.teacher_check_state})
             if on:
                 self._build_check_model(cm)
+        # the student-forward monitor: off (None) unless --student_check_iters N > 0.  Every N-th optimizer step runs the
+        # student's weights of that step through `model_SK`, a network of its own on --student_check_mode operands (fp32: the masters
+        # themselves on the fp32 family), over the batch the step trained on, and scores the training forward against that pass.  The
+        # counters are state of the run (`student_check.counters` of extra_state); model_SK is not: every check overwrites it
+        self.student_check_state = self.model_SK = self._scheck_ctx = self.student_check_last = None
+        self._scheck_iters = int(getattr(args, "student_check_iters", 0) or 0)
+        if self._scheck_iters < 0:
+            raise ValueError(f"student_check_iters {self._scheck_iters!r}: 0 (off) or a positive number of optimizer steps")
+        if self._scheck_iters > 0:
+            sm = str(getattr(args, "student_check_mode", "fp32"))
+            args.student_check_mode = sm
+            if sm.partition("-")[0] not in NOGRAD_PRECISIONS:
+                raise ValueError(f"student_check_mode {sm!r}: one of {', '.join(NOGRAD_PRECISIONS)} (VITNetwork.set_nograd_precision's names)")
+            self.student.check_nograd_precision(sm)       # (on the host too: a mode the encoder is not built for fails here, not in a step)
+            if device.type == "cuda" and not on:
+                raise NotImplementedError("student_check_iters: the check scores the 16-bit training forward; this trainer's compute dtype "
+                                          "has none")
+            self.student_check_state = seg_helper.new_student_check(args.num_classes, device)
+            self.extra_state = dict(getattr(self, "extra_state", {}), **{"student_check.counters": self.student_check_state})
+            if on:
+                self._build_student_check_model(sm)
         if on:
             for sh in (self._teacher_shadows, self._student_shadows):
                 if sh is not None:
@@ -337,10 +361,10 @@ class CoSATrainer:
             st.begin_eager()
         return self._s_out
 
-    def _build_check_model(self, mode):
-        """model_CK: a network of its own (parameters, 16-bit shadows, operand and CAM buffers: nn_ops._owner_of is keyed by parameter), built
-        without drawing from any RNG the run reads: the network is initialised on the host and the host generators' states are put back.
-        Its initial weights never matter -- every check begins by copying the teacher's"""
+    def _new_check_network(self, mode):
+        """a network of its own (parameters, 16-bit shadows, operand and CAM buffers: nn_ops._owner_of is keyed by parameter) on `mode`
+        operands, built without drawing from any RNG the run reads: it is initialised on the host and the host generators' states are put
+        back.  Its initial weights never matter -- every check begins by copying the checked network's"""
         import random
         states = torch.get_rng_state(), np.random.get_state(), random.getstate()
         try:
@@ -353,12 +377,79 @@ class CoSATrainer:
         for p in ck.parameters():
             p.requires_grad = False
         ck.set_nograd_precision(mode)
+        return ck
+
+    def _build_check_model(self, mode):
+        """model_CK, the --teacher_check network (_new_check_network)"""
+        ck = self._new_check_network(mode)
         self.model_CK = ck
         self._ck_params = list(ck.parameters())
         assert len(self._ck_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ck_params, self._ema_pairs[0]))
         # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads model_CK's fp32 parameters)
         self._ck_shadows = nn_ops.ensure_shadows(ck, ck.compute_dtype) if ck.compute_dtype != torch.float32 else None
         self._ck_buffers = {}                                                 # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
+
+    def _build_student_check_model(self, mode):
+        """model_SK, the --student_check network (_new_check_network): not shared with model_CK -- both monitors may be on in one run"""
+        sk = self._new_check_network(mode)
+        self.model_SK = sk
+        self._sk_params = list(sk.parameters())
+        assert len(self._sk_params) == len(self._ema_pairs[1]) and all(a.shape == b.shape for a, b in zip(self._sk_params, self._ema_pairs[1]))
+        # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads model_SK's fp32 parameters)
+        self._sk_shadows = nn_ops.ensure_shadows(sk, sk.compute_dtype) if sk.compute_dtype != torch.float32 else None
+
+    def _is_student_check_step(self, n_iter):
+        """_is_check_step's rule for --student_check_iters"""
+        return self.model_SK is not None and (n_iter + 1) % self._scheck_iters == 0 and self._micro_k == self._accum_steps - 1
+
+    @torch.no_grad()
+    def _student_check(self):
+        """One check, eagerly on the current stream AFTER the step's backward and BEFORE its optimizer update: the
+        student's fp32 masters of this step (the weights the training forward read through its shadows) into model_SK, its full no-grad
+        forward over the step's strong images, the step's four losses on that pass's outputs against the step's own label maps, cam-loss
+        targets, labels and blend weights (forward kernels only; the regulariser, whose forward owns per-step lattice state, is not
+        re-evaluated), and the reduction.  No host sync, no RNG, and nothing the training path reads is written: model_SK's weights, shadows
+        and operand buffers are its own, the library workspaces it needs are slots of their own (_C.workspace_scope), and the backward
+        that read the training forward's workspaces has already run.  `student_check_last` keeps what went into the reduction."""
+        ctx, self._scheck_ctx = self._scheck_ctx, None
+        args = self.args
+        torch._foreach_copy_(self._sk_params, self._ema_pairs[1])                  # (the unwrapped student's parameters, not DDP's)
+        held = nn_ops.stamps, nn_ops.gemm_stamps           # (a benchmark's kernel-span slots are the training kernels')
+        nn_ops.stamps = nn_ops.gemm_stamps = None
+        lab, simg, (mask, mask_aux) = ctx["cls_label"], ctx["simg"], ctx["masks"]
+        try:
+            with _C.workspace_scope("student_check"):
+                cls_b, clsaux_b, _feat, seg_b, cam_b, aux_b = self.model_SK(simg, cam_only=False, detach='none')
+                cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
+                l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
+                l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
+                if self.fused_losses:
+                    l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
+                                                             aux_alpha=args.aux_cam2seg_alpha)
+                    cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
+                else:
+                    up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
+                    l_seg = seg_helper.seg_loss(up, mask, fg_alpha=args.segfg_alpha)
+                    if mask_aux is not None:
+                        l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
+                    cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
+                l_cam = cam_l(cam_b)
+                if args.aux_seg2cam:
+                    l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
+                loss_b = torch.stack([t.reshape(()).float() for t in (l_cls, l_cls_aux, l_seg, l_cam)])
+        finally:
+            nn_ops.stamps, nn_ops.gemm_stamps = held
+        a, loss_a = ctx["outputs"], torch.stack([t.reshape(()).float() for t in ctx["losses"]])
+        b = dict(seg=seg_b, cam=cam_b, cam_aux=aux_b, cls=cls_b, cls_aux=clsaux_b)
+        seg_helper.student_check(*[(a[k], b[k]) for k in seg_helper.STUDENT_CHECK_TENSORS], (loss_a, loss_b), lab, self.student_check_state)
+        self.student_check_last = dict(a=a, b=b, loss_a=loss_a, loss_b=loss_b, cls_label=lab)
+
+    def student_check(self):
+        """the summary (seg_helper.student_check_summary) of the checks accumulated since the counters were last zeroed (synchronises: for
+        tests and the log interval); None when --student_check_iters is 0"""
+        if self.student_check_state is None:
+            return None
+        return seg_helper.student_check_summary(self.student_check_state, self.args.num_classes)
 
     def _is_check_step(self, n_iter):
         """the step that closes every N-th optimizer iteration; with --accum_steps its last micro-batch"""
@@ -426,6 +517,7 @@ class CoSATrainer:
         self._join_teacher()
         cls_loss = seg_helper.multilabel_soft_margin(cls_final, cls_label)          # main.py:127-128, one kernel each
         cls_loss_aux = seg_helper.multilabel_soft_margin(cls_aux, cls_label)
+        seg_lr = seg_pred                                                          # (the low-res logits: --student_check scores them)
         with torch.no_grad():
             if args.use_cammix:
                 cam_ps = (cam_ps + cam_aux_ps) / 2
@@ -471,7 +563,7 @@ class CoSATrainer:
                 tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:], args.seg_softmaxtemp,
                                                   after_softmax=args.after_softmax)
             cam_loss = seg_helper.cam_loss_from_targets(cam_pred, tgt)
-            check_tgt = tgt
+            check_tgt = check_tgt_s = tgt
             if args.aux_seg2cam:
                 cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + \
                     args.aux_seg2cam_alpha * seg_helper.cam_loss_from_targets(cam_aux_pred, tgt)
@@ -480,12 +572,19 @@ class CoSATrainer:
                 valid_seg_ps = seg_helper.seg_refine_by_label(seg_ps, cls_label, softmaxtemp=args.seg_softmaxtemp,
                                                               after_softmax=args.after_softmax)
             cam_loss = seg_helper.cam_loss(cam_pred, valid_seg_ps)
+            check_tgt_s = valid_seg_ps
             if args.aux_seg2cam:
                 cam_aux_loss = seg_helper.cam_loss(cam_aux_pred, valid_seg_ps)
                 cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + args.aux_seg2cam_alpha * cam_aux_loss
         if self.model_CK is not None and self._is_check_step(n_iter):
             self._teacher_check(wimg, img_denorm, img_box, cls_label, (cam_ps, cam_aux_ps), (refine_mask_label, refine_mask_label_aux),
                                 ((threhigh, threlow), (auxthrehigh, auxthrelow)), check_tgt)
+        if self._is_student_check_step(n_iter):
+            # what the check after this step's backward (_student_check) reads: detached references, nothing is copied or computed here
+            self._scheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux), tgt=check_tgt_s,
+                                    outputs=dict(seg=seg_lr.detach(), cam=cam_pred.detach(), cam_aux=cam_aux_pred.detach(),
+                                                 cls=cls_final.detach(), cls_aux=cls_aux.detach()),
+                                    losses=tuple(t.detach() for t in (cls_loss, cls_loss_aux, seg_loss, cam_loss)))
         # main.py:230-236: the weighted sum of the five losses (warm-up: classification losses only) as one dot product
         wkey = n_iter <= args.warmup_iters
         wvec = self._loss_weights.get(wkey)
@@ -524,6 +623,8 @@ class CoSATrainer:
         if self.device.type == "cuda" and self._student_shadows is not None:
             nn_ops.wgrad_arena_begin(self.device)        # one clear for all weight gradients of this step (they are consumed below)
         loss.backward()
+        if self._scheck_ctx is not None:                 # (--student_check_iters: after the backward, before the weights move)
+            self._student_check()
         return self._apply_gradients(logs)
 
     def _apply_gradients(self, logs):
@@ -570,6 +671,8 @@ class CoSATrainer:
                     if a is not None:
                         p.grad.copy_(a)
             self._accum = None
+        if self._scheck_ctx is not None:                 # (--student_check_iters: the closing micro-batch, before the weights move)
+            self._student_check()
         return self._apply_gradients(logs)
 
     def guard_counters(self):

@@ -791,6 +791,50 @@ int cosa_teacher_check(const float *camA, const float *camB, const float *auxA, 
                        const float *cls_label, const int32_t *boxes, int B, int C, int K, int S, int h, int w, int ignore_index,
                        float bar, unsigned long long *counters, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The --student_check monitor: the student's training forward (a) against a second forward of the
+ * same weights on the same images (b, the fp32 family by default), scored by one reduction, accumulated on the device in a
+ * vector of uint64 counters (passed as long long: the values stay below 2^63).
+ * cosa_student_check_counters(K): the number of elements, COSA_STUDENT_CHECK_HEAD + 2K; 0 for K outside 2..256.
+ * The vector, in elements:
+ *   0 checks (calls accumulated);  1 flags (sticky OR: bit t -- tensor t held a non-finite element or a term outside its
+ *   fixed-point range, which then contributed to no sum; bit 8 + j -- the same for loss term j);
+ *   2 + 7 t + f, tensors t = seg, cam, cam_aux, cls, cls_aux, fields f = elements compared, non-finite elements of a, of
+ *   b, the largest finite |a - b| and the largest finite |b| as fp32 bit patterns (non-negative floats order as unsigned
+ *   integers), sum (a - b)^2 with COSA_STUDENT_CHECK_D2_FRAC fractional bits, sum b^2 with COSA_STUDENT_CHECK_B2_FRAC;
+ *   37 cells compared;  38 cells whose seg argmax differs;  39..42 those cells binned by the b pass's top-1 minus top-2
+ *   margin: < 1e-3, < 1e-2, < 1e-1, the rest (the edges as fp32; a NaN margin, inf - inf, falls in the last bin);
+ *   43, 44 columns of cls / cls_aux with sign(a) != sign(b) over all K-1 columns (the sign of NaN is 0);  45 columns seen
+ *   per matrix (B (K-1) a call);
+ *   46 + 4 j + f, loss terms j = cls, cls_aux, seg, cam, fields f = sum |a - b| and sum |b| with
+ *   COSA_STUDENT_CHECK_LOSS_FRAC fractional bits, the largest |a - b| as bits, checks counted for the term;
+ *   62 .. 62 + K: cells the b pass labels class k;  62 + K .. 62 + 2K: those among them where the a pass agrees.
+ * Which elements: seg channels 0 (background) and 1 + c for every class c with cls_label[b][c] != 0; the CAM planes and the
+ *   cls columns of those classes.  The argmax of a cell runs over the same seg channels (seg_validation's rule), NaN read as
+ *   -inf, the lowest channel index among equals.
+ * Fixed point: a term is computed in fp32 with round-to-nearest operations (d = a - b, d * d, b * b, |d|), multiplied by
+ *   2^FRAC in double (exact) and rounded to an integer half-to-even.  It is added only when both elements are finite and the
+ *   term is below 2^INT; FRAC + INT = 42, so 2^22 terms fit whatever their values.  (a - b)^2: 2^-32 resolves |a - b| down
+ *   to 2e-5, the range reaches |a - b| < 32; b^2: logits and CAM scores of |b| < 2048 at a resolution of 1e-6; the losses:
+ *   below 1024 at 2e-10.
+ * Every figure is an integer sum, maximum or OR: the same counters in any order of arrival, on every run.  One launch, no
+ *   workspace.  Envelope: every pointer non-NULL, counters 8-byte aligned, B, h, w > 0, 2 <= K <= 256, B K h w < 2^31;
+ *   anything else is COSA_EINVAL and nothing is launched.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_STUDENT_CHECK_MAX_K 256
+#define COSA_STUDENT_CHECK_HEAD 62
+#define COSA_STUDENT_CHECK_D2_FRAC 32
+#define COSA_STUDENT_CHECK_D2_INT 10
+#define COSA_STUDENT_CHECK_B2_FRAC 20
+#define COSA_STUDENT_CHECK_B2_INT 22
+#define COSA_STUDENT_CHECK_LOSS_FRAC 32
+#define COSA_STUDENT_CHECK_LOSS_INT 10
+size_t cosa_student_check_counters(int K);
+int cosa_student_check(const float *seg_a, const float *seg_b, const float *cam_a, const float *cam_b, const float *aux_a,
+                       const float *aux_b, const float *cls_a, const float *cls_b, const float *clsaux_a, const float *clsaux_b,
+                       const float *loss_a, const float *loss_b, const float *cls_label, long long *counters, int B, int K, int h,
+                       int w, void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
