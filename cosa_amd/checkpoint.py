@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _C
+from .monitors import BY_NAME, MONITORS
 
 MAGIC = b"COSASTAT"
 VERSION = 1
@@ -303,11 +304,7 @@ class TrainState:
     """Every tensor that defines the future of `trainer`'s run, by stable name, and its arena."""
 
     TRACKERS = ("ema_lowthre", "ema_highthre", "ema_auxlowthre", "ema_auxhighthre")
-    GUARD = "guard.state"
-    LABEL_STATS = "aux.label_stats.counters"         # CoSATrainer.extra_state["label_stats.counters"]
-    TENSOR_BLAME = "aux.tensor_stats.blame"          # CoSATrainer.tensor_stats_state (--tensor_stats behind a gradient guard)
-    TEACHER_CHECK = "aux.teacher_check.counters"     # CoSATrainer.extra_state["teacher_check.counters"] (--teacher_check_iters N > 0)
-    STUDENT_CHECK = "aux.student_check.counters"     # CoSATrainer.extra_state["student_check.counters"] (--student_check_iters N > 0)
+    GUARD = BY_NAME["guard"].state_name              # (the other optional entries: the `state_name`s of cosa_amd/monitors.py's table)
 
     def __init__(self, trainer, part="all"):
         """part: "all" (a world of one), or under a process group "shared" (networks and moments: identical on every rank, written by
@@ -352,7 +349,7 @@ class TrainState:
         if part != "local" and getattr(tr, "tensor_stats_state", None) is not None:
             # --tensor_stats' blame counters: in the shared part, because the gradients they are derived from are identical on every rank
             # behind the all-reduce.  Optional like the guard record that follows (_reconcile_optional)
-            entries.append((self.TENSOR_BLAME, tr.tensor_stats_state))
+            entries.append((BY_NAME["tensor_stats"].state_name, tr.tensor_stats_state))
         if part != "local" and getattr(tr, "guard_state", None) is not None:
             # the gradient guard's record (its counters; identical on every rank).  LAST, so that a file differs from one written without a
             # guard by its tail only: load() reconciles the two (_reconcile_optional), and with the guard off nothing here changes
@@ -535,27 +532,11 @@ class TrainState:
 
     def _optional_notes(self):
         """{name of an optional tensor: (note when the file has it and this run does not, note when only this run has it)}"""
-        return {
-            self.GUARD: ("the file holds a gradient guard's counters and this run has no guard (--clip_grad_norm 0, --skip_nonfinite "
-                         "false): the entry is ignored",
-                         "written without a gradient guard: this run's guard counters start at zero"),
-            self.LABEL_STATS: ("the file holds pseudo-label statistics and this run does not collect them (--label_stats false): the entry "
-                               "is ignored",
-                               "written without pseudo-label statistics: this run's label counters start at zero"),
-            self.TENSOR_BLAME: ("the file holds per-tensor blame counters and this run does not keep them (--tensor_stats false, or no "
-                                "gradient guard): the entry is ignored",
-                                "written without per-tensor blame counters: this run's blame counters start at zero"),
-            self.TEACHER_CHECK: ("the file holds a teacher check's counters and this run makes no checks (--teacher_check_iters 0): the entry "
-                                 "is ignored",
-                                 "written without a teacher check: this run's check counters start at zero"),
-            self.STUDENT_CHECK: ("the file holds a student check's counters and this run makes no checks (--student_check_iters 0): the entry "
-                                 "is ignored",
-                                 "written without a student check: this run's check counters start at zero"),
-        }
+        return {m.state_name: m.notes for m in MONITORS}
 
     def _reconcile_optional(self, header, a_len, path):
-        """Five tensors are optional: the guard record (the arena's last), --tensor_stats' blame counters (in front of it), and
-        --label_stats', --teacher_check_iters' and --student_check_iters' counters (among the launcher's tensors).  ->
+        """The monitors' tensors are optional (cosa_amd/monitors.py's `state_name`s): the guard record (the arena's last), --tensor_stats'
+        blame counters (in front of it), and the counters the monitors keep in `extra_state` (among the launcher's tensors).  ->
         (header as this run would have written it, its arena bytes, [(file offset, arena offset, bytes)] to read, [(arena offset,
         bytes)] to zero).  A file without one of them loads into a run that has it with the tensor zero (counters start at zero); a
         file with one loads into a run without it, the entry ignored.  Each with a note.  Any other difference is left as it is, for

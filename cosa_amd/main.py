@@ -9,7 +9,6 @@ loss_dataframe.pt).  What differs is where the work runs: one process per GPU ov
 input pipeline, the fused training step (CoSATrainer.step: no per-iteration host sync -- the losses and the classification AP of an
 iteration stay on the device and are read back once per `log_iters`), device-resident evaluation.  `--usepar true` is live."""
 import datetime
-import json
 import os
 import random
 import sys
@@ -22,12 +21,13 @@ import torch.distributed as dist
 
 from . import args as cosa_args
 from . import checkpoint
+from . import monitors
 from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
-from .train_step import CoSATrainer, default_args
-from .utils import seg_helper, torch_helper
+from .train_step import CoSATrainer, check_iters, default_args
+from .utils import torch_helper
 
 
 def init_distributed_mode(args):
@@ -71,10 +71,8 @@ def check_supported(args):
     get_backbone(args.backbone)                                   # NotImplementedError listing the built encoders
     if getattr(args, "accum_steps", 1) < 1:
         raise ValueError(f"--accum_steps {args.accum_steps}: a positive number of micro-batches per optimizer step")
-    if getattr(args, "teacher_check_iters", 0) < 0:
-        raise ValueError(f"--teacher_check_iters {args.teacher_check_iters}: 0 (off) or a positive number of optimizer steps")
-    if getattr(args, "student_check_iters", 0) < 0:
-        raise ValueError(f"--student_check_iters {args.student_check_iters}: 0 (off) or a positive number of optimizer steps")
+    for which in ("teacher", "student"):
+        check_iters(args, which, flag="--")
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
@@ -84,131 +82,22 @@ def check_supported(args):
         print("note:", n, flush=True)
 
 
-def label_stats_line(summary):
-    """what --label_stats adds to the interval's log line"""
-    return " ignore: %.3f, fg: %.3f, aux_agree: %.3f, student_miou: %.3f, teacher_nonfinite: %d" % (
-        summary["ignore_frac"], summary["fg_frac"], summary["aux_agree"], summary["student_miou"], summary["teacher_nonfinite"])
-
-
-def label_stats_record(summary, n_iter):
-    """one line of <output_dir>/label_stats.jsonl: the full summary of an interval, per-class lists included"""
-    return json.dumps(dict(summary, iters=int(n_iter)))
-
-
-def append_label_stats(output_dir, summary, n_iter):
-    with (Path(output_dir) / "label_stats.jsonl").open("a") as f:
-        f.write(label_stats_record(summary, n_iter) + "\n")
-
-
-def tensor_stats_line(summary):
-    """what --tensor_stats adds to the interval's log line: the global relative EMA gap, and the blamed / non-finite tensor's name or -"""
-    return " ema_gap: %.3e, worst: %s" % (summary["global"]["ema_gap_rel"], summary["worst"] if summary["worst"] is not None else "-")
-
-
-def tensor_stats_record(summary, n_iter):
-    """one line of <output_dir>/tensor_stats.jsonl: the full summary of an interval's sample, every tensor included"""
-    return json.dumps(dict(summary, iters=int(n_iter)))
-
-
-def append_tensor_stats(output_dir, summary, n_iter):
-    with (Path(output_dir) / "tensor_stats.jsonl").open("a") as f:
-        f.write(tensor_stats_record(summary, n_iter) + "\n")
-
-
-def teacher_check_line(summary, check_mode):
-    """what --teacher_check_iters adds to the log line of an interval that held a check: the worst figure over the map sets, the planes
-    over the literal bar, the lowest agreement and mIoU over the label pairs"""
-    w = seg_helper.teacher_check_worst(summary)
-    return " tcheck[%s]: worst %.1e, over %d/%d, agree %.5f, miou %.5f" % (check_mode, w["worst"], w["over"], w["planes"], w["agree"], w["miou"])
-
-
-def teacher_check_record(summary, n_iter, mode, check_mode):
-    """one line of <output_dir>/teacher_check.jsonl: the full summary of an interval's checks and the two operand modes compared"""
-    return json.dumps(dict(summary, iters=int(n_iter), mode=mode, check_mode=check_mode))
-
-
-def append_teacher_check(output_dir, summary, n_iter, mode, check_mode):
-    with (Path(output_dir) / "teacher_check.jsonl").open("a") as f:
-        f.write(teacher_check_record(summary, n_iter, mode, check_mode) + "\n")
-
-
-def student_check_line(summary, check_mode):
-    """what --student_check_iters adds to the log line of an interval that held a check, exactly:
-    ` scheck[MODE]: seg rel 1.2e-03, agree 0.99987, flips>=1e-1 0, loss rel 3.1e-04` -- the seg logits' relative L2 difference, the share of
-    cells with the same argmax, the differing cells whose check-pass margin is at least 1e-1 (real flips, not near-ties), and the largest
-    relative difference over the four loss terms"""
-    return " scheck[%s]: seg rel %.1e, agree %.5f, flips>=1e-1 %d, loss rel %.1e" % (
-        check_mode, summary["seg"]["rel_l2"], summary["seg_agree"], summary["flip_hist"][3], summary["loss_rel"])
-
-
-def student_check_record(summary, n_iter, mode, check_mode):
-    """one line of <output_dir>/student_check.jsonl: the full summary of an interval's checks, the training forward's operand mode (`mode`)
-    and the check pass's (`check_mode`)"""
-    return json.dumps(dict(summary, iters=int(n_iter), mode=mode, check_mode=check_mode))
-
-
-def append_student_check(output_dir, summary, n_iter, mode, check_mode):
-    with (Path(output_dir) / "student_check.jsonl").open("a") as f:
-        f.write(student_check_record(summary, n_iter, mode, check_mode) + "\n")
-
-
-def read_interval(acc, log_iters, guard, stats, tensor_stats=None, teacher_check=None, student_check=None):
-    """The log interval's ONE host sync: -> (means of the running sums `acc`, [grad_norm, skipped, clipped] of the guard record or None,
-    the label counters as ints or None).  The guard's own tensor and the label counters ride along in the same transfer (`acc` keeps
-    its length; counts are exact in a double: an interval's stay far below 2^53).  `acc` and the label counters are an interval's:
-    both are zeroed on the device afterwards; the guard's counters are the run's and stay.
-    tensor_stats: (--tensor_stats' table, its blame counters or None); they ride along too and a fourth value is returned, (the table's
-    values as [T][6] floats, the blame counters as ints or None).  The table is the sample of the interval's last step and is not
-    accumulated; the blame counters are the run's: neither is zeroed.
-    teacher_check: --teacher_check_iters' counters; they ride along too, are an interval's (zeroed afterwards), and FIVE values are
-    returned: the three, the tensor_stats pair or None, and the counters as ints.
-    student_check: --student_check_iters' counters; they ride along too, are an interval's (zeroed afterwards), and SIX values are returned:
-    the five (None for what is off) and these counters as ints.  Their fixed-point sums may pass 2^53, so each travels as two doubles,
-    its high and its low 32 bits."""
-    parts = [acc / log_iters]
-    if guard is not None:
-        parts += [torch_helper.guard_norm(guard).double().reshape(1), guard[3:5].double()]
-    if stats is not None:
-        parts.append(stats.double())
-    if tensor_stats is not None:
-        table, blame = tensor_stats
-        parts.append(torch_helper.tensor_stats_values(table).reshape(-1))
-        if blame is not None:
-            parts.append(blame.double())
-    if teacher_check is not None:
-        parts.append(teacher_check.double())               # (the largest value, a bit pattern below 2^32, is exact in a double too)
-    if student_check is not None:
-        parts += [(student_check >> 32).double(), (student_check & 0xffffffff).double()]
+def read_interval(acc, log_iters, monitors):
+    """The log interval's ONE host sync: -> (means of the running sums `acc`, {monitor name: its host values}).  monitors: [(Monitor, its
+    tensors)] of the ones that are on (monitors.active).  What each packs rides along in the same transfer, in the list's order, and each
+    unpacks its own slice front to back (`acc` keeps its length); then `acc` and what a monitor holds per interval are zeroed on the device,
+    what is the run's stays (cosa_amd/monitors.py)."""
+    packed = [[v.reshape(-1) for v in m.pack(t)] for m, t in monitors]
+    parts = [acc / log_iters] + [v for p in packed for v in p]
     vals = (torch.cat(parts) if len(parts) > 1 else parts[0]).tolist()
-    n = acc.numel()
-    vals, rest = vals[:n], vals[n:]
-    if student_check is not None:
-        m = student_check.numel()
-        rest, hi, lo = rest[:len(rest) - 2 * m], rest[len(rest) - 2 * m:len(rest) - m], rest[len(rest) - m:]
-        scvals = [(int(h) << 32) | int(l) for h, l in zip(hi, lo)]
-        student_check.zero_()
-    gvals, rest = (rest[:3], rest[3:]) if guard is not None else (None, rest)
-    svals = None
-    if stats is not None:
-        svals, rest = [int(v) for v in rest[:stats.numel()]], rest[stats.numel():]
+    host, at = {}, acc.numel()
     acc.zero_()
-    if stats is not None:
-        stats.zero_()
-    cvals = None
-    if teacher_check is not None:
-        rest, cvals = rest[:len(rest) - teacher_check.numel()], [int(v) for v in rest[len(rest) - teacher_check.numel():]]
-        teacher_check.zero_()
-    tpair = None
-    if tensor_stats is not None:
-        T, W = table.shape
-        tvals = [rest[i * W:(i + 1) * W] for i in range(T)]
-        bvals = [int(v) for v in rest[T * W:]] if blame is not None else None
-        tpair = (tvals, bvals)
-    if student_check is not None:
-        return vals, gvals, svals, tpair, cvals, scvals
-    if tensor_stats is None:
-        return (vals, gvals, svals) if teacher_check is None else (vals, gvals, svals, None, cvals)
-    return (vals, gvals, svals, tpair) if teacher_check is None else (vals, gvals, svals, tpair, cvals)
+    for (m, t), p in zip(monitors, packed):
+        n = sum(v.numel() for v in p)
+        host[m.name] = m.unpack(t, vals[at:at + n])
+        m.zero(t)
+        at += n
+    return vals[:acc.numel()], host
 
 
 def next_batch(it, new_iter, pos):
@@ -261,7 +150,7 @@ def main(args):
     keys = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
     acc = torch.zeros(len(keys), device=device, dtype=torch.float64)           # running sums of the interval, on the device
     # ... and part of a state file: saved and restored in place, no sync (next to what the trainer keeps there: --label_stats' counters)
-    trainer.extra_state = dict(getattr(trainer, "extra_state", {}), **{"launcher.acc": acc})
+    trainer._add_extra_state("launcher.acc", acc)
     resume = args.resume
     if resume == "auto":
         resume = checkpoint.newest_state(output_dir)                                # none: a fresh start
@@ -301,20 +190,7 @@ def main(args):
                     logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
                     (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
         if (n_iter + 1) % args.log_iters == 0:
-            guard, stats = trainer.guard_state, trainer.label_stats_state         # None: no gradient guard / no --label_stats, the line as ever
-            tvals = cvals = scvals = None
-            if trainer.student_check_state is not None:                           # (--student_check_iters: its counters in the same transfer)
-                vals, gvals, svals, tvals, cvals, scvals = read_interval(
-                    acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state) if tstats_on else None,
-                    teacher_check=trainer.teacher_check_state, student_check=trainer.student_check_state)
-            elif trainer.teacher_check_state is not None:                           # (--teacher_check_iters: its counters in the same transfer)
-                vals, gvals, svals, tvals, cvals = read_interval(
-                    acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state) if tstats_on else None,
-                    teacher_check=trainer.teacher_check_state)
-            elif tstats_on:
-                vals, gvals, svals, tvals = read_interval(acc, args.log_iters * n_micro, guard, stats, (trainer.tensor_stats_table, trainer.tensor_stats_state))
-            else:
-                vals, gvals, svals = read_interval(acc, args.log_iters * n_micro, guard, stats)   # the one host sync of the interval
+            vals, host = read_interval(acc, args.log_iters * n_micro, monitors.active(trainer))   # the one host sync of the interval
             now = time.time()
             itertime, tick = (now - tick) / args.log_iters, now
             delta = datetime.datetime.now().replace(microsecond=0) - time0
@@ -326,26 +202,13 @@ def main(args):
                 line = ("Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  "
                         "cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, reg_loss: %.4f ..."
                         % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
-                if guard is not None:
-                    line += " grad_norm: %.4f, skipped: %d, clipped: %d" % (gvals[0], int(gvals[1]), int(gvals[2]))
-                if stats is not None:
-                    summary = seg_helper.label_stats_summary(svals, args.num_classes)
-                    line += label_stats_line(summary)
-                    append_label_stats(output_dir, summary, n_iter + 1)
-                if tvals is not None:
-                    tsummary = trainer.tensor_stats(tvals)
-                    line += tensor_stats_line(tsummary)
-                    append_tensor_stats(output_dir, tsummary, n_iter + 1)
-                if cvals is not None:
-                    csummary = seg_helper.teacher_check_summary(cvals, args.num_classes)
-                    if csummary["checks"] > 0:                                    # (an interval without a check step: the line as ever)
-                        line += teacher_check_line(csummary, targs.teacher_check_mode)
-                        append_teacher_check(output_dir, csummary, n_iter + 1, targs.teacher_precision, targs.teacher_check_mode)
-                if scvals is not None:
-                    ssummary = seg_helper.student_check_summary(scvals, args.num_classes)
-                    if ssummary["checks"] > 0:                                    # (an interval without a check step: the line as ever)
-                        line += student_check_line(ssummary, targs.student_check_mode)
-                        append_student_check(output_dir, ssummary, n_iter + 1, "bf16", targs.student_check_mode)
+                for m in monitors.MONITORS:                                             # (a monitor that is off: the line as ever)
+                    if m.name in host:
+                        summary = host[m.name] if m.summary is None else m.summary(trainer, args, host[m.name])
+                        if m.gate(summary):
+                            line += m.line(summary, targs)
+                            if m.record_extra is not None:
+                                monitors.append_monitor(output_dir, m, summary, n_iter + 1, targs)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,

@@ -10,6 +10,7 @@ differences, none of which change the maths:
   * the per-iteration barrier (main.py:385) is dropped: the gradient all-reduce already orders ranks
   * encoder.head (never used, vit.py:257,325) is frozen so DDP needs no find_unused_parameters
 """
+import contextlib
 import math
 import os
 from types import SimpleNamespace
@@ -88,6 +89,15 @@ def resolve_teacher_check_mode(mode, teacher_precision):
     if mode != "auto":
         return mode
     return "bf16x3" if teacher_precision == "fp16x3" else "fp16x3"
+
+
+def check_iters(args, which, flag=""):
+    """--<which>_check_iters of `args` (which: "teacher" / "student") as an int; a negative one is refused, here for the trainer and, with
+    flag="--", for the launcher's check_supported"""
+    n = int(getattr(args, which + "_check_iters", 0) or 0)
+    if n < 0:
+        raise ValueError(f"{flag}{which}_check_iters {n!r}: 0 (off) or a positive number of optimizer steps")
+    return n
 
 
 @torch.no_grad()
@@ -237,16 +247,14 @@ class CoSATrainer:
         if bool(getattr(args, "label_stats", False)):
             self.label_stats_state = seg_helper.new_label_stats(args.num_classes, device)
             self._step_scale = torch.ones(1, device=device, dtype=torch.float32)
-            self.extra_state = {"label_stats.counters": self.label_stats_state}
+            self._add_extra_state("label_stats.counters", self.label_stats_state)
         # the teacher-precision monitor: off (None) unless --teacher_check_iters N > 0.  Every N-th optimizer step runs
         # the teacher's pass once more on `model_CK`, a third network on --teacher_check_mode operands that takes the teacher's weights at
         # that moment, and scores the two passes against each other.  The counters are state of the run (`teacher_check.counters` of
         # extra_state); model_CK is not: every check overwrites it
         self.teacher_check_state = self.model_CK = None
-        self._check_iters = int(getattr(args, "teacher_check_iters", 0) or 0)
-        if self._check_iters < 0:
-            raise ValueError(f"teacher_check_iters {self._check_iters!r}: 0 (off) or a positive number of optimizer steps")
-        if self._check_iters > 0:
+        self._check_iters = {which: check_iters(args, which) for which in ("teacher", "student")}
+        if self._check_iters["teacher"] > 0:
             cm = resolve_teacher_check_mode(getattr(args, "teacher_check_mode", "auto"), tp)
             args.teacher_check_mode = cm
             self.model_AN.check_nograd_precision(cm)      # (on the host too: a mode the encoder is not built for fails here, not in a step)
@@ -254,18 +262,15 @@ class CoSATrainer:
                 raise NotImplementedError("teacher_check_iters: the check compares 16-bit operand modes of the teacher's no-grad passes; "
                                           "this trainer's compute dtype has none")
             self.teacher_check_state = seg_helper.new_teacher_check(args.num_classes, device)
-            self.extra_state = dict(getattr(self, "extra_state", {}), **{"teacher_check.counters": self.teacher_check_state})
+            self._add_extra_state("teacher_check.counters", self.teacher_check_state)
             if on:
-                self._build_check_model(cm)
+                self._build_check("teacher")
         # the student-forward monitor: off (None) unless --student_check_iters N > 0.  Every N-th optimizer step runs the
         # student's weights of that step through `model_SK`, a network of its own on --student_check_mode operands (fp32: the masters
         # themselves on the fp32 family), over the batch the step trained on, and scores the training forward against that pass.  The
         # counters are state of the run (`student_check.counters` of extra_state); model_SK is not: every check overwrites it
         self.student_check_state = self.model_SK = self._scheck_ctx = self.student_check_last = None
-        self._scheck_iters = int(getattr(args, "student_check_iters", 0) or 0)
-        if self._scheck_iters < 0:
-            raise ValueError(f"student_check_iters {self._scheck_iters!r}: 0 (off) or a positive number of optimizer steps")
-        if self._scheck_iters > 0:
+        if self._check_iters["student"] > 0:
             sm = str(getattr(args, "student_check_mode", "fp32"))
             args.student_check_mode = sm
             if sm.partition("-")[0] not in NOGRAD_PRECISIONS:
@@ -275,9 +280,9 @@ class CoSATrainer:
                 raise NotImplementedError("student_check_iters: the check scores the 16-bit training forward; this trainer's compute dtype "
                                           "has none")
             self.student_check_state = seg_helper.new_student_check(args.num_classes, device)
-            self.extra_state = dict(getattr(self, "extra_state", {}), **{"student_check.counters": self.student_check_state})
+            self._add_extra_state("student_check.counters", self.student_check_state)
             if on:
-                self._build_student_check_model(sm)
+                self._build_check("student")
         if on:
             for sh in (self._teacher_shadows, self._student_shadows):
                 if sh is not None:
@@ -379,28 +384,45 @@ class CoSATrainer:
         ck.set_nograd_precision(mode)
         return ck
 
-    def _build_check_model(self, mode):
-        """model_CK, the --teacher_check network (_new_check_network)"""
-        ck = self._new_check_network(mode)
-        self.model_CK = ck
-        self._ck_params = list(ck.parameters())
-        assert len(self._ck_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ck_params, self._ema_pairs[0]))
-        # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads model_CK's fp32 parameters)
-        self._ck_shadows = nn_ops.ensure_shadows(ck, ck.compute_dtype) if ck.compute_dtype != torch.float32 else None
-        self._ck_buffers = {}                                                 # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
+    def _build_check(self, which):
+        """model_CK, the --teacher_check network, or model_SK, the --student_check one (_new_check_network on args.<which>_check_mode): two
+        networks, not one shared -- both monitors may be on in one run"""
+        tag, half = {"teacher": ("ck", 0), "student": ("sk", 1)}[which]
+        net = self._new_check_network(getattr(self.args, which + "_check_mode"))
+        params = list(net.parameters())
+        assert len(params) == len(self._ema_pairs[half]) and all(a.shape == b.shape for a, b in zip(params, self._ema_pairs[half]))
+        setattr(self, "model_" + tag.upper(), net)
+        setattr(self, f"_{tag}_params", params)
+        # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads the network's fp32 parameters)
+        setattr(self, f"_{tag}_shadows", nn_ops.ensure_shadows(net, net.compute_dtype) if net.compute_dtype != torch.float32 else None)
+        if which == "teacher":
+            self._ck_buffers = {}                                             # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
 
-    def _build_student_check_model(self, mode):
-        """model_SK, the --student_check network (_new_check_network): not shared with model_CK -- both monitors may be on in one run"""
-        sk = self._new_check_network(mode)
-        self.model_SK = sk
-        self._sk_params = list(sk.parameters())
-        assert len(self._sk_params) == len(self._ema_pairs[1]) and all(a.shape == b.shape for a, b in zip(self._sk_params, self._ema_pairs[1]))
-        # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads model_SK's fp32 parameters)
-        self._sk_shadows = nn_ops.ensure_shadows(sk, sk.compute_dtype) if sk.compute_dtype != torch.float32 else None
+    def _is_check_step(self, n_iter, which="teacher"):
+        """the step that closes every N-th optimizer iteration (N: --<which>_check_iters); with --accum_steps its last micro-batch"""
+        return (getattr(self, which + "_check_state") is not None and (n_iter + 1) % self._check_iters[which] == 0
+                and self._micro_k == self._accum_steps - 1)
 
-    def _is_student_check_step(self, n_iter):
-        """_is_check_step's rule for --student_check_iters"""
-        return self.model_SK is not None and (n_iter + 1) % self._scheck_iters == 0 and self._micro_k == self._accum_steps - 1
+    @contextlib.contextmanager
+    def _check_pass(self, name):
+        """what a check's extra pass runs inside: no kernel-span stamps (a benchmark's slots are the training kernels') and library
+        workspaces of its own (_C.workspace_scope)"""
+        held = nn_ops.stamps, nn_ops.gemm_stamps
+        nn_ops.stamps = nn_ops.gemm_stamps = None
+        try:
+            with _C.workspace_scope(name):
+                yield
+        finally:
+            nn_ops.stamps, nn_ops.gemm_stamps = held
+
+    def _add_extra_state(self, name, tensor):
+        """`tensor` travels in a state file as `aux.<name>` (checkpoint.TrainState; `extra_state` exists only once something is in it)"""
+        self.extra_state = dict(getattr(self, "extra_state", {}), **{name: tensor})
+
+    def _summary_of(self, counters, summarise):
+        """a monitor's summary of the counters accumulated since they were last zeroed (synchronises: for tests and the log interval); None
+        when the monitor is off"""
+        return None if counters is None else summarise(counters, self.args.num_classes)
 
     @torch.no_grad()
     def _student_check(self):
@@ -414,46 +436,34 @@ class CoSATrainer:
         ctx, self._scheck_ctx = self._scheck_ctx, None
         args = self.args
         torch._foreach_copy_(self._sk_params, self._ema_pairs[1])                  # (the unwrapped student's parameters, not DDP's)
-        held = nn_ops.stamps, nn_ops.gemm_stamps           # (a benchmark's kernel-span slots are the training kernels')
-        nn_ops.stamps = nn_ops.gemm_stamps = None
         lab, simg, (mask, mask_aux) = ctx["cls_label"], ctx["simg"], ctx["masks"]
-        try:
-            with _C.workspace_scope("student_check"):
-                cls_b, clsaux_b, _feat, seg_b, cam_b, aux_b = self.model_SK(simg, cam_only=False, detach='none')
-                cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
-                l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
-                l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
-                if self.fused_losses:
-                    l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
-                                                             aux_alpha=args.aux_cam2seg_alpha)
-                    cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
-                else:
-                    up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
-                    l_seg = seg_helper.seg_loss(up, mask, fg_alpha=args.segfg_alpha)
-                    if mask_aux is not None:
-                        l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
-                    cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
-                l_cam = cam_l(cam_b)
-                if args.aux_seg2cam:
-                    l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
-                loss_b = torch.stack([t.reshape(()).float() for t in (l_cls, l_cls_aux, l_seg, l_cam)])
-        finally:
-            nn_ops.stamps, nn_ops.gemm_stamps = held
+        with self._check_pass("student_check"):
+            cls_b, clsaux_b, _feat, seg_b, cam_b, aux_b = self.model_SK(simg, cam_only=False, detach='none')
+            cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
+            l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
+            l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
+            if self.fused_losses:
+                l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
+                                                         aux_alpha=args.aux_cam2seg_alpha)
+                cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
+            else:
+                up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
+                l_seg = seg_helper.seg_loss(up, mask, fg_alpha=args.segfg_alpha)
+                if mask_aux is not None:
+                    l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
+                cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
+            l_cam = cam_l(cam_b)
+            if args.aux_seg2cam:
+                l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
+            loss_b = torch.stack([t.reshape(()).float() for t in (l_cls, l_cls_aux, l_seg, l_cam)])
         a, loss_a = ctx["outputs"], torch.stack([t.reshape(()).float() for t in ctx["losses"]])
         b = dict(seg=seg_b, cam=cam_b, cam_aux=aux_b, cls=cls_b, cls_aux=clsaux_b)
         seg_helper.student_check(*[(a[k], b[k]) for k in seg_helper.STUDENT_CHECK_TENSORS], (loss_a, loss_b), lab, self.student_check_state)
         self.student_check_last = dict(a=a, b=b, loss_a=loss_a, loss_b=loss_b, cls_label=lab)
 
     def student_check(self):
-        """the summary (seg_helper.student_check_summary) of the checks accumulated since the counters were last zeroed (synchronises: for
-        tests and the log interval); None when --student_check_iters is 0"""
-        if self.student_check_state is None:
-            return None
-        return seg_helper.student_check_summary(self.student_check_state, self.args.num_classes)
-
-    def _is_check_step(self, n_iter):
-        """the step that closes every N-th optimizer iteration; with --accum_steps its last micro-batch"""
-        return self.teacher_check_state is not None and (n_iter + 1) % self._check_iters == 0 and self._micro_k == self._accum_steps - 1
+        """_summary_of --student_check_iters' counters (seg_helper.student_check_summary)"""
+        return self._summary_of(self.student_check_state, seg_helper.student_check_summary)
 
     @torch.no_grad()
     def _teacher_check(self, wimg, img_denorm, img_box, cls_label, cams, masks, thresholds, tgt):
@@ -465,25 +475,17 @@ class CoSATrainer:
         its own, the library workspaces it needs are slots of their own (_C.workspace_scope)."""
         args = self.args
         torch._foreach_copy_(self._ck_params, self._ema_pairs[0])
-        held = nn_ops.stamps, nn_ops.gemm_stamps           # (a benchmark's kernel-span slots are the training kernels')
-        nn_ops.stamps = nn_ops.gemm_stamps = None
-        try:
-            with _C.workspace_scope("teacher_check"):
-                (cam_b, aux_b), (mask_b, mask_aux_b), tgt_b = teacher_products(
-                    self.model_CK, args, wimg, img_denorm, img_box, cls_label, thresholds, self.fused_losses,
-                    tgt.shape[-2:] if tgt is not None else None, self._ck_buffers, self.refine_model)
-        finally:
-            nn_ops.stamps, nn_ops.gemm_stamps = held
+        with self._check_pass("teacher_check"):
+            (cam_b, aux_b), (mask_b, mask_aux_b), tgt_b = teacher_products(
+                self.model_CK, args, wimg, img_denorm, img_box, cls_label, thresholds, self.fused_losses,
+                tgt.shape[-2:] if tgt is not None else None, self._ck_buffers, self.refine_model)
         seg_helper.teacher_check((cams[0], cam_b), (cams[1], aux_b), (tgt, tgt_b) if tgt is not None else None, (masks[0], mask_b),
                                  (masks[1], mask_aux_b) if masks[1] is not None else None, None if args.use_cammix else cls_label, img_box,
                                  self.teacher_check_state, ignore_index=args.ignore_index, bar=seg_helper.TEACHER_CHECK_BAR)
 
     def teacher_check(self):
-        """the summary (seg_helper.teacher_check_summary) of the checks accumulated since the counters were last zeroed (synchronises: for
-        tests and the log interval); None when --teacher_check_iters is 0"""
-        if self.teacher_check_state is None:
-            return None
-        return seg_helper.teacher_check_summary(self.teacher_check_state, self.args.num_classes)
+        """_summary_of --teacher_check_iters' counters (seg_helper.teacher_check_summary)"""
+        return self._summary_of(self.teacher_check_state, seg_helper.teacher_check_summary)
 
     def _join_teacher(self):
         if self._teacher_pending:
@@ -579,7 +581,7 @@ class CoSATrainer:
         if self.model_CK is not None and self._is_check_step(n_iter):
             self._teacher_check(wimg, img_denorm, img_box, cls_label, (cam_ps, cam_aux_ps), (refine_mask_label, refine_mask_label_aux),
                                 ((threhigh, threlow), (auxthrehigh, auxthrelow)), check_tgt)
-        if self._is_student_check_step(n_iter):
+        if self.model_SK is not None and self._is_check_step(n_iter, "student"):
             # what the check after this step's backward (_student_check) reads: detached references, nothing is copied or computed here
             self._scheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux), tgt=check_tgt_s,
                                     outputs=dict(seg=seg_lr.detach(), cam=cam_pred.detach(), cam_aux=cam_aux_pred.detach(),
@@ -703,7 +705,7 @@ class CoSATrainer:
     def tensor_stats(self, values=None):
         """the summary (torch_helper.tensor_stats_summary) of the last sample and of the run's blame counters (synchronises: for tests);
         None when --tensor_stats is off.  values: (table values, blame counts or None) already on the host -- what the launcher's
-        read_interval returns -- are summarised instead, without a sync."""
+        read_interval's host["tensor_stats"] -- are summarised instead, without a sync."""
         if not self._tensor_stats:
             return None
         table, blame = (self.tensor_stats_table, self.tensor_stats_state) if values is None else values
@@ -719,11 +721,8 @@ class CoSATrainer:
                   ignore_index=self.args.ignore_index, step_scale=self._step_scale)
 
     def label_stats(self):
-        """the summary (seg_helper.label_stats_summary) of the counters accumulated since they were last zeroed (synchronises: for tests
-        and the log interval); None when --label_stats is off"""
-        if self.label_stats_state is None:
-            return None
-        return seg_helper.label_stats_summary(self.label_stats_state, self.args.num_classes)
+        """_summary_of --label_stats' counters (seg_helper.label_stats_summary)"""
+        return self._summary_of(self.label_stats_state, seg_helper.label_stats_summary)
 
     # -- full-state checkpoints (cosa_amd/checkpoint.py, DESIGN.md section 9) --
     def train_state(self):

@@ -185,8 +185,9 @@ def test_host_trainer_counts_and_carries_its_counters_through_a_state_file(tmp_p
 
 
 def test_launcher_line_and_jsonl_record_from_a_counter_vector():
-    from cosa_amd import main as launcher
+    from cosa_amd import monitors
     from cosa_amd.utils import seg_helper
+    m = monitors.BY_NAME["label_stats"]
     K = 3
     off, n = R.layout(K)
     c = np.zeros(n, np.int64)
@@ -198,19 +199,20 @@ def test_launcher_line_and_jsonl_record_from_a_counter_vector():
     c[off["inter"]:off["inter"] + K] = [400, 200, 100]
     c[off["bad_cam_aux"]] = 4
     s = seg_helper.label_stats_summary(c.astype(np.float64).tolist(), K)          # as the launcher reads them: doubles out of the interval's one sync
-    line = launcher.label_stats_line(s)
+    line = m.line(s, None)
     miou = (400 / 575 + 200 / 350 + 100 / 125) / 3
     assert line == " ignore: 0.125, fg: 0.375, aux_agree: 0.875, student_miou: %.3f, teacher_nonfinite: 4" % miou
-    rec = json.loads(launcher.label_stats_record(s, 40))
+    rec = json.loads(monitors.monitor_record(m, s, 40, None))
     assert rec["iters"] == 40 and rec["steps"] == 20 and rec["student_iou"] == [400 / 575, 200 / 350, 100 / 125]
     assert rec["class_pixels"] == [500, 250, 125, 125] and rec["aux_class_pixels"] == [500, 250, 125, 125]
-    assert rec["teacher_nonfinite_aux"] == 4 and "\n" not in launcher.label_stats_record(s, 40)
+    assert rec["teacher_nonfinite_aux"] == 4 and "\n" not in monitors.monitor_record(m, s, 40, None)
 
 
 @pytest.mark.parametrize("with_guard", [False, True])
 @pytest.mark.parametrize("with_stats", [False, True])
 def test_launcher_reads_an_interval_in_one_transfer_and_zeroes_what_is_the_intervals(with_guard, with_stats, tmp_path):
     from cosa_amd import main as launcher
+    from cosa_amd import monitors
     from cosa_amd.utils import seg_helper, torch_helper
     K = 3
     off, n = R.layout(K)
@@ -223,8 +225,11 @@ def test_launcher_reads_an_interval_in_one_transfer_and_zeroes_what_is_the_inter
     stats = None
     if with_stats:
         stats = torch.arange(n, dtype=torch.int64) + 100
-    vals, gvals, svals = launcher.read_interval(acc, 20, guard, stats)
+    on = [(monitors.BY_NAME[k], t) for k, t in (("guard", guard), ("label_stats", stats)) if t is not None]
+    vals, host = launcher.read_interval(acc, 20, on)
     assert vals == [float(i) for i in range(8)] and int(acc.abs().sum()) == 0 and acc.numel() == 8
+    assert set(host) == {m.name for m, _ in on}
+    gvals, svals = host.get("guard"), host.get("label_stats")
     assert gvals == ([2.5, 2.0, 1.0] if with_guard else None)
     if with_guard:
         assert guard[2:5].tolist() == [17, 2, 1]                      # the guard's counters are the run's
@@ -232,7 +237,7 @@ def test_launcher_reads_an_interval_in_one_transfer_and_zeroes_what_is_the_inter
         assert svals == list(range(100, 100 + n)) and all(isinstance(v, int) for v in svals) and int(stats.abs().sum()) == 0
         summary = seg_helper.label_stats_summary(svals, K)
         for it in (20, 40):
-            launcher.append_label_stats(tmp_path, summary, it)
+            monitors.append_monitor(tmp_path, monitors.BY_NAME["label_stats"], summary, it, None)
         lines = (tmp_path / "label_stats.jsonl").read_text().splitlines()
         assert [json.loads(x)["iters"] for x in lines] == [20, 40] and json.loads(lines[0])["steps"] == 100
     else:

@@ -198,19 +198,22 @@ def test_flags_parse_and_a_negative_interval_is_refused():
 
 
 def test_log_line_and_jsonl_record(tmp_path):
-    from cosa_amd import main as launcher
+    from types import SimpleNamespace
+    from cosa_amd import monitors
+    m, targs = monitors.BY_NAME["student_check"], SimpleNamespace(student_check_mode="fp32")
     summary = {"seg": {"rel_l2": 1.2e-3}, "seg_agree": 0.99987, "flip_hist": [4, 2, 1, 0], "loss_rel": 3.1e-4, "checks": 2}
-    assert launcher.student_check_line(summary, "fp32") == " scheck[fp32]: seg rel 1.2e-03, agree 0.99987, flips>=1e-1 0, loss rel 3.1e-04"
-    rec = json.loads(launcher.student_check_record(summary, 40, "bf16", "fp32"))
+    assert m.line(summary, targs) == " scheck[fp32]: seg rel 1.2e-03, agree 0.99987, flips>=1e-1 0, loss rel 3.1e-04"
+    rec = json.loads(monitors.monitor_record(m, summary, 40, targs))
     assert rec["iters"] == 40 and rec["mode"] == "bf16" and rec["check_mode"] == "fp32" and rec["flip_hist"] == [4, 2, 1, 0]
-    launcher.append_student_check(tmp_path, summary, 20, "bf16", "fp32")
-    launcher.append_student_check(tmp_path, summary, 40, "bf16", "fp32")
+    monitors.append_monitor(tmp_path, m, summary, 20, targs)
+    monitors.append_monitor(tmp_path, m, summary, 40, targs)
     assert [json.loads(x)["iters"] for x in (tmp_path / "student_check.jsonl").read_text().splitlines()] == [20, 40]
 
 
 @pytest.mark.parametrize("with_teacher_check", [False, True])
 def test_read_interval_carries_and_zeroes_the_counters(with_teacher_check):
     from cosa_amd import main as launcher
+    from cosa_amd import monitors
     from cosa_amd.utils import seg_helper, torch_helper
     K = 3
     _, n = seg_helper.student_check_layout(K)
@@ -227,15 +230,16 @@ def test_read_interval_carries_and_zeroes_the_counters(with_teacher_check):
     if with_teacher_check:
         tc = torch.arange(seg_helper.teacher_check_layout(K)[1], dtype=torch.int64) + 5
         tc_want = tc.tolist()
-    out = launcher.read_interval(acc, 20, guard, stats, None, teacher_check=tc, student_check=check)
-    assert len(out) == 6 and acc.numel() == 8
-    vals, gvals, svals, tvals, cvals, scvals = out
+    on = dict(guard=guard, label_stats=stats, teacher_check=tc, student_check=check)
+    vals, host = launcher.read_interval(acc, 20, [(m, on[m.name]) for m in monitors.MONITORS if on.get(m.name) is not None])
+    assert set(host) == {"guard", "label_stats", "student_check"} | ({"teacher_check"} if with_teacher_check else set()) and acc.numel() == 8
+    gvals, svals, tvals, cvals, scvals = (host.get(k) for k in ("guard", "label_stats", "tensor_stats", "teacher_check", "student_check"))
     assert vals == [float(i) for i in range(8)] and gvals == [2.5, 2.0, 1.0] and svals == list(range(100, 119)) and tvals is None
     assert scvals == want and all(isinstance(v, int) for v in scvals) and int(check.abs().sum()) == 0 and int(acc.abs().sum()) == 0
     assert cvals == (tc_want if with_teacher_check else None)
     # without the argument: what it was
     acc = torch.arange(8, dtype=torch.float64) * 20
-    assert launcher.read_interval(acc, 20, None, None) == ([float(i) for i in range(8)], None, None)
+    assert launcher.read_interval(acc, 20, []) == ([float(i) for i in range(8)], {})
 
 
 class _TinyNet(torch.nn.Module):

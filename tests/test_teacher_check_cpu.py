@@ -249,8 +249,10 @@ def test_summary_on_hand_made_counters():
 
 
 def test_log_line_and_jsonl_record(tmp_path):
-    from cosa_amd import main as launcher
+    from types import SimpleNamespace
+    from cosa_amd import monitors
     from cosa_amd.utils import seg_helper
+    m, targs = monitors.BY_NAME["teacher_check"], SimpleNamespace(teacher_precision="fp16x3", teacher_check_mode="bf16x3")
     K = 3
     off, n = seg_helper.teacher_check_layout(K)
     c = np.zeros(n, np.int64)
@@ -264,14 +266,14 @@ def test_log_line_and_jsonl_record(tmp_path):
         c[off[p + ".inter"]:off[p + ".inter"] + K] = [49995, 49996, 0]
     s = seg_helper.teacher_check_summary(c, K)
     miou = (49995 / 50005 + 49996 / 50004) / 2
-    assert launcher.teacher_check_line(s, "bf16x3") == " tcheck[bf16x3]: worst 3.1e-04, over 0/84, agree 0.99987, miou %.5f" % miou
-    rec = launcher.teacher_check_record(s, 40, "fp16x3", "bf16x3")
+    assert m.line(s, targs) == " tcheck[bf16x3]: worst 3.1e-04, over 0/84, agree 0.99987, miou %.5f" % miou
+    rec = monitors.monitor_record(m, s, 40, targs)
     assert "\n" not in rec
     rec = json.loads(rec)
     assert rec["iters"] == 40 and rec["mode"] == "fp16x3" and rec["check_mode"] == "bf16x3" and rec["checks"] == 1
     assert rec["cam"]["planes"] == 28 and rec["exemption_evaluated"] is False and rec["conforms"] is True
     for it in (20, 40):
-        launcher.append_teacher_check(tmp_path, s, it, "fp16x3", "bf16x3")
+        monitors.append_monitor(tmp_path, m, s, it, targs)
     assert [json.loads(x)["iters"] for x in (tmp_path / "teacher_check.jsonl").read_text().splitlines()] == [20, 40]
 
 
@@ -285,18 +287,25 @@ def _interval_inputs():
     return acc, guard, stats
 
 
+def _on(**tensors):
+    """read_interval's monitor list of what is given (not None), in the table's order"""
+    from cosa_amd import monitors
+    return [(m, tensors[m.name]) for m in monitors.MONITORS if tensors.get(m.name) is not None]
+
+
 def test_read_interval_without_the_argument_is_what_it_was():
     from cosa_amd import main as launcher
     acc, guard, stats = _interval_inputs()
-    out = launcher.read_interval(acc, 20, guard, stats)
-    assert len(out) == 3 and out[0] == [float(i) for i in range(8)] and out[1] == [2.5, 2.0, 1.0] and out[2] == list(range(100, 119))
+    vals, host = launcher.read_interval(acc, 20, _on(guard=guard, label_stats=stats))
+    assert set(host) == {"guard", "label_stats"} and vals == [float(i) for i in range(8)] and host["guard"] == [2.5, 2.0, 1.0]
+    assert host["label_stats"] == list(range(100, 119))
     acc, _, _ = _interval_inputs()
-    out = launcher.read_interval(acc, 20, None, None)
-    assert out == ([float(i) for i in range(8)], None, None)
+    out = launcher.read_interval(acc, 20, [])
+    assert out == ([float(i) for i in range(8)], {})
     acc, guard, stats = _interval_inputs()
     table, blame = torch.arange(12, dtype=torch.float64).reshape(2, 6), torch.tensor([5, 0])
-    out = launcher.read_interval(acc, 20, guard, stats, (table, blame))
-    assert len(out) == 4 and out[3][1] == [5, 0] and len(out[3][0]) == 2
+    _, host = launcher.read_interval(acc, 20, _on(guard=guard, label_stats=stats, tensor_stats=(table, blame)))
+    assert set(host) == {"guard", "label_stats", "tensor_stats"} and host["tensor_stats"][1] == [5, 0] and len(host["tensor_stats"][0]) == 2
 
 
 @pytest.mark.parametrize("with_tensor_stats", [False, True])
@@ -309,7 +318,9 @@ def test_read_interval_carries_and_zeroes_the_check_counters(with_tensor_stats):
     check = torch.arange(n, dtype=torch.int64) + 1000
     check[3] = 0x7f800000                                                               # a bit pattern: exact through the double
     ts = (torch.arange(12, dtype=torch.float64).reshape(2, 6), torch.tensor([5, 0])) if with_tensor_stats else None
-    vals, gvals, svals, tvals, cvals = launcher.read_interval(acc, 20, guard, stats, ts, teacher_check=check)
+    vals, host = launcher.read_interval(acc, 20, _on(guard=guard, label_stats=stats, tensor_stats=ts, teacher_check=check))
+    assert set(host) == {"guard", "label_stats", "teacher_check"} | ({"tensor_stats"} if with_tensor_stats else set())
+    gvals, svals, tvals, cvals = host["guard"], host["label_stats"], host.get("tensor_stats"), host["teacher_check"]
     assert vals == [float(i) for i in range(8)] and gvals == [2.5, 2.0, 1.0] and svals == list(range(100, 119))
     want = list(range(1000, 1000 + n))
     want[3] = 0x7f800000

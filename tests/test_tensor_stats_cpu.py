@@ -243,7 +243,9 @@ def test_blame_counters_reconcile_with_state_files_in_both_directions(tmp_path, 
 @pytest.mark.parametrize("with_blame", [False, True])
 def test_launcher_reads_table_and_blame_in_the_intervals_one_transfer(with_blame, tmp_path):
     from cosa_amd import main as launcher
+    from cosa_amd import monitors
     from cosa_amd.utils import torch_helper
+    M = monitors.BY_NAME
     names, student, teacher, grads, groups = _toy()
     sizes = [p.numel() for p in student]
     table = torch_helper.tensor_stats_torch(student, teacher, grads)
@@ -253,7 +255,9 @@ def test_launcher_reads_table_and_blame_in_the_intervals_one_transfer(with_blame
     guard = torch_helper.new_guard_state("cpu")
     guard[2:5] = torch.tensor([17, 3, 0])
     stats = torch.arange(27, dtype=torch.int64)
-    vals, gvals, svals, (tvals, bvals) = launcher.read_interval(acc, 20, guard, stats, (table, blame))
+    vals, host = launcher.read_interval(acc, 20, [(M["guard"], guard), (M["label_stats"], stats), (M["tensor_stats"], (table, blame))])
+    assert set(host) == {"guard", "label_stats", "tensor_stats"}
+    gvals, svals, (tvals, bvals) = host["guard"], host["label_stats"], host["tensor_stats"]
     assert vals == [float(i) for i in range(8)] and acc.numel() == 8 and int(acc.abs().sum()) == 0
     assert gvals[1:] == [3.0, 0.0] and svals == list(range(27)) and int(stats.abs().sum()) == 0
     assert torch.equal(table, kept)                                   # a sample, not an accumulator: nothing is zeroed
@@ -261,19 +265,21 @@ def test_launcher_reads_table_and_blame_in_the_intervals_one_transfer(with_blame
     assert bvals == ([0, 0, 0, 0, 0, 0, 3, 0] if with_blame else None)
     if with_blame:
         assert blame.tolist() == bvals                                # the run's: never zeroed
-    # without the new argument the call and its three values are what they were
-    assert len(launcher.read_interval(acc, 20, guard, None)) == 3
-    v2, _, _, (t2, b2) = launcher.read_interval(acc, 20, None, None, (table, blame))
+    # without the monitor its values are absent, and alone it reads the same
+    assert set(launcher.read_interval(acc, 20, [(M["guard"], guard)])[1]) == {"guard"}
+    v2, h2 = launcher.read_interval(acc, 20, [(M["tensor_stats"], (table, blame))])
+    assert set(h2) == {"tensor_stats"}
+    t2, b2 = h2["tensor_stats"]
     assert t2 == tvals and b2 == bvals and len(v2) == 8
     summary = torch_helper.tensor_stats_summary(tvals, bvals, names, groups, sizes)
     want = R.summary(R.decode(kept.numpy()).tolist(), bvals, names, groups, sizes)
     assert summary["global"] == pytest.approx(want["global"], rel=1e-12, abs=0) and summary["worst"] == "planted_g"
-    line = launcher.tensor_stats_line(summary)
+    line = M["tensor_stats"].line(summary, None)
     assert line == " ema_gap: %.3e, worst: planted_g" % want["global"]["ema_gap_rel"]
     quiet = torch_helper.tensor_stats_summary(torch_helper.tensor_stats_torch(student[:2], teacher[:2], grads[:2]), None, names[:2], groups[:2])
-    assert launcher.tensor_stats_line(quiet).endswith(", worst: -")
+    assert M["tensor_stats"].line(quiet, None).endswith(", worst: -")
     for it in (20, 40):
-        launcher.append_tensor_stats(tmp_path, summary, it)
+        monitors.append_monitor(tmp_path, M["tensor_stats"], summary, it, None)
     lines = (tmp_path / "tensor_stats.jsonl").read_text().splitlines()
     recs = [json.loads(x) for x in lines]
     assert [r["iters"] for r in recs] == [20, 40] and recs[0]["worst"] == "planted_g" and list(recs[0]["tensors"]) == names
