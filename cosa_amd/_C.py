@@ -40,6 +40,7 @@ _SIGS = {
     "cosa_augment_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cosa_augment_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    "cosa_augment_labels": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "cosa_gmm_workspace_bytes": (c_size_t, []),
     "cosa_gmm_fit_thresholds": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_double, ctypes.c_double, c_int,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -100,6 +101,9 @@ _SIGS = {
                                    c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "cosa_label_stats_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
     "cosa_label_stats": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cosa_gt_stats_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
+    "cosa_gt_stats": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p]),
+    "cosa_gt_stats_uses_lds": (c_int, [c_int]),
     "cosa_teacher_check_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
     "cosa_teacher_check_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cosa_teacher_check": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),

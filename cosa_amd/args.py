@@ -83,6 +83,12 @@ EXTRA = [
                                              # <output_dir>/student_check.jsonl every log_iters; training is untouched
     ("student_check_mode", str, "fp32"),     # any --teacher_precision value but auto; fp32: the reference's arithmetic on the fp32 masters; bf16: the no-grad
                                              # path evaluate(s_or_t='s') runs
+    # pseudo labels against ground truth; off: nothing changes, no PNG is read
+    ("gt_stats", str2bool, False),           # decode each training image's ground-truth map, crop it on the device with the image's own draws and count
+                                             # the main / auxiliary pseudo labels and the student's prediction against it (confusion matrices, mIoU);
+                                             # logged and written to <output_dir>/gt_stats.jsonl every log_iters; training is untouched
+    ("gt_dir", str, None),                   # where --gt_stats finds <name>.png (default: the dataset root's SegmentationClassAug for VOC12,
+                                             # SegmentationClass/train2014 for COCO: what the Seg datasets read)
 ]
 
 

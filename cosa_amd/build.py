@@ -44,6 +44,7 @@ SOURCES = {
     "optim_kernels.hip": ["-ffp-contract=off"],
     "teacher_check_kernels.hip": EXACT,
     "student_check_kernels.hip": EXACT,
+    "gt_stats_kernels.hip": EXACT,        # (the student's label by the same spec-R calls as eval_kernels.hip: csrc/student_label.hpp)
     # the "f32" operand family: fp32 operands on the f32-input MFMA.  No contraction: the MFMA's chain is the only fused arithmetic, what
     # else is an fma is written fmaf; no fast math (expf / erff at their full accuracy, infinities honoured by the tail-key mask)
     "f32_kernels.hip": EXACT,

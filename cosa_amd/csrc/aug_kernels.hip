@@ -318,6 +318,24 @@ __global__ __launch_bounds__(256) void aug_apply_kernel(const AugImage *__restri
     }
 }
 
+// Ground-truth maps through the crop's geometry (--gt_stats): NEAREST resize, flip, pad and crop are one source row
+// and one source column per output row and column, drawn up by the host (dataloaders/augment.py: label_tables).  One thread per pixel;
+// maps[b] = (byte offset of the [rows][pitch] uint8 map in raw, pitch, rows); tables[b] = src_y[S] | src_x[S], -1 outside the image.
+// An entry outside its map, or a map that does not lie inside raw's raw_bytes, reads nothing and gives 255, as -1 does.
+__global__ __launch_bounds__(256) void aug_labels_kernel(const uint8_t *__restrict__ raw, long long raw_bytes,
+                                                        const long long *__restrict__ maps, const int32_t *__restrict__ tables, int S,
+                                                        uint8_t *__restrict__ out)
+{
+    const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
+    if (X >= S) return;
+    const long long off = maps[3 * b], pitch = maps[3 * b + 1], rows = maps[3 * b + 2];
+    const int32_t *t = tables + (size_t)b * 2 * S;
+    const int sy = t[Y], sx = t[S + X];
+    const bool inside = off >= 0 && pitch > 0 && rows > 0 && pitch <= raw_bytes && rows <= raw_bytes / pitch && off <= raw_bytes - rows * pitch;
+    const bool ok = inside && sy >= 0 && sx >= 0 && sy < rows && sx < pitch;
+    out[((size_t)b * S + Y) * S + X] = ok ? raw[off + (long long)sy * pitch + sx] : (uint8_t)255;
+}
+
 }  // namespace
 }  // namespace cosa
 
@@ -375,6 +393,19 @@ extern "C" int cosa_augment_batch(const uint8_t *raw, const void *records, int B
     hipLaunchKernelGGL(aug_plan_kernel, dim3(B), dim3(64), 0, st, imgs, hist, lut, mean_l);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(aug_apply_kernel, gx, blk, 0, st, imgs, weak, lut, mean_l, wimg, simg, strong_u8, S);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+extern "C" int cosa_augment_labels(const uint8_t *raw, size_t raw_bytes, const long long *maps, const int32_t *tables, int B, int S,
+                                   uint8_t *out, void *stream)
+{
+    COSA_REQUIRE(raw && maps && tables && out, "cosa_augment_labels: null pointer");
+    COSA_REQUIRE(B > 0 && B <= 65535 && S > 0 && S <= 65535 && raw_bytes > 0 && raw_bytes < ((size_t)1 << 62),
+                 "cosa_augment_labels: bad shape (B %d, S %d, raw_bytes %zu)", B, S, raw_bytes);
+    COSA_REQUIRE(((size_t)maps & 7) == 0 && ((size_t)tables & 3) == 0, "cosa_augment_labels: maps must be 8-byte and tables 4-byte aligned");
+    hipLaunchKernelGGL(aug_labels_kernel, dim3((S + 255) / 256, S, B), dim3(256), 0, as_stream(stream), raw, (long long)raw_bytes, maps,
+                       tables, S, out);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

@@ -13,31 +13,10 @@
 // bit-identical to the reference's on the golden vectors (tests/golden/eval.npz).
 #include "kernels.hpp"
 #include "spec_math.hpp"
+#include "student_label.hpp"      // src_index_r, bilerp, student_label4, wave_count
 
 namespace cosa {
 namespace {
-
-__device__ __forceinline__ void src_index_r(int dst, int in, float scale, int &i0, int &i1, float &l0, float &l1)
-{
-    float src = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
-    src = src < 0.0f ? 0.0f : src;
-    int i = (int)src;
-    i = i > in - 1 ? in - 1 : i;
-    float lam = src - (float)i;
-    lam = lam < 0.0f ? 0.0f : (lam > 1.0f ? 1.0f : lam);
-    i0 = i;
-    i1 = i < in - 1 ? i + 1 : i;
-    l1 = lam;
-    l0 = 1.0f - lam;
-}
-
-__device__ __forceinline__ float bilerp(const float *__restrict__ pl, int w, int y0, int y1, int x0, int x1, float ly0, float ly1,
-                                        float lx0, float lx1)
-{
-    const float r0 = __builtin_fmaf(pl[(size_t)y0 * w + x0], lx0, pl[(size_t)y0 * w + x1] * lx1);
-    const float r1 = __builtin_fmaf(pl[(size_t)y1 * w + x0], lx0, pl[(size_t)y1 * w + x1] * lx1);
-    return __builtin_fmaf(r0, ly0, r1 * ly1);
-}
 
 // cam [B,C,S,S], seg [B,C+1,S,S], cls [B,C] -> three uint8 maps [B,H,W]
 __global__ __launch_bounds__(256) void eval_labels_kernel(const float *__restrict__ cam, const float *__restrict__ seg,
@@ -408,9 +387,7 @@ __global__ __launch_bounds__(256) void refine_merge_kernel(const RefineArgs a, c
 // ---- per-step pseudo-label statistics and the teacher finite check -----------------------------------------------
 // THE definition of the counter vector (uint64 elements) for the device and the host: off[i] of steps, pix, main[K+1], aux[K+1], agree,
 // inter[K], pred[K], bad_cam, bad_cam_aux; -> the number of elements
-constexpr int kStatsMaxK = 128;
 constexpr int kStatsSlots = 4 * kStatsMaxK + 7;
-constexpr unsigned kStatsMaxGroups = 1024;
 __host__ __device__ inline int label_stats_offsets(int K, int (&off)[COSA_LABEL_STATS_SLOTS])
 {
     off[0] = 0;                  // steps
@@ -433,31 +410,6 @@ struct LabelStatsArgs {
     int B, K, S, h, w, vec;                 // vec: every full-resolution row may be read as float4 (S % 4 == 0, 16-byte aligned bases)
     float sy, sx, ignore;
 };
-
-// ctr[slot] += 1 for every lane with `valid`, one LDS atomic per distinct slot of the wavefront (a crop holds a handful of labels: a
-// plain atomic per lane would serialise 64 deep on one address).  `todo` is wave-uniform, so every lane leaves the loop together.
-__device__ __forceinline__ void wave_count(unsigned long long *ctr, int slot, bool valid)
-{
-    unsigned long long todo = __ballot(valid);
-    while (todo) {
-        const int leader = __ffsll(todo) - 1;
-        const int s = __builtin_amdgcn_readlane(slot, leader);
-        const unsigned long long same = __ballot(valid && slot == s);
-        if ((int)__lane_id() == leader) atomicAdd(&ctr[s], (unsigned long long)__popcll(same));
-        todo &= ~same;
-    }
-}
-
-__device__ __forceinline__ void load_f32x4(const float *__restrict__ p, int X, int S, int vec, float (&v)[4])
-{
-    if (vec) {
-        const float4 t = *reinterpret_cast<const float4 *>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = X + k < S ? p[k] : 0.0f;
-    }
-}
 
 __device__ __forceinline__ bool nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
@@ -505,28 +457,10 @@ __global__ __launch_bounds__(256) void label_stats_kernel(const LabelStatsArgs a
             if (a.mask_aux) load_f32x4(a.mask_aux + o, X, S, a.vec, av);
         }
         for (int bb = b_lo; bb <= b_hi; bb++) {
-            // present[0] bit i: class i + 1 is in image bb's label row (i < 64); present[1]: classes 65..128
-            const float *cl = a.cls + (size_t)bb * (K - 1);
-            const unsigned long long present[2] = {__ballot(lane < K - 1 && cl[lane < K - 1 ? lane : 0] != 0.0f),
-                                                   __ballot(lane + 64 < K - 1 && cl[lane + 64 < K - 1 ? lane + 64 : 0] != 0.0f)};
+            unsigned long long present[2];
+            present_classes(a.cls, bb, K, lane, present);
             if (!(any && b == bb)) continue;
-            int y0, y1, x0[4], x1[4];
-            float ly0, ly1, lx0[4], lx1[4];
-            src_index_r(Y, a.h, a.sy, y0, y1, ly0, ly1);
-#pragma unroll
-            for (int k = 0; k < 4; k++) src_index_r(X + k < S ? X + k : S - 1, a.w, a.sx, x0[k], x1[k], lx0[k], lx1[k]);
-            const float *sb = a.seg + (size_t)bb * K * hw;
-            float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int c = 0; c < K; c++) {
-                // seg_validation: an absent class is -1e5, its plane unread (a scalar branch: `present` is wave-uniform)
-                const bool live = c == 0 || ((present[(c - 1) >> 6] >> ((c - 1) & 63)) & 1ull);
-                const float *pl = sb + (size_t)c * hw;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float v = live ? bilerp(pl, a.w, y0, y1, x0[k], x1[k], ly0, ly1, lx0[k], lx1[k]) : -1e5f;
-                    if (c == 0 || v > bv[k]) { bv[k] = v; iv[k] = c; }
-                }
-            }
+            student_label4(a.seg + (size_t)bb * K * hw, K, a.h, a.w, a.sy, a.sx, S, Y, X, present, iv);
             for (int g = 0; g < 2; g++) {
                 const float *cams = g ? a.cam_aux : a.cam;
                 if (!cams) continue;

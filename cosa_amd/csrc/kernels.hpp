@@ -18,4 +18,9 @@ int par_launch_affinity(const float *imgs, float *aff, int B, int h, int w, cons
 int par_launch_step(const float *aff, const float *src, float *dst, int B, int Kmax, const int *kcount, int halves,
                     size_t plane_stride, int h, int w, const ParPlan &plan, hipStream_t st);
 
+// eval_kernels.hip (cosa_label_stats) and gt_stats_kernels.hip (cosa_gt_stats) -------------
+// the two per-step reductions over the label maps share their envelope, their grid and the device functions of student_label.hpp
+constexpr int kStatsMaxK = 128;              // classes, background included
+constexpr unsigned kStatsMaxGroups = 1024;   // workgroups of 256 (four per CU: one resident round); the rest by grid stride
+
 }  // namespace cosa

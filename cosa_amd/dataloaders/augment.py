@@ -18,6 +18,7 @@ import random
 
 import numpy as np
 import torch
+from PIL import Image
 
 from .. import _C
 
@@ -50,6 +51,29 @@ def draw_params(h, w, crop_size=448, scale_range=(0.5, 2.0), blur_p=0.5, radius_
            min(crop_size, new_w + W_pad - W_start))
     return dict(h=h, w=w, new_h=new_h, new_w=new_w, flip=bool(flip), H_pad=H_pad, W_pad=W_pad, H_start=H_start, W_start=W_start,
                 blur=bool(blur), radius=radius, op=op, magnitude=magnitude, img_box=np.asarray(box, np.int16))
+
+
+def _nearest_sources(n_in, n_out):
+    """int32 [n_out]: the source index Pillow's NEAREST resize n_in -> n_out reads for every output index.  Pillow walks an accumulated
+    double, not a product, so the table is Pillow's own: it resizes an index ramp."""
+    ramp = Image.fromarray(np.arange(n_in, dtype=np.int32).reshape(1, n_in))               # mode "I"
+    return np.asarray(ramp.resize((n_out, 1), Image.NEAREST)).reshape(n_out).astype(np.int32)
+
+
+def label_tables(p, crop_size):
+    """(src_y [S], src_x [S]) int32 of one image's draws `p`: what the reference does to a label map that travels with its image
+    (transforms.py:61-77,101-114,145-202: resize NEAREST to (new_w, new_h), np.fliplr when drawn, pad with 255 at (H_pad, W_pad), crop at
+    (H_start, W_start)) as one source row per crop row and one source column per crop column, -1 outside the image (= outside img_box):
+    gt_crop[y][x] = gt[src_y[y]][src_x[x]], 255 where either is -1.  No random number is drawn."""
+    out = []
+    for n_in, n_new, pad, start, flip in ((p["h"], p["new_h"], p["H_pad"], p["H_start"], False),
+                                          (p["w"], p["new_w"], p["W_pad"], p["W_start"], p["flip"])):
+        src = _nearest_sources(n_in, n_new)
+        at = np.arange(crop_size) + (start - pad)                          # the crop's rows / columns in the resized image
+        inside = (at >= 0) & (at < n_new)
+        at = np.where(inside, n_new - 1 - at if flip else at, 0)
+        out.append(np.where(inside, src[at], -1).astype(np.int32))
+    return out[0], out[1]
 
 
 def _box_weights(radius):
@@ -104,7 +128,10 @@ def _record(p, raw_off, crop_size):
 
 class DeviceAugmenter:
     """`aug(images, params) -> (wimg, simg, img_box)`: images = list of decoded uint8 [h,w,3] arrays, params = list of
-    draw_params(...) dicts.  `debug=True` also returns the uint8 stages (crop, weak, strong) for parity tests."""
+    draw_params(...) dicts.  `debug=True` also returns the uint8 stages (crop, weak, strong) for parity tests.
+    `labels` (--gt_stats): a list of (gt uint8 [h,w], src_y, src_x) per image (label_tables); the maps and tables ride in the same pinned
+    staging buffer and the same H2D copy as the images, cosa_augment_labels gathers them into gt [B,S,S] uint8 on the device, and that
+    tensor is returned as one more element.  Without `labels` the call and its return are what they were."""
 
     def __init__(self, crop_size=448, device="cuda"):
         self.crop_size = crop_size
@@ -113,7 +140,7 @@ class DeviceAugmenter:
         if L.cosa_augment_record_bytes() != _REC_INTS * 4:
             raise _C.CosaError("DeviceAugmenter: record layout mismatch with libcosa_hip")
 
-    def __call__(self, images, params, debug=False):
+    def __call__(self, images, params, debug=False, labels=None):
         B, S, dev = len(images), self.crop_size, self.device
         if B == 0 or len(params) != B:
             raise ValueError("DeviceAugmenter: one parameter dict per image")
@@ -123,6 +150,20 @@ class DeviceAugmenter:
                 raise ValueError("DeviceAugmenter: images must be uint8 [h,w,3] matching their parameters")
             offs.append(total)
             total += (im.size + 255) // 256 * 256
+        if labels is not None:
+            # behind the images: the B maps (each 256-byte aligned), then maps int64 [B][3] and tables int32 [B][2][S] of cosa_augment_labels
+            if len(labels) != B:
+                raise ValueError("DeviceAugmenter: one (gt, src_y, src_x) per image")
+            gt_offs = []
+            for (gt, sy, sx), p in zip(labels, params):
+                if gt.dtype != np.uint8 or gt.shape != (p["h"], p["w"]):
+                    raise ValueError("DeviceAugmenter: a ground-truth map must be uint8 [h,w] of its image's size")
+                if any(t.dtype != np.int32 or t.shape != (S,) for t in (sy, sx)) or sy.max() >= p["h"] or sx.max() >= p["w"]:
+                    raise ValueError("DeviceAugmenter: source tables must be int32 [crop_size] with entries inside the map (label_tables)")
+                gt_offs.append(total)
+                total += (gt.size + 255) // 256 * 256
+            maps_off, tables_off = total, total + (B * 24 + 255) // 256 * 256
+            total = tables_off + B * 2 * S * 4
         raw = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         rawn = raw.numpy()
         recs = torch.empty((B, _REC_INTS), dtype=torch.int32, pin_memory=True)
@@ -132,6 +173,13 @@ class DeviceAugmenter:
             rec, rows = _record(p, offs[i], S)
             recs[i] = torch.from_numpy(rec)
             max_rows = max(max_rows, rows)
+        if labels is not None:
+            maps = rawn[maps_off:maps_off + B * 24].view(np.int64).reshape(B, 3)
+            tables = rawn[tables_off:tables_off + B * 2 * S * 4].view(np.int32).reshape(B, 2, S)
+            for i, (gt, sy, sx) in enumerate(labels):
+                rawn[gt_offs[i]:gt_offs[i] + gt.size] = np.ascontiguousarray(gt).reshape(-1)
+                maps[i] = (gt_offs[i], gt.shape[1], gt.shape[0])
+                tables[i, 0], tables[i, 1] = sy, sx
         raw_d = raw.to(dev, non_blocking=True)
         recs_d = recs.to(dev, non_blocking=True)
         wimg = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
@@ -143,6 +191,10 @@ class DeviceAugmenter:
                                       _C.ptr(stages[1]), _C.ptr(stages[2]), _C.ptr(ws), ws.numel(), _C.stream_ptr()),
                  "cosa_augment_batch")
         img_box = torch.from_numpy(np.stack([p["img_box"] for p in params]))
-        if debug:
-            return wimg, simg, img_box, stages
-        return wimg, simg, img_box
+        out = (wimg, simg, img_box, stages) if debug else (wimg, simg, img_box)
+        if labels is None:
+            return out
+        gt_d = torch.empty((B, S, S), device=dev, dtype=torch.uint8)
+        _C.check(L.cosa_augment_labels(_C.ptr(raw_d), raw_d.numel(), _C.ptr(raw_d[maps_off:]), _C.ptr(raw_d[tables_off:]), B, S, _C.ptr(gt_d),
+                                       _C.stream_ptr()), "cosa_augment_labels")
+        return out + (gt_d,)

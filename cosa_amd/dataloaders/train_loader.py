@@ -6,7 +6,9 @@ Pillow pipeline per image; here the workers decode and DRAW (same generators, sa
 the worker process), and the batch is augmented on the GPU by DeviceAugmenter.  Iterating yields what main.py:114 unpacks:
 
     img_name (list of str), wimg [b,3,S,S], simg [b,3,S,S] (device float32), cls_label [b,C] (uint8 -> as stored), img_box [b,4]
-"""
+
+With --gt_stats the dataset has a `gt_dir`: the worker also decodes the image's ground-truth map and draws up its
+source tables, and the loader yields a sixth element, gt [b,S,S] uint8 on the device.  Without it nothing here reads a PNG."""
 import os
 
 import numpy as np
@@ -14,7 +16,7 @@ import torch
 from PIL import Image
 from torch.utils.data import DataLoader, Dataset
 
-from .augment import DeviceAugmenter, draw_params
+from .augment import DeviceAugmenter, draw_params, label_tables
 
 
 def load_img_name_list(img_name_list_path):
@@ -26,11 +28,13 @@ def load_cls_label_list(name_list_dir):
 
 
 class _ClsDatasetNew(Dataset):
-    """image list + one-hot labels; __getitem__ -> (img_name, decoded uint8 image, draws, cls_label)"""
+    """image list + one-hot labels; __getitem__ -> (img_name, decoded uint8 image, draws, cls_label), and with a `gt_dir` one more
+    element: (ground-truth map uint8 [h,w], src_y, src_x) -- decoded after the draws, without a random number"""
 
-    def __init__(self, img_dir, name_list_dir, split, rescale_range, crop_size, num_classes):
+    def __init__(self, img_dir, name_list_dir, split, rescale_range, crop_size, num_classes, gt_dir=None):
         super().__init__()
         self.img_dir = img_dir
+        self.gt_dir = gt_dir
         self.name_list = load_img_name_list(os.path.join(name_list_dir, split + '.txt'))
         self.label_list = load_cls_label_list(name_list_dir=name_list_dir)
         self.rescale_range = rescale_range
@@ -44,32 +48,43 @@ class _ClsDatasetNew(Dataset):
         img_name = str(self.name_list[idx])
         image = np.asarray(Image.open(os.path.join(self.img_dir, img_name + '.jpg')).convert('RGB'))
         params = draw_params(image.shape[0], image.shape[1], crop_size=self.crop_size, scale_range=self.rescale_range)
-        return img_name, image, params, self.label_list[img_name]
+        if self.gt_dir is None:
+            return img_name, image, params, self.label_list[img_name]
+        path = os.path.join(self.gt_dir, img_name + '.png')
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"--gt_stats: no ground-truth map {path}")
+        gt = np.asarray(Image.open(path))                                    # class indices (L or P mode), as _SegDataset reads them
+        if gt.dtype != np.uint8 or gt.shape != image.shape[:2]:
+            raise ValueError(f"--gt_stats: {path} is {gt.dtype} {gt.shape}, its image is {image.shape[:2]}: a uint8 map of the image's size "
+                             f"is expected")
+        return img_name, image, params, self.label_list[img_name], (gt,) + label_tables(params, self.crop_size)
 
 
 class VOC12ClsDatasetNew(_ClsDatasetNew):
     """dataloaders/voc.py:219-305"""
 
     def __init__(self, root_dir, name_list_dir=None, split='train_aug', stage='train', rescale_range=[0.5, 2.0], crop_size=448,
-                 img_fliplr=True, ignore_index=255, num_classes=21, aug=True, **kwargs):
+                 img_fliplr=True, ignore_index=255, num_classes=21, aug=True, gt_dir=None, **kwargs):
         assert aug
         super().__init__(os.path.join(root_dir, 'JPEGImages_test' if split == 'test' else 'JPEGImages'), name_list_dir, split,
-                         rescale_range, crop_size, num_classes)
+                         rescale_range, crop_size, num_classes, gt_dir=gt_dir)
 
 
 class COCOClsDatasetNew(_ClsDatasetNew):
     """dataloaders/coco.py:70-140"""
 
     def __init__(self, root_dir, name_list_dir=None, split='train', stage='train', rescale_range=[0.5, 2.0], crop_size=448,
-                 img_fliplr=True, ignore_index=255, num_classes=81, aug=True, **kwargs):
+                 img_fliplr=True, ignore_index=255, num_classes=81, aug=True, gt_dir=None, **kwargs):
         assert aug
         splitclean = 'val' if split[:3] == 'val' else split
-        super().__init__(os.path.join(root_dir, splitclean + '2014'), name_list_dir, split, rescale_range, crop_size, num_classes)
+        super().__init__(os.path.join(root_dir, splitclean + '2014'), name_list_dir, split, rescale_range, crop_size, num_classes,
+                         gt_dir=gt_dir)
 
 
 def _collate(samples):
-    names, images, params, labels = zip(*samples)
-    return list(names), list(images), list(params), torch.from_numpy(np.stack([np.asarray(l) for l in labels]))
+    names, images, params, labels, *gts = zip(*samples)
+    out = list(names), list(images), list(params), torch.from_numpy(np.stack([np.asarray(l) for l in labels]))
+    return out + (list(gts[0]),) if gts else out                 # (a dataset with a gt_dir: the (gt, src_y, src_x) of every image)
 
 
 class DeviceTrainLoader:
@@ -99,9 +114,25 @@ class DeviceTrainLoader:
         return self._augmented(inner)
 
     def _augmented(self, inner):
-        for names, images, params, labels in inner:
-            wimg, simg, img_box = self.augment(images, params)
-            yield names, wimg, simg, labels, img_box
+        for names, images, params, labels, *gts in inner:
+            if gts:                                              # a dataset with a gt_dir: the 6-tuple
+                wimg, simg, img_box, gt = self.augment(images, params, labels=gts[0])
+                yield names, wimg, simg, labels, img_box, gt
+            else:
+                wimg, simg, img_box = self.augment(images, params)
+                yield names, wimg, simg, labels, img_box
+
+
+def train_gt_dir(args):
+    """the directory of the training images' ground-truth maps when --gt_stats is set, else None: --gt_dir, or the one the Seg datasets
+    read (VOC12SegDataset / COCOSegDataset below)"""
+    if not getattr(args, "gt_stats", False):
+        return None
+    if getattr(args, "gt_dir", None):
+        return args.gt_dir
+    if args.dataset == 'VOC12':
+        return os.path.join(args.voc12_root, 'SegmentationClassAug')
+    return os.path.join(args.coco_root, 'SegmentationClass/train2014')
 
 
 def build_train_datasetv2(args):
@@ -110,11 +141,11 @@ def build_train_datasetv2(args):
     if args.dataset == 'VOC12':
         return VOC12ClsDatasetNew(root_dir=args.voc12_root, name_list_dir=name_dir or './dataloaders/voc/', split='train_aug',
                                   stage='train', aug=True, rescale_range=args.scales, crop_size=args.crop_size, img_fliplr=True,
-                                  ignore_index=args.ignore_index, num_classes=args.num_classes)
+                                  ignore_index=args.ignore_index, num_classes=args.num_classes, gt_dir=train_gt_dir(args))
     if args.dataset == 'COCO':
         return COCOClsDatasetNew(root_dir=args.coco_root, name_list_dir=name_dir or './dataloaders/coco/', split='train', stage='train',
                                  aug=True, rescale_range=args.scales, crop_size=args.crop_size, img_fliplr=True,
-                                 ignore_index=args.ignore_index, num_classes=args.num_classes)
+                                 ignore_index=args.ignore_index, num_classes=args.num_classes, gt_dir=train_gt_dir(args))
     raise NotImplementedError
 
 

@@ -78,6 +78,10 @@ def check_supported(args):
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
     if args.segconf_thre != 0.25:
         notes.append("--segconf_thre: only read by cam_loss v3, which is not built")
+    if getattr(args, "gt_stats", False) and not (getattr(args, "gt_dir", None) or
+                                                 (args.voc12_root if args.dataset == 'VOC12' else args.coco_root)):
+        raise ValueError("--gt_stats true needs the ground-truth maps of the training images: give the dataset root (--voc12_root / "
+                         "--coco_root: its SegmentationClassAug / SegmentationClass/train2014) or --gt_dir")
     for n in notes:
         print("note:", n, flush=True)
 
@@ -180,9 +184,9 @@ def main(args):
         if tstats_on and (n_iter + 1) % args.log_iters == 0:
             trainer.request_tensor_stats()                                         # this step closes the interval: it samples the table
         for _micro in range(n_micro):                                             # the last call applies the mean gradient; `acc` sums over all
-            it, (img_name, wimg, simg, cls_label, img_box) = next_batch(it, new_iter, pos)
+            it, (img_name, wimg, simg, cls_label, img_box, *gt) = next_batch(it, new_iter, pos)      # (gt: the sixth element of --gt_stats)
             cls_label = cls_label.to(device, non_blocking=True)
-            logs = trainer.step(wimg, simg, cls_label, img_box, n_iter)
+            logs = trainer.step(wimg, simg, cls_label, img_box, n_iter, *gt)
             with torch.no_grad():                                                 # main.py:257-268, without the per-iteration .item() syncs
                 ap, ok = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_logits"].float()))
                 apa, oka = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_aux_logits"].float()))
@@ -202,7 +206,7 @@ def main(args):
                 line = ("Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  "
                         "cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, reg_loss: %.4f ..."
                         % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
-                for m in monitors.MONITORS:                                             # (a monitor that is off: the line as ever)
+                for m in monitors.ROWS:                                                 # (a monitor that is off: the line as ever)
                     if m.name in host:
                         summary = host[m.name] if m.summary is None else m.summary(trainer, args, host[m.name])
                         if m.gate(summary):

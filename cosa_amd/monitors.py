@@ -1,5 +1,5 @@
-"""The optional run-time monitors as ONE table: the gradient guard, --label_stats, --tensor_stats, --teacher_check_iters
-and --student_check_iters.  A row says what the launcher's log interval (main.read_interval and the log block), the jsonl files and the
+"""The optional run-time monitors as ONE table: the gradient guard, --label_stats, --tensor_stats, --teacher_check_iters,
+--student_check_iters and (ROWS' last) --gt_stats.  A row says what the launcher's log interval (main.read_interval and the log block), the jsonl files and the
 state files (checkpoint.TrainState) need to know about a monitor; the kernels, their torch partners and the summaries are the monitors' own
 and live where they always did (utils/seg_helper.py, utils/torch_helper.py, CoSATrainer).  Adding a monitor is adding a row."""
 import json
@@ -89,6 +89,14 @@ def _student_check_line(summary, targs):
         targs.student_check_mode, summary["seg"]["rel_l2"], summary["seg_agree"], summary["flip_hist"][3], summary["loss_rel"])
 
 
+def _gt_stats_line(summary, targs):
+    """` gt: main 0.412 (lab 0.731), aux 0.388, student 0.295`: the mIoUs against ground truth as fractions -- the main labels' over the
+    pixels that carry one, with the share of ground-truth pixels that do; `-` for the auxiliary map where the run has none"""
+    aux = "%.3f" % summary["aux"]["miou"] if summary["aux"]["pixels"] else "-"
+    return " gt: main %.3f (lab %.3f), aux %s, student %.3f" % (summary["main"]["miou"], summary["main"]["labelled"], aux,
+                                                                 summary["student"]["miou"])
+
+
 # in the order in which the log line shows them
 MONITORS = (
     Monitor("guard", lambda tr: tr.guard_state, _guard_pack, lambda g, flat: list(flat), _keep, None, _guard_line, None, _always,
@@ -121,12 +129,22 @@ MONITORS = (
             ("the file holds a student check's counters and this run makes no checks (--student_check_iters 0): the entry is ignored",
              "written without a student check: this run's check counters start at zero")),
 )
-BY_NAME = {m.name: m for m in MONITORS}
+# MONITORS is the five monitors of the training arithmetic, as tests/test_monitors_cpu.py pins it row by row (and with it
+# checkpoint.TrainState._optional_notes); ROWS is the whole table: those five and the monitor of the data, --gt_stats.  What walks the table
+# -- active(), the launcher's log block, the state files' optional entries -- walks ROWS.
+ROWS = MONITORS + (
+    Monitor("gt_stats", lambda tr: getattr(tr, "gt_stats_state", None), _counts_pack, _counts_unpack, _zero,
+            lambda tr, args, v: seg_helper.gt_stats_summary(v, args.num_classes), _gt_stats_line, lambda targs: {}, _always,
+            "aux.gt_stats.counters",
+            ("the file holds ground-truth statistics and this run does not collect them (--gt_stats false): the entry is ignored",
+             "written without ground-truth statistics: this run's ground-truth counters start at zero")),
+)
+BY_NAME = {m.name: m for m in ROWS}
 
 
 def active(trainer):
     """[(Monitor, its tensors)] of the monitors `trainer` has on, in the table's order: what main.read_interval takes"""
-    return [(m, t) for m, t in ((m, m.tensors(trainer)) for m in MONITORS) if t is not None]
+    return [(m, t) for m, t in ((m, m.tensors(trainer)) for m in ROWS) if t is not None]
 
 
 def monitor_record(m, summary, n_iter, targs):

@@ -40,7 +40,7 @@ def default_args(dataset="VOC12", **over):
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
              clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
-             teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32")
+             teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -248,6 +248,12 @@ class CoSATrainer:
             self.label_stats_state = seg_helper.new_label_stats(args.num_classes, device)
             self._step_scale = torch.ones(1, device=device, dtype=torch.float32)
             self._add_extra_state("label_stats.counters", self.label_stats_state)
+        # pseudo labels against ground truth: off (None) unless --gt_stats true.  The counters are state of the run
+        # (`gt_stats.counters` of extra_state) and, under data parallelism, this rank's own, as --label_stats' are
+        self.gt_stats_state = None
+        if bool(getattr(args, "gt_stats", False)):
+            self.gt_stats_state = seg_helper.new_gt_stats(args.num_classes, device)
+            self._add_extra_state("gt_stats.counters", self.gt_stats_state)
         # the teacher-precision monitor: off (None) unless --teacher_check_iters N > 0.  Every N-th optimizer step runs
         # the teacher's pass once more on `model_CK`, a third network on --teacher_check_mode operands that takes the teacher's weights at
         # that moment, and scores the two passes against each other.  The counters are state of the run (`teacher_check.counters` of
@@ -506,8 +512,12 @@ class CoSATrainer:
         return ema_low.get(), ema_high.get()
 
     # main.py:114-252 -------------------------------------------------------------------------------
-    def forward_losses(self, wimg, simg, cls_label, img_box, n_iter):
+    def forward_losses(self, wimg, simg, cls_label, img_box, n_iter, gt=None):
+        """gt: the ground-truth crops uint8 [b,S,S] of --gt_stats (required with the flag on, ignored with it off): read by the monitor's
+        reduction only, nothing the losses are made of sees it"""
         args = self.args
+        if self.gt_stats_state is not None and gt is None:
+            raise ValueError("gt_stats: the trainer was built with gt_stats=True and the step got no ground-truth crops (gt=None)")
         img_denorm = torch_helper.denormalize_img(simg) if self.refine_model is not None else simg
         fused = self.fused_losses
         if fused and self._lattice is not None:
@@ -546,6 +556,8 @@ class CoSATrainer:
             if self.label_stats_state is not None:
                 self.update_label_stats(refine_mask_label, refine_mask_label_aux, seg_pred, cls_label, img_box,
                                         cam_ps, cam_aux_ps if args.aux_cam2seg else None)
+            if self.gt_stats_state is not None:
+                self.update_gt_stats(gt, refine_mask_label, refine_mask_label_aux, seg_pred, cls_label, img_box)
         if fused:
             # one forward + one backward kernel instead of ~10 full-resolution passes (same maths, main.py:167-212)
             seg_loss, reg_loss = seg_helper.fused_seg_and_energy_loss(seg_pred, refine_mask_label, refine_mask_label_aux, simg,
@@ -617,10 +629,14 @@ class CoSATrainer:
             self._student_shadows.refresh(force=True)    # the wrap broadcast rank 0's masters: the copies were made from this rank's own
         self._ddp_pending = False
 
-    def step(self, wimg, simg, cls_label, img_box, n_iter):
+    def _gt_kw(self, gt):
+        """forward_losses' keyword of --gt_stats: with the flag off the call is what it was (a gt is ignored)"""
+        return {} if self.gt_stats_state is None else {"gt": gt}
+
+    def step(self, wimg, simg, cls_label, img_box, n_iter, gt=None):
         if self._accum_steps > 1:
-            return self._micro_step(wimg, simg, cls_label, img_box, n_iter)
-        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter)
+            return self._micro_step(wimg, simg, cls_label, img_box, n_iter, gt)
+        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
         self.optimizer.zero_grad(set_to_none=True)
         if self.device.type == "cuda" and self._student_shadows is not None:
             nn_ops.wgrad_arena_begin(self.device)        # one clear for all weight gradients of this step (they are consumed below)
@@ -647,14 +663,14 @@ class CoSATrainer:
             logs["grad_norm"] = torch_helper.guard_norm(self.guard_state).clone()     # a device scalar: no sync
         return logs
 
-    def _micro_step(self, wimg, simg, cls_label, img_box, n_iter):
+    def _micro_step(self, wimg, simg, cls_label, img_box, n_iter, gt=None):
         """--accum_steps N > 1: one micro-batch of the optimizer step `n_iter`.  Forward, losses and backward are
         a step's own (so the teacher, the warm-up weights and the LR are those of `n_iter` for all N calls; the label counters add up;
         with --usegmm the queues and trackers move on every call); the gradients go into the accumulator, and only the N-th call applies
         their mean -- optimizer, EMA, shadows, guard, the armed --tensor_stats sample.  Under DDP every call's backward all-reduces and the
         accumulator takes reduced gradients (correct by linearity; skipping the first N - 1 reductions is not built)."""
         k, n = self._micro_k, self._accum_steps
-        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter)
+        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
         self.optimizer.zero_grad(set_to_none=True)
         if self.device.type == "cuda" and self._student_shadows is not None:
             nn_ops.wgrad_arena_begin(self.device)        # this micro-step's weight gradients: consumed by accumulate() below
@@ -723,6 +739,17 @@ class CoSATrainer:
     def label_stats(self):
         """_summary_of --label_stats' counters (seg_helper.label_stats_summary)"""
         return self._summary_of(self.label_stats_state, seg_helper.label_stats_summary)
+
+    # -- pseudo labels against ground truth (DESIGN.md section 19) --
+    @torch.no_grad()
+    def update_gt_stats(self, gt, mask_main, mask_aux, seg_logits, cls_label, img_box):
+        """accumulate one step into the counters (the HIP reduction on the GPU, its torch restatement on a host trainer); no sync"""
+        fn = seg_helper.gt_stats if self.device.type == "cuda" else seg_helper.gt_stats_torch
+        fn(gt, mask_main, mask_aux, seg_logits, cls_label, img_box, self.gt_stats_state, ignore_index=self.args.ignore_index)
+
+    def gt_stats(self):
+        """_summary_of --gt_stats' counters (seg_helper.gt_stats_summary)"""
+        return self._summary_of(self.gt_stats_state, seg_helper.gt_stats_summary)
 
     # -- full-state checkpoints (cosa_amd/checkpoint.py, DESIGN.md section 9) --
     def train_state(self):

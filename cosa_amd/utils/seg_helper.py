@@ -362,6 +362,127 @@ def label_stats_summary(counters, K):
 
 
 # --------------------------------------------------------------------------------------------
+# --gt_stats: pseudo labels and the student's prediction against the ground truth of the training crops
+# --------------------------------------------------------------------------------------------
+GT_STATS_SLOTS = ("steps", "pix", "valid", "gt_other", "main", "aux", "student")     # cosa_gt_stats_layout's order
+
+
+def gt_stats_layout(K):
+    """cosa_gt_stats_layout: ({slot name: offset in elements}, number of elements) of the counter vector for K = num_classes (background
+    included): steps, pix, valid, gt_other, main[K][K+1], aux[K][K+1], student[K][K] (row: the ground-truth class; column K of main and
+    aux: the label map's ignore).  Needs no device."""
+    off = (ctypes.c_size_t * len(GT_STATS_SLOTS))()
+    n = _C.lib().cosa_gt_stats_layout(int(K), off)
+    if n == 0:
+        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
+    return {name: int(off[i]) for i, name in enumerate(GT_STATS_SLOTS)}, int(n)
+
+
+def new_gt_stats(K, device):
+    """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay far below 2^63)"""
+    return torch.zeros(gt_stats_layout(K)[1], dtype=torch.int64, device=device)
+
+
+def _gt_stats_shapes(gt, mask_main, mask_aux, seg_logits, cls_label, counters):
+    B, S = mask_main.shape[0], mask_main.shape[-1]
+    K = seg_logits.shape[1]
+    h, w = seg_logits.shape[-2:]
+    if gt.dtype != torch.uint8 or gt.shape != (B, S, S) or mask_main.shape != (B, S, S) or \
+            (mask_aux is not None and mask_aux.shape != (B, S, S)) or seg_logits.shape != (B, K, h, w) or cls_label.shape != (B, K - 1):
+        raise ValueError("gt_stats: gt must be uint8 [B,S,S], the masks [B,S,S], seg_logits [B,K,h,w] and cls_label [B,K-1]")
+    n = 4 + 2 * K * (K + 1) + K * K
+    if counters.dtype != torch.int64 or counters.shape != (n,) or not counters.is_contiguous():
+        raise ValueError(f"gt_stats: counters must be a contiguous int64 vector of {n} elements (new_gt_stats)")
+    return B, K, S, int(h), int(w)
+
+
+def gt_stats(gt, mask_main, mask_aux, seg_logits, cls_label, img_box, counters, ignore_index=255):
+    """One reduction (cosa_gt_stats) accumulated into `counters` on the device: the confusion matrices of the main label map, the
+    auxiliary one (may be None: its block stays as it is) and the student's own segmentation against the ground-truth crop `gt`
+    (uint8 [B,S,S], 255 = no ground truth), over the pixels inside the crop boxes whose ground truth is a class.  No host sync."""
+    _C.require_cuda(gt, mask_main, mask_aux, seg_logits, cls_label, counters)
+    f = lambda t: t.detach().contiguous().float() if t is not None else None
+    mask_main, mask_aux, seg_logits, cls_label = (f(t) for t in (mask_main, mask_aux, seg_logits, cls_label))
+    gt = gt.contiguous()
+    B, K, S, h, w = _gt_stats_shapes(gt, mask_main, mask_aux, seg_logits, cls_label, counters)
+    boxes = _boxes_to_device(img_box, mask_main.device)
+    _C.check(_C.lib().cosa_gt_stats(_C.ptr(gt), _C.ptr(mask_main), _C.ptr(mask_aux), _C.ptr(seg_logits), _C.ptr(cls_label), _C.ptr(boxes),
+                                    B, K, S, h, w, int(ignore_index), _C.ptr(counters), _C.stream_ptr()), "cosa_gt_stats")
+
+
+@torch.no_grad()
+def gt_stats_torch(gt, mask_main, mask_aux, seg_logits, cls_label, img_box, counters, ignore_index=255):
+    """gt_stats in plain torch, for host trainers (the role label_stats_torch plays): F.interpolate + argmax instead of the kernel's
+    spec-R resize (torch's argmax takes the first maximum, as the kernel does), the same counters in the same layout."""
+    f = lambda t: t.detach().float() if t is not None else None
+    mask_main, mask_aux, seg_logits, cls_label = (f(t) for t in (mask_main, mask_aux, seg_logits, cls_label))
+    B, K, S, h, w = _gt_stats_shapes(gt, mask_main, mask_aux, seg_logits, cls_label, counters)
+    if K > LABEL_STATS_MAX_K or h > S or w > S or 0 <= int(ignore_index) < K:
+        raise ValueError(f"gt_stats: outside the envelope (K {K} <= {LABEL_STATS_MAX_K}, h {h} and w {w} <= S {S}, ignore_index no class)")
+    dev = mask_main.device
+    off, _ = gt_stats_layout(K)
+    box = torch.as_tensor(img_box).to(device=dev, dtype=torch.int64)
+    ar = torch.arange(S, device=dev)
+    inside = ((ar[None, :, None] >= box[:, 0, None, None]) & (ar[None, :, None] < box[:, 1, None, None]) &
+              (ar[None, None, :] >= box[:, 2, None, None]) & (ar[None, None, :] < box[:, 3, None, None]))
+    g = gt.to(dev).long()
+    valid = inside & (g < K)
+    add = torch.zeros_like(counters)
+    add[off["steps"]] = 1
+    add[off["pix"]] = inside.sum()
+    add[off["valid"]] = valid.sum()
+    add[off["gt_other"]] = (inside & (g >= K) & (g != 255)).sum()
+    for name, mask in (("main", mask_main), ("aux", mask_aux)):
+        if mask is None:
+            continue
+        slot = torch.where(mask == ignore_index, torch.full_like(mask, K), mask)
+        ok = valid & (slot >= 0) & (slot <= K) & (slot == slot.floor())          # a value that is no label is not counted
+        add[off[name]:off[name] + K * (K + 1)] = torch.bincount(g[ok] * (K + 1) + slot[ok].long(), minlength=K * (K + 1))
+    student = seg_validation(F.interpolate(seg_logits, size=(S, S), mode="bilinear", align_corners=False), cls_label).argmax(dim=1)
+    add[off["student"]:off["student"] + K * K] = torch.bincount(g[valid] * K + student[valid], minlength=K * K)
+    counters += add
+
+
+def _iou_rows(mat, K, cols, strict_col=None):
+    """per-class IoU of a [K][cols] confusion matrix (row: ground truth) over its first K columns: inter / (row + column - inter); with
+    strict_col the pixels of that column (the label map's ignore) stay in their ground-truth class's union and in no intersection.  An
+    empty union gives None.  -> (iou[K], mean over the classes with a union, 0.0 when there is none)"""
+    iou = []
+    for k in range(K):
+        inter = mat[k * cols + k]
+        row = sum(mat[k * cols + c] for c in range(K)) + (mat[k * cols + strict_col] if strict_col is not None else 0)
+        col = sum(mat[t * cols + k] for t in range(K))
+        union = row + col - inter
+        iou.append(inter / union if union else None)
+    live = [v for v in iou if v is not None]
+    return iou, (sum(live) / len(live) if live else 0.0)
+
+
+def gt_stats_summary(counters, K):
+    """The counter vector (tensor, array or list; a device tensor synchronises) as figures: steps, pix, valid_frac (valid / pix) and
+    gt_other at the top; for `main` and `aux` the share of valid pixels that carry a label (`labelled`), `miou` / `iou[K]` from the
+    confusion matrix with the ignore column dropped (the quality of the labels that exist), and `miou_strict` / `iou_strict[K]`, where an
+    ignore pixel is a miss: in its ground-truth class's union, in no intersection (quality times coverage); for `student` `miou` and
+    `iou[K]`.  A class with an empty union is None and stays out of its mean; all-zero counters give zeros, not NaN."""
+    c = [int(v) for v in (counters.tolist() if hasattr(counters, "tolist") else counters)]
+    off, n = gt_stats_layout(K)
+    if len(c) != n:
+        raise ValueError(f"gt_stats_summary: {len(c)} counters, K = {K} has {n}")
+    pix, valid = c[off["pix"]], c[off["valid"]]
+    out = {"steps": c[off["steps"]], "pix": pix, "valid_frac": valid / pix if pix else 0.0, "gt_other": c[off["gt_other"]]}
+    for name in ("main", "aux"):
+        mat = c[off[name]:off[name] + K * (K + 1)]
+        total, ign = sum(mat), sum(mat[k * (K + 1) + K] for k in range(K))
+        iou, miou = _iou_rows(mat, K, K + 1)
+        iou_s, miou_s = _iou_rows(mat, K, K + 1, strict_col=K)
+        out[name] = {"labelled": (total - ign) / valid if valid else 0.0, "miou": miou, "iou": iou, "miou_strict": miou_s, "iou_strict": iou_s,
+                     "pixels": total}
+    iou, miou = _iou_rows(c[off["student"]:off["student"] + K * K], K, K)
+    out["student"] = {"miou": miou, "iou": iou}
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # the --teacher_check monitor: two teacher passes on two operand modes, scored against each other (DESIGN.md section 15)
 # --------------------------------------------------------------------------------------------
 TEACHER_CHECK_SETS = ("cam", "aux", "tgt")                       # map sets, then label pairs: cosa_teacher_check_layout's order

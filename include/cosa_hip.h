@@ -109,6 +109,15 @@ size_t cosa_augment_workspace_bytes(int B, int S, int max_rows);
 int cosa_augment_batch(const uint8_t *raw, const void *records, int B, int S, int max_rows, float *wimg, float *simg,
                        uint8_t *crop_u8, uint8_t *weak_u8, uint8_t *strong_u8, void *workspace, size_t workspace_bytes,
                        void *stream);
+/* Ground-truth maps through the same geometry (--gt_stats): out[b][y][x] = map_b[src_y[y]][src_x[x]], or 255
+ * where either table entry is -1 (or lies outside its map, or the map outside raw: nothing is read there).  raw: device uint8
+ * [raw_bytes], the buffer the maps ride in;
+ * maps: device int64 [B][3] = (byte offset of image b's [rows][pitch] uint8 map in raw, pitch, rows), 8-byte aligned; tables: device
+ * int32 [B][2][S] = src_y | src_x (cosa_amd/dataloaders/augment.py: label_tables: Pillow's NEAREST resize, the flip, the padding and
+ * the crop as one source row per output row and one source column per output column); out: device uint8 [B,S,S].  One launch.
+ * Anything outside the envelope is COSA_EINVAL with nothing launched. */
+int cosa_augment_labels(const uint8_t *raw, size_t raw_bytes, const long long *maps, const int32_t *tables, int B, int S, uint8_t *out,
+                        void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * utils/seg_helper.py:924-943  rungmm -- the adaptive-threshold fit of main.py:138-151,174-184:
@@ -717,6 +726,34 @@ size_t cosa_label_stats_layout(int K, size_t *offsets);
 int cosa_label_stats(const float *mask_main, const float *mask_aux, const float *seg_logits, const float *cls_label,
                      const int32_t *boxes, const float *cam, const float *cam_aux, int B, int K, int S, int h, int w,
                      int ignore_index, unsigned long long *counters, float *step_scale, void *workspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * --gt_stats: pseudo labels and the student's prediction scored against the ground truth of the
+ * training crops, one reduction per step accumulated on the device in a vector of uint64 counters.
+ * cosa_gt_stats_layout: THE definition of that vector for host and device.  K = num_classes (background included, 2..128).
+ *   offsets[COSA_GT_STATS_SLOTS] (in elements) of, in order: steps; pix (pixels inside the crop boxes); valid (of those, the
+ *   ones whose ground truth is a class 0..K-1); gt_other (in-box pixels whose ground truth is neither a class nor 255: treated
+ *   as ignore); main[K][K+1] (row: ground-truth class, column: the main label map's value, column K = its ignore);
+ *   aux[K][K+1]; student[K][K] (column: the student's label).  Returns the number of elements, 4 + 2K(K+1) + K^2; 0 on bad
+ *   arguments.
+ * cosa_gt_stats: gt uint8 [B,S,S] (cosa_augment_labels' output); mask_main / mask_aux fp32 [B,S,S] in {0..K-1, ignore_index}
+ *   (cosa_cam2mask_multi's output), mask_aux may be NULL: the aux block's bytes stay as they are; seg_logits fp32 [B,K,h,w];
+ *   cls_label fp32 [B,K-1]; boxes int32 [B,4] (y0,y1,x0,x1).  Only pixels inside an image's box with a class as ground truth
+ *   reach the matrices: pixels outside a box, an empty box and gt = 255 contribute nothing.  A mask value that is neither an
+ *   integer in 0..K-1 nor ignore_index is counted in pix and valid only.  Student label: cosa_label_stats' (the same device
+ *   function): planes resized by spec R, absent classes at -1e5, first maximum in class order.  The counters accumulate from
+ *   call to call with 64-bit integer atomics (the same bytes in any order and on every run) and steps advances by one.  Where
+ *   the three matrices fit 40 KiB of LDS as u32 (K <= 58) a workgroup counts there and flushes its non-zero entries; above
+ *   that the counts go to global memory directly.  Envelope as cosa_label_stats: K <= 128, S, h, w > 0, h and w <= S,
+ *   ignore_index no class; anything else is COSA_EINVAL, nothing is launched or clamped.  One launch, no workspace.
+ * cosa_gt_stats_uses_lds: 1 when K takes the LDS path, 0 for global atomics, -1 on bad K.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_GT_STATS_SLOTS 7
+size_t cosa_gt_stats_layout(int K, size_t *offsets);
+int cosa_gt_stats(const uint8_t *gt, const float *mask_main, const float *mask_aux, const float *seg_logits, const float *cls_label,
+                  const int32_t *boxes, int B, int K, int S, int h, int w, int ignore_index, unsigned long long *counters,
+                  void *stream);
+int cosa_gt_stats_uses_lds(int K);
 
 /* ---------------------------------------------------------------------------------------
  * Per-tensor training diagnostics: norms, the EMA gap and the blame counters, over the record table
