@@ -186,6 +186,16 @@ _SIGS.update({
     "cosa_attn_fwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
     "cosa_layernorm_f32out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "cosa_im2col_flip_f32_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # the "f64" operand family (csrc/f64_kernels.hip; mode "fp64") and the criterion per plane (csrc/conformance_kernels.hip)
+    "cosa_gemm_f64": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
+    "cosa_conv3x3_dilated_f64": (c_int, [c_void_p] * 3 + [c_int] * 10 + [c_void_p]),
+    "cosa_attn_fwd_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_int, c_void_p]),
+    "cosa_layernorm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
+    "cosa_im2col_flip_f64_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "cosa_resize_bilinear_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "cosa_cam_flip_merge_upsample_f64": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p]),
+    "cosa_cam_minmax_norm_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cosa_conformance_planes": (c_int, [c_void_p] * 6 + [c_int, c_int] + [ctypes.c_double] * 3 + [c_void_p] * 3),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

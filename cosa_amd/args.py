@@ -75,7 +75,8 @@ EXTRA = [
                                              # mIoU); logged and written to <output_dir>/teacher_check.jsonl every log_iters; training is untouched
     ("teacher_check_mode", str, "auto"),     # any --teacher_precision value; auto: bf16x3 against an fp16x3 teacher (the same kernels with fp32's
                                              # exponent range: an fp16 overflow shows), fp16x3 against every other teacher mode; fp32: the teacher's mode against
-                                             # the reference's arithmetic -- the figure is then the conformance criterion's own
+                                             # the reference's arithmetic -- the figure is then the conformance criterion's own;
+                                             # fp64: against a float64 pass on the f64 MFMA (section 20; a check mode only: --teacher_precision fp64 is refused)
     # the student-forward monitor; 0: nothing changes
     ("student_check_iters", int, 0),         # every N-th optimizer step runs the student's weights of that step through a second, no-grad forward on
                                              # --student_check_mode operands over the batch it trained on and scores the training forward against it on the

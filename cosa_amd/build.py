@@ -48,6 +48,9 @@ SOURCES = {
     # the "f32" operand family: fp32 operands on the f32-input MFMA.  No contraction: the MFMA's chain is the only fused arithmetic, what
     # else is an fma is written fmaf; no fast math (expf / erff at their full accuracy, infinities honoured by the tail-key mask)
     "f32_kernels.hip": EXACT,
+    # the "f64" operand family on the f64 MFMA (mode "fp64") and the criterion's per-plane reduction: the same rules in float64
+    "f64_kernels.hip": EXACT,
+    "conformance_kernels.hip": EXACT,
 }
 
 

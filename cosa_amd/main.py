@@ -26,7 +26,7 @@ from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
-from .train_step import CoSATrainer, check_iters, default_args
+from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher
 from .utils import torch_helper
 
 
@@ -73,6 +73,7 @@ def check_supported(args):
         raise ValueError(f"--accum_steps {args.accum_steps}: a positive number of micro-batches per optimizer step")
     for which in ("teacher", "student"):
         check_iters(args, which, flag="--")
+    refuse_fp64_teacher(getattr(args, "teacher_precision", "auto"), flag="--")
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")

@@ -52,6 +52,15 @@ class LargeFOV(nn.Module):
             seg = nn_ops.reference_op("linear", f"LargeFOV.conv8 ({tuple(w8.shape)}, fp32)", y, w8, None).float()
         return seg.view(B, h, w, -1).permute(0, 3, 1, 2).contiguous()
 
+    def forward_tokens_f64(self, tok, B, h, w):
+        """no-grad float64 path (mode "fp64"): conv6 / conv7 as implicit GEMMs on the f64 MFMA over the float64 tokens and the fp32 master
+        weights, conv8 through cosa_gemm_f64 at its own width.  tok [B, h*w, 768] float64 (may be the strided view) -> seg [B, classes, h, w]"""
+        y = nn_ops.conv3x3_dilated_f64(tok, self.conv6.weight, B, h, w, self.dilation, relu=True)
+        y = nn_ops.conv3x3_dilated_f64(y.view(B, h * w, -1), self.conv7.weight, B, h, w, self.dilation, relu=True)
+        w8 = self.conv8.weight.detach().reshape(self.conv8.weight.shape[0], -1)
+        seg = nn_ops.gemm_f64(y, w8, None, B * h * w, w8.shape[0], w8.shape[1])
+        return seg.view(B, h, w, -1).permute(0, 3, 1, 2).contiguous()
+
     def forward_tokens_train(self, tok, B, h, w):
         """bf16 training path (autograd): conv6 / conv7 forward, input- and weight-gradient on our MFMA kernels
         (nn_ops.DilatedConvReluFn), conv8 (1x1) as a GEMM over the tokens.  tok [B, h*w, 768] bf16 -> seg [B, classes, h, w] fp32"""
@@ -80,6 +89,7 @@ class VITNetwork(nn.Module):
     # GEMMs: evaluate() turns it on so that grouped loader items reproduce the one-at-a-time scores exactly; the training step's
     # teacher keeps the (tuned) library GEMMs, which are faster there (skinny VALU kernel: 1.57 ms per step against ~0.4 ms)
     batch_invariant_heads = False
+    F64_CHUNK = 8          # images per float64 pass of forward_multi: 0.34 GB of operand rows per image at 448^2 x 3 scales x 2 flips -> 2.7 GB
 
     def __init__(self, backbone, num_classes, pretrained=True, aux_layer=-3, isgap=False, decoder='LargeFOV',
                  compute_dtype=torch.bfloat16, pretrained_path=None):
@@ -114,7 +124,9 @@ class VITNetwork(nn.Module):
     def set_nograd_precision(self, mode):
         """operand precision of the no-grad passes (teacher pseudo-labels, evaluation): "bf16" (8 significant bits), "fp16" (11; the
         same kernels built for fp16 operands), "fp32" (the reference's arithmetic: fp32 operands from the fp32 masters on the f32-input MFMA, fp32
-        decoder; no suffix, no 16-bit copy of anything), "bf16x3" (16; hi + lo bf16 halves, three MFMA terms), "fp16x3" (22: hi + lo fp16 halves, the same three
+        decoder; no suffix, no 16-bit copy of anything), "fp64" (every no-grad pass in float64 on the f64 MFMA, the
+        fp32 masters widened inside the kernels, float64 outputs; no suffix; the float64 side of the criterion -- a check mode, refused as a training
+        teacher; section 20), "bf16x3" (16; hi + lo bf16 halves, three MFMA terms), "fp16x3" (22: hi + lo fp16 halves, the same three
         terms at the same cost), "fp16c8" (fp16 + 8-bit correction
         terms on the block-scaled MFMA, ~14 bits at twice the 16-bit work; attention operands plain fp16) or "fp16c4" (the same with FP4 MX-block
         correction terms at 4x the fp16 rate: ~1.6x the 16-bit work); "-n" suffix: blocks from index n on plain fp16, "-nmk": their MLP halves (fc1, fc2) from
@@ -125,12 +137,12 @@ class VITNetwork(nn.Module):
         mx = re.fullmatch(r"(?:x(\d+)(?:m(\d+))?)?(?:c(\d+))?", tail) if tail and not m else None     # "fp16c8-x6": the blocks BELOW index 6 on bf16x3
         #                       operands (round 5); "fp16c8-x6m4": their attention halves below 6, their MLP halves below 4; "fp16c8-x2c6" / "fp16c8-c6":
         #                       the blocks from index 6 on take qkv / fc1 / fc2 on fp16c4 operands (fp16c8 base only)
-        assert base in ("bf16", "fp16", "fp32", "bf16x3", "fp16x3", "fp16c8", "fp16c4") and (bool(tail) == bool(sep)) and \
+        assert base in ("bf16", "fp16", "fp32", "fp64", "bf16x3", "fp16x3", "fp16c8", "fp16c4") and (bool(tail) == bool(sep)) and \
             (not tail or (base in ("fp16c8", "fp16c4") and (m or mx))), mode
         self.check_nograd_precision(mode)
-        self.set_compute_dtype(torch.float32 if base == "fp32" else torch.float16 if base in ("fp16", "fp16x3", "fp16c8", "fp16c4") else torch.bfloat16)
+        self.set_compute_dtype(torch.float32 if base == "fp32" else torch.float64 if base == "fp64" else torch.float16 if base in ("fp16", "fp16x3", "fp16c8", "fp16c4") else torch.bfloat16)
         # "fp16x3" (round 6): the three-term path with fp16 halves (hi + lo: 11 + 11 significant bits; bf16x3: 8 + 8) -- same kernels, same cost
-        self.encoder.precision = "bf16x3" if base == "fp16x3" else "f32" if base == "fp32" else (base if base in ("bf16x3", "fp16c8", "fp16c4") else None)
+        self.encoder.precision = "bf16x3" if base == "fp16x3" else "f32" if base == "fp32" else "f64" if base == "fp64" else (base if base in ("bf16x3", "fp16c8", "fp16c4") else None)
         self.encoder.x3_dtype = torch.float16 if base == "fp16x3" else torch.bfloat16
         self.encoder.c8_plain_from = int(m.group(1)) if m else None
         self.encoder.c8_plain_mlp_from = int(m.group(2)) if m and m.group(2) else None
@@ -186,8 +198,8 @@ class VITNetwork(nn.Module):
         return y
 
     def refresh_shadows(self):
-        """16-bit shadows of every parameter, current as of this call (nn_ops.ensure_shadows); a no-op in fp32 mode / on the host"""
-        if self.compute_dtype != torch.float32 and self.classifier.weight.is_cuda:
+        """16-bit shadows of every parameter, current as of this call (nn_ops.ensure_shadows); a no-op in the fp32 / fp64 modes / on the host"""
+        if self.compute_dtype not in (torch.float32, torch.float64) and self.classifier.weight.is_cuda:
             nn_ops.ensure_shadows(self, self.compute_dtype)
 
     def forward_multi(self, xs, flip_pairs=False, need_cls=True):
@@ -198,6 +210,13 @@ class VITNetwork(nn.Module):
         for x in xs:
             _C.require_cuda(x)
         self.refresh_shadows()
+        if self.encoder.precision == "f64" and xs[0].shape[0] > self.F64_CHUNK:
+            # float64 operand rows of a whole b = 16 x 448^2 batch are 5.4 GB: walk the batch in chunks of images.  Every kernel of the
+            # family is batch-invariant, so this moves no bit.
+            parts = [self.forward_multi([x[i:i + self.F64_CHUNK] for x in xs], flip_pairs, need_cls) for i in range(0, xs[0].shape[0], self.F64_CHUNK)]
+            nf = 2 if flip_pairs else 1
+            join = lambda ts: None if ts[0] is None else torch.cat([t.reshape((nf, -1) + tuple(t.shape[1:])) for t in ts], dim=1).flatten(0, 1)
+            return [tuple(join([pt[si][k] for pt in parts]) for k in range(6)) for si in range(len(xs))]
         feats = self.encoder._forward_features_fused_multi(xs, flip_pairs=flip_pairs)
         if flip_pairs:          # _heads reads only the shape of its image argument
             xs = [torch.empty((2 * x.shape[0],) + tuple(x.shape[1:]), device="meta") for x in xs]
@@ -241,9 +260,39 @@ class VITNetwork(nn.Module):
         cls_aux = self._cls_head(self._pool(a_cls), self.aux_classifier.weight, dt)
         return cls_x4, cls_aux, x4, seg, cam, cam_aux
 
+    def _heads_f64(self, x, feats, cam_only, seg_only, need_cls):
+        """the heads of a float64 no-grad pass: decoder, CAM heads and classification heads through cosa_gemm_f64 on the fp32 master weights;
+        every output float64"""
+        B = x.shape[0]
+        _, tok, tok_aux, _ = feats
+        p = self.encoder.patch_size
+        h, w = x.shape[-2] // p, x.shape[-1] // p
+        D = tok.shape[-1]
+        x4 = tok.reshape(B, h, w, -1).permute(0, 3, 1, 2)
+        seg = self.decoder.forward_tokens_f64(tok, B, h, w)
+        if seg_only:
+            return seg
+        w2 = lambda m: m.weight.detach().reshape(m.weight.shape[0], -1)
+
+        def head(t, m):          # t [R, D] float64 rows (a strided view of the token buffer is fine: unit column stride) -> [R, classes]
+            return nn_ops.gemm_f64(t, w2(m), None, t.shape[0], m.weight.shape[0], D)
+
+        rows = lambda t: t.reshape(B * h * w, D) if t.is_contiguous() else t.contiguous().view(B * h * w, D)
+        nchw = lambda y: y.view(B, h, w, -1).permute(0, 3, 1, 2).contiguous()
+        cam, cam_aux = nchw(head(rows(tok), self.classifier)), nchw(head(rows(tok_aux), self.aux_classifier))
+        if cam_only:
+            return cam, cam_aux
+        if not need_cls:
+            return None, None, x4, seg, cam, cam_aux
+        cls_x4 = head(self._pool(tok).contiguous(), self.classifier)
+        cls_aux = head(self._pool(tok_aux).contiguous(), self.aux_classifier)
+        return cls_x4, cls_aux, x4, seg, cam, cam_aux
+
     def _heads(self, x, feats, cam_only, seg_only, detach, need_cls=True):
         if isinstance(feats, vitencoder.FP32Tokens):
             return self._heads_train_f32(x, feats, cam_only, seg_only, detach)
+        if self.encoder.precision == "f64" and feats[1].dtype == torch.float64:
+            return self._heads_f64(x, feats, cam_only, seg_only, need_cls)
         dt = self.compute_dtype
         B = x.shape[0]
         _, tok, tok_aux, tok32 = feats

@@ -35,7 +35,8 @@ class FP32Tokens:
 class OperandMap(typing.NamedTuple):
     """operand formats of a no-grad pass (VisionTransformer._operand_map): of the patch projection -- the family that assembles the tokens and
     closes with its LayerNorm -- and per block of the attention half and the MLP half: "plain", "x3", "c8", "c4" (qkv / fc1 / fc2 on fp16c4
-    operands in an otherwise fp16c8 half) or "f32" (fp32 operands read from the fp32 masters: all of the pass or none of it)"""
+    operands in an otherwise fp16c8 half), "f32" (fp32 operands read from the fp32 masters: all of the pass or none of it) or "f64" (float64
+    activations on the f64 MFMA, the fp32 masters widened inside the kernels: all or none likewise)"""
     patch: str
     attn: tuple
     mlp: tuple
@@ -139,6 +140,7 @@ class VisionTransformer(nn.Module):
         self.compute_dtype = compute_dtype
         self.precision = None          # "bf16x3" / "fp16c8" / "fp16c4": parity-grade operand representations of the no-grad passes;
         #                                "f32": fp32 operands on the f32-input MFMA (mode string "fp32")
+        #                                "f64": float64 operands on the f64 MFMA (mode string "fp64", section 20: a check mode)
         # residual stream of the TRAINING path: "fp32" (default since round 4: the reference trains in fp32, main.py:124-246 -- the sums
         # x + attn(..), x + mlp(..) and the gradient sums of the skip connections are formed and kept in fp32; MFMA operands stay bf16) or
         # "bf16" (rounds 1-3: the stream itself rounded to 8 significant bits after every add; kept for A/B measurements)
@@ -281,6 +283,8 @@ class VisionTransformer(nn.Module):
         depth = len(self.blocks)
         if self.precision == "f32":                   # (no 16-bit type anywhere: weights are the masters, activations fp32 buffers)
             return OperandMap("f32", ("f32",) * depth, ("f32",) * depth, False, False, None, None)
+        if self.precision == "f64":                   # (float64 activation buffers; no weight set, no shadows: the masters are widened as they are read)
+            return OperandMap("f64", ("f64",) * depth, ("f64",) * depth, False, False, None, None)
         if self.precision not in ("bf16x3", "fp16c8", "fp16c4"):
             return OperandMap("plain", ("plain",) * depth, ("plain",) * depth, False, False, self.compute_dtype, None)
         if self.precision == "bf16x3":                # (hi / lo halves of x3_dtype: "bf16x3" or "fp16x3")
@@ -348,7 +352,7 @@ class VisionTransformer(nn.Module):
     _BUFS_MAX = 8          # cached geometries (each holds ~M x 7 KB of activations): evaluation over many image sizes must not pin them all
 
     def _operand_buffers(self, fmt, dtype, pk, cols=False):
-        """persistent "x3" / "c8" / "f32" activations for the token rows of `pk` ("f32": plain fp32 rows, no augmentation block); the (1, 1, 0, ...) augmentation block of the fc1 output is set once
+        """persistent "x3" / "c8" / "f32" / "f64" activations for the token rows of `pk` ("f32" / "f64": plain fp32 / float64 rows, no augmentation block); the (1, 1, 0, ...) augmentation block of the fc1 output is set once
         here (the GEMM epilogues write the operand halves only), the other buffers get theirs from their producing kernels.  Keyed on the FULL
         token geometry (the (images, tokens) split per scale and the patch width), not on M alone: the token-shaped patch operand `cols`
         relies on its class-token rows staying zero, and another split of the same M puts class tokens where stale patch rows sit (ADVICE
@@ -359,13 +363,13 @@ class VisionTransformer(nn.Module):
         mk = lambda n: torch.zeros((pk.M, n), device=pk.dev, dtype=dtype)
         if ent is None:
             D, Hd = self.embed_dim, self.blocks[0].mlp.fc1.weight.shape[0]
-            if fmt == "f32":
+            if fmt in ("f32", "f64"):
                 ent = {"y": mk(D), "qkv": mk(3 * D), "o": mk(D), "h": mk(Hd)}
             else:
                 ent = {"y": mk(nn_ops.split_ld(D)), "qkv": mk((2 if fmt == "x3" else 1) * 3 * D), "o": mk(nn_ops.split_ld(D)), "h": mk(nn_ops.split_ld(Hd))}
                 ent["h"][:, 2 * Hd:2 * Hd + 2] = 1
         if cols and "cols" not in ent:
-            ent["cols"] = mk(pk.Kp if fmt == "f32" else nn_ops.split_ld(pk.Kp))      # (class-token rows: zero for good)
+            ent["cols"] = mk(pk.Kp if fmt in ("f32", "f64") else nn_ops.split_ld(pk.Kp))      # (class-token rows: zero for good)
         bufs[key] = ent                             # (re-inserted last: the dict is the LRU order)
         if torch.cuda.is_current_stream_capturing():
             ent["pinned"] = True
@@ -420,6 +424,10 @@ class VisionTransformer(nn.Module):
             bufs = {"f32": self._operand_buffers("f32", torch.float32, pk, cols=True)}
             xr, aux = self._blocks_nograd(self._tokens_f32(xs, pk, bufs["f32"]), pk, fmap, {}, bufs)
             a16 = xn32 = nn_ops.layernorm_f32out(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps)      # (no 16-bit tokens: the decoder runs fp32 too)
+        elif fmap.patch == "f64":
+            bufs = {"f64": self._operand_buffers("f64", torch.float64, pk, cols=True)}
+            xr, aux = self._blocks_nograd(self._tokens_f64(xs, pk, bufs["f64"]), pk, fmap, {}, bufs)
+            a16 = xn32 = nn_ops.layernorm_f64(xr, f(self.norm.weight), f(self.norm.bias), self.norm.eps)      # (float64 tokens for every head)
         else:
             c = lambda p_: nn_ops.cast_param(p_, fmap.dt16)
             xr, aux = self._blocks_nograd(self._tokens_plain(xs, pk, fmap.dt16, flip_pairs), pk, fmap, {}, {})
@@ -495,6 +503,42 @@ class VisionTransformer(nn.Module):
             xr[o0:o1].view(B, N, D)[:, 0] = row
         return xr
 
+    def _pos_f64(self, h, w):
+        """the position rows [h*w + 1, D] of a token geometry in float64: F.interpolate(bicubic) on the float64 copy of pos_embed, formed once
+        per geometry and kept until pos_embed is written again (its version counter: frozen for the student, EMA-touched for a teacher)"""
+        pe = self.pos_embed
+        key = (h, w, pe.device, "f64")
+        ent = self._pos_cache.get(key)
+        if ent is None or ent["version"] != pe._version or ent["ptr"] != pe.data_ptr():
+            with torch.no_grad():
+                g = pe[0, 1:].double().reshape(1, self._size, self._size, -1).permute(0, 3, 1, 2)
+                g = F.interpolate(g, size=(h, w), mode="bicubic", align_corners=False).reshape(-1, h * w).t()
+                rows = torch.cat((pe[0, :1].double(), g), dim=0).contiguous()
+            ent = self._pos_cache[key] = {"version": pe._version, "ptr": pe.data_ptr(), "rows": rows}
+        return ent["rows"]
+
+    def _tokens_f64(self, xs, pk, bf):
+        """the float64 family's token assembly, as `_tokens_f32`: the stream starts as the position rows, the float64 im2col rows go through
+        the patch projection on the fp32 master weight (widened in the kernel) and its residual epilogue into the stream in place, all scales
+        in one launch; the class-token rows (zero operand rows that received the bias) are written afterwards as cls + pos_0"""
+        from .. import _C
+        D, p = self.embed_dim, self.patch_size
+        xr = torch.empty((pk.M, D), device=pk.dev, dtype=torch.float64)
+        cls = self.cls_token.detach().double().reshape(D)
+        first = []
+        for x, (B, N, o0, o1) in zip(xs, pk.scales()):
+            pos = self._pos_f64(x.shape[2] // p, x.shape[3] // p)
+            xr[o0:o1].view(B, N, D).copy_(pos.unsqueeze(0).expand(B, N, D))
+            first.append(cls + pos[0])
+            xd = x.double().contiguous()                 # (fp32 inputs widen exactly; the rescaled ones arrive as float64 planes)
+            _C.check(_C.lib().cosa_im2col_flip_f64_tokens(_C.ptr(xd), _C.ptr(bf["cols"][o0:o1]), x.shape[0], x.shape[1], x.shape[2], x.shape[3], p,
+                                                          pk.nf, 1, _C.stream_ptr()), "cosa_im2col_flip_f64_tokens")
+        pe = self.patch_embed.proj
+        nn_ops.gemm_f64(bf["cols"], pe.weight.detach().reshape(D, -1), pe.bias.detach(), pk.M, D, pk.Kp, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+        for row, (B, N, o0, o1) in zip(first, pk.scales()):
+            xr[o0:o1].view(B, N, D)[:, 0] = row
+        return xr
+
     def _tokens_c8(self, xs, pk, bf, w_patch):
         from .. import _C
         xr = self._stream_and_cols(xs, pk, bf["cols"], _C.lib().cosa_im2col_flip_c8_tokens, "cosa_im2col_flip_c8_tokens")
@@ -518,6 +562,8 @@ class VisionTransformer(nn.Module):
                 self._attn_x3(xr, xn, blk, pk, bufs["x3"], W["x3"], i)
             elif fmap.attn[i] == "f32":
                 self._attn_f32(xr, xn, blk, pk, bufs["f32"])
+            elif fmap.attn[i] == "f64":
+                self._attn_f64(xr, xn, blk, pk, bufs["f64"])
             else:
                 self._attn_c8(xr, xn, blk, pk, bufs["c8"], W, i, fmap)
             xr = xn
@@ -527,6 +573,8 @@ class VisionTransformer(nn.Module):
                 self._mlp_x3(xr, blk, pk, bufs["x3"], W["x3"], i)
             elif fmap.mlp[i] == "f32":
                 self._mlp_f32(xr, blk, pk, bufs["f32"])
+            elif fmap.mlp[i] == "f64":
+                self._mlp_f64(xr, blk, pk, bufs["f64"])
             else:
                 self._mlp_c8(xr, blk, pk, bufs["c8"], W, i, fmap.mlp[i] == "c4")
             if i == aux_idx and aux_idx != depth - 1:
@@ -578,6 +626,23 @@ class VisionTransformer(nn.Module):
         nn_ops.layernorm_f32out(xr, d(blk.norm2.weight), d(blk.norm2.bias), blk.norm2.eps, out=bf["y"])
         nn_ops.gemm_f32(bf["y"], d(blk.mlp.fc1.weight), d(blk.mlp.fc1.bias), M, Hd, D, nn_ops.EPI_GELU, out=bf["h"])
         nn_ops.gemm_f32(bf["h"], d(blk.mlp.fc2.weight), d(blk.mlp.fc2.bias), M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+
+    def _attn_f64(self, xr, xn, blk, pk, bf):
+        """float64 attention half: float64 activations, the fp32 master weights and biases widened inside the kernels -- no weight set"""
+        M, D = pk.M, self.embed_dim
+        d = lambda p_: None if p_ is None else p_.detach()
+        nn_ops.layernorm_f64(xr, d(blk.norm1.weight), d(blk.norm1.bias), blk.norm1.eps, out=bf["y"])
+        nn_ops.gemm_f64(bf["y"], d(blk.attn.qkv.weight), d(blk.attn.qkv.bias), M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"])
+        for B, N, o0, o1 in pk.scales():
+            nn_ops.attn_fwd_f64(bf["qkv"][o0:o1], B, N, self.num_heads, bf["o"][o0:o1])
+        nn_ops.gemm_f64(bf["o"], d(blk.attn.proj.weight), d(blk.attn.proj.bias), M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
+
+    def _mlp_f64(self, xr, blk, pk, bf):
+        M, D, Hd = pk.M, self.embed_dim, blk.mlp.fc1.weight.shape[0]
+        d = lambda p_: p_.detach()
+        nn_ops.layernorm_f64(xr, d(blk.norm2.weight), d(blk.norm2.bias), blk.norm2.eps, out=bf["y"])
+        nn_ops.gemm_f64(bf["y"], d(blk.mlp.fc1.weight), d(blk.mlp.fc1.bias), M, Hd, D, nn_ops.EPI_GELU, out=bf["h"])
+        nn_ops.gemm_f64(bf["h"], d(blk.mlp.fc2.weight), d(blk.mlp.fc2.bias), M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
 
     def _attn_c8(self, xr, xn, blk, pk, bf, W, i, fmap):
         """fp16c8 attention half; its qkv projection may run on plain fp16 (`c8_plain_qkv`) or fp16c4 operands, its output projection on
@@ -673,7 +738,7 @@ class VisionTransformer(nn.Module):
         return FP32Tokens(xn, aux)                              # their gradients are summed in fp32; aux = block aux_idx's output, pre-norm
 
     def use_fused(self, x):
-        return (not torch.is_grad_enabled()) and (self.compute_dtype in _OP16 or self.precision == "f32") and x.is_cuda and self.embed_dim == 768
+        return (not torch.is_grad_enabled()) and (self.compute_dtype in _OP16 or self.precision in ("f32", "f64")) and x.is_cuda and self.embed_dim == 768
 
     # -- vit.py:302-321: returns cls token, final tokens, aux-layer tokens (pre final norm unless aux is the last) --
     def forward_features(self, x):

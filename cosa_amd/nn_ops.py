@@ -488,6 +488,83 @@ def conv3x3_dilated_f32(tok, weight, B, h, w, dilation, relu=True):
 
 
 # --------------------------------------------------------------------------------------------
+# "f64" operands: the no-grad passes in float64 on the f64 MFMA (include/cosa_hip.h; csrc/f64_kernels.hip).  Activations float64 rows, the
+#   weights the fp32 masters widened inside the kernels (or float64 rows); mode string "fp64" (DESIGN.md section 20): a check mode
+# --------------------------------------------------------------------------------------------
+def _f64_rows(t, what):
+    if t.dtype != torch.float64 or t.dim() != 2 or t.stride(1) != 1:
+        raise _C.CosaError(f"{what}: float64 rows of unit column stride, got {t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    return t
+
+
+def _w_is_f32(w, b, what):
+    if w.dtype not in (torch.float32, torch.float64) or w.dim() != 2 or w.stride(1) != 1 or \
+            (b is not None and (b.dtype != w.dtype or not b.is_contiguous())):
+        raise _C.CosaError(f"{what}: weight rows fp32 or float64 of unit column stride, the bias of the same type")
+    return int(w.dtype == torch.float32)
+
+
+def gemm_f64(x, w, b, M, N, K, epilogue=EPI_BIAS, residual=None, out=None):
+    """x [M, >= K] float64 rows, w [N, >= K] fp32 or float64 rows (any row stride), b [N] of w's type or None -> float64 [M, N] (out: rows of
+    any stride >= N) = x w^T + b, then GELU (epilogue 1) or + residual (epilogue 2: float64 rows, in place allowed)"""
+    _f64_rows(x, "gemm_f64 x")
+    wf = _w_is_f32(w, b, "gemm_f64")
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float64)
+    _f64_rows(out, "gemm_f64 out")
+    if residual is not None:
+        _f64_rows(residual, "gemm_f64 residual")
+    assert x.shape[0] >= M and w.shape[0] >= N and out.shape[0] >= M and out.shape[1] >= N
+    with _C.profiled("gemm_f64"):
+        _C.check(_C.lib().cosa_gemm_f64(_C.ptr(x), _C.ptr(w), _C.ptr(b), _C.ptr(residual), _C.ptr(out), M, N, K, x.stride(0), w.stride(0),
+                                        residual.stride(0) if residual is not None else 0, out.stride(0), epilogue, wf, _C.stream_ptr()),
+                 "cosa_gemm_f64")
+    _flops["gemm_f64"] = _flops.get("gemm_f64", 0) + 2.0 * M * N * K
+    return out
+
+
+def attn_fwd_f64(qkv, B, N, H, out):
+    """attention on float64 qkv rows [B*N, >= 3*H*64] (the projection's own [3, H, 64] layout) -> float64 rows out [B*N, >= H*64]"""
+    _f64_rows(qkv, "attn_fwd_f64 qkv"), _f64_rows(out, "attn_fwd_f64 out")
+    assert qkv.shape[0] >= B * N and out.shape[0] >= B * N and qkv.shape[1] >= 3 * H * 64 and out.shape[1] >= H * 64
+    with _C.profiled("attn_f64"):
+        _C.check(_C.lib().cosa_attn_fwd_f64(_C.ptr(qkv), _C.ptr(out), B, N, H, 64, 0.125, qkv.stride(0), out.stride(0), _C.stream_ptr()),
+                 "cosa_attn_fwd_f64")
+    _flops["attn_f64"] = _flops.get("attn_f64", 0) + 4.0 * B * H * N * N * 64
+    return out
+
+
+def layernorm_f64(x, g, b, eps, out=None):
+    """LayerNorm over contiguous float64 rows with fp32 gamma / beta -> float64 rows of the same shape"""
+    rows, D = x.shape
+    assert x.dtype == torch.float64 and x.is_contiguous() and g.dtype == torch.float32 and b.dtype == torch.float32 and g.numel() == b.numel() == D
+    if out is None:
+        out = torch.empty((rows, D), device=x.device, dtype=torch.float64)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.shape == x.shape
+    _C.check(_C.lib().cosa_layernorm_f64(_C.ptr(x), _C.ptr(g.contiguous()), _C.ptr(b.contiguous()), _C.ptr(out), rows, D, float(eps),
+                                         _C.stream_ptr()), "cosa_layernorm_f64")
+    return out
+
+
+def conv3x3_dilated_f64(tok, weight, B, h, w, dilation, relu=True):
+    """LargeFOV conv on float64 NHWC tokens, an implicit GEMM on the f64 MFMA.  tok [B, h*w, Cin] float64 (possibly the row-strided view
+    without the class-token rows); weight [Cout, Cin, 3, 3] fp32 (the master) or float64.  Returns float64 [B*h*w, Cout]."""
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    assert tok.dtype == torch.float64 and weight.dtype in (torch.float32, torch.float64) and tok.stride(2) == 1 and tok.shape[1] == h * w \
+        and tok.shape[2] == Cin
+    ldx = tok.stride(1)
+    img_rows = tok.stride(0) // ldx if B > 1 else h * w
+    assert B == 1 or tok.stride(0) == img_rows * ldx
+    wt = weight.detach().permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous()          # tap-major [Cout, (ky, kx, cin)], made per pass
+    y = torch.empty((B * h * w, Cout), device=tok.device, dtype=torch.float64)
+    with _C.profiled("conv3x3_f64"):
+        _C.check(_C.lib().cosa_conv3x3_dilated_f64(_C.ptr(tok), _C.ptr(wt), _C.ptr(y), B, h, w, Cin, Cout, int(dilation), img_rows, ldx, int(relu),
+                                                   int(wt.dtype == torch.float32), _C.stream_ptr()), "cosa_conv3x3_dilated_f64")
+    _flops["conv3x3_f64"] = _flops.get("conv3x3_f64", 0) + 2.0 * B * h * w * Cout * Cin * 9
+    return y
+
+
+# --------------------------------------------------------------------------------------------
 # fp16c8 operands: parity-grade no-grad passes at 2x the 16-bit MFMA work (include/cosa_hip.h; csrc/c8.hpp)
 #   a c8 row of logical width K, in bytes: [hi fp16 (2K) | lo8 e5m2 (K) | hi8 e5m2 (K) | aug fp16 (128)]; held as fp16 tensors of
 #   2K + 64 columns (the same stride as a bf16x3 row)

@@ -50,7 +50,16 @@ def default_args(dataset="VOC12", **over):
     return SimpleNamespace(**a)
 
 
-NOGRAD_PRECISIONS = ("bf16", "fp16", "fp32", "bf16x3", "fp16x3", "fp16c8", "fp16c4")     # VITNetwork.set_nograd_precision's base names
+NOGRAD_PRECISIONS = ("bf16", "fp16", "fp32", "fp64", "bf16x3", "fp16x3", "fp16c8", "fp16c4")     # VITNetwork.set_nograd_precision's base names
+
+
+def refuse_fp64_teacher(mode, flag=""):
+    """"fp64" is a check mode (--teacher_check_mode, --student_check_mode, tools/teacher_check.py): as the training teacher it is refused,
+    here for the trainer and, with flag="--", for the launcher's check_supported"""
+    if str(mode).partition("-")[0] == "fp64":
+        raise ValueError(f"{flag}teacher_precision {mode!r}: float64 is a check mode, not a training teacher -- fp32 IS the reference's arithmetic "
+                         f"(--teacher_precision fp32), so a float64 teacher has no use and costs several times fp32's time; score a mode "
+                         f"against float64 with --teacher_check_mode fp64, --student_check_mode fp64 or tools/teacher_check.py --criterion")
 
 
 def wrap_ddp(module, device):
@@ -108,6 +117,8 @@ def teacher_products(model, args, wimg, img_denorm, img_box, cls_label, threshol
     this model.  The --teacher_check pass (CoSATrainer._teacher_check) and tools/teacher_check.py; no host sync, no RNG."""
     cam, aux, seg = seg_helper.multi_scale_camseg(model, wimg, args.pseudo_scales, _active_labels=None if args.use_cammix else cls_label,
                                                   _seg_scales=seg_scales, _buffers=buffers)
+    if cam.dtype == torch.float64:          # a network in mode "fp64": rounded to fp32 ONCE, here at the comparison boundary
+        cam, aux, seg = cam.float(), aux.float(), ([s.float() for s in seg] if seg_scales else seg.float())
     if args.use_cammix:
         cam = (cam + aux) / 2
     (hi, lo), (hi_aux, lo_aux) = thresholds
@@ -185,6 +196,7 @@ class CoSATrainer:
         # needs bf16's range for its gradients, stays bf16.
         tp = resolve_teacher_precision(getattr(args, "teacher_precision", "auto"), args.crop_size, bool(getattr(args, "usepar", False)))
         args.teacher_precision = tp
+        refuse_fp64_teacher(tp)
         self.model_AN.check_nograd_precision(tp)          # (on the host too: a mode the encoder is not built for fails here, not in a step)
         if on:
             self.model_AN.set_nograd_precision(tp)
@@ -399,8 +411,8 @@ class CoSATrainer:
         assert len(params) == len(self._ema_pairs[half]) and all(a.shape == b.shape for a, b in zip(params, self._ema_pairs[half]))
         setattr(self, "model_" + tag.upper(), net)
         setattr(self, f"_{tag}_params", params)
-        # not optimizer-owned: refreshed at the entry of every pass ("fp32": none, the check reads the network's fp32 parameters)
-        setattr(self, f"_{tag}_shadows", nn_ops.ensure_shadows(net, net.compute_dtype) if net.compute_dtype != torch.float32 else None)
+        # not optimizer-owned: refreshed at the entry of every pass ("fp32" / "fp64": none, the check reads the network's fp32 parameters)
+        setattr(self, f"_{tag}_shadows", nn_ops.ensure_shadows(net, net.compute_dtype) if net.compute_dtype not in (torch.float32, torch.float64) else None)
         if which == "teacher":
             self._ck_buffers = {}                                             # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
 

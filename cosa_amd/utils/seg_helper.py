@@ -68,7 +68,71 @@ def cam_minmax_norm_(cam, active=None):
     return cam
 
 
-def multi_scale_camseg(model, imgs, scales, _active_labels=None, _seg_scales=False, _buffers=None):
+def resize_bilinear_f64(x, size):
+    """F.interpolate(x.double(), size=size, mode='bilinear', align_corners=False): NCHW fp32 in, float64 planes out (the "fp64" mode's input rescale)"""
+    x = x.contiguous().float()
+    b, c, h, w = x.shape
+    out = torch.empty((b, c, int(size[0]), int(size[1])), device=x.device, dtype=torch.float64)
+    _C.check(_C.lib().cosa_resize_bilinear_f64(_C.ptr(x), _C.ptr(out), b * c, h, w, int(size[0]), int(size[1]), _C.stream_ptr()),
+             "cosa_resize_bilinear_f64")
+    return out
+
+
+def _flip_merge_upsample_f64(src, dst, B, S, mode, accumulate, active=None, rawmax=None):
+    """the float64 tail kernel: src [2B, C, h, w] float64 -> dst [B, C, S, S] float64 (+= with accumulate); rawmax [B, C] float64 or None:
+    (+)= per plane max |src| over the plane and its mirror image's plane"""
+    assert src.dtype == torch.float64 and dst.dtype == torch.float64 and dst.is_contiguous() and (rawmax is None or rawmax.dtype == torch.float64)
+    src = src.contiguous()
+    _, C, h, w = src.shape
+    _C.check(_C.lib().cosa_cam_flip_merge_upsample_f64(_C.ptr(src), _C.ptr(dst), B, C, h, w, S, mode, int(accumulate), _C.ptr(active),
+                                                       _C.ptr(rawmax), _C.stream_ptr()), "cosa_cam_flip_merge_upsample_f64")
+
+
+def cam_minmax_norm_f64_(cam, active=None, peak=None):
+    """cam_minmax_norm_ on float64 planes, in place; peak [b, c] float64 or None: what each live plane was divided by (max of plane - min, + 1e-5)"""
+    assert cam.dtype == torch.float64 and cam.is_contiguous() and (peak is None or (peak.dtype == torch.float64 and peak.is_contiguous()))
+    b, c, h, w = cam.shape
+    _C.check(_C.lib().cosa_cam_minmax_norm_f64(_C.ptr(cam), b * c, h * w, _C.ptr(active), _C.ptr(peak), _C.stream_ptr()), "cosa_cam_minmax_norm_f64")
+    return cam
+
+
+def _is_f64_model(model):
+    return getattr(getattr(getattr(model, "module", model), "encoder", None), "precision", None) == "f64"
+
+
+def _multi_scale_camseg_f64(model, imgs, scales, act, seg_scales, return_scale):
+    """multi_scale_camseg for a network in mode "fp64": float64 from the input rescale to the normalised CAM.  -> float64 cam, cam_aux, seg
+    (or the per-scale float64 seg list) and, with return_scale, ((peak, rawmax) of cam, (peak, rawmax) of cam_aux), each [b, C] float64: peak =
+    max of the un-normalised plane minus its minimum, + 1e-5 (what the normalisation divides by); rawmax = the sum over the scales of max |class
+    logit| over the plane and its mirror image's (the last scale alone for cam_aux) -- the test-suite's CPU restatement defines them the same way"""
+    b, c, h, w = imgs.shape
+    dev = imgs.device
+    seg_list = []
+    with torch.no_grad():
+        scaled = [imgs.double() if s == 1.0 else resize_bilinear_f64(imgs, (int(s * h), int(s * w))) for s in scales]
+        if not model.can_forward_multi(scaled[0]):
+            raise _C.CosaError("multi_scale_camseg: the fp64 mode runs on the fused no-grad HIP path only")
+        multi = model.forward_multi(scaled, flip_pairs=True, need_cls=False)
+        C, K = multi[0][4].shape[1], multi[0][3].shape[1]
+        z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float64)
+        cam, cam_aux, seg = z(b, C, h, w), z(b, C, h, w), (None if seg_scales else z(b, K, h, w))
+        peak, rawmax, peak_aux, rawmax_aux = z(b, C), z(b, C), z(b, C), z(b, C)
+        for si in range(len(scales)):
+            _, _, _, _seg, _cam, _cam_aux = multi[si]
+            _flip_merge_upsample_f64(_cam, cam, b, h, 0, si > 0, act, rawmax)
+            if si == len(scales) - 1:                                   # only the last scale survives (:258)
+                _flip_merge_upsample_f64(_cam_aux, cam_aux, b, h, 0, False, act, rawmax_aux)
+            if seg_scales:
+                seg_list.append(_seg.contiguous())
+            else:
+                _flip_merge_upsample_f64(_seg, seg, b, h, 1, si > 0)
+        cam_minmax_norm_f64_(cam, act, peak)
+        cam_minmax_norm_f64_(cam_aux, act, peak_aux)
+    out = (cam, cam_aux, seg_list if seg_scales else seg)
+    return out + ((peak, rawmax), (peak_aux, rawmax_aux)) if return_scale else out
+
+
+def multi_scale_camseg(model, imgs, scales, _active_labels=None, _seg_scales=False, _buffers=None, _return_scale=False):
     """Teacher forward over scales x {orig, flip}; returns (cam, cam_aux, seg) at input size.
 
     utils/seg_helper.py:232-275.  Per scale one fused kernel does bilinear-up + un-flip + max/sum
@@ -82,11 +146,18 @@ def multi_scale_camseg(model, imgs, scales, _active_labels=None, _seg_scales=Fal
     `_buffers` (a dict owned by the caller, with `_active_labels` only): the returned cam / cam_aux then live in buffers kept in that dict
     from call to call (planes absent now and last time are not re-zeroed) -- they are VALID ONLY UNTIL THE NEXT CALL with the same dict
     and shapes, and must not be written in place by the caller.  Without it every call returns fresh tensors.
+    A network in mode "fp64"  runs the float64 tail and returns float64 tensors, always fresh ones; `_return_scale=True`
+    (that mode only) appends ((peak, rawmax) of cam, (peak, rawmax) of cam_aux), [b, C] float64 each.
     """
     b, c, h, w = imgs.shape
     assert 1.0 in scales, 'scale 1.0 must be in scales'
     assert h == w, "square crops only"
     _C.require_cuda(imgs)
+    if _is_f64_model(model):
+        act64 = _active_labels.contiguous().float() if _active_labels is not None else None
+        return _multi_scale_camseg_f64(model, imgs, scales, act64, _seg_scales, _return_scale)
+    if _return_scale:
+        raise ValueError("multi_scale_camseg: _return_scale needs a network in mode 'fp64' (the scale figures come from the float64 pass)")
     cam = cam_aux = seg = None
     seg_list = []
     act = _active_labels.contiguous().float() if _active_labels is not None else None
@@ -664,6 +735,61 @@ def teacher_check_worst(summary):
     worst = max([float(s["worst"]) for s in sets], default=0.0)
     return {"worst": worst, "over": sum(s["over"] for s in sets), "planes": sum(s["planes"] for s in sets),
             "agree": min([p["agree"] for p in pairs], default=1.0), "miou": min([p["miou"] for p in pairs], default=1.0)}
+
+
+# --------------------------------------------------------------------------------------------
+# the conformance criterion per plane on the device (DESIGN.md sections 3 and 20): rules (a) literal bar and (b) float64-bounded exemption
+# --------------------------------------------------------------------------------------------
+CAM_BAR, COND_MAX, FP64_FACTOR = 1e-3, 50.0, 4.0                  # THE product's copy of the pre-registered constants (tests/test_precision_gpu.py)
+AGREE_BAR, MIOU_BAR = 0.999, 0.999                                # rule (c): label agreement per draw, pooled mask mIoU
+CONFORMANCE_FIGS = ("d", "lit", "cond", "own", "e_ref", "e_hip", "bound", "max32")      # COSA_CONFORMANCE_FIGS columns of cosa_conformance_planes
+CONFORMANCE_VERDICTS = {-1: "inactive", 0: "ok", 1: "exempt", 2: "fail"}
+
+
+def conformance_planes(camA, cam32, cam64, active, peak64, rawmax64, cam_bar=CAM_BAR, cond_max=COND_MAX, fp64_factor=FP64_FACTOR):
+    """The criterion's rules (a) and (b) for every plane of one CAM set, by one launch (cosa_conformance_planes): camA [B,C,S,S] fp32 the mode
+    under test, cam32 the "fp32" pass, cam64 float64, active [B,C] (or None: every plane), peak64 / rawmax64 [B,C] float64 from the float64
+    pass (multi_scale_camseg(..., _return_scale=True)).  -> {"fig": [B,C,8] float64 in CONFORMANCE_FIGS order, "verdict": [B,C] int32 (-1
+    inactive, 0 ok, 1 exempt, 2 fail), "nonfinite": [B,C] int32}.  A float64 camA / cam32 is rounded to fp32 here, once.  No host sync."""
+    f32 = lambda t: t.detach().contiguous().float()
+    camA, cam32 = f32(camA), f32(cam32)
+    cam64, peak64, rawmax64 = (t.detach().contiguous() for t in (cam64, peak64, rawmax64))
+    act = f32(active) if active is not None else None
+    _C.require_cuda(camA, cam32, cam64, act, peak64, rawmax64)
+    B, C, S, S2 = camA.shape
+    if cam32.shape != camA.shape or cam64.shape != camA.shape or cam64.dtype != torch.float64 or peak64.shape != (B, C) or rawmax64.shape != (B, C) \
+            or peak64.dtype != torch.float64 or rawmax64.dtype != torch.float64 or (act is not None and act.shape != (B, C)):
+        raise ValueError("conformance_planes: the three CAM sets must be [B,C,S,S] (cam64 float64), active / peak64 / rawmax64 [B,C] (the last two float64)")
+    fig = torch.empty((B, C, len(CONFORMANCE_FIGS)), device=camA.device, dtype=torch.float64)
+    vd = torch.empty((B, C, 2), device=camA.device, dtype=torch.int32)
+    _C.check(_C.lib().cosa_conformance_planes(_C.ptr(camA), _C.ptr(cam32), _C.ptr(cam64), _C.ptr(act), _C.ptr(peak64), _C.ptr(rawmax64), B * C, S * S2,
+                                              float(cam_bar), float(cond_max), float(fp64_factor), _C.ptr(fig), _C.ptr(vd), _C.stream_ptr()),
+             "cosa_conformance_planes")
+    return {"fig": fig, "verdict": vd[:, :, 0], "nonfinite": vd[:, :, 1]}
+
+
+def conformance_summary(tables):
+    """{set name: conformance_planes table} (tensors or arrays; device tensors synchronise) -> per set planes / literal_ok / exempt / failed,
+    the worst lit / own / cond / e_hip over the active planes, and `over`: one record per plane over the literal bar (img, cls, cond, lit, own,
+    e_hip, bound, verdict)"""
+    out = {}
+    for name, t in tables.items():
+        fig, vd = (np.asarray(t[k].cpu() if hasattr(t[k], "cpu") else t[k]) for k in ("fig", "verdict"))
+        live = vd >= 0
+        col = lambda k: fig[:, :, CONFORMANCE_FIGS.index(k)]
+        worst = {k: (float(col(k)[live].max()) if live.any() else 0.0) for k in ("lit", "own", "cond", "e_hip")}
+        over = [{"img": int(i), "cls": int(c), "verdict": CONFORMANCE_VERDICTS[int(vd[i, c])],
+                 **{k: float(col(k)[i, c]) for k in ("cond", "lit", "own", "e_hip", "bound")}} for i, c in zip(*np.nonzero(vd > 0))]
+        out[name] = {"planes": int(live.sum()), "literal_ok": int((vd == 0).sum()), "exempt": int((vd == 1).sum()), "failed": int((vd == 2).sum()),
+                     "worst": worst, "over": over}
+    return out
+
+
+def conformance_line(s):
+    """one set of a conformance_summary in the accuracy record's format (tests/test_precision_gpu.py: `| planes N literal-ok L ...`)"""
+    notes = [f"[img {r['img']} cls {r['cls']}: cond {r['cond']:.1f} lit {r['lit']:.3e} own {r['own']:.3e} fp64 {r['e_hip']:.3e} bound {r['bound']:.3e} "
+             f"{'ok' if r['verdict'] == 'exempt' else 'FAIL'}]" for r in s["over"]]
+    return " ".join([f"planes {s['planes']} literal-ok {s['literal_ok']} exempt {s['exempt']} fail {s['failed']}"] + notes)
 
 
 # --------------------------------------------------------------------------------------------

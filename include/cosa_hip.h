@@ -404,6 +404,54 @@ int cosa_layernorm_f32out(const float *x, const float *gamma, const float *beta,
 int cosa_im2col_flip_f32_tokens(const float *x, float *rows, int B, int C, int H, int W, int P, int flips, int cls_rows, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * "f64" operands (csrc/f64_kernels.hip; mode string "fp64"): the no-grad passes in float64 on the f64 MFMA
+ * (v_mfma_f64_16x16x4_f64), from the input rescale to the normalised CAM -- the float64 side of the criterion's exemption leg on the device.
+ * A check mode, never a training teacher.  Weights are the fp32 masters, widened as the kernels read them (w_is_f32) or float64 rows.
+ *   cosa_gemm_f64             Y[M, N] (ldy) = X[M, K] (ldx, float64) W[N, K]^T (ldw; W and bias fp32 with w_is_f32, else float64); epilogue 0:
+ *                             + bias, 1: + bias then erf-form GELU (double erf), 2: + bias + residual (float64, ldr; may alias Y).  bias may
+ *                             be null.  Every output element is ONE accumulator of the MFMA, fed the products of ascending k in steps of 4
+ *                             from zero, the epilogue applied afterwards in float64: no split-K, no atomics, no dependence on M, on the row's
+ *                             position or on the other rows (NaN and 1e300 rows included).  |err| <= gamma_{K+2} (sum |x||w| + |bias| + |res|)
+ *                             with u = 2^-53.  Envelope: M >= 1, N >= 1 (tail rows and columns guarded: the head widths 20, 21, 80, 81
+ *                             directly), K % 16 == 0, ldx % 2 == 0, ldw % 4 (fp32) or % 2 (float64) == 0 on 16-byte aligned bases; anything
+ *                             else is COSA_EINVAL and nothing is launched.
+ *   cosa_conv3x3_dilated_f64  cosa_conv3x3_dilated_f32's implicit GEMM on that kernel: K = 9 * Cin, a stage never straddles a tap (Cin % 16
+ *                             == 0), padded taps contribute exact zeros, ReLU fused; Wt [Cout, 9 * Cin] tap-major
+ *   cosa_attn_fwd_f64         cosa_attn_fwd_f32 in float64: queries in blocks of 64, key tiles of 16 through LDS, exp in double, tail keys
+ *                             masked; a (batch, head) slice's result depends on that slice alone.  head_dim 64, N >= 1.
+ *   cosa_layernorm_f64        nn.LayerNorm(dim, eps) over contiguous float64 rows with the fp32 gamma / beta: two-pass mean and variance
+ *   cosa_im2col_flip_f64_tokens  cosa_im2col_flip_f32_tokens on float64 images: a selection, exact
+ *   cosa_resize_bilinear_f64  F.interpolate(x.double(), (OH, OW), "bilinear", align_corners=False): fp32 planes in, float64 planes out
+ *   cosa_cam_flip_merge_upsample_f64  cosa_cam_flip_merge_upsample on float64 maps (modes 0 / 1, accumulate, active [B*C] fp32 or null);
+ *                             rawmax [B*C] or null: (+)= max |src| over a plane and its mirror image's plane, accumulated like dst
+ *   cosa_cam_minmax_norm_f64  x = (x - min) / (max(x - min) + 1e-5) per plane in place; peak [BC] or null: that divisor
+ * ------------------------------------------------------------------------------------- */
+int cosa_gemm_f64(const double *X, const void *W, const void *bias, const double *residual, double *Y, int M, int N, int K, int ldx, int ldw,
+                  int ldr, int ldy, int epilogue, int w_is_f32, void *stream);
+int cosa_conv3x3_dilated_f64(const double *tok, const void *Wt, double *Y, int B, int h, int w, int Cin, int Cout, int dilation, int img_rows,
+                             int ldx, int relu, int w_is_f32, void *stream);
+int cosa_attn_fwd_f64(const double *qkv, double *out, int B, int N, int H, int head_dim, double scale, int ldq, int ldo, void *stream);
+int cosa_layernorm_f64(const double *x, const float *gamma, const float *beta, double *y, int rows, int dim, double eps, void *stream);
+int cosa_im2col_flip_f64_tokens(const double *x, double *rows, int B, int C, int H, int W, int P, int flips, int cls_rows, void *stream);
+int cosa_resize_bilinear_f64(const float *src, double *dst, int planes, int H, int W, int OH, int OW, void *stream);
+int cosa_cam_flip_merge_upsample_f64(const double *src, double *dst, int B, int C, int h, int w, int S, int mode, int accumulate,
+                                     const float *active, double *rawmax, void *stream);
+int cosa_cam_minmax_norm_f64(double *cam, int BC, int HW, const float *active, double *peak, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The CAM criterion per plane (csrc/conformance_kernels.hip; DESIGN.md sections 3 and 20).  camA (the mode under test) and cam32 (the "fp32"
+ * pass) fp32 [planes, HW], cam64 float64, active [planes] fp32 or null, peak64 / rawmax64 [planes] float64 from the float64 pass.  One
+ * workgroup per plane, fixed reduction tree.  fig [planes, COSA_CONFORMANCE_FIGS] float64 = d = max |A - c32|, lit = d / max(max |c32|, 1e-6),
+ * cond = rawmax / peak, own = d peak / max(rawmax, 1e-30), e_ref = max |c32 - c64|, e_hip = max |A - c64|, bound = cam_bar + fp64_factor
+ * e_ref, max |c32|; verdict [planes, 2] int32 = (-1 inactive | 0 ok: lit <= cam_bar | 1 exempt: cond > cond_max and own <= cam_bar and
+ * e_hip <= bound | 2 fail, also any plane of A with a non-finite element), count of non-finite elements of A.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_CONFORMANCE_FIGS 8
+int cosa_conformance_planes(const float *camA, const float *cam32, const double *cam64, const float *active, const double *peak64,
+                            const double *rawmax64, int planes, int HW, double cam_bar, double cond_max, double fp64_factor, double *fig,
+                            int *verdict, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * utils/seg_helper.py:961-996 (DenseCRF / crf_inference_infv2, final evaluation only): the position-only Gaussian kernel of the dense
  * CRF -- pydensecrf's addPairwiseGaussian: features (x / sxy, y / sxy) -- as a permutohedral-lattice filter on a 2-D lattice (the lattice
  * kernels of the bilateral filter, csrc/permuto_kernels.hip, compiled a second time with -DCOSA_PD=2).  ins / outs [N, K, H, W] fp32.

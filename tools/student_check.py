@@ -1,7 +1,7 @@
 """Score the student's TRAINING forward (bf16 operands over an fp32 residual stream) against a no-grad forward of the same weights on
 another operand mode, on a CHECKPOINT, without training: the stand-alone form of --student_check_iters.
 
-    python tools/student_check.py --checkpoint best_seg.pth [--check_mode fp32 | bf16 | ...] [--batches 1] \
+    python tools/student_check.py --checkpoint best_seg.pth [--check_mode fp32 | fp64 | bf16 | ...] [--batches 1] \
         (--synthetic | --dataset VOC12 --voc12_root ... | --dataset COCO --coco_root ...) [--crop_size 448] [--batch_size 16] [launcher flags]
 
 The checkpoint (best_seg.pth / best_cam.pth layout, read as cosa_amd.predict reads it: the restricted unpickler, --trust_checkpoint for the
@@ -22,7 +22,7 @@ def get_parser():
     p.prog = "python tools/student_check.py"
     p.description = "Compare the student's training forward with a no-grad forward of the same weights on a checkpoint"
     p.add_argument("--checkpoint", type=str, default=None, help="best_seg.pth / best_cam.pth of a run (reference key names)")
-    p.add_argument("--check_mode", type=str, default="fp32", help="operand mode of the check pass (any --student_check_mode value)")
+    p.add_argument("--check_mode", type=str, default="fp32", help="operand mode of the check pass (any --student_check_mode value; fp64: a float64 pass, DESIGN.md section 20)")
     p.add_argument("--batches", type=int, default=1)
     p.add_argument("--synthetic", action="store_true", help="synthetic batches (train_step.synthetic_batch) instead of a dataset")
     p.add_argument("--trust_checkpoint", action="store_true",
