@@ -196,6 +196,9 @@ _SIGS.update({
     "cosa_cam_flip_merge_upsample_f64": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p]),
     "cosa_cam_minmax_norm_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cosa_conformance_planes": (c_int, [c_void_p] * 6 + [c_int, c_int] + [ctypes.c_double] * 3 + [c_void_p] * 3),
+    # the --act_stats_iters monitor (csrc/act_stats_kernels.hip)
+    "cosa_range_stats_f32": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
+    "cosa_attn_stats_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, ctypes.c_longlong, c_void_p, c_void_p]),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

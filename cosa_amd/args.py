@@ -90,6 +90,11 @@ EXTRA = [
                                              # logged and written to <output_dir>/gt_stats.jsonl every log_iters; training is untouched
     ("gt_dir", str, None),                   # where --gt_stats finds <name>.png (default: the dataset root's SegmentationClassAug for VOC12,
                                              # SegmentationClass/train2014 for COCO: what the Seg datasets read)
+    # activation range and attention sharpness; 0: nothing changes
+    ("act_stats_iters", int, 0),             # every N-th optimizer step runs the teacher's weights of that step through an fp32 pass of its own over the
+                                             # weak images and reduces, per block, the range of q / k / v / o / h / x (bits of headroom under fp16's 65504)
+                                             # and per head the attention logits' magnitude and row entropy; logged and written to
+                                             # <output_dir>/act_stats.jsonl every log_iters; training is untouched
 ]
 
 

@@ -51,6 +51,8 @@ SOURCES = {
     # the "f64" operand family on the f64 MFMA (mode "fp64") and the criterion's per-plane reduction: the same rules in float64
     "f64_kernels.hip": EXACT,
     "conformance_kernels.hip": EXACT,
+    # the --act_stats_iters monitor: integer reductions over the fp32 family's buffers and the QK^T half of its attention kernel
+    "act_stats_kernels.hip": EXACT,
 }
 
 

@@ -79,6 +79,49 @@ class TokenPack(typing.NamedTuple):
         return outs
 
 
+ACT_SITES = ("q", "k", "v", "o", "h", "x")      # the range sites of a block, in the table's order (seg_helper.act_stats_layout)
+
+
+class ActProbe:
+    """what `VisionTransformer.act_probe` holds: an int64 table [depth][6 * 6 + H * 7] on the device, row i = block i:
+    six words per range site (ACT_SITES), then seven per head.  The fp32 no-grad path calls `site` after the launch that produced a site
+    and `attn` per scale before the attention launch's output is consumed; both add into row `layer` (nn_ops.range_stats / attn_stats),
+    on the current stream, without a host sync.  `table` may be a view of a longer vector (the trainer's counters)."""
+
+    def __init__(self, depth, heads, device=None, table=None):
+        self.depth, self.heads, self.width = int(depth), int(heads), 6 * len(ACT_SITES) + 7 * int(heads)
+        self.table = torch.zeros((self.depth, self.width), dtype=torch.int64, device=device) if table is None else table
+        assert self.table.shape == (self.depth, self.width) and self.table.dtype == torch.int64 and self.table.is_contiguous()
+
+    def site(self, layer, name, x, col0=0, cols=None):
+        j = ACT_SITES.index(name)
+        nn_ops.range_stats(x, self.table[layer, 6 * j:6 * j + 6], col0, cols)
+
+    def attn(self, layer, qkv, B, N, H):
+        assert H == self.heads
+        nn_ops.attn_stats(qkv, B, N, H, self.table[layer, 6 * len(ACT_SITES):])
+
+
+@torch.no_grad()
+def qk_gain_(module, gain):
+    """multiply the q rows and the k rows (weights and biases) of every Block's qkv projection under `module` by sqrt(gain), in place: every
+    attention logit becomes `gain` times larger, nothing else of the network is touched (v, the output projection and the MLP read the
+    same inputs; only the softmax sharpens).  The "sharp attention" recipe of the conformance tools (--qk_gain); 1 touches nothing."""
+    gain = float(gain)
+    if not gain > 0 or gain == float("inf"):
+        raise ValueError(f"qk_gain {gain!r}: a positive finite factor")
+    if gain == 1.0:
+        return module
+    f = gain ** 0.5
+    for blk in module.modules():
+        if isinstance(blk, Block):
+            two_d = 2 * blk.attn.qkv.weight.shape[0] // 3
+            blk.attn.qkv.weight[:two_d] *= f
+            if blk.attn.qkv.bias is not None:
+                blk.attn.qkv.bias[:two_d] *= f
+    return module
+
+
 class Mlp(nn.Module):
     def __init__(self, in_features, hidden_features):
         super().__init__()
@@ -158,6 +201,8 @@ class VisionTransformer(nn.Module):
         # the auxiliary CAM's worst error goes from 4.5e-4 to 5.1e-4 (margin on the 1e-3 bar 2.2x -> 1.95x) for 0.15 ms per step, so it is off:
         # proj stays on fp16c8 operands (e5m2 corrections), 10 % of the projection work
         self.c4_proj = False
+        self.act_probe = None          # an ActProbe: the fp32 no-grad path reports every block's q / k / v / o / h / x and its attention logits to it
+        #                                (--act_stats_iters); None: nothing is launched.  Only the "f32" family is probed
         self._pos_cache = {}
         _trunc_normal_(self.pos_embed)
         _trunc_normal_(self.cls_token)
@@ -397,6 +442,9 @@ class VisionTransformer(nn.Module):
         the packed qkv buffer.  Token assembly and the closing LayerNorm belong to the operand family of the patch projection."""
         fmap, pk = self._operand_map(), self._token_pack(xs, flip_pairs)
         D = self.embed_dim
+        if self.act_probe is not None and fmap.patch != "f32":
+            raise RuntimeError(f"act_probe: only the fp32 no-grad path (mode \"fp32\") is probed -- its qkv / o / h buffers are plain fp32; "
+                               f"this network runs its passes on {fmap.patch!r} operands")
         f = lambda t: t.detach()
         if fmap.patch == "x3":
             W = {"x3": self._operand_rows(fmap, "x3")}
@@ -561,7 +609,7 @@ class VisionTransformer(nn.Module):
             elif fmap.attn[i] == "x3":
                 self._attn_x3(xr, xn, blk, pk, bufs["x3"], W["x3"], i)
             elif fmap.attn[i] == "f32":
-                self._attn_f32(xr, xn, blk, pk, bufs["f32"])
+                self._attn_f32(xr, xn, blk, pk, bufs["f32"], i)
             elif fmap.attn[i] == "f64":
                 self._attn_f64(xr, xn, blk, pk, bufs["f64"])
             else:
@@ -572,7 +620,7 @@ class VisionTransformer(nn.Module):
             elif fmap.mlp[i] == "x3":
                 self._mlp_x3(xr, blk, pk, bufs["x3"], W["x3"], i)
             elif fmap.mlp[i] == "f32":
-                self._mlp_f32(xr, blk, pk, bufs["f32"])
+                self._mlp_f32(xr, blk, pk, bufs["f32"], i)
             elif fmap.mlp[i] == "f64":
                 self._mlp_f64(xr, blk, pk, bufs["f64"])
             else:
@@ -610,22 +658,36 @@ class VisionTransformer(nn.Module):
         nn_ops.gemm_x3(bf["y"], W[f"{i}.fc1"], M, Hd, D, nn_ops.EPI_GELU, out=bf["h"], ldy=bf["h"].shape[1])
         nn_ops.gemm_x3(bf["h"], W[f"{i}.fc2"], M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
 
-    def _attn_f32(self, xr, xn, blk, pk, bf):
-        """fp32 attention half: the projections read the fp32 master weights and biases themselves -- no weight set, nothing rebuilt per pass"""
+    def _attn_f32(self, xr, xn, blk, pk, bf, i):
+        """fp32 attention half: the projections read the fp32 master weights and biases themselves -- no weight set, nothing rebuilt per pass.
+        `act_probe`, when set, reads block i's q / k / v windows, the logits per scale and o after the launches that produced them"""
         M, D = pk.M, self.embed_dim
         d = lambda p_: None if p_ is None else p_.detach()
+        probe = self.act_probe
         nn_ops.layernorm_f32out(xr, d(blk.norm1.weight), d(blk.norm1.bias), blk.norm1.eps, out=bf["y"])
         nn_ops.gemm_f32(bf["y"], d(blk.attn.qkv.weight), d(blk.attn.qkv.bias), M, 3 * D, D, nn_ops.EPI_BIAS, out=bf["qkv"])
+        if probe is not None:
+            for j, name in enumerate(("q", "k", "v")):
+                probe.site(i, name, bf["qkv"][:M], j * D, D)
         for B, N, o0, o1 in pk.scales():
             nn_ops.attn_fwd_f32(bf["qkv"][o0:o1], B, N, self.num_heads, bf["o"][o0:o1])
+            if probe is not None:
+                probe.attn(i, bf["qkv"][o0:o1], B, N, self.num_heads)
+        if probe is not None:
+            probe.site(i, "o", bf["o"][:M])
         nn_ops.gemm_f32(bf["o"], d(blk.attn.proj.weight), d(blk.attn.proj.bias), M, D, D, nn_ops.EPI_RESIDUAL, residual=xr, out=xn)
 
-    def _mlp_f32(self, xr, blk, pk, bf):
+    def _mlp_f32(self, xr, blk, pk, bf, i):
         M, D, Hd = pk.M, self.embed_dim, blk.mlp.fc1.weight.shape[0]
         d = lambda p_: p_.detach()
+        probe = self.act_probe
         nn_ops.layernorm_f32out(xr, d(blk.norm2.weight), d(blk.norm2.bias), blk.norm2.eps, out=bf["y"])
         nn_ops.gemm_f32(bf["y"], d(blk.mlp.fc1.weight), d(blk.mlp.fc1.bias), M, Hd, D, nn_ops.EPI_GELU, out=bf["h"])
+        if probe is not None:
+            probe.site(i, "h", bf["h"][:M])                  # fc1 + GELU
         nn_ops.gemm_f32(bf["h"], d(blk.mlp.fc2.weight), d(blk.mlp.fc2.bias), M, D, Hd, nn_ops.EPI_RESIDUAL, residual=xr, out=xr)
+        if probe is not None:
+            probe.site(i, "x", xr[:M])                       # the stream after the block
 
     def _attn_f64(self, xr, xn, blk, pk, bf):
         """float64 attention half: float64 activations, the fp32 master weights and biases widened inside the kernels -- no weight set"""

@@ -1,5 +1,5 @@
 """The optional run-time monitors as ONE table: the gradient guard, --label_stats, --tensor_stats, --teacher_check_iters,
---student_check_iters and (ROWS' last) --gt_stats.  A row says what the launcher's log interval (main.read_interval and the log block), the jsonl files and the
+--student_check_iters, (ROWS' last) --gt_stats and (ALL's last, section 21) --act_stats_iters.  A row says what the launcher's log interval (main.read_interval and the log block), the jsonl files and the
 state files (checkpoint.TrainState) need to know about a monitor; the kernels, their torch partners and the summaries are the monitors' own
 and live where they always did (utils/seg_helper.py, utils/torch_helper.py, CoSATrainer).  Adding a monitor is adding a row."""
 import json
@@ -139,12 +139,29 @@ ROWS = MONITORS + (
             ("the file holds ground-truth statistics and this run does not collect them (--gt_stats false): the entry is ignored",
              "written without ground-truth statistics: this run's ground-truth counters start at zero")),
 )
-BY_NAME = {m.name: m for m in ROWS}
+
+
+def _act_stats_summary(trainer, args, values):
+    depth, heads = trainer.act_stats_shape
+    return seg_helper.act_stats_summary(values, depth, heads)
+
+
+# ALL is what walks the table now -- active(), the launcher's log block, BY_NAME, the state files' optional entries: ROWS (pinned by
+# tests/test_gt_stats_cpu.py as MONITORS + --gt_stats) and the monitor of the activations, --act_stats_iters.  Its fixed-point sums (2^-32
+# units, one term per attention row) pass 2^53 within an interval: they travel as --student_check_iters' do, in 32-bit halves
+ALL = ROWS + (
+    Monitor("act_stats", lambda tr: getattr(tr, "act_stats_state", None), _student_check_pack, _student_check_unpack, _zero,
+            _act_stats_summary, lambda summary, targs: seg_helper.act_stats_line(summary), lambda targs: dict(mode="fp32"), _held_a_check,
+            "aux.act_stats.counters",
+            ("the file holds activation statistics and this run collects none (--act_stats_iters 0): the entry is ignored",
+             "written without activation statistics: this run's activation counters start at zero")),
+)
+BY_NAME = {m.name: m for m in ALL}
 
 
 def active(trainer):
     """[(Monitor, its tensors)] of the monitors `trainer` has on, in the table's order: what main.read_interval takes"""
-    return [(m, t) for m, t in ((m, m.tensors(trainer)) for m in ROWS) if t is not None]
+    return [(m, t) for m, t in ((m, m.tensors(trainer)) for m in ALL) if t is not None]
 
 
 def monitor_record(m, summary, n_iter, targs):

@@ -459,6 +459,45 @@ def attn_fwd_f32(qkv, B, N, H, out):
     return out
 
 
+RANGE_STATS_WORDS, ATTN_STATS_WORDS = 6, 7          # COSA_ACT_STATS_RANGE_WORDS / _HEAD_WORDS (include/cosa_hip.h: the words)
+
+
+def _stats_words(out, n, what):
+    if out.dtype != torch.int64 or out.dim() != 1 or out.shape[0] != n or out.stride(0) != 1:
+        raise _C.CosaError(f"{what}: the output must be {n} contiguous int64 words, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def range_stats(x, out, col0=0, cols=None):
+    """the --act_stats range reduction (cosa_range_stats_f32) over columns col0 : col0 + cols of the fp32 rows x (a window of a wider matrix:
+    q / k / v out of packed qkv rows), ADDED into the six int64 words `out`: finite, bits of max |x|, > 65504, > 32768, 0 < |x| < 2^-14,
+    non-finite.  No host sync."""
+    _f32_rows(x, "range_stats x")
+    cols = x.shape[1] - col0 if cols is None else int(cols)
+    if col0 < 0 or cols < 1 or col0 + cols > x.shape[1] or x.shape[0] < 1:
+        raise _C.CosaError(f"range_stats: columns {col0}:{col0 + cols} of rows {tuple(x.shape)}")
+    _C.require_cuda(x, out)
+    _stats_words(out, RANGE_STATS_WORDS, "range_stats")
+    with _C.profiled("range_stats"):
+        _C.check(_C.lib().cosa_range_stats_f32(_C.c_void_p(x.data_ptr() + 4 * col0), x.shape[0], cols, x.stride(0), _C.ptr(out), _C.stream_ptr()),
+                 "cosa_range_stats_f32")
+    return out
+
+
+def attn_stats(qkv, B, N, H, out):
+    """the --act_stats attention reduction (cosa_attn_stats_f32) over fp32 qkv rows [B*N, >= 3*H*64] as attn_fwd_f32 reads them, ADDED into
+    the int64 words `out` [H * 7]: per head rows, sum Hn, sum top1 (2^-32 units), peaked rows, bits of max |s|, bits of max (1 - Hn),
+    rows with a non-finite logit.  No host sync."""
+    _f32_rows(qkv, "attn_stats qkv")
+    assert qkv.shape[0] >= B * N and qkv.shape[1] >= 3 * H * 64
+    _C.require_cuda(qkv, out)
+    _stats_words(out, H * ATTN_STATS_WORDS, "attn_stats")
+    with _C.profiled("attn_stats"):
+        _C.check(_C.lib().cosa_attn_stats_f32(_C.ptr(qkv), B, N, H, 64, 0.125, qkv.stride(0), _C.ptr(out), _C.stream_ptr()), "cosa_attn_stats_f32")
+    _flops["attn_stats"] = _flops.get("attn_stats", 0) + 2.0 * B * H * N * N * 64
+    return out
+
+
 def layernorm_f32out(x, g, b, eps, out=None):
     """LayerNorm(768) over fp32 rows with fp32 gamma / beta -> fp32 [rows, 768]: layernorm_split's `want_f32` output alone, same bits"""
     rows, D = x.shape

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from . import nn_ops
 from .models import build_model
 from .models.PAR import PAR
+from .models.vit import ActProbe
 from . import _C
 from .utils import seg_helper, torch_helper
 
@@ -40,7 +41,8 @@ def default_args(dataset="VOC12", **over):
              detach='none', use_cammix=False, usegmm=False, usegmmaux=False, gmmscale=16, gmmfilter_thre=0.05, gmmemadecay=0.99,
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
              clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
-             teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None)
+             teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None,
+             act_stats_iters=0)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -101,11 +103,12 @@ def resolve_teacher_check_mode(mode, teacher_precision):
 
 
 def check_iters(args, which, flag=""):
-    """--<which>_check_iters of `args` (which: "teacher" / "student") as an int; a negative one is refused, here for the trainer and, with
-    flag="--", for the launcher's check_supported"""
-    n = int(getattr(args, which + "_check_iters", 0) or 0)
+    """--<which>_check_iters of `args` (which: "teacher" / "student"), or --act_stats_iters (which: "act_stats"), as an int; a negative one is
+    refused, here for the trainer and, with flag="--", for the launcher's check_supported"""
+    name = "act_stats_iters" if which == "act_stats" else which + "_check_iters"
+    n = int(getattr(args, name, 0) or 0)
     if n < 0:
-        raise ValueError(f"{flag}{which}_check_iters {n!r}: 0 (off) or a positive number of optimizer steps")
+        raise ValueError(f"{flag}{name} {n!r}: 0 (off) or a positive number of optimizer steps")
     return n
 
 
@@ -271,7 +274,7 @@ class CoSATrainer:
         # that moment, and scores the two passes against each other.  The counters are state of the run (`teacher_check.counters` of
         # extra_state); model_CK is not: every check overwrites it
         self.teacher_check_state = self.model_CK = None
-        self._check_iters = {which: check_iters(args, which) for which in ("teacher", "student")}
+        self._check_iters = {which: check_iters(args, which) for which in ("teacher", "student", "act_stats")}
         if self._check_iters["teacher"] > 0:
             cm = resolve_teacher_check_mode(getattr(args, "teacher_check_mode", "auto"), tp)
             args.teacher_check_mode = cm
@@ -301,6 +304,26 @@ class CoSATrainer:
             self._add_extra_state("student_check.counters", self.student_check_state)
             if on:
                 self._build_check("student")
+        # activation range and attention sharpness: off (None) unless --act_stats_iters N > 0.  Every N-th optimizer
+        # step runs the teacher's weights of that step through `model_AK`, a network of its own in mode "fp32" whose encoder carries an
+        # ActProbe, over the weak images.  The counters are state of the run (`act_stats.counters` of extra_state: the probe's table and the
+        # number of passes) and, under data parallelism, this rank's own; model_AK is not: every pass overwrites it
+        self.act_stats_state = self.model_AK = self.act_stats_shape = None
+        if self._check_iters["act_stats"] > 0:
+            self.model_AN.check_nograd_precision("fp32")
+            if device.type == "cuda" and not on:
+                raise NotImplementedError("act_stats_iters: the monitor runs the fp32 no-grad path of the HIP encoder; this trainer's compute "
+                                          "dtype has none")
+            enc = self.model_AN.encoder
+            self.act_stats_shape = (len(enc.blocks), enc.num_heads)
+            self.act_stats_state = seg_helper.new_act_stats(*self.act_stats_shape, device)
+            self._add_extra_state("act_stats.counters", self.act_stats_state)
+            if on:
+                self.model_AK = self._new_check_network("fp32")
+                self._ak_params = list(self.model_AK.parameters())
+                assert len(self._ak_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ak_params, self._ema_pairs[0]))
+                self.model_AK.encoder.act_probe = ActProbe(*self.act_stats_shape, table=seg_helper.act_stats_table(self.act_stats_state, *self.act_stats_shape))
+                self._ak_buffers = {}                                             # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
         if on:
             for sh in (self._teacher_shadows, self._student_shadows):
                 if sh is not None:
@@ -418,8 +441,8 @@ class CoSATrainer:
 
     def _is_check_step(self, n_iter, which="teacher"):
         """the step that closes every N-th optimizer iteration (N: --<which>_check_iters); with --accum_steps its last micro-batch"""
-        return (getattr(self, which + "_check_state") is not None and (n_iter + 1) % self._check_iters[which] == 0
-                and self._micro_k == self._accum_steps - 1)
+        state = self.act_stats_state if which == "act_stats" else getattr(self, which + "_check_state")
+        return state is not None and (n_iter + 1) % self._check_iters[which] == 0 and self._micro_k == self._accum_steps - 1
 
     @contextlib.contextmanager
     def _check_pass(self, name):
@@ -504,6 +527,25 @@ class CoSATrainer:
     def teacher_check(self):
         """_summary_of --teacher_check_iters' counters (seg_helper.teacher_check_summary)"""
         return self._summary_of(self.teacher_check_state, seg_helper.teacher_check_summary)
+
+    @torch.no_grad()
+    def _act_stats(self, wimg, cls_label):
+        """One pass of the --act_stats_iters monitor, eagerly on the current stream after the teacher's pass has been
+        joined: the teacher's weights of THIS step (the EMA update comes later) into model_AK, the teacher's multi-scale pass over the same
+        weak images in mode "fp32" with the encoder's probe set, its outputs dropped.  The probe's launches add into `act_stats_state`, whose
+        last word counts the passes.  No host sync, no RNG, and nothing the training path reads is written: model_AK's weights, operand and
+        CAM buffers are its own, the library workspaces it needs are slots of their own (_C.workspace_scope)."""
+        args = self.args
+        torch._foreach_copy_(self._ak_params, self._ema_pairs[0])
+        with self._check_pass("act_stats"):
+            seg_helper.multi_scale_camseg(self.model_AK, wimg, args.pseudo_scales, _active_labels=None if args.use_cammix else cls_label,
+                                          _seg_scales=self.fused_losses, _buffers=self._ak_buffers)
+        self.act_stats_state[-1:] += 1
+
+    def act_stats(self):
+        """the summary (seg_helper.act_stats_summary) of --act_stats_iters' counters since they were last zeroed (synchronises: for tests
+        and the log interval); None when the monitor is off"""
+        return None if self.act_stats_state is None else seg_helper.act_stats_summary(self.act_stats_state, *self.act_stats_shape)
 
     def _join_teacher(self):
         if self._teacher_pending:
@@ -605,6 +647,8 @@ class CoSATrainer:
         if self.model_CK is not None and self._is_check_step(n_iter):
             self._teacher_check(wimg, img_denorm, img_box, cls_label, (cam_ps, cam_aux_ps), (refine_mask_label, refine_mask_label_aux),
                                 ((threhigh, threlow), (auxthrehigh, auxthrelow)), check_tgt)
+        if self.model_AK is not None and self._is_check_step(n_iter, "act_stats"):
+            self._act_stats(wimg, cls_label)
         if self.model_SK is not None and self._is_check_step(n_iter, "student"):
             # what the check after this step's backward (_student_check) reads: detached references, nothing is copied or computed here
             self._scheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux), tgt=check_tgt_s,

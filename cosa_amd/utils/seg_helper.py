@@ -986,6 +986,113 @@ def student_check_summary(counters, K):
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# the --act_stats_iters monitor: activation range and attention sharpness of an fp32 pass on the teacher's weights
+# --------------------------------------------------------------------------------------------
+ACT_STATS_SITES = ("q", "k", "v", "o", "h", "x")                               # models/vit.py: ACT_SITES, the order of a block's range sites
+ACT_STATS_F16_SITES = ("q", "k", "v", "o", "h")                                 # ... those an fp16x3 pass stores as fp16 halves (x is the fp32 stream)
+_AS_RANGE_FIELDS = ("finite", "absmax", "over", "near", "tiny", "nonfinite")    # cosa_range_stats_f32's six words
+_AS_HEAD_FIELDS = ("rows", "ent_fix", "top1_fix", "peaked", "smax", "sharp", "nonfinite_rows")      # cosa_attn_stats_f32's seven per head
+ACT_STATS_FRAC = 32                                                             # COSA_ACT_STATS_FRAC: ent_fix and top1_fix count 2^-32
+F16_MAX = 65504.0
+
+
+def act_stats_layout(depth, H):
+    """({slot name: offset in elements}, number of elements) of the --act_stats counters for `depth` blocks of H heads: block i holds
+    "<i>.<site>.<field>" for the sites q, k, v, o, h, x (six words each: finite, absmax, over, near, tiny, nonfinite) at i * W + 6 * site,
+    then "<i>.head<h>.<field>" (seven each: rows, ent_fix, top1_fix, peaked, smax, sharp, nonfinite_rows) at i * W + 36 + 7 * h, with
+    W = "width" = 36 + 7 H; "checks", the passes accumulated, is the last element (depth * W).  The first depth * W elements viewed as
+    [depth][W] are the table an encoder's act_probe adds into.  Needs no device."""
+    depth, H = int(depth), int(H)
+    if depth < 1 or H < 1:
+        raise ValueError(f"act_stats_layout: depth {depth} and heads {H} must be positive")
+    W = len(_AS_RANGE_FIELDS) * len(ACT_STATS_SITES) + len(_AS_HEAD_FIELDS) * H
+    off = {"width": W}
+    for i in range(depth):
+        for j, site in enumerate(ACT_STATS_SITES):
+            for f, field in enumerate(_AS_RANGE_FIELDS):
+                off[f"{i}.{site}.{field}"] = i * W + 6 * j + f
+        for h in range(H):
+            for f, field in enumerate(_AS_HEAD_FIELDS):
+                off[f"{i}.head{h}.{field}"] = i * W + 36 + 7 * h + f
+    off["checks"] = depth * W
+    return off, depth * W + 1
+
+
+def new_act_stats(depth, H, device):
+    """a zeroed counter vector (int64) of act_stats_layout's length"""
+    return torch.zeros(act_stats_layout(depth, H)[1], dtype=torch.int64, device=device)
+
+
+def act_stats_table(counters, depth, H):
+    """the [depth][36 + 7 H] view of a counter vector that an ActProbe takes as its table"""
+    W = 36 + 7 * int(H)
+    return counters[:int(depth) * W].view(int(depth), W)
+
+
+def act_stats_summary(counters, depth, H):
+    """The counter vector (tensor, array or list; a device tensor synchronises) as figures.  `layers`[i]: `sites` {site: absmax, over, near,
+    tiny, nonfinite, finite} and `heads`[h] {rows, ent (mean normalised row entropy), top1 (mean largest probability), peaked (share of rows
+    with top1 > 0.5), smax (largest |logit| after the scale), sharpest (the lowest row entropy seen: 1 - max(1 - Hn); None: no row),
+    nonfinite_rows}.  Globals: `headroom_bits` = log2(65504 / absmax) at its minimum over the sites an fp16 split stores (q, k, v, o, h)
+    with `headroom_at` [site, layer] (None while every such site is zero or unseen); `smax` with `smax_at` [layer, head]; `ent_mean` (over
+    all rows) and `ent_min` with `ent_min_at` [layer, head]; `over` (those five sites) and `nonfinite` (all six, plus `nonfinite_rows`);
+    `checks`."""
+    import struct
+    c = [int(v) for v in (counters.tolist() if hasattr(counters, "tolist") else counters)]
+    off, n = act_stats_layout(depth, H)
+    if len(c) != n:
+        raise ValueError(f"act_stats_summary: {len(c)} counters, depth {depth} x {H} heads has {n}")
+    as_f = lambda b: struct.unpack("<f", struct.pack("<I", b & 0xffffffff))[0]
+    unit = 2.0 ** ACT_STATS_FRAC
+    out = {"checks": c[off["checks"]], "layers": [], "headroom_bits": None, "headroom_at": None, "smax": 0.0, "smax_at": None,
+           "ent_mean": None, "ent_min": None, "ent_min_at": None, "over": 0, "nonfinite": 0, "nonfinite_rows": 0}
+    rows_all = ent_all = 0
+    for i in range(depth):
+        sites, heads = {}, []
+        for site in ACT_STATS_SITES:
+            g = lambda f: c[off[f"{i}.{site}.{f}"]]
+            e = {"absmax": as_f(g("absmax")), "over": g("over"), "near": g("near"), "tiny": g("tiny"), "nonfinite": g("nonfinite"),
+                 "finite": g("finite")}
+            sites[site] = e
+            out["nonfinite"] += e["nonfinite"]
+            if site in ACT_STATS_F16_SITES:
+                out["over"] += e["over"]
+                if e["absmax"] > 0:
+                    bits = math.log2(F16_MAX / e["absmax"])
+                    if out["headroom_bits"] is None or bits < out["headroom_bits"]:
+                        out["headroom_bits"], out["headroom_at"] = bits, [site, i]
+        for h in range(H):
+            g = lambda f: c[off[f"{i}.head{h}.{f}"]]
+            rows = g("rows")
+            e = {"rows": rows, "ent": g("ent_fix") / unit / rows if rows else None, "top1": g("top1_fix") / unit / rows if rows else None,
+                 "peaked": g("peaked") / rows if rows else None, "smax": as_f(g("smax")),
+                 "sharpest": 1.0 - as_f(g("sharp")) if rows else None, "nonfinite_rows": g("nonfinite_rows")}
+            heads.append(e)
+            out["nonfinite_rows"] += e["nonfinite_rows"]
+            rows_all += rows
+            ent_all += g("ent_fix")
+            if rows and (out["smax_at"] is None or e["smax"] > out["smax"]):
+                out["smax"], out["smax_at"] = e["smax"], [i, h]
+            if rows and (out["ent_min"] is None or e["ent"] < out["ent_min"]):
+                out["ent_min"], out["ent_min_at"] = e["ent"], [i, h]
+        out["layers"].append({"sites": sites, "heads": heads})
+    if rows_all:
+        out["ent_mean"] = ent_all / unit / rows_all
+    return out
+
+
+def act_stats_line(s):
+    """` act: headroom 9.3b (h L11), max|s| 41.2 (L9 h3), ent 0.62 (min 0.31 L9 h3), over 0` -- the bits left under 65504 at the site and
+    block closest to it, the largest attention logit with its block and head, the mean normalised row entropy with the lowest head's, and
+    the elements an fp16 half could not hold; `-` where nothing was seen"""
+    head = "headroom %.1fb (%s L%d)" % (s["headroom_bits"], s["headroom_at"][0], s["headroom_at"][1]) if s["headroom_bits"] is not None else "headroom -"
+    if s["smax_at"] is None:
+        return " act: %s, max|s| -, ent -, over %d" % (head, s["over"])
+    return " act: %s, max|s| %.1f (L%d h%d), ent %.2f (min %.2f L%d h%d), over %d" % (
+        head, s["smax"], s["smax_at"][0], s["smax_at"][1], s["ent_mean"], s["ent_min"], s["ent_min_at"][0], s["ent_min_at"][1], s["over"])
+
+
 def seg_loss_forward_only(seg_lr, mask_main, mask_aux, img, img_box, fg_alpha=0.5, aux_alpha=0.5):
     """the seg-loss half of fused_seg_and_energy_loss by its forward kernel alone (_seg_loss_launch, _seg_loss_value: the same call, the
     same value): no regulariser, nothing kept for a backward.  For the --student_check pass."""

@@ -920,6 +920,35 @@ int cosa_student_check(const float *seg_a, const float *seg_b, const float *cam_
                        const float *loss_a, const float *loss_b, const float *cls_label, long long *counters, int B, int K, int h,
                        int w, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The --act_stats_iters monitor: activation range and attention sharpness of an fp32 no-grad pass
+ * (csrc/act_stats_kernels.hip).  Both reductions ADD into int64 words that the caller zeroes: counts, per-row terms in fixed
+ * point with COSA_ACT_STATS_FRAC fractional bits (rint of term * 2^32 in double), and maxima as the bit pattern of a finite
+ * non-negative fp32 value under an integer max.  The same input gives the same bytes in any order of arrival; a second call
+ * on the same words doubles counts and sums and keeps maxima.  One launch each, no workspace, no host sync.
+ *   cosa_range_stats_f32   a column window of an fp32 matrix: `cols` columns from x, `rows` rows of stride ld (elements).
+ *                          out6: 0 finite elements;  1 bits of the largest finite |x|;  2 finite |x| > 65504 (an fp16 hi
+ *                          half would be inf);  3 finite |x| > 32768 (less than one bit of headroom);  4 elements with
+ *                          0 < |x| < 2^-14 (the hi half goes subnormal);  5 non-finite elements.  Each byte of the window
+ *                          is read once and nothing outside it; float4 loads where x is 16-byte aligned and ld % 4 == 0, a
+ *                          scalar path otherwise.  Refused: a NULL pointer, rows < 1, cols < 1, ld < cols.
+ *   cosa_attn_stats_f32    the logits of cosa_attn_fwd_f32 (same blocks, key tiles and MFMA orientation, scale applied to the
+ *                          fp32 chain) without the PV product; nothing of size N^2 or N d is written.  Per query row, online:
+ *                          the maximum m, l = sum e^(s-m), t = sum e^(s-m)(s-m) (expf in fp32, the sums carried in double);
+ *                          H = log l - t / l, Hn = H / log N clamped to [0, 1] (0 for N = 1), top1 = 1 / l.
+ *                          out [H][COSA_ACT_STATS_HEAD_WORDS]: 0 rows;  1 sum rint(Hn 2^32);  2 sum rint(top1 2^32);
+ *                          3 rows with top1 > 0.5;  4 bits of the largest finite |s|;  5 bits of max (1 - Hn) as fp32 (0:
+ *                          nothing seen);  6 rows with a non-finite logit, which are left out of words 0..5.
+ *                          Envelope as cosa_attn_fwd_f32: head_dim == 64, ldq >= 3 H 64, ldq % 4 == 0, 16-byte aligned qkv.
+ * Anything else is COSA_EINVAL, nothing is launched and the words are untouched.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_ACT_STATS_RANGE_WORDS 6
+#define COSA_ACT_STATS_HEAD_WORDS 7
+#define COSA_ACT_STATS_FRAC 32
+int cosa_range_stats_f32(const float *x, long long rows, int cols, long long ld, int64_t *out6, void *stream);
+int cosa_attn_stats_f32(const float *qkv, int B, int N, int H, int head_dim, float scale, long long ldq, int64_t *out /* [H][7] */,
+                        void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 

@@ -2,7 +2,8 @@
 stand-alone form of --teacher_check_iters, for the day released weights are at hand.
 
     python tools/teacher_check.py --checkpoint best_seg.pth [--mode fp16x3] [--check_mode fp16c8-x2 | fp32 | fp64] [--batches 8] [--criterion] \
-        (--synthetic | --dataset VOC12 --voc12_root ... | --dataset COCO --coco_root ...) [--crop_size 448] [--batch_size 16] [launcher flags]
+        (--synthetic | --dataset VOC12 --voc12_root ... | --dataset COCO --coco_root ...) [--crop_size 448] [--batch_size 16] [--qk_gain G] \
+        [launcher flags]
 
 The checkpoint (best_seg.pth / best_cam.pth layout, read as cosa_amd.predict reads it: the restricted unpickler, --trust_checkpoint for the
 full one) goes into two networks, one per mode; every batch runs what a training step derives from a teacher pass -- multi-scale CAMs,
@@ -14,12 +15,22 @@ cam2mask with the flags' thresholds, the cam-loss targets -- on both, and cosa_t
 cosa_conformance_planes applies the literal bar and the float64-bounded exemption to every active plane of cam and cam_aux.  Per batch and
 set one line in the accuracy record's format (`planes N literal-ok L exempt E fail F [img i cls c: cond .. lit .. own .. fp64 .. bound ..
 ok|FAIL]`); at the end ONE JSON object: the summary above (mode A against fp32) plus `criterion_planes` with the pooled counts, and `conforms` = no
-failed plane, label agreement and pooled mask mIoU at the project's bars."""
+failed plane, label agreement and pooled mask mIoU at the project's bars.
+
+--qk_gain G (default 1: nothing changes) multiplies the q and k rows of every block's qkv projection by sqrt(G) before the networks are made,
+so every attention logit is G times larger: the comparison, or with --criterion the criterion, then runs on sharp attention instead of a
+random initialisation's near-uniform one.  tools/act_stats.py --qk_gain G says what |s| and row entropy that reached."""
 import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def scale_qk(model, gain):
+    """--qk_gain: cosa_amd.models.vit.qk_gain_ on the network the others are copied from"""
+    from cosa_amd.models.vit import qk_gain_
+    return qk_gain_(model, gain)
 
 
 def get_parser():
@@ -37,6 +48,8 @@ def get_parser():
     p.add_argument("--synthetic", action="store_true", help="synthetic batches (train_step.synthetic_batch) instead of a dataset")
     p.add_argument("--trust_checkpoint", action="store_true",
                    help="allow the full unpickler for a checkpoint that torch.load(weights_only=True) refuses (runs code from the file)")
+    p.add_argument("--qk_gain", type=float, default=1.0,
+                   help="multiply every attention logit by G (the q and k rows of every qkv projection by sqrt(G)); 1: the weights as they are")
     return p
 
 
@@ -51,6 +64,8 @@ def main(argv=None):
         parser.error("--usegmm true: the adaptive thresholds are state of a training run; this tool compares at the fixed --high_thre / --low_thre")
     if args.criterion and args.check_mode not in ("auto", "fp32"):
         parser.error("--criterion scores --mode against fp32 and float64: --check_mode must be fp32 (or left at auto)")
+    if not 0 < args.qk_gain < float("inf"):
+        parser.error("--qk_gain must be a positive finite factor")
     if args.criterion and args.use_cammix:
         parser.error("--criterion: the criterion speaks of cam and cam_aux as multi_scale_camseg returns them, not of their --use_cammix mean")
     import torch
@@ -71,6 +86,7 @@ def main(argv=None):
     first = build_model(targs)
     if args.checkpoint:
         load_checkpoint(first, args.checkpoint, trust=args.trust_checkpoint)
+    scale_qk(first, args.qk_gain)
     models = []
     for mode in (args.mode, check_mode) + (("fp64",) if args.criterion else ()):      # networks of their own: shadows and buffers are keyed by parameter
         m = build_model(targs) if models else first
@@ -122,7 +138,8 @@ def main(argv=None):
                 pl["over"] += [dict(r, batch=n) for r in s["over"]]
         n += 1
     res = dict(seg_helper.teacher_check_summary(counters, K), mode=args.mode, check_mode=check_mode, batches=n, crop_size=S, batch_size=b,
-               checkpoint=os.path.abspath(args.checkpoint) if args.checkpoint else None, synthetic=bool(args.synthetic))
+               checkpoint=os.path.abspath(args.checkpoint) if args.checkpoint else None, synthetic=bool(args.synthetic),
+               **({"qk_gain": args.qk_gain} if args.qk_gain != 1.0 else {}))
     if args.criterion:
         failed = sum(pl["failed"] for pl in pooled.values())
         pairs = [res[p] for p in seg_helper.TEACHER_CHECK_PAIRS if res[p]["pix"]]
