@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _C
-from .monitors import ALL, BY_NAME, MONITORS
+from .monitors import BY_NAME, MONITORS
 
 MAGIC = b"COSASTAT"
 VERSION = 1
@@ -541,7 +541,7 @@ class TrainState:
         bytes)] to zero).  A file without one of them loads into a run that has it with the tensor zero (counters start at zero); a
         file with one loads into a run without it, the entry ignored.  Each with a note.  Any other difference is left as it is, for
         check_header to refuse."""
-        notes = dict(self._optional_notes(), **{m.state_name: m.notes for m in ALL[len(MONITORS):]})      # (--gt_stats, --act_stats_iters: monitors.ALL)
+        notes = self._optional_notes()
         theirs = header["tensors"]
         their_names, my_names = {t["name"] for t in theirs}, set(self.names)
         extra = [n for n in notes if n in their_names and n not in my_names]

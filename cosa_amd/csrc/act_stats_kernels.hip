@@ -4,45 +4,25 @@
 //
 //   cosa_range_stats_f32   one streaming pass over a column window of an fp32 matrix: finite / over 65504 / over 32768 / below 2^-14 /
 //                          non-finite counts and the largest finite |x|
-//   cosa_attn_stats_f32    the QK^T half of attn_fwd_f32_kernel (same blocks, tiles and MFMA orientation) without the PV product: per head
+//   cosa_attn_stats_f32    the QK^T half of attn_fwd_f32_kernel (f32_attn_tile.hpp: the same code) without the PV product: per head
 //                          the mean normalised row entropy, the mean top-1 probability, the peaked rows, the largest |logit|
 //
 // Everything that is added is an integer: counts, and per-row terms in 64-bit fixed point (rint of the term times 2^32 in double, once per
 // row).  Every maximum is an integer maximum of the bit pattern of a finite non-negative fp32 value.  So the words do not depend on the order
 // in which the wavefronts arrive: the same inputs give the same bytes on every run, and a second call on a table that was not zeroed
 // doubles counts and sums and keeps maxima.  Built with -ffp-contract=off: what is an fma here is written fmaf / fma.
-#include "common.hpp"
+#include "wave_reduce.hpp"
+#include "f32_attn_tile.hpp"
 
 namespace cosa {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
 constexpr unsigned kAbsMask = 0x7fffffffu, kInfBits = 0x7f800000u;
 constexpr unsigned kF16MaxBits = 0x477fe000u;        // 65504.0f: the largest finite fp16
 constexpr unsigned kF16HalfBits = 0x47000000u;       // 32768.0f: one bit of headroom left
 constexpr unsigned kF16MinNormalBits = 0x38800000u;  // 2^-14: below it the fp16 hi half is subnormal
-
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, d), hi = __shfl_xor((unsigned)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_max32(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // ---- range -------------------------------------------------------------------------------------------------------------------------------
 enum { rFinite = 0, rAbsMax, rOver, rNear, rTiny, rNonFinite, rWords };
@@ -115,25 +95,18 @@ __global__ __launch_bounds__(256) void range_stats_f32_kernel(const float *__res
         if (n_bad) atomicAdd(&red[rNonFinite], n_bad);
     }
     __syncthreads();
-    if (threadIdx.x < rWords) {
-        const u64 v = red[threadIdx.x];
-        if (v) {
-            if (threadIdx.x == rAbsMax) atomicMax(&out[threadIdx.x], v); else atomicAdd(&out[threadIdx.x], v);
-        }
-    }
+    flush_counters(red, out, rWords, 256, [](int i) { return i == rAbsMax; });
 }
 
 // ---- attention -----------------------------------------------------------------------------------------------------------------------------
-// As attn_fwd_f32_kernel (csrc/f32_kernels.hip): one block = 128 queries of one (batch, head) slice, 4 waves of 32 queries, key tiles of 32
+// As attn_fwd_f32_kernel (csrc/f32_kernels.hip), through the calls of f32_attn_tile.hpp:
+// one block = 128 queries of one (batch, head) slice, 4 waves of 32 queries, key tiles of 32
 // through LDS, S^T[key][query] = K[key][d] Q^T[d][query] on the f32-input MFMA with Q held in 32 VGPRs, the chain over d ascending.  A
 // lane's column is its query; the two lane halves hold different keys of the same query and share one maximum per tile.  Per query the
 // kernel carries the running maximum m (fp32, as the softmax sees it) and, in double so that no summation order shows,
 //     l = sum e^(s - m),   t = sum e^(s - m) (s - m)            (e^ is expf of the fp32 difference, as in the forward kernel)
 // with l <- alpha l, t <- alpha (t + (m - m') l), alpha = e^(m - m'), when m rises to m'.  A row ends as H = log l - t / l.
-constexpr int AQ = 128, AK = 32, HD = 64, K_LD = HD + 1;
 enum { aRows = 0, aEntFix, aTop1Fix, aPeaked, aSmax, aSharp, aNonFiniteRows, aWords };
-
-__device__ __forceinline__ int cd_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 __global__ __launch_bounds__(256) void attn_stats_f32_kernel(const float *__restrict__ qkv, u64 *__restrict__ out, int N, int H, float scale,
                                                              long long ldq)
@@ -147,55 +120,28 @@ __global__ __launch_bounds__(256) void attn_stats_f32_kernel(const float *__rest
     const float *qp = base + (size_t)head * HD, *kp = base + (size_t)(H + head) * HD;
     const int query = blockIdx.x * AQ + wave * 32 + (lane & 31);
 
-    float qreg[HD / 2];          // Q^T as the B operand: step s is d = 2s, 2s + 1
-#pragma unroll
-    for (int s = 0; s < HD / 2; s++) qreg[s] = query < N ? qp[(size_t)query * ldq + 2 * s + half] : 0.f;
+    float qreg[HD / 2];
+    attn_load_q(qp, query, N, ldq, half, qreg);
 
     float m = -INFINITY;
     double l = 0.0, t = 0.0;
     unsigned smax = 0, bad = 0;
 
-    // staging: thread -> key (tid + 256 i) >> 4, d quarter-row (tid & 15) * 4; keys past N are zeros and are masked below
-    float4 rk[2];
-    auto load_tile = [&](int key0) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int key = key0 + ((tid + 256 * i) >> 4), d = (tid & 15) * 4;
-            rk[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (key < N) rk[i] = *reinterpret_cast<const float4 *>(kp + (size_t)key * ldq + d);
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int key = (tid + 256 * i) >> 4, d = (tid & 15) * 4;
-            Ks[key][d] = rk[i].x; Ks[key][d + 1] = rk[i].y; Ks[key][d + 2] = rk[i].z; Ks[key][d + 3] = rk[i].w;
-        }
-    };
+    float4 rk[2];          // staging: keys past N are zeros and are masked below
 
     const int tiles = (N + AK - 1) / AK;
-    load_tile(0);
-    store_tile();
+    attn_load_rows(kp, 0, N, ldq, tid, rk);
+    attn_store_k(Ks, tid, rk);
     __syncthreads();
     for (int kt = 0; kt < tiles; kt++) {
-        if (kt + 1 < tiles) load_tile((kt + 1) * AK);
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; r++) s[r] = 0.f;
-#pragma unroll
-        for (int st = 0; st < HD / 2; st++) s = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[lane & 31][2 * st + half], qreg[st], s, 0, 0, 0);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const bool live = kt * AK + cd_row(r, lane) < N;
-            s[r] = live ? s[r] * scale : -INFINITY;
-            const unsigned a = __float_as_uint(s[r]) & kAbsMask;
+        if (kt + 1 < tiles) attn_load_rows(kp, (kt + 1) * AK, N, ldq, tid, rk);
+        f32x16 s = attn_scores(Ks, qreg, lane);
+        const float mx = attn_mask_max(s, kt * AK, N, scale, lane, [&](float v, bool live) {
+            const unsigned a = __float_as_uint(v) & kAbsMask;
             if (live) {
                 if (a >= kInfBits) bad = 1; else smax = a > smax ? a : smax;
             }
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        });
         const float m_new = fmaxf(m, mx);                                    // finite from the first tile on: key 0 exists
         const float alpha = expf(m - m_new);                                 // (first tile: expf(-inf) = 0 on l = 0, t = 0)
         const float dm = m == -INFINITY ? 0.f : m - m_new;                   // (... whose -inf must not meet that 0)
@@ -212,7 +158,7 @@ __global__ __launch_bounds__(256) void attn_stats_f32_kernel(const float *__rest
         m = m_new;
         __syncthreads();
         if (kt + 1 < tiles) {
-            store_tile();
+            attn_store_k(Ks, tid, rk);
             __syncthreads();
         }
     }
@@ -245,10 +191,7 @@ __global__ __launch_bounds__(256) void attn_stats_f32_kernel(const float *__rest
         }
     }
     __syncthreads();
-    if (tid < aWords && red[tid]) {
-        u64 *o = out + (size_t)head * aWords + tid;
-        if (tid == aSmax || tid == aSharp) atomicMax(o, red[tid]); else atomicAdd(o, red[tid]);
-    }
+    flush_counters(red, out + (size_t)head * aWords, aWords, 256, [](int i) { return i == aSmax || i == aSharp; });
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -4,25 +4,11 @@
 // butterfly, four partials through LDS in index order) and thread 0 forms the figures and the verdict in float64.  Maxima and integer counts
 // are exact whatever the order, and the order is fixed anyway: the same bytes on every run.  NaN never enters a maximum (fmax drops it); a
 // plane of the mode under test that holds a non-finite element fails.
-#include "common.hpp"
+#include "wave_reduce.hpp"
 #include <cmath>
 
 namespace cosa {
 namespace {
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void conformance_planes_kernel(const float *__restrict__ camA, const float *__restrict__ cam32,
                                                                  const double *__restrict__ cam64, const float *__restrict__ active,
@@ -46,14 +32,14 @@ __global__ __launch_bounds__(256) void conformance_planes_kernel(const float *__
     unsigned bad = 0;
     for (int i = tid; i < HW; i += 256) {
         const double av = (double)a[i], cv = (double)c32[i], rv = c64[i];
-        bad += (__float_as_uint(a[i]) & 0x7f800000u) == 0x7f800000u;
+        bad += nonfinite_bits(a[i]);
         d = fmax(d, fabs(av - cv));
         m32 = fmax(m32, fabs(cv));
         e_ref = fmax(e_ref, fabs(cv - rv));
         e_hip = fmax(e_hip, fabs(av - rv));
     }
     d = wave_max(d); m32 = wave_max(m32); e_ref = wave_max(e_ref); e_hip = wave_max(e_hip);
-    bad = wave_sum(bad);
+    bad = wave_sum32(bad);
     if (lane == 0) { sh[wid][0] = d; sh[wid][1] = m32; sh[wid][2] = e_ref; sh[wid][3] = e_hip; shn[wid] = bad; }
     __syncthreads();
     if (tid != 0) return;

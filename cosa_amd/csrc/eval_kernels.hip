@@ -13,7 +13,7 @@
 // bit-identical to the reference's on the golden vectors (tests/golden/eval.npz).
 #include "kernels.hpp"
 #include "spec_math.hpp"
-#include "student_label.hpp"      // src_index_r, bilerp, student_label4, wave_count
+#include "student_label.hpp"      // src_index_r, bilerp, student_label4; wave_reduce.hpp: wave_count, nonfinite_bits, flush_counters
 
 namespace cosa {
 namespace {
@@ -411,8 +411,6 @@ struct LabelStatsArgs {
     float sy, sx, ignore;
 };
 
-__device__ __forceinline__ bool nonfinite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-
 // A thread owns four adjacent pixels of a row: the source rows and their weights once per thread, the source columns once per pixel,
 // the K low-resolution logit planes (L2-resident) through the same src_index_r / bilerp calls as eval_labels_kernel's lab_vd.  The two
 // masks and the CAM planes of the present classes are the only full-resolution streams, read once as float4.  A wavefront's 64 items
@@ -496,8 +494,7 @@ __global__ __launch_bounds__(256) void label_stats_kernel(const LabelStatsArgs a
     if (n_bad[0]) atomicAdd(&ctr[off[7]], (unsigned long long)n_bad[0]);
     if (n_bad[1]) atomicAdd(&ctr[off[8]], (unsigned long long)n_bad[1]);
     __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 256)
-        if (ctr[i]) atomicAdd(&a.counters[i], ctr[i]);
+    flush_counters(ctr, a.counters, n, 256);
     if (threadIdx.x == 0 && (ctr[off[7]] | ctr[off[8]])) atomicOr(a.flag, 1u);
 }
 

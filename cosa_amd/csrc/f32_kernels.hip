@@ -13,11 +13,10 @@
 // accumulator is the only sum there is: no split-K, no atomics, the same chain whatever M is, wherever the row sits and whatever the other
 // rows hold.  The epilogue follows in fp32.  This translation unit is built with -ffp-contract=off: what is an fma here is written fmaf.
 #include "kernels.hpp"
+#include "f32_attn_tile.hpp"      // f32x16, cd_row; the QK^T half of the attention kernel
 
 namespace cosa {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128;        // block tile rows
 constexpr int BK = 16;         // k per LDS stage (K % 16 == 0: 192 = 12 stages; a conv tap's Cin is a multiple, so a stage never straddles taps)
@@ -33,9 +32,6 @@ struct GemmArgs {
     int h, w, Cin, dil;
     long long img_stride;
 };
-
-// row of the C/D tile a lane holds in accumulator register r (32x32 MFMA; the column is lane & 31)
-__device__ __forceinline__ int cd_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // BN: 128 (2 x 2 waves, 2 x 2 tiles of 32 x 32 each) when N % 128 == 0, else 64 (4 x 1 waves, 1 x 2 tiles).  The tile shape moves no bit:
 // an element's chain is over k alone.
@@ -182,7 +178,7 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 //     O^T[d][query]   += V^T[d][key] P^T[key][query]     B = the probabilities as the score accumulators hold them, A = V tile from LDS
 // A lane's column is its query in both results, so the running maximum, the rescale and the row sum are per lane; the two lane halves hold
 // different keys of the same query and meet in one exchange per tile.  exp is expf (no exp2 folding, no fast variant).
-constexpr int AQ = 128, AK = 32, HD = 64, K_LD = HD + 1, V_LD = HD + 4;
+constexpr int V_LD = HD + 4;          // (AQ, AK, HD, K_LD: f32_attn_tile.hpp)
 
 __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float *__restrict__ qkv, float *__restrict__ out, int N, int H, float scale,
                                                            long long ldq, long long ldo)
@@ -195,9 +191,8 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float *__restri
     const float *qp = base + (size_t)head * HD, *kp = base + (size_t)(H + head) * HD, *vp = base + (size_t)(2 * H + head) * HD;
     const int query = blockIdx.x * AQ + wave * 32 + (lane & 31);
 
-    float qreg[HD / 2];          // Q^T as the B operand: step s is d = 2s, 2s + 1
-#pragma unroll
-    for (int s = 0; s < HD / 2; s++) qreg[s] = query < N ? qp[(size_t)query * ldq + 2 * s + half] : 0.f;
+    float qreg[HD / 2];
+    attn_load_q(qp, query, N, ldq, half, qreg);
 
     f32x16 o[2];
 #pragma unroll
@@ -206,26 +201,16 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float *__restri
         for (int r = 0; r < 16; r++) o[t][r] = 0.f;
     float m = -INFINITY, l = 0.f;
 
-    // staging: thread -> key (tid + 256 i) >> 4, d quarter-row (tid & 15) * 4; keys past N are zeros (their probability is an exact 0)
+    // staging: keys past N are zeros (their probability is an exact 0)
     float4 rk[2], rv[2];
     auto load_tile = [&](int key0) {
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int key = key0 + ((tid + 256 * i) >> 4), d = (tid & 15) * 4;
-            rk[i] = rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (key < N) {
-                rk[i] = *reinterpret_cast<const float4 *>(kp + (size_t)key * ldq + d);
-                rv[i] = *reinterpret_cast<const float4 *>(vp + (size_t)key * ldq + d);
-            }
-        }
+        attn_load_rows(kp, key0, N, ldq, tid, rk);
+        attn_load_rows(vp, key0, N, ldq, tid, rv);
     };
     auto store_tile = [&]() {
+        attn_store_k(Ks, tid, rk);
 #pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int key = (tid + 256 * i) >> 4, d = (tid & 15) * 4;
-            Ks[key][d] = rk[i].x; Ks[key][d + 1] = rk[i].y; Ks[key][d + 2] = rk[i].z; Ks[key][d + 3] = rk[i].w;
-            *reinterpret_cast<float4 *>(&Vs[key][d]) = rv[i];
-        }
+        for (int i = 0; i < 2; i++) *reinterpret_cast<float4 *>(&Vs[(tid + 256 * i) >> 4][(tid & 15) * 4]) = rv[i];
     };
 
     const int tiles = (N + AK - 1) / AK;
@@ -234,19 +219,8 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float *__restri
     __syncthreads();
     for (int kt = 0; kt < tiles; kt++) {
         if (kt + 1 < tiles) load_tile((kt + 1) * AK);
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; r++) s[r] = 0.f;
-#pragma unroll
-        for (int st = 0; st < HD / 2; st++) s = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[lane & 31][2 * st + half], qreg[st], s, 0, 0, 0);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int key = kt * AK + cd_row(r, lane);
-            s[r] = key < N ? s[r] * scale : -INFINITY;
-            mx = fmaxf(mx, s[r]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        f32x16 s = attn_scores(Ks, qreg, lane);
+        const float mx = attn_mask_max(s, kt * AK, N, scale, lane);
         const float m_new = fmaxf(m, mx);            // finite from the first tile on: key 0 exists
         const float alpha = expf(m - m_new);         // (first tile: expf(-inf) = 0 on l = 0, o = 0)
         float psum = 0.f;

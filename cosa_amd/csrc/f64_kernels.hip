@@ -16,7 +16,7 @@
 // steps of 4 starting from zero: no split-K, no atomics, the same sequence whatever M is, wherever the row sits and whatever the other rows
 // hold (a lane's accumulator registers belong to one column and four rows; the MFMA forms each element from its own row of A and column of
 // B alone).  The epilogue follows in float64.  Built with -ffp-contract=off -fno-fast-math: erf and exp are the double routines.
-#include "common.hpp"
+#include "wave_reduce.hpp"      // wave_max
 #include <algorithm>
 #include <cmath>
 
@@ -285,12 +285,6 @@ __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
     return v;
 }
 

@@ -127,11 +127,9 @@ __global__ __launch_bounds__(256) void gt_stats_kernel(const GtStatsArgs a)
     if (n_valid) atomicAdd(&scal[1], n_valid);
     if (n_other) atomicAdd(&scal[2], n_other);
     __syncthreads();
-    if (threadIdx.x < 3 && scal[threadIdx.x]) atomicAdd(&a.counters[1 + threadIdx.x], (unsigned long long)scal[threadIdx.x]);
+    flush_counters(scal, a.counters + 1, 3, 256);
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.counters[0], 1ull);          // steps
-    if (kLds)
-        for (int i = threadIdx.x; i < T; i += 256)
-            if (hist[i]) atomicAdd(&gmat[i], (unsigned long long)hist[i]);
+    if (kLds) flush_counters(hist, gmat, T, 256);
 }
 
 }  // namespace

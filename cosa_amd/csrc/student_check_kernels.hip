@@ -10,7 +10,7 @@
 // Layout of the work: one wavefront per cell (b, y, x) with the class on the lane (lane l owns channels l, l + 64, l + 128, l + 192: K <=
 // 256), four wavefronts per workgroup, kCellsPerWave cells per wavefront.  The two [B,K-1] logit matrices and the loss vectors are tiny:
 // workgroup 0 takes them after its cells.  Counts meet in workgroup-private LDS counters and leave with one global atomic per touched slot.
-#include "common.hpp"
+#include "wave_reduce.hpp"
 
 namespace cosa {
 namespace {
@@ -35,42 +35,6 @@ __host__ __device__ inline bool slot_is_max(int s)
         return f == fMaxD || f == fMaxB;
     }
     return s >= kLoss0 && s < kLoss0 + 4 * kLossFields && (s - kLoss0) % kLossFields == 2;
-}
-
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & kInfBits) != kInfBits; }
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, d), hi = __shfl_xor((unsigned)(v >> 32), d);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_sum32(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_max32(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_or32(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v |= __shfl_xor(v, d);
-    return v;
 }
 
 // a term t >= 0 in fixed point with `frac` fractional bits, or "not representable": t >= 2^int_bits (NaN and +inf land here too).  frac +

@@ -1,8 +1,10 @@
 // student_label.hpp -- what the per-step monitors of the label maps share (eval_kernels.hip: cosa_label_stats; gt_stats_kernels.hip:
-// cosa_gt_stats): spec R's source index and bilinear sample, the student's label of four adjacent pixels, and the wave-aggregated count.
+// cosa_gt_stats) and --teacher_check's label pass (teacher_check_kernels.hip): spec R's source index and bilinear sample, the student's label
+// of four adjacent pixels, the four-pixel load and a label's histogram slot; the wave-aggregated count comes with wave_reduce.hpp.
 // Include from a translation unit compiled with -ffp-contract=off (build.py: EXACT): what is an fma here is written as one.
 #pragma once
 #include "kernels.hpp"
+#include "wave_reduce.hpp"
 
 namespace cosa {
 namespace {
@@ -28,39 +30,6 @@ __device__ __forceinline__ float bilerp(const float *__restrict__ pl, int w, int
     const float r0 = __builtin_fmaf(pl[(size_t)y0 * w + x0], lx0, pl[(size_t)y0 * w + x1] * lx1);
     const float r1 = __builtin_fmaf(pl[(size_t)y1 * w + x0], lx0, pl[(size_t)y1 * w + x1] * lx1);
     return __builtin_fmaf(r0, ly0, r1 * ly1);
-}
-
-// ctr[slot] += 1 for every lane with `valid`, one atomic per distinct slot of the wavefront (a crop holds a handful of labels: a
-// plain atomic per lane would serialise 64 deep on one address).  `todo` is wave-uniform, so every lane leaves the loop together.
-// T: unsigned long long or unsigned int counters, in LDS or in global memory.  Every lane of the wavefront must make the call.
-template <typename T>
-__device__ __forceinline__ void wave_count(T *ctr, int slot, bool valid)
-{
-    unsigned long long todo = __ballot(valid);
-    while (todo) {
-        const int leader = __ffsll(todo) - 1;
-        const int s = __builtin_amdgcn_readlane(slot, leader);
-        const unsigned long long same = __ballot(valid && slot == s);
-        if ((int)__lane_id() == leader) atomicAdd(&ctr[s], (T)__popcll(same));
-        todo &= ~same;
-    }
-}
-
-// wave_count for slots that may be many per wavefront (a [K][K] matrix under a speckled map): the two most wanted slots -- the leaders' --
-// leave aggregated as above, what is left after them adds one by one, where few lanes share an address.  The same sums.
-template <typename T>
-__device__ __forceinline__ void wave_count_mixed(T *ctr, int slot, bool valid)
-{
-    unsigned long long todo = __ballot(valid);
-    for (int round = 0; round < 2 && todo; round++) {
-        const int leader = __ffsll(todo) - 1;
-        const int s = __builtin_amdgcn_readlane(slot, leader);
-        const unsigned long long same = __ballot(valid && slot == s);
-        if ((int)__lane_id() == leader) atomicAdd(&ctr[s], (T)__popcll(same));
-        valid = valid && slot != s;
-        todo &= ~same;
-    }
-    if (valid) atomicAdd(&ctr[slot], (T)1);
 }
 
 // image b's label row cls[b][K-1] as a wave-uniform bit mask, with two loads and two ballots: present[0] bit i: class i + 1 is in the row

@@ -3,7 +3,7 @@
 //
 // Everything that is added is an integer; the per-plane figure max |a - b| is a float maximum of exactly computed fp32 differences (no
 // NaN ever enters it), kept as its bit pattern and combined with integer atomic maxima: the same bits in any order, on every run.
-#include "common.hpp"
+#include "student_label.hpp"      // label_slot, load_f32x4; wave_reduce.hpp: wave_sum32, wave_max, wave_count, nonfinite_bits
 
 namespace cosa {
 namespace {
@@ -58,35 +58,6 @@ struct TeacherCheckArgs {
     float ignore;
 };
 
-__device__ __forceinline__ bool nonfinite_bits(float v) { return (__float_as_uint(v) & kInfBits) == kInfBits; }
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
-    return v;
-}
-
-// ctr[slot] += 1 for every lane with `valid`, one LDS atomic per distinct slot of the wavefront; `todo` is wave-uniform
-__device__ __forceinline__ void wave_count(unsigned long long *ctr, int slot, bool valid)
-{
-    unsigned long long todo = __ballot(valid);
-    while (todo) {
-        const int leader = __ffsll(todo) - 1;
-        const int s = __builtin_amdgcn_readlane(slot, leader);
-        const unsigned long long same = __ballot(valid && slot == s);
-        if ((int)__lane_id() == leader) atomicAdd(&ctr[s], (unsigned long long)__popcll(same));
-        todo &= ~same;
-    }
-}
-
 // the map pass of one workgroup: kChunk elements of ONE plane of one set.  A plane of an absent class is left before its first load.
 __device__ __forceinline__ void map_chunk(const TeacherCheckArgs &a, int set, unsigned wg, const int (&off)[COSA_TEACHER_CHECK_SLOTS])
 {
@@ -101,17 +72,8 @@ __device__ __forceinline__ void map_chunk(const TeacherCheckArgs &a, int set, un
         const unsigned e = chunk * kChunk + (it * 256u + threadIdx.x) * 4u;
         if (e >= n) continue;
         float va[4], vb[4];
-        if (a.vec[set]) {                                   // n % 4 == 0: e + 3 < n
-            const float4 ta = *reinterpret_cast<const float4 *>(pa + e), tb = *reinterpret_cast<const float4 *>(pb + e);
-            va[0] = ta.x; va[1] = ta.y; va[2] = ta.z; va[3] = ta.w;
-            vb[0] = tb.x; vb[1] = tb.y; vb[2] = tb.z; vb[3] = tb.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                va[k] = e + k < n ? pa[e + k] : 0.0f;
-                vb[k] = e + k < n ? pb[e + k] : 0.0f;
-            }
-        }
+        load_f32x4(pa + e, (int)e, (int)n, a.vec[set], va);          // (vec: n % 4 == 0, so e + 3 < n; n < 2^31: entry point)
+        load_f32x4(pb + e, (int)e, (int)n, a.vec[set], vb);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const bool na = nonfinite_bits(va[k]), nb = nonfinite_bits(vb[k]);
@@ -122,22 +84,14 @@ __device__ __forceinline__ void map_chunk(const TeacherCheckArgs &a, int set, un
         }
     }
     fig = wave_max(fig);
-    bad_a = wave_sum(bad_a);
-    bad_b = wave_sum(bad_b);
+    bad_a = wave_sum32(bad_a);
+    bad_b = wave_sum32(bad_b);
     if (__lane_id() == 0) {
         // non-negative floats order as their bit patterns: an integer maximum, exact in any order
         if (fig > 0.0f) atomicMax(&a.fig[(size_t)set * a.B * a.C + plane], __float_as_uint(fig));
         if (bad_a) atomicAdd(&a.counters[off[1 + 6 * set + 4]], (unsigned long long)bad_a);
         if (bad_b) atomicAdd(&a.counters[off[1 + 6 * set + 5]], (unsigned long long)bad_b);
     }
-}
-
-// is v a label, and which slot of [cnt[K] | ignore] does it own?
-__device__ __forceinline__ int label_slot(float v, int K, float ignore)
-{
-    if (v == ignore) return K;
-    if (v >= 0.0f && v < (float)K && v == (float)(int)v) return (int)v;
-    return -1;
 }
 
 // the label pass of one workgroup: 256 items of four adjacent pixels of a row, both pairs
@@ -163,12 +117,12 @@ __device__ __forceinline__ void label_chunk(const TeacherCheckArgs &a, unsigned 
     unsigned n_pix = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) n_pix += in[k] ? 1u : 0u;
-    n_pix = wave_sum(n_pix);
+    n_pix = wave_sum32(n_pix);
     for (int p = 0; p < kPairs; p++) {
         if (!a.la[p]) continue;                                                              // (uniform)
         float va[4] = {0.0f, 0.0f, 0.0f, 0.0f}, vb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (any) {
-            if (a.lvec) {
+            if (a.lvec) {                                    // (both maps under ONE branch: two load_f32x4 calls cost 7 SGPRs)
                 const float4 ta = *reinterpret_cast<const float4 *>(a.la[p] + o), tb = *reinterpret_cast<const float4 *>(a.lb[p] + o);
                 va[0] = ta.x; va[1] = ta.y; va[2] = ta.z; va[3] = ta.w;
                 vb[0] = tb.x; vb[1] = tb.y; vb[2] = tb.z; vb[3] = tb.w;
@@ -191,7 +145,7 @@ __device__ __forceinline__ void label_chunk(const TeacherCheckArgs &a, unsigned 
             wave_count(c, sb == K ? 3 : 4 + K + sb, in[k] && sb >= 0);
             wave_count(c, 4 + 2 * K + sa, in[k] && sa >= 0 && sa < K && sa == sb);
         }
-        n_agree = wave_sum(n_agree);
+        n_agree = wave_sum32(n_agree);
         if (__lane_id() == 0) {
             if (n_pix) atomicAdd(&c[0], (unsigned long long)n_pix);
             if (n_agree) atomicAdd(&c[1], (unsigned long long)n_agree);
@@ -221,7 +175,7 @@ __global__ __launch_bounds__(256) void teacher_check_kernel(const TeacherCheckAr
     for (int p = 0; p < kPairs; p++) {
         if (!a.la[p]) continue;
         const int base = off[1 + 6 * kSets + 7 * p];                                       // the pair's slots are contiguous from `pix` on
-        for (int i = threadIdx.x; i < per; i += 256)
+        for (int i = threadIdx.x; i < per; i += 256)          // (flush_counters' loop written out: the helper moves this kernel's register count)
             if (ctr[p * kPairSlots + i]) atomicAdd(&a.counters[base + i], ctr[p * kPairSlots + i]);
     }
 }

@@ -207,7 +207,7 @@ def main(args):
                 line = ("Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  "
                         "cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, reg_loss: %.4f ..."
                         % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
-                for m in monitors.ALL:                                                  # (a monitor that is off: the line as ever)
+                for m in monitors.MONITORS:                                                # (a monitor that is off: the line as ever)
                     if m.name in host:
                         summary = host[m.name] if m.summary is None else m.summary(trainer, args, host[m.name])
                         if m.gate(summary):

@@ -1,6 +1,6 @@
 """The optional run-time monitors as ONE table: the gradient guard, --label_stats, --tensor_stats, --teacher_check_iters,
---student_check_iters, (ROWS' last) --gt_stats and (ALL's last, section 21) --act_stats_iters.  A row says what the launcher's log interval (main.read_interval and the log block), the jsonl files and the
-state files (checkpoint.TrainState) need to know about a monitor; the kernels, their torch partners and the summaries are the monitors' own
+--student_check_iters, --gt_stats and --act_stats_iters (section 21).  A row says what the launcher's log interval
+(main.read_interval and the log block), the jsonl files and the state files (checkpoint.TrainState) need to know about a monitor; the kernels, their torch partners and the summaries are the monitors' own
 and live where they always did (utils/seg_helper.py, utils/torch_helper.py, CoSATrainer).  Adding a monitor is adding a row."""
 import json
 from pathlib import Path
@@ -97,6 +97,11 @@ def _gt_stats_line(summary, targs):
                                                                  summary["student"]["miou"])
 
 
+def _act_stats_summary(trainer, args, values):
+    depth, heads = trainer.act_stats_shape
+    return seg_helper.act_stats_summary(values, depth, heads)
+
+
 # in the order in which the log line shows them
 MONITORS = (
     Monitor("guard", lambda tr: tr.guard_state, _guard_pack, lambda g, flat: list(flat), _keep, None, _guard_line, None, _always,
@@ -128,40 +133,24 @@ MONITORS = (
             "aux.student_check.counters",
             ("the file holds a student check's counters and this run makes no checks (--student_check_iters 0): the entry is ignored",
              "written without a student check: this run's check counters start at zero")),
-)
-# MONITORS is the five monitors of the training arithmetic, as tests/test_monitors_cpu.py pins it row by row (and with it
-# checkpoint.TrainState._optional_notes); ROWS is the whole table: those five and the monitor of the data, --gt_stats.  What walks the table
-# -- active(), the launcher's log block, the state files' optional entries -- walks ROWS.
-ROWS = MONITORS + (
     Monitor("gt_stats", lambda tr: getattr(tr, "gt_stats_state", None), _counts_pack, _counts_unpack, _zero,
             lambda tr, args, v: seg_helper.gt_stats_summary(v, args.num_classes), _gt_stats_line, lambda targs: {}, _always,
             "aux.gt_stats.counters",
             ("the file holds ground-truth statistics and this run does not collect them (--gt_stats false): the entry is ignored",
              "written without ground-truth statistics: this run's ground-truth counters start at zero")),
-)
-
-
-def _act_stats_summary(trainer, args, values):
-    depth, heads = trainer.act_stats_shape
-    return seg_helper.act_stats_summary(values, depth, heads)
-
-
-# ALL is what walks the table now -- active(), the launcher's log block, BY_NAME, the state files' optional entries: ROWS (pinned by
-# tests/test_gt_stats_cpu.py as MONITORS + --gt_stats) and the monitor of the activations, --act_stats_iters.  Its fixed-point sums (2^-32
-# units, one term per attention row) pass 2^53 within an interval: they travel as --student_check_iters' do, in 32-bit halves
-ALL = ROWS + (
+    # its fixed-point sums (2^-32 units, one term per attention row) pass 2^53 within an interval: they travel as --student_check_iters' do
     Monitor("act_stats", lambda tr: getattr(tr, "act_stats_state", None), _student_check_pack, _student_check_unpack, _zero,
             _act_stats_summary, lambda summary, targs: seg_helper.act_stats_line(summary), lambda targs: dict(mode="fp32"), _held_a_check,
             "aux.act_stats.counters",
             ("the file holds activation statistics and this run collects none (--act_stats_iters 0): the entry is ignored",
              "written without activation statistics: this run's activation counters start at zero")),
 )
-BY_NAME = {m.name: m for m in ALL}
+BY_NAME = {m.name: m for m in MONITORS}
 
 
 def active(trainer):
     """[(Monitor, its tensors)] of the monitors `trainer` has on, in the table's order: what main.read_interval takes"""
-    return [(m, t) for m, t in ((m, m.tensors(trainer)) for m in ALL) if t is not None]
+    return [(m, t) for m, t in ((m, m.tensors(trainer)) for m in MONITORS) if t is not None]
 
 
 def monitor_record(m, summary, n_iter, targs):

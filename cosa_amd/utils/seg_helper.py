@@ -303,6 +303,30 @@ def eval_label_maps(cam, seg, cls_label, size, bkg_thre):
 
 
 # --------------------------------------------------------------------------------------------
+# the monitors' counter vectors: each C layout function is THE definition of its vector, the lengths here come from it
+# --------------------------------------------------------------------------------------------
+def _c_layout(fn, slots, K):
+    """a C layout function's answer as ({slot name: offset in elements}, number of elements)"""
+    off = (ctypes.c_size_t * len(slots))()
+    n = fn(int(K), off)
+    if n == 0:
+        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
+    return {name: int(off[i]) for i, name in enumerate(slots)}, int(n)
+
+
+def _new_counters(layout, device):
+    """a zeroed counter vector of `layout`'s length (int64: the uint64 counters of the C ABI, which stay below 2^63)"""
+    return torch.zeros(layout[1], dtype=torch.int64, device=device)
+
+
+def _check_counters(counters, layout, who):
+    """`counters` is a contiguous int64 vector of `layout`'s length, as new_<who> makes it"""
+    n = layout[1]
+    if counters.dtype != torch.int64 or counters.shape != (n,) or not counters.is_contiguous():
+        raise ValueError(f"{who}: counters must be a contiguous int64 vector of {n} elements (new_{who})")
+
+
+# --------------------------------------------------------------------------------------------
 # per-step pseudo-label statistics and the teacher finite check (DESIGN.md section 11)
 # --------------------------------------------------------------------------------------------
 LABEL_STATS_SLOTS = ("steps", "pix", "main", "aux", "agree", "inter", "pred", "bad_cam", "bad_cam_aux")     # cosa_label_stats_layout's order
@@ -312,16 +336,12 @@ LABEL_STATS_MAX_K = 128
 def label_stats_layout(K):
     """cosa_label_stats_layout: ({slot name: offset in elements}, number of elements) of the counter vector for K = num_classes
     (background included).  Needs no device."""
-    off = (ctypes.c_size_t * len(LABEL_STATS_SLOTS))()
-    n = _C.lib().cosa_label_stats_layout(int(K), off)
-    if n == 0:
-        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
-    return {name: int(off[i]) for i, name in enumerate(LABEL_STATS_SLOTS)}, int(n)
+    return _c_layout(_C.lib().cosa_label_stats_layout, LABEL_STATS_SLOTS, K)
 
 
 def new_label_stats(K, device):
     """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay far below 2^63)"""
-    return torch.zeros(label_stats_layout(K)[1], dtype=torch.int64, device=device)
+    return _new_counters(label_stats_layout(K), device)
 
 
 def _label_stats_shapes(mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux, counters):
@@ -331,8 +351,7 @@ def _label_stats_shapes(mask_main, mask_aux, seg_logits, cls_label, cam, cam_aux
     if mask_main.shape != (B, S, S) or (mask_aux is not None and mask_aux.shape != (B, S, S)) or seg_logits.shape != (B, K, h, w) or \
             cls_label.shape != (B, K - 1) or any(c is not None and c.shape != (B, K - 1, S, S) for c in (cam, cam_aux)):
         raise ValueError("label_stats: masks must be [B,S,S], seg_logits [B,K,h,w], cls_label [B,K-1] and the CAMs [B,K-1,S,S]")
-    if counters.dtype != torch.int64 or counters.shape != (4 * K + 7,) or not counters.is_contiguous():
-        raise ValueError(f"label_stats: counters must be a contiguous int64 vector of {4 * K + 7} elements (new_label_stats)")
+    _check_counters(counters, label_stats_layout(K), "label_stats")
     return B, K, S, int(h), int(w)
 
 
@@ -442,16 +461,12 @@ def gt_stats_layout(K):
     """cosa_gt_stats_layout: ({slot name: offset in elements}, number of elements) of the counter vector for K = num_classes (background
     included): steps, pix, valid, gt_other, main[K][K+1], aux[K][K+1], student[K][K] (row: the ground-truth class; column K of main and
     aux: the label map's ignore).  Needs no device."""
-    off = (ctypes.c_size_t * len(GT_STATS_SLOTS))()
-    n = _C.lib().cosa_gt_stats_layout(int(K), off)
-    if n == 0:
-        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
-    return {name: int(off[i]) for i, name in enumerate(GT_STATS_SLOTS)}, int(n)
+    return _c_layout(_C.lib().cosa_gt_stats_layout, GT_STATS_SLOTS, K)
 
 
 def new_gt_stats(K, device):
     """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay far below 2^63)"""
-    return torch.zeros(gt_stats_layout(K)[1], dtype=torch.int64, device=device)
+    return _new_counters(gt_stats_layout(K), device)
 
 
 def _gt_stats_shapes(gt, mask_main, mask_aux, seg_logits, cls_label, counters):
@@ -461,9 +476,7 @@ def _gt_stats_shapes(gt, mask_main, mask_aux, seg_logits, cls_label, counters):
     if gt.dtype != torch.uint8 or gt.shape != (B, S, S) or mask_main.shape != (B, S, S) or \
             (mask_aux is not None and mask_aux.shape != (B, S, S)) or seg_logits.shape != (B, K, h, w) or cls_label.shape != (B, K - 1):
         raise ValueError("gt_stats: gt must be uint8 [B,S,S], the masks [B,S,S], seg_logits [B,K,h,w] and cls_label [B,K-1]")
-    n = 4 + 2 * K * (K + 1) + K * K
-    if counters.dtype != torch.int64 or counters.shape != (n,) or not counters.is_contiguous():
-        raise ValueError(f"gt_stats: counters must be a contiguous int64 vector of {n} elements (new_gt_stats)")
+    _check_counters(counters, gt_stats_layout(K), "gt_stats")
     return B, K, S, int(h), int(w)
 
 
@@ -572,16 +585,12 @@ def teacher_check_layout(K):
     """cosa_teacher_check_layout: ({slot name: offset in elements}, number of elements) of the counter vector for K = num_classes
     (background included).  Slot names are "checks", "<set>.<field>" for the map sets cam / aux / tgt and "<pair>.<field>" for the label
     pairs main / aux_label.  Needs no device."""
-    off = (ctypes.c_size_t * len(TEACHER_CHECK_SLOTS))()
-    n = _C.lib().cosa_teacher_check_layout(int(K), off)
-    if n == 0:
-        raise ValueError(_C.lib().cosa_last_error().decode("utf-8", "replace"))
-    return {name: int(off[i]) for i, name in enumerate(TEACHER_CHECK_SLOTS)}, int(n)
+    return _c_layout(_C.lib().cosa_teacher_check_layout, TEACHER_CHECK_SLOTS, K)
 
 
 def new_teacher_check(K, device):
     """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay far below 2^63)"""
-    return torch.zeros(teacher_check_layout(K)[1], dtype=torch.int64, device=device)
+    return _new_counters(teacher_check_layout(K), device)
 
 
 def _teacher_check_shapes(cams, auxs, tgts, labels, aux_labels, cls_label, counters):
@@ -600,8 +609,7 @@ def _teacher_check_shapes(cams, auxs, tgts, labels, aux_labels, cls_label, count
     K = C + 1
     if K > TEACHER_CHECK_MAX_K or h > S or w > S:
         raise ValueError(f"teacher_check: outside the envelope (C {C} <= {TEACHER_CHECK_MAX_K - 1}, h {h} and w {w} <= S {S})")
-    if counters.dtype != torch.int64 or counters.shape != (48 + 6 * K,) or not counters.is_contiguous():
-        raise ValueError(f"teacher_check: counters must be a contiguous int64 vector of {48 + 6 * K} elements (new_teacher_check)")
+    _check_counters(counters, teacher_check_layout(K), "teacher_check")
     return B, C, K, S, h, w
 
 
@@ -826,7 +834,7 @@ def student_check_layout(K):
 
 def new_student_check(K, device):
     """a zeroed counter vector (int64: the uint64 counters of the C ABI, which stay below 2^63)"""
-    return torch.zeros(student_check_layout(K)[1], dtype=torch.int64, device=device)
+    return _new_counters(student_check_layout(K), device)
 
 
 def _student_check_shapes(seg, cam, aux, cls, clsaux, losses, cls_label, counters):
@@ -839,8 +847,7 @@ def _student_check_shapes(seg, cam, aux, cls, clsaux, losses, cls_label, counter
                          "the loss vectors [4]")
     if K < 2 or K > STUDENT_CHECK_MAX_K or B * K * h * w >= 2 ** 31:
         raise ValueError(f"student_check: outside the envelope (2 <= K {K} <= {STUDENT_CHECK_MAX_K}, B K h w < 2^31)")
-    if counters.dtype != torch.int64 or counters.shape != (STUDENT_CHECK_HEAD + 2 * K,) or not counters.is_contiguous():
-        raise ValueError(f"student_check: counters must be a contiguous int64 vector of {STUDENT_CHECK_HEAD + 2 * K} elements (new_student_check)")
+    _check_counters(counters, student_check_layout(K), "student_check")
     return int(B), int(K), h, w
 
 
@@ -1021,12 +1028,12 @@ def act_stats_layout(depth, H):
 
 def new_act_stats(depth, H, device):
     """a zeroed counter vector (int64) of act_stats_layout's length"""
-    return torch.zeros(act_stats_layout(depth, H)[1], dtype=torch.int64, device=device)
+    return _new_counters(act_stats_layout(depth, H), device)
 
 
 def act_stats_table(counters, depth, H):
     """the [depth][36 + 7 H] view of a counter vector that an ActProbe takes as its table"""
-    W = 36 + 7 * int(H)
+    W = act_stats_layout(depth, H)[0]["width"]
     return counters[:int(depth) * W].view(int(depth), W)
 
 

@@ -132,15 +132,14 @@ def test_summary_of_an_empty_table_and_of_overflowing_sites():
 
 def test_the_monitor_table_keeps_its_pinned_tuples_and_ends_with_the_new_row():
     from cosa_amd import checkpoint, monitors
-    assert [m.name for m in monitors.MONITORS] == ["guard", "label_stats", "tensor_stats", "teacher_check", "student_check"]
-    assert monitors.ROWS[:-1] == monitors.MONITORS and monitors.ROWS[-1].name == "gt_stats" and len(monitors.ROWS) == 6
-    assert monitors.ALL[:-1] == monitors.ROWS and monitors.ALL[-1].name == "act_stats" and monitors.ALL[-1].state_name == "aux.act_stats.counters"
-    assert set(monitors.BY_NAME) == {m.name for m in monitors.ALL}
+    assert [m.name for m in monitors.MONITORS] == ["guard", "label_stats", "tensor_stats", "teacher_check", "student_check", "gt_stats", "act_stats"]
+    assert monitors.MONITORS[-1].state_name == "aux.act_stats.counters"
+    assert set(monitors.BY_NAME) == {m.name for m in monitors.MONITORS} and all(monitors.BY_NAME[m.name] is m for m in monitors.MONITORS)
     on = SimpleNamespace(guard_state=None, label_stats_state=None, tensor_stats_table=None, tensor_stats_state=None, teacher_check_state=None,
                          student_check_state=None, gt_stats_state=None, act_stats_state=torch.zeros(3, dtype=torch.int64))
     assert [m.name for m, _ in monitors.active(on)] == ["act_stats"]
     assert monitors.active(SimpleNamespace(**dict(vars(on), act_stats_state=None))) == []
-    assert checkpoint.ALL is monitors.ALL
+    assert checkpoint.MONITORS is monitors.MONITORS
 
 
 def _tool(name):

@@ -254,7 +254,7 @@ def test_launcher_line_record_and_interval_read(tmp_path):
     from cosa_amd.utils import seg_helper
     K = 3
     m = monitors.BY_NAME["gt_stats"]
-    assert monitors.ROWS[-1] is m and monitors.ROWS[:-1] == monitors.MONITORS
+    assert monitors.MONITORS[5] is m and m.state_name == "aux.gt_stats.counters"
     off, n = R.layout(K)
     c = torch.zeros(n, dtype=torch.int64)
     c[off["steps"]], c[off["pix"]], c[off["valid"]] = 2, 50, 40

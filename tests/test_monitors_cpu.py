@@ -12,6 +12,8 @@ K = 3
 FLAGS = {"guard": dict(clip_grad_norm=1.0), "label_stats": dict(label_stats=True), "tensor_stats": dict(tensor_stats=True, clip_grad_norm=1.0),
          "teacher_check": dict(teacher_check_iters=2), "student_check": dict(student_check_iters=2)}
 ALL_ON = {k: v for f in FLAGS.values() for k, v in f.items()}
+# the table's seven rows in its order: the five a host trainer can turn on (FLAGS), then --gt_stats and --act_stats_iters
+NAMES = list(FLAGS) + ["gt_stats", "act_stats"]
 # the notes of the parent commit's TrainState._optional_notes, entry by entry: (the file has it and the run does not, only the run has it)
 NOTES = {
     "guard.state": ("the file holds a gradient guard's counters and this run has no guard (--clip_grad_norm 0, --skip_nonfinite "
@@ -29,7 +31,18 @@ NOTES = {
     "aux.student_check.counters": ("the file holds a student check's counters and this run makes no checks (--student_check_iters 0): the entry "
                                    "is ignored",
                                    "written without a student check: this run's check counters start at zero"),
+    "aux.gt_stats.counters": ("the file holds ground-truth statistics and this run does not collect them (--gt_stats false): the entry is "
+                              "ignored",
+                              "written without ground-truth statistics: this run's ground-truth counters start at zero"),
+    "aux.act_stats.counters": ("the file holds activation statistics and this run collects none (--act_stats_iters 0): the entry is ignored",
+                               "written without activation statistics: this run's activation counters start at zero"),
 }
+
+
+def _five():
+    """the rows of FLAGS, in the table's order"""
+    from cosa_amd import monitors
+    return monitors.MONITORS[:len(FLAGS)]
 
 
 def _tensors():
@@ -49,7 +62,7 @@ def _tensors():
 def test_every_subset_reads_what_the_full_set_reads_in_one_transfer(monkeypatch):
     from cosa_amd import main as launcher
     from cosa_amd import monitors
-    assert [m.name for m in monitors.MONITORS] == list(FLAGS)
+    assert [m.name for m in monitors.MONITORS] == NAMES
     calls, tolist = [], torch.Tensor.tolist
     monkeypatch.setattr(torch.Tensor, "tolist", lambda t: calls.append(t.numel()) or tolist(t))
 
@@ -87,9 +100,8 @@ def test_state_names_are_the_trainers_optional_entries(monkeypatch, on):
 
 
 def test_state_files_between_all_monitors_on_and_none(tmp_path, monkeypatch, capsys):
-    from cosa_amd import monitors
     full, none = SC._host_trainer(monkeypatch, seed=1, **ALL_ON), SC._host_trainer(monkeypatch, seed=2)
-    for m in monitors.MONITORS:                                                        # counters that a load must carry or leave alone
+    for m in _five():                                                        # counters that a load must carry or leave alone
         t = m.tensors(full)
         (t[1] if isinstance(t, tuple) else t).fill_(3)
     with_all, without = str(tmp_path / "state_00000003.cosa"), str(tmp_path / "state_00000000.cosa")
@@ -100,11 +112,11 @@ def test_state_files_between_all_monitors_on_and_none(tmp_path, monkeypatch, cap
     want, want_none = ([p.detach().clone() for p in tr.student.parameters()] for tr in (full, none))
     capsys.readouterr()
     assert none.load_state(with_all)["n_iter"] == 2
-    assert capsys.readouterr().out.splitlines() == [f"note: {with_all}: {NOTES[m.state_name][0]}" for m in monitors.MONITORS]
+    assert capsys.readouterr().out.splitlines() == [f"note: {with_all}: {NOTES[m.state_name][0]}" for m in _five()]
     assert all(torch.equal(p, q) for p, q in zip(none.student.parameters(), want)) and not hasattr(none, "extra_state")
     assert full.load_state(without)["n_iter"] == -1
-    assert capsys.readouterr().out.splitlines() == [f"note: {without}: {NOTES[m.state_name][1]}" for m in monitors.MONITORS]
+    assert capsys.readouterr().out.splitlines() == [f"note: {without}: {NOTES[m.state_name][1]}" for m in _five()]
     assert all(torch.equal(p, q) for p, q in zip(full.student.parameters(), want_none))
-    for m in monitors.MONITORS:
+    for m in _five():
         t = m.tensors(full)
         assert not (t[1] if isinstance(t, tuple) else t).any(), m.name
