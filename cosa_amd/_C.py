@@ -199,6 +199,9 @@ _SIGS.update({
     # the --act_stats_iters monitor (csrc/act_stats_kernels.hip)
     "cosa_range_stats_f32": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
     "cosa_attn_stats_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, ctypes.c_longlong, c_void_p, c_void_p]),
+    # per-image evaluation counters (csrc/image_scores_kernels.hip)
+    "cosa_image_scores_words": (c_size_t, [c_int, c_int]),
+    "cosa_image_scores": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_size_t, c_int, c_void_p, c_void_p]),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

@@ -95,6 +95,10 @@ EXTRA = [
                                              # weak images and reduces, per block, the range of q / k / v / o / h / x (bits of headroom under fp16's 65504)
                                              # and per head the attention logits' magnitude and row entropy; logged and written to
                                              # <output_dir>/act_stats.jsonl every log_iters; training is untouched
+    # per-image evaluation scores; off: nothing changes
+    ("image_scores", str2bool, False),       # every evaluate() of the run also counts each image's label maps against its ground truth on the
+                                             # device and writes <output_dir>/<iteration>/image_scores_<s|t>.jsonl and iou_dic_<s|t>.pth (the
+                                             # reference's iou_dic.pth); read them with tools/image_scores.py
 ]
 
 

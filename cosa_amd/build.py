@@ -53,6 +53,8 @@ SOURCES = {
     "conformance_kernels.hip": EXACT,
     # the --act_stats_iters monitor: integer reductions over the fp32 family's buffers and the QK^T half of its attention kernel
     "act_stats_kernels.hip": EXACT,
+    # per-image evaluation counters: integer byte work
+    "image_scores_kernels.hip": EXACT,
 }
 
 

@@ -17,12 +17,16 @@ high = 1 - t, low = t) of the main and the auxiliary CAMs at the ground truth's 
 softmax -> one mean-field step of the dense CRF (`seg_helper.crf_inference_infv2`: two permutohedral-lattice filters on the device) ->
 argmax, scored as the row `Seg_crf`.  Parity of that row with pydensecrf is unpinned (see seg_helper.DenseCRF).
 
-`evaluate` itself writes no files (`save_result`, `save_rawcam` raise NotImplementedError); `export_predictions` below does: the same
+`evaluate` writes no image files (`save_result`, `save_rawcam` raise NotImplementedError) -- only, with `image_scores=...`, the per-image score
+files of DESIGN.md section 22 (off by default: nothing changes); `export_predictions` below does: the same
 forward, one `cosa_export_maps` record per image at the image's own size, one asynchronous copy to pinned memory, a pool of writer
 threads (command line: `python -m cosa_amd.predict`).
 """
+import os
 import time
+from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
@@ -62,7 +66,10 @@ class _GraphedCamSeg:
 
 
 def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=False, epoch=None, threshold_filters=None, getcrf=False,
-             s_or_t='t', get_camiou=False, isfinal=False, class_list=None, use_graph=True, eval_group=4):
+             s_or_t='t', get_camiou=False, isfinal=False, class_list=None, use_graph=True, eval_group=4, image_scores=None):
+    """`image_scores`: None (default) adds nothing.  A directory, or True for args.output_dir/<epoch, five digits>/, scores every label map
+    this call produces against the ground truth per image on the device (evaluation.ImageScores: one launch per image, one copy at the
+    end) and has rank 0 write image_scores_<s_or_t>.jsonl and iou_dic_<s_or_t>.pth there."""
     if save_result or save_rawcam:
         raise NotImplementedError("evaluate: save_result / save_rawcam (image dumps) are not part of the device path of evaluate(); "
                                   "files are written by evaluation_engine.export_predictions / python -m cosa_amd.predict")
@@ -80,6 +87,13 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
     for thre in threshold_filters:                    # pseudo_scores' relabelling: a prediction of 255 drops the pixel (utils/evaluation.py:43-46)
         meters[f"cam_{thre}"] = evaluation.ConfusionMeter(nc, device, pseudo=True)
         meters[f"camaux_{thre}"] = evaluation.ConfusionMeter(nc, device, pseudo=True)
+    scores, score_meta = None, []                     # per-image counters of the same maps, in the meters' order (off: nothing is built)
+    if image_scores is not None and image_scores is not False:
+        try:
+            capacity = len(data_loader)
+        except TypeError:
+            capacity = 64
+        scores = evaluation.ImageScores(nc, list(meters), [m.pseudo for m in meters.values()], capacity, device)
     ap_sum = torch.zeros(2, device=device, dtype=torch.float64)          # sums of per-batch mean AP (cls, cls_aux) ...
     ap_cnt = 0                                                           # ... over the batches (AverageMeter semantics, :86-92)
     was_training = model.training
@@ -101,7 +115,7 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
         nonlocal ap_cnt
         inputs = torch.cat([g[0] for g in group], dim=0)
         cams, cams_aux, seg_ps, cls_final, cls_aux = camseg(inputs)
-        for i, (_, labels, cls_label, img_org) in enumerate(group):
+        for i, (_, labels, cls_label, img_org, meta) in enumerate(group):
             # classification AP of this item (:86-92; cls_* are sums over scales and flips, compared with every label row)
             for j, logit in enumerate((cls_final[i:i + 1], cls_aux[i:i + 1])):
                 ap, valid = torch_helper.average_precision(cls_label, torch.sigmoid(logit.float()).expand_as(cls_label))
@@ -115,6 +129,7 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
             meters["cam_aux"].update(gt, cam_aux_label)
             meters["seg_ps"].update(gt, pred_ps)
             meters["seg_vd"].update(gt, pred_vd)
+            maps = {"cam": cam_label, "cam_aux": cam_aux_label, "seg_ps": pred_ps, "seg_vd": pred_vd}
             if getcrf:
                 # evaluation_engine.py:204-211: softmax of the validated logits at the ground truth's size, the de-normalised uint8 image,
                 # one mean-field step, argmax
@@ -122,7 +137,8 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
                 vd = seg_helper.seg_validation(rs, cls_label).softmax(dim=1)[0]
                 ori = torch_helper.denormalize_img_(img_org)[0].permute(1, 2, 0)
                 q = seg_helper.crf_inference_infv2(ori, vd.contiguous())
-                meters["seg_crf"].update(gt, q.argmax(dim=0, keepdim=True).to(torch.uint8))
+                maps["seg_crf"] = q.argmax(dim=0, keepdim=True).to(torch.uint8)
+                meters["seg_crf"].update(gt, maps["seg_crf"])
             if threshold_filters:
                 # evaluation_engine.py:132-152: the CAMs resized to the ground truth's size, validated, then cam2mask with the box
                 # [0, -1, 0, -1] (Python slice semantics: the last row and column stay `ignore`, as in the reference) and no refine model
@@ -132,12 +148,18 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
                         rc = F.interpolate(c[i:i + 1], size=size, mode='bilinear', align_corners=False)
                         m = seg_helper.cam2mask(images=shape_only, img_boxes=[[0, -1, 0, -1]], cams=seg_helper.cam_validation(rc, cls_label),
                                                 cls_labels=cls_label, threshold_high=1 - thre, threshold_low=thre)
-                        meters[key].update(gt, m.to(torch.uint8))
+                        maps[key] = m.to(torch.uint8)
+                        meters[key].update(gt, maps[key])
+            if scores is not None:                    # every map of this image exists: one launch (per eight maps), no host wait
+                scores.add(len(score_meta), gt, [maps[k] for k in meters])
+                score_meta.append(meta + (int(size[0]), int(size[1])))
 
     with torch.no_grad():
         group = []
         for data in data_loader:
             name, img_org, labels, cls_label = data
+            names = [name] if isinstance(name, str) else list(name)
+            cls_host = cls_label                          # the loader's tensor: the score file's `present` is read from it after the loop
             labels = labels.to(device, non_blocking=True)
             cls_label = cls_label.to(device, non_blocking=True).float()
             img_org = img_org.to(device, non_blocking=True)
@@ -146,15 +168,23 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
                 flush(group)
                 group = []
                 for i in range(inputs.shape[0]):
-                    flush([(inputs[i:i + 1], labels[i:i + 1], cls_label[i:i + 1], img_org[i:i + 1])])
+                    flush([(inputs[i:i + 1], labels[i:i + 1], cls_label[i:i + 1], img_org[i:i + 1], (str(names[i]), cls_host[i]))])
                 continue
-            group.append((inputs, labels, cls_label, img_org if getcrf else None))
+            group.append((inputs, labels, cls_label, img_org if getcrf else None, (str(names[0]), cls_host[0])))
             if len(group) >= max(1, int(eval_group)):
                 flush(group)
                 group = []
         flush(group)
     for m in meters.values():
         m.all_reduce()
+    score_records = None
+    if scores is not None:
+        # DistributedSampler(shuffle=False) hands rank r the dataset positions r, r + world, ...: the k-th item of this rank is r + k world
+        world = dist.get_world_size() if distributed else 1
+        rows = scores.rows(len(score_meta))
+        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(torch.as_tensor(cl).reshape(-1)).reshape(-1) + 1).tolist(),
+                                                            rows[k])) for k, (nm, cl, h, w) in enumerate(score_meta)]
+        score_records = evaluation.gather_records(local)
     if heads_before is not None:
         net.batch_invariant_heads = heads_before
         net.decoder.batch_invariant = heads_before
@@ -163,6 +193,19 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
     if rank != 0:
         return (None,) * (5 if get_camiou else 4)
 
+    if scores is not None:
+        out_dir = Path(args.output_dir) / str(epoch).zfill(5) if image_scores is True else Path(image_scores)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        settings = {"maps": scores.map_names, "pseudo": scores.pseudo_flags, "num_classes": nc, "epoch": epoch, "s_or_t": s_or_t,
+                    "world_size": dist.get_world_size() if distributed else 1, "checkpoint": getattr(args, "checkpoint", None)}
+        evaluation.write_score_file(out_dir / f"image_scores_{s_or_t}.jsonl", settings, score_records)
+        vd = scores.map_names.index("seg_vd")
+        iou_dic = {}
+        for rec in score_records:                         # the reference's iou_dic.pth (evaluation_engine.py:160-168,282-283); means as Python floats
+            cl = [1 if c + 1 in rec["present"] else 0 for c in range(nc - 1)]
+            a = evaluation.assist_from_row(rec["row"], nc, vd, cl)
+            iou_dic[rec["name"]] = {k: (float(v) if k in ("miou", "wmiou") else v) for k, v in a.items()}
+        torch.save(iou_dic, out_dir / f"iou_dic_{s_or_t}.pth")
     cam_score, cam_aux_score, seg_vd_score = meters["cam"].scores(), meters["cam_aux"].scores(), meters["seg_vd"].scores()
     metrics, names = [cam_score, cam_aux_score, seg_vd_score], ["CAM", "aux_CAM", "Seg_vd"]
     if isfinal:
@@ -199,6 +242,7 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
 # ---------------------------------------------------------------------------------------------------------------------------------
 EXPORT_PRODUCTS = tuple(seg_helper.EXPORT_BITS)                   # seg, pseudo, pseudo_aux, rawcam, rawcam_aux, pseudo_par, pseudo_aux_par
 CAM_PRODUCTS = tuple(p for p in EXPORT_PRODUCTS if p != "seg")    # these need the image-level label row
+SCORED_PRODUCTS = ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par", "seg_crf")      # the uint8 label maps: scores=True
 
 
 class _ExportSlot:
@@ -244,7 +288,7 @@ def _sharded(data_loader, rank, world):
 
 
 def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=False, high_thre=None, low_thre=None, eval_group=4,
-                       use_graph=True, writers=4, settings=None):
+                       use_graph=True, writers=4, settings=None, scores=False):
     """Write the predictions of `model` over `data_loader` (items `(name, image [1,3,H,W], labels, cls_label [1,C])` as the evaluation
     loaders give them; an item without a label row -- `cls_label` None or not 2-D, the `test` stage -- can only give `seg`) into
     `out_dir` (layout: utils/export_io.py).  The forward is evaluate()'s: resize to crop_size, the captured multi-scale pass, groups of
@@ -252,6 +296,9 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     `getcrf` adds `seg_crf` (the lines of evaluate()'s Seg_crf row).  Thresholds default to args.high_thre / args.low_thre.
     `pseudo_par` / `pseudo_aux_par` are the labels CoSA trains on: cam2mask with PAR(num_iter=10, dilations=[1,2,4,8,12,24]) at
     `args.par_downscale` (2 or 0) on the image's own size (seg_helper.export_refine), into the same record as the other products.
+    `scores=True` (items must carry their ground-truth map as third element): every uint8 product of an image -- seg, pseudo*, pseudo*_par,
+    seg_crf -- is scored against it straight from the device record (evaluation.ImageScores; pseudo* maps with pseudo=1), rank 0 writes
+    `scores.jsonl` and the result gains "scores": {product: {"miou", "labelled"}}; off: nothing changes.
     Returns {"images", "seconds", "img_per_s", "bytes_written"} of this process."""
     what = tuple(what)
     mask = seg_helper.export_what_mask(what)
@@ -275,6 +322,16 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     products = what + (("seg_crf",) if getcrf else ())
     writer = export_io.PredictionWriter(out_dir, products, writers)
     slots = _export_slots(device, writers + 1)
+    score_names = [p for p in products if p in SCORED_PRODUCTS] if scores else []
+    table, score_meta = None, []
+    if scores:
+        if not score_names:
+            raise ValueError(f"export_predictions: scores=True needs a label-map product (one of {list(SCORED_PRODUCTS)}), got {list(products)}")
+        try:
+            capacity = len(data_loader) // world + 1
+        except TypeError:
+            capacity = 64
+        table = evaluation.ImageScores(args.num_classes, score_names, [p.startswith("pseudo") for p in score_names], capacity, device)
     was_training = model.training
     model.eval()
     net = model.module if hasattr(model, "module") else model
@@ -304,7 +361,7 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         if not group:
             return
         cams, cams_aux, seg_ps, _, _ = camseg(torch.cat([g[1] for g in group], dim=0))
-        for i, (name, _, cls_dev, k_live, img_org) in enumerate(group):
+        for i, (name, _, cls_dev, k_live, img_org, gt, cls_host) in enumerate(group):
             H, W = int(img_org.shape[-2]), int(img_org.shape[-1])
             item_mask = mask if cls_dev is not None else seg_helper.EXPORT_BITS["seg"]
             _, nbytes = seg_helper.export_record_layout(C, H, W, k_live, item_mask)
@@ -327,6 +384,12 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 ori = torch_helper.denormalize_img_(img_org)[0].permute(1, 2, 0)
                 q = seg_helper.crf_inference_infv2(ori, vd.contiguous())
                 slot.dev[crf_off:crf_off + H * W].copy_(q.argmax(dim=0).to(torch.uint8).reshape(-1))
+            if table is not None:                   # scored where it lies, before the copy: one launch, no host wait
+                if item_mask != mask or gt is None or gt.numel() != H * W:
+                    raise ValueError(f"export_predictions: scores=True needs the label row and a ground-truth map of the image's size ({name!r})")
+                offs = dict(seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0], seg_crf=crf_off)
+                table.add(len(score_meta), gt, [slot.dev[offs[p]:offs[p] + H * W] for p in score_names])
+                score_meta.append((name, cls_host, H, W))
             slot.host[:total].copy_(slot.dev[:total], non_blocking=True)          # the one device-to-host copy of the image
             slot.event.record()
             slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off))
@@ -337,7 +400,7 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         with torch.no_grad():
             group = []
             for data in _sharded(data_loader, rank, world):
-                names, img_org, _, cls_label = data
+                names, img_org, labels, cls_label = data
                 names = [names] if isinstance(names, str) else list(names)
                 has_cls = torch.is_tensor(cls_label) and cls_label.dim() == 2
                 if not has_cls and (mask & ~seg_helper.EXPORT_BITS["seg"]):
@@ -347,9 +410,10 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 cls_dev = cls_label.to(device, non_blocking=True).float() if has_cls else None
                 img_org = img_org.to(device, non_blocking=True)
                 inputs = F.interpolate(img_org, size=[args.crop_size, args.crop_size], mode='bilinear', align_corners=False)
+                gts = labels.to(device, non_blocking=True).to(torch.uint8) if scores and torch.is_tensor(labels) else None
                 for i in range(inputs.shape[0]):
                     group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if has_cls else None, int(k_lives[i]),
-                                  img_org[i:i + 1]))
+                                  img_org[i:i + 1], gts[i] if gts is not None and gts.dim() == 3 else None, cls_label[i] if has_cls else None))
                     if len(group) >= max(1, int(eval_group)):
                         flush(group)
                         group = []
@@ -376,6 +440,20 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         dist.all_gather_object(gathered, images)
         images = sorted(x for part in gathered for x in part)
         dist.barrier()                              # every rank's files are on disk
+    score_summary = None
+    if table is not None:                           # _sharded: the k-th item of this rank is dataset position rank + k world
+        rows = table.rows(len(score_meta))
+        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(cl.reshape(-1)).reshape(-1) + 1).tolist(), rows[k]))
+                 for k, (nm, cl, h, w) in enumerate(score_meta)]
+        records = evaluation.gather_records(local)
+        if rank == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            evaluation.write_score_file(os.path.join(out_dir, "scores.jsonl"),
+                                        {"maps": score_names, "pseudo": table.pseudo_flags, "num_classes": args.num_classes, "epoch": None,
+                                         "s_or_t": (settings or {}).get("s_or_t"), "world_size": world,
+                                         "checkpoint": (settings or {}).get("checkpoint")}, records)
+            ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), args.num_classes) if records else []
+            score_summary = {p: {"miou": evaluation.nan_to_none(d["miou"]), "labelled": evaluation.nan_to_none(d["labelled"])} for p, d in zip(score_names, ds)}
     if rank == 0:
         info = {"split": getattr(data_loader.dataset, "split", None) if hasattr(data_loader, "dataset") else None,
                 "products": list(products), "high_thre": high_thre, "low_thre": low_thre, "ignore_index": ignore_index,
@@ -385,5 +463,8 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
             info["par"] = {"num_iter": seg_helper.PAR_NUM_ITER, "dilations": list(seg_helper.PAR_DILATIONS), "downscale": par_downscale}
         info.update(settings or {})
         export_io.write_manifest_file(out_dir, info, images)
-    return {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,
-            "bytes_written": writer.bytes_written}
+    res = {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,
+           "bytes_written": writer.bytes_written}
+    if scores:
+        res["scores"] = score_summary
+    return res

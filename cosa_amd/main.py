@@ -216,14 +216,15 @@ def main(args):
                                 monitors.append_monitor(output_dir, m, summary, n_iter + 1, targs)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
+            score_kw = {"image_scores": True} if args.image_scores else {}           # (off: the calls as ever)
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,
-                             threshold_filters=args.eval_threshold_filters)
+                             threshold_filters=args.eval_threshold_filters, **score_kw)
             if is_main:
                 tab, segvd, camiou, df, aps = res_o
                 log(f'ON Model Classification: cls:{aps[0]}, clsaux: {aps[1]}')
                 log(tab)
             res_a = evaluate(trainer.model_AN, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='t', get_camiou=True,
-                             threshold_filters=args.eval_threshold_filters)
+                             threshold_filters=args.eval_threshold_filters, **score_kw)
             if is_main:
                 tab_a, segvd_a, camiou_a, df, aps_a = res_a
                 log(f'AN: cls:{aps_a[0]}, clsaux: {aps_a[1]}')
@@ -271,7 +272,7 @@ def finaleval(args):
     torch_helper.load_best(model, args.bestseg_path, strict=True)
     model = model.to(device)
     res = evaluate(model, build_test_loader(args), args, df=None, epoch='best1', isfinal=True, getcrf=True,   # main.py:414-425
-                   threshold_filters=None)
+                   threshold_filters=None, **({"image_scores": output_dir / "best1"} if getattr(args, "image_scores", False) else {}))
     if getattr(args, "rank", 0) == 0:
         print('Final Model Result:\n' + res[0], flush=True)
         with (output_dir / "log_val.txt").open("a") as f:

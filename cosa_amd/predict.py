@@ -1,7 +1,8 @@
 """Write a trained model's predictions as files:
 
     python -m cosa_amd.predict NAME --checkpoint best_seg.pth --dataset VOC12 --voc12_root $VOC --split val|test|train|train_aug \
-        --out DIR --what seg[,pseudo,pseudo_aux,pseudo_par,pseudo_aux_par,rawcam,rawcam_aux] [--crf] [--high_thre H --low_thre L] [--writers N]
+        --out DIR --what seg[,pseudo,pseudo_aux,pseudo_par,pseudo_aux_par,rawcam,rawcam_aux] [--crf] [--high_thre H --low_thre L] [--writers N] \
+        [--scores]
 
 Segmentation PNGs of `val` / `test` (what the VOC evaluation server takes), pseudo-label PNGs of `train_aug` / `train` for a second-stage
 network (`pseudo`: thresholds only; `pseudo_par`: refined by PAR(num_iter=10, dilations=[1,2,4,8,12,24]) at `--par_downscale` 2 or 0, the
@@ -9,7 +10,9 @@ labels CoSA itself trains on), raw CAMs as `.npy` dictionaries.  Every flag of t
 `--crop_size`, `--num_classes`, `--name_list_dir`, ...); the thresholds default to the run's `--high_thre` / `--low_thre`.  The
 checkpoint is loaded strictly, as `finaleval` loads it.  `--split test` has no ground truth and no image-level labels: `seg` only.
 Under `torchrun` the images are sharded over the ranks (`index % world == rank`), each written exactly once; rank 0 writes
-`manifest.json` last.  Prints the engine's result as one JSON line."""
+`manifest.json` last.  Prints the engine's result as one JSON line.  `--scores` (splits with ground-truth maps on disk: val, train,
+train_aug) also reads each image's mask, scores every exported label map against it on the device and writes `scores.jsonl` (per-image
+integer counters; read it with tools/image_scores.py); the result line gains the products' mIoU and labelled share."""
 import json
 import os
 import sys
@@ -30,6 +33,7 @@ def get_parser():
     p.add_argument("--out", type=str, required=True, help="output directory")
     p.add_argument("--what", type=str, default="seg", help="comma-separated products out of " + ", ".join(PRODUCTS))
     p.add_argument("--crf", action="store_true", help="also write seg_crf/ (dense-CRF post-processing, as finaleval scores it)")
+    p.add_argument("--scores", action="store_true", help="score every exported label map against the ground-truth mask: scores.jsonl")
     p.add_argument("--writers", type=int, default=4, help=f"PNG / npy writer threads (1..{MAX_WRITERS})")
     p.add_argument("--eval_group", type=int, default=4)
     p.add_argument("--trust_checkpoint", action="store_true",
@@ -47,6 +51,10 @@ def parse(argv=None):
         parser.error(f"--what: products are {', '.join(PRODUCTS)} (each once); got {args.what!r}")
     if args.split == "test" and any(w != "seg" for w in what):
         parser.error(f"--split test has no image-level labels: only `seg` can be exported (got --what {args.what})")
+    if args.scores and args.split == "test":
+        parser.error("--scores needs ground-truth maps: --split test has none")
+    if args.scores and not (args.crf or any(w in ("seg",) or w.startswith("pseudo") for w in what)):
+        parser.error(f"--scores needs a label-map product (seg, pseudo*, --crf), got --what {args.what}")
     if not 1 <= args.writers <= MAX_WRITERS:
         parser.error(f"--writers must be in 1..{MAX_WRITERS} (got {args.writers})")
     if args.usepar:
@@ -122,11 +130,12 @@ def main(argv=None):
     model = build_model(_trainer_args(args))
     ckpt = load_checkpoint(model, args.checkpoint, trust=args.trust_checkpoint)
     model = model.to(device).eval()
-    loader = DataLoader(dataset=_ImagesOnly(build_dataset(args)), batch_size=1, shuffle=False, num_workers=args.num_workers, pin_memory=False)
+    dataset = build_dataset(args)                 # (its items read the ground-truth mask: only --scores wants it)
+    loader = DataLoader(dataset=dataset if args.scores else _ImagesOnly(dataset), batch_size=1, shuffle=False, num_workers=args.num_workers, pin_memory=False)
     settings = {"checkpoint": os.path.abspath(args.checkpoint), "checkpoint_epoch": ckpt.get("epoch"), "s_or_t": ckpt.get("s_or_t"),
                 "dataset": args.dataset, "split": args.split, "crf": bool(args.crf)}
     res = export_predictions(model, loader, args, args.out, what=what, getcrf=args.crf, eval_group=args.eval_group, writers=args.writers,
-                             settings=settings)
+                             settings=settings, **({"scores": True} if args.scores else {}))
     print(json.dumps(res), flush=True)
     if args.distributed:
         dist.destroy_process_group()

@@ -5,6 +5,9 @@ on the GPU: the maps go through `cosa_confusion_hist` (LDS-privatised counters) 
 is the streaming form the evaluation engine uses: device-resident accumulation over the whole validation set, one all-reduce across
 ranks at the end (the reference gathers every prediction map on rank 0 through temp files, evaluation_engine.py:203-216).
 """
+import json
+import warnings
+
 import numpy as np
 import torch
 
@@ -74,3 +77,198 @@ def scores(label_trues, label_preds, num_classes):
 def pseudo_scores(label_trues, label_preds, num_classes):
     """utils/evaluation.py:37-70 (the inputs are NOT modified in place, unlike the reference's `lt[lp==255] = 255`)"""
     return _scores(label_trues, label_preds, num_classes, True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# per-image scores (DESIGN.md section 22): the counters of cosa_image_scores, the reference's assist_seg from them, the score files
+# ---------------------------------------------------------------------------------------------------------------------------------
+MAX_MAPS = 8                                      # COSA_IMAGE_SCORES_MAX_MAPS: maps per launch
+
+
+def row_words(num_classes, n_maps):
+    """words of one row: [n, n_valid, then per map and class I, P, G, A]"""
+    return 2 + int(n_maps) * int(num_classes) * 4
+
+
+class ImageScores:
+    """Device table [capacity, words] int64 of per-image counters: row `index` = [n, n_valid, then for map m, class c: I, P, G, A]
+    (cosa_image_scores; include/cosa_hip.h).  `add` launches and returns -- no host wait; `rows()` is the one device-to-host copy.
+    More than eight maps go in chunks of eight, each launch re-reading the ground truth; a chunk's launch writes its own [n, n_valid]
+    in front of its maps, so the table keeps one such pair per chunk and `rows()` drops all but the first."""
+
+    def __init__(self, num_classes, map_names, pseudo_flags, capacity, device=None):
+        device = torch.device(device if device is not None else "cuda")
+        if device.type != "cuda":
+            raise RuntimeError("ImageScores counts on the GPU (cosa_image_scores); no CPU path")
+        self.num_classes, self.map_names = int(num_classes), [str(m) for m in map_names]
+        self.pseudo_flags = [int(bool(p)) for p in pseudo_flags]
+        if len(self.pseudo_flags) != len(self.map_names) or not self.map_names or len(set(self.map_names)) != len(self.map_names):
+            raise ValueError("ImageScores: one pseudo flag per map, at least one map, every name once")
+        self._chunks, off = [], 0                 # (first map, maps, word offset in the table's row)
+        for first in range(0, len(self.map_names), MAX_MAPS):
+            k = min(MAX_MAPS, len(self.map_names) - first)
+            words = _C.lib().cosa_image_scores_words(self.num_classes, k)
+            if not words:
+                _C.check(1, "cosa_image_scores_words")
+            self._chunks.append((first, k, off))
+            off += words
+        self.table = torch.zeros((max(int(capacity), 1), off), device=device, dtype=torch.int64)
+
+    def add(self, index, gt, preds):
+        """score the uint8 device maps `preds` (one per map name) of one image against its uint8 ground truth into row `index`"""
+        index = int(index)
+        if len(preds) != len(self.map_names):
+            raise ValueError(f"ImageScores.add: {len(self.map_names)} maps expected, got {len(preds)}")
+        if index < 0:
+            raise IndexError(index)
+        if index >= self.table.shape[0]:             # a loader that did not tell its length: grow on the device, no host wait
+            grown = torch.zeros((max(2 * self.table.shape[0], index + 1), self.table.shape[1]), device=self.table.device, dtype=torch.int64)
+            grown[:self.table.shape[0]] = self.table
+            self.table = grown
+        _C.require_cuda(gt, *preds)
+        n = gt.numel()
+        maps = []
+        for p in preds:
+            if p.dtype != torch.uint8 or gt.dtype != torch.uint8 or p.numel() != n:
+                raise ValueError("ImageScores.add: uint8 maps of the ground truth's size")
+            maps.append(p.contiguous())
+        gt = gt.contiguous()
+        fn, st = _C.lib().cosa_image_scores, _C.stream_ptr()
+        for first, k, off in self._chunks:
+            ptrs = (_C.c_void_p * k)(*[m.data_ptr() for m in maps[first:first + k]])
+            row = _C.c_void_p(self.table.data_ptr() + 8 * (index * self.table.shape[1] + off))
+            _C.check(fn(_C.ptr(gt), ptrs, _C.int_array(self.pseudo_flags[first:first + k]), k, n, self.num_classes, row, st), "cosa_image_scores")
+
+    def rows(self, count=None):
+        """-> numpy [count or capacity, 2 + maps * num_classes * 4] int64: the single device-to-host copy"""
+        t = self.table.cpu().numpy()
+        if count is not None:
+            t = t[:count]
+        parts = [t[:, :2]]
+        for _, k, off in self._chunks:
+            parts.append(t[:, off + 2:off + 2 + k * self.num_classes * 4])
+        return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+
+def split_row(row, num_classes):
+    """one row -> (n, n_valid, counts [maps, num_classes, 4] in the order I, P, G, A)"""
+    row = np.asarray(row, dtype=np.int64)
+    return int(row[0]), int(row[1]), row[2:].reshape(-1, int(num_classes), 4)
+
+
+def assist_from_counts(I, A, G_all, n, cls_label):
+    """The reference's assist_seg (evaluation_engine.py:311-329) from integer counts: per class id c (1-based: entry c - 1 of cls_label is
+    set) I = #{seg == c and gt == c}, A = #{seg == c}, G_all = #{gt == c}, all over the n pixels of the image; arrays indexed by class
+    id.  -> {c: (iou, gt_ratio), 'miou', 'wmiou'} in the reference's arithmetic: sums of bool tensors are integers and their quotient is a
+    float32 division of the two integers cast to float32 (0 / 0 is NaN and stays one in `miou`), the union is A + G_all - I, the means are
+    numpy's over Python floats."""
+    ious = {}
+    for c, j in enumerate(np.asarray(cls_label).reshape(-1)):
+        if j > 0:
+            k = c + 1
+            with np.errstate(divide="ignore", invalid="ignore"):
+                iou = np.float32(int(I[k])) / np.float32(int(A[k]) + int(G_all[k]) - int(I[k]))
+                ratio = np.float32(int(G_all[k])) / np.float32(int(n))
+            ious[k] = (float(iou), float(ratio))
+    with np.errstate(divide="ignore", invalid="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)          # an image without a present class: the mean of nothing, NaN as the reference
+        mean_iou = np.mean([ious[i][0] for i in ious])
+        wmean = np.sum([ious[i][0] * ious[i][1] for i in ious]) / np.sum([ious[i][1] for i in ious])
+    ious['miou'] = mean_iou
+    ious['wmiou'] = wmean
+    return ious
+
+
+def assist_from_row(row, num_classes, map_index, cls_label):
+    """assist_from_counts of one map of a row.  G_all is the map's own G: the ground-truth area over the pixels the map labels with a
+    class -- for a map that labels every pixel (seg_vd, seg_crf, cam, ...: all but the pseudo maps) that is #{gt == c} of the whole image,
+    the reference's gt_area."""
+    n, _, cnt = split_row(row, num_classes)
+    c = cnt[map_index]
+    return assist_from_counts(c[:, 0], c[:, 3], c[:, 2], n, cls_label)
+
+
+def dataset_scores(rows, num_classes):
+    """rows [images, words] -> per map {"iou": [num_classes], "miou"} from the summed I, P, G: scores_from_hist's formula and `valid` rule on
+    the matrix's diagonal, column sums and row sums."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, np.shape(rows)[-1])
+    cnt = rows[:, 2:].sum(axis=0).reshape(-1, int(num_classes), 4).astype(np.float64)
+    out = []
+    for c in cnt:
+        I, P, G = c[:, 0], c[:, 1], c[:, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            iu = I / (G + P - I)
+        valid = G > 0
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            out.append({"iou": iu, "miou": np.nanmean(iu[valid]) if valid.any() else float("nan"),
+                        "labelled": float(P.sum() / rows[:, 1].sum()) if rows[:, 1].sum() else float("nan")})
+    return out
+
+
+def nan_to_none(x):
+    x = float(x)
+    return None if x != x else x                 # NaN is written as null
+
+
+def score_record(name, h, w, present, row):
+    """one image of a score file (host data only): `present` = the class ids of cls_label (1-based), `row` its counters"""
+    return {"name": str(name), "h": int(h), "w": int(w), "present": [int(c) for c in present], "row": np.asarray(row, dtype=np.int64)}
+
+
+def merge_records(shards):
+    """shards: per rank the list of (dataset position, record).  -> records in dataset order; a name met twice keeps its first row"""
+    seen, out = set(), []
+    for _, rec in sorted((pr for shard in shards for pr in shard), key=lambda pr: pr[0]):
+        if rec["name"] not in seen:
+            seen.add(rec["name"])
+            out.append(rec)
+    return out
+
+
+def write_score_file(path, settings, records):
+    """settings line, then one line per image: name, h, w, n, n_valid, present, and per map the non-zero classes with their integer
+    I, P, G, A and assist_seg's miou / wmiou"""
+    nc, maps = int(settings["num_classes"]), list(settings["maps"])
+    lines = [json.dumps(dict(settings, image_scores=1), sort_keys=True)]
+    for rec in records:
+        n, n_valid, cnt = split_row(rec["row"], nc)
+        cls_label = np.zeros(max(nc - 1, 0), np.int64)
+        cls_label[[c - 1 for c in rec["present"]]] = 1
+        per_map = {}
+        for m, name in enumerate(maps):
+            a = assist_from_counts(cnt[m][:, 0], cnt[m][:, 3], cnt[m][:, 2], n, cls_label)
+            per_map[name] = {"classes": {str(c): [int(v) for v in cnt[m][c]] for c in range(nc) if cnt[m][c].any()},
+                             "miou": nan_to_none(a["miou"]), "wmiou": nan_to_none(a["wmiou"])}
+        lines.append(json.dumps({"name": rec["name"], "h": rec["h"], "w": rec["w"], "n": n, "n_valid": n_valid, "present": rec["present"],
+                                 "maps": per_map}))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def read_score_file(path):
+    """-> (settings, records) with every record's `row` rebuilt"""
+    with open(path) as f:
+        lines = [json.loads(ln) for ln in f if ln.strip()]
+    settings = lines[0]
+    nc, maps = int(settings["num_classes"]), list(settings["maps"])
+    records = []
+    for d in lines[1:]:
+        row = np.zeros(row_words(nc, len(maps)), np.int64)
+        row[0], row[1] = d["n"], d["n_valid"]
+        cnt = row[2:].reshape(len(maps), nc, 4)
+        for m, name in enumerate(maps):
+            for c, v in d["maps"][name]["classes"].items():
+                cnt[m, int(c)] = v
+        records.append(score_record(d["name"], d["h"], d["w"], d["present"], row))
+    return settings, records
+
+
+def gather_records(local):
+    """`local`: this rank's [(dataset position, record)].  -> on rank 0 the merged records in dataset order, elsewhere None"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        shards = [None] * dist.get_world_size()
+        dist.all_gather_object(shards, local)
+        return merge_records(shards) if dist.get_rank() == 0 else None
+    return merge_records([local])

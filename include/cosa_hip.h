@@ -698,6 +698,27 @@ int cosa_confusion_hist(const uint8_t *gt, const uint8_t *pred, size_t n, int nu
                         unsigned long long *hist, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-image evaluation counters (what the reference's assist_seg, evaluation_engine.py:311-329, takes
+ * from a prediction).  One launch scores ONE image: gt and n_maps label maps of it (uint8, n pixels each, 255 = ignore) ADD
+ * into a caller-zeroed row of cosa_image_scores_words(num_classes, n_maps) uint64 words
+ *   row = [ n, n_valid, then for map m, class c: I, P, G, A ]            (2 + n_maps * num_classes * 4 words)
+ * n_valid = #{gt < num_classes}.  A pixel is counted for map m under the rule of cosa_confusion_hist: gt < num_classes and
+ * pred < num_classes -- a prediction that is no class drops the pixel, 255 included, so pseudo[m] (pseudo_scores' "a
+ * prediction of 255 drops the pixel") changes no count at num_classes <= 255; it is taken for symmetry with that entry and
+ * recorded by the host.  Over counted pixels I = #{gt == c and pred == c}, P = #{pred == c}, G = #{gt == c}; A = #{pred == c}
+ * over all n pixels, ignored truth included (assist_seg's seg_area).  Rows summed over a dataset give the diagonal (I), the
+ * column sums (P) and the row sums (G) of cosa_confusion_hist's matrix for the same maps, exactly.  Integer atomics only: the
+ * row holds the same bytes on every run.  preds and pseudo are HOST arrays of n_maps entries; the maps are device pointers of
+ * any byte alignment.  Envelope: gt, preds, every preds[m], pseudo and row non-NULL, row 8-byte aligned,
+ * 1 <= num_classes <= 255, 1 <= n_maps <= COSA_IMAGE_SCORES_MAX_MAPS, 1 <= n < 2^32; anything else is COSA_EINVAL, nothing is
+ * launched and the row is untouched.  One launch, no workspace, no host sync.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_IMAGE_SCORES_MAX_MAPS 8
+size_t cosa_image_scores_words(int num_classes, int n_maps);   /* uint64 words of one row; 0 on bad arguments */
+int cosa_image_scores(const uint8_t *gt, const uint8_t *const *preds, const int *pseudo, int n_maps, size_t n,
+                      int num_classes, unsigned long long *row, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Export: every file product of ONE image, at the image's own (generally non-square) H x W, in one
  * packed record, from what multi_scale_camsegv3 returns for it: cam / cam_aux [C,S,S], seg [C+1,S,S], cls_label [C] or
  * NULL (no image-level labels: seg only, plain argmax).  `what` is a mask of COSA_EXPORT_* bits:
