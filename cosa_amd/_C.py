@@ -202,6 +202,9 @@ _SIGS.update({
     # per-image evaluation counters (csrc/image_scores_kernels.hip)
     "cosa_image_scores_words": (c_size_t, [c_int, c_int]),
     "cosa_image_scores": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_size_t, c_int, c_void_p, c_void_p]),
+    # label-free export (csrc/predict_kernels.hip)
+    "cosa_predict_classes": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cosa_export_overlay": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

@@ -55,6 +55,8 @@ SOURCES = {
     "act_stats_kernels.hip": EXACT,
     # per-image evaluation counters: integer byte work
     "image_scores_kernels.hip": EXACT,
+    # label-free export: the class row from the logits (comparisons only) and the overlay (x * std + mean rounded twice, integer blend)
+    "predict_kernels.hip": EXACT,
 }
 
 

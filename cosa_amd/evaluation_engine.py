@@ -288,7 +288,7 @@ def _sharded(data_loader, rank, world):
 
 
 def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=False, high_thre=None, low_thre=None, eval_group=4,
-                       use_graph=True, writers=4, settings=None, scores=False):
+                       use_graph=True, writers=4, settings=None, scores=False, classes=None, cls_thre=0.5, cls_min=1, overlay_alpha=0.5):
     """Write the predictions of `model` over `data_loader` (items `(name, image [1,3,H,W], labels, cls_label [1,C])` as the evaluation
     loaders give them; an item without a label row -- `cls_label` None or not 2-D, the `test` stage -- can only give `seg`) into
     `out_dir` (layout: utils/export_io.py).  The forward is evaluate()'s: resize to crop_size, the captured multi-scale pass, groups of
@@ -299,9 +299,30 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     `scores=True` (items must carry their ground-truth map as third element): every uint8 product of an image -- seg, pseudo*, pseudo*_par,
     seg_crf -- is scored against it straight from the device record (evaluation.ImageScores; pseudo* maps with pseudo=1), rank 0 writes
     `scores.jsonl` and the result gains "scores": {product: {"miou", "labelled"}}; off: nothing changes.
+    `classes`: where an image's class row comes from.  None (default): what the items carry -- their row, or none
+    (`seg` only).  "given": the same, but an item without a row is an error.  "none": no row even where the items carry one.  "predicted":
+    the model's own head -- per group one `seg_helper.predict_classes` launch on the pass's `cls_final` logits (`cls_thre`, `cls_min`) and
+    one small copy that the loop waits for (k_live sizes the records); every product is then made as with a given row, rank 0 writes
+    `classes.jsonl`, and where the items carry rows too the result gains "classes": predicted against given, from integer counts.
+    `what` may also name `overlay`: the written `seg` map over the image (`overlay_alpha`), RGB bytes behind the record's other slots.
     Returns {"images", "seconds", "img_per_s", "bytes_written"} of this process."""
     what = tuple(what)
-    mask = seg_helper.export_what_mask(what)
+    overlay = "overlay" in what
+    if what.count("overlay") > 1:
+        raise ValueError(f"export_predictions: `overlay` named twice in {list(what)}")
+    mask = seg_helper.export_what_mask(tuple(w for w in what if w != "overlay")) if what != ("overlay",) else 0
+    if overlay:                                     # the overlay shows the seg map: its slot is computed even where no seg file is asked for
+        mask |= seg_helper.EXPORT_BITS["seg"]
+        seg_helper.overlay_alpha256(overlay_alpha)  # [0, 1], or a ValueError before anything runs
+    if classes not in (None, "given", "predicted", "none"):
+        raise ValueError(f"export_predictions: classes must be None, 'given', 'predicted' or 'none' (got {classes!r})")
+    predicted = classes == "predicted"
+    if classes == "none" and (mask & ~seg_helper.EXPORT_BITS["seg"]):
+        raise ValueError(f"export_predictions: classes='none' leaves only 'seg' (and its overlay) to export (asked for {list(what)})")
+    if predicted:
+        seg_helper.cls_threshold_logit(cls_thre)    # (0, 1), or a ValueError before anything runs
+        if not 0 <= int(cls_min) <= args.num_classes - 1:
+            raise ValueError(f"export_predictions: cls_min must be in 0..{args.num_classes - 1} (got {cls_min})")
     writers = export_io.check_writers(writers)
     if getattr(args, "usepar", False):
         raise NotImplementedError("export_predictions: `usepar` does not select an export product; the PAR-refined labels are the products "
@@ -341,33 +362,70 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         net.decoder.batch_invariant = True
     camseg = _GraphedCamSeg(model, EVAL_SCALES, enabled=use_graph and getattr(model, "can_forward_multi", None) is not None)
     count = 0
+    class_records, class_wait = [], 0.0             # classes="predicted": (dataset position, record) per image; seconds spent in the group waits
+    if predicted:                                   # one group's [rows | logits | k_live | nonfinite], 4-byte words, on the device and pinned
+        gmax = max(1, int(eval_group))
+        pack_dev = torch.empty(gmax * (2 * C + 2), device=device, dtype=torch.float32)
+        pack_host = torch.empty(gmax * (2 * C + 2), dtype=torch.float32).pin_memory()
+        pack_event = torch.cuda.Event()
 
-    def host_products(slot, H, W, k_live, item_mask, crf_off):
+    def host_products(slot, H, W, k_live, item_mask, crf_off, ov_off):
         def get():
             slot.event.synchronize()                # in the writer thread: the loop itself never waits for a copy
             rec = slot.host.numpy()
             v = seg_helper.export_record_views(rec, C, H, W, k_live, item_mask)
-            out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par") if p in v}
+            out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par") if p in v and p in products}
             for p in ("rawcam", "rawcam_aux"):
                 if p in v:
                     out[p] = (v[p], v[p + "_idx"])
             if crf_off is not None:
                 out["seg_crf"] = rec[crf_off:crf_off + H * W].reshape(H, W)
+            if ov_off is not None:
+                out["overlay"] = rec[ov_off:ov_off + 3 * H * W].reshape(H, W, 3)
             return out
         return get
+
+    def predicted_rows(group, cls_final):
+        """the group's class rows by the kernel, and the one wait for them: -> (rows on the device [G,C], host rows, k_live, nonfinite, logits)"""
+        nonlocal class_wait
+        G = len(group)
+        if cls_final.shape != (G, C):
+            raise RuntimeError(f"export_predictions: the pass returned logits {tuple(cls_final.shape)} for {G} images of {C} classes")
+        rows, logits = pack_dev[:G * C].view(G, C), pack_dev[G * C:2 * G * C].view(G, C)
+        ints = pack_dev[2 * G * C:2 * G * C + 2 * G].view(torch.int32)
+        logits.copy_(cls_final)
+        seg_helper.predict_classes(logits, cls_thre, cls_min, out=(rows, ints[:G], ints[G:]))
+        n = G * (2 * C + 2)
+        pack_host[:n].copy_(pack_dev[:n], non_blocking=True)
+        pack_event.record()
+        t = time.perf_counter()
+        pack_event.synchronize()                    # the only host wait of the predicted path: once per group
+        class_wait += time.perf_counter() - t
+        h = pack_host[:n].numpy().copy()
+        hi = h[2 * G * C:].view(np.int32)
+        return rows, h[:G * C].reshape(G, C), hi[:G], hi[G:], h[G * C:2 * G * C].reshape(G, C)
 
     def flush(group):
         nonlocal count
         if not group:
             return
-        cams, cams_aux, seg_ps, _, _ = camseg(torch.cat([g[1] for g in group], dim=0))
+        cams, cams_aux, seg_ps, cls_final, _ = camseg(torch.cat([g[1] for g in group], dim=0))
+        if predicted:
+            rows_dev, rows_h, k_h, nf_h, logits_h = predicted_rows(group, cls_final)
         for i, (name, _, cls_dev, k_live, img_org, gt, cls_host) in enumerate(group):
             H, W = int(img_org.shape[-2]), int(img_org.shape[-1])
+            if predicted:
+                cls_dev, k_live = rows_dev[i:i + 1], int(k_h[i])
+                rec = export_io.class_record(name, logits_h[i], rows_h[i], k_live, nf_h[i])
+                rec["given"] = None if cls_host is None else (cls_host.reshape(-1) != 0).numpy()
+                class_records.append((rank + count * world, rec))
             item_mask = mask if cls_dev is not None else seg_helper.EXPORT_BITS["seg"]
             _, nbytes = seg_helper.export_record_layout(C, H, W, k_live, item_mask)
-            crf_off, total = None, nbytes
+            crf_off, ov_off, total = None, None, nbytes
             if getcrf:
                 crf_off, total = nbytes, nbytes + ((H * W + 15) & ~15)
+            if overlay:                             # behind every other slot, seg_crf included
+                ov_off, total = total, total + ((3 * H * W + 15) & ~15)
             slot = slots[count % len(slots)]
             slot.reserve(total)
             maps_mask = item_mask & seg_helper.EXPORT_MAPS_MASK
@@ -378,6 +436,9 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 seg_helper.export_refine(torch_helper.denormalize_img(img_org), cams[i] if item_mask & 0x20 else None,
                                          cams_aux[i] if item_mask & 0x40 else None, cls_dev, item_mask, high_thre, low_thre,
                                          ignore_index=ignore_index, downscale=par_downscale, out=slot.dev, k_live=k_live)
+            if overlay:                             # the seg slot as just written, over the still normalised image (the CRF lines below rescale it in place)
+                seg_off = seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0]["seg"]
+                seg_helper.export_overlay(img_org, slot.dev[seg_off:seg_off + H * W], overlay_alpha, out=slot.dev[ov_off:ov_off + 3 * H * W])
             if getcrf:                              # evaluate()'s Seg_crf lines
                 rs = F.interpolate(seg_ps[i:i + 1], size=(H, W), mode='bilinear', align_corners=False)
                 vd = seg_helper.seg_validation(rs, cls_dev).softmax(dim=1)[0]
@@ -389,10 +450,10 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                     raise ValueError(f"export_predictions: scores=True needs the label row and a ground-truth map of the image's size ({name!r})")
                 offs = dict(seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0], seg_crf=crf_off)
                 table.add(len(score_meta), gt, [slot.dev[offs[p]:offs[p] + H * W] for p in score_names])
-                score_meta.append((name, cls_host, H, W))
+                score_meta.append((name, cls_host if cls_host is not None or not predicted else torch.from_numpy(rows_h[i]), H, W))
             slot.host[:total].copy_(slot.dev[:total], non_blocking=True)          # the one device-to-host copy of the image
             slot.event.record()
-            slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off))
+            slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off, ov_off))
             count += 1
 
     t0 = time.perf_counter()
@@ -403,16 +464,17 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 names, img_org, labels, cls_label = data
                 names = [names] if isinstance(names, str) else list(names)
                 has_cls = torch.is_tensor(cls_label) and cls_label.dim() == 2
-                if not has_cls and (mask & ~seg_helper.EXPORT_BITS["seg"]):
+                if not has_cls and ((mask & ~seg_helper.EXPORT_BITS["seg"]) or classes == "given") and not predicted:
                     raise ValueError(f"export_predictions: item {names[0]!r} has no image-level label row; only 'seg' can be exported "
                                      f"for it (asked for {list(what)})")
-                k_lives = (cls_label != 0).sum(dim=1).tolist() if has_cls else [0] * len(names)      # the loader's host tensor: no device wait
-                cls_dev = cls_label.to(device, non_blocking=True).float() if has_cls else None
+                use_cls = has_cls and classes in (None, "given")                # predicted rows come per group, in flush
+                k_lives = (cls_label != 0).sum(dim=1).tolist() if use_cls else [0] * len(names)      # the loader's host tensor: no device wait
+                cls_dev = cls_label.to(device, non_blocking=True).float() if use_cls else None
                 img_org = img_org.to(device, non_blocking=True)
                 inputs = F.interpolate(img_org, size=[args.crop_size, args.crop_size], mode='bilinear', align_corners=False)
                 gts = labels.to(device, non_blocking=True).to(torch.uint8) if scores and torch.is_tensor(labels) else None
                 for i in range(inputs.shape[0]):
-                    group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if has_cls else None, int(k_lives[i]),
+                    group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if use_cls else None, int(k_lives[i]),
                                   img_org[i:i + 1], gts[i] if gts is not None and gts.dim() == 3 else None, cls_label[i] if has_cls else None))
                     if len(group) >= max(1, int(eval_group)):
                         flush(group)
@@ -454,6 +516,15 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                                          "checkpoint": (settings or {}).get("checkpoint")}, records)
             ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), args.num_classes) if records else []
             score_summary = {p: {"miou": evaluation.nan_to_none(d["miou"]), "labelled": evaluation.nan_to_none(d["labelled"])} for p, d in zip(score_names, ds)}
+    class_summary = None
+    if predicted:                                   # gathered as the score records are: dataset order, rank 0 writes
+        records = evaluation.gather_records(class_records)
+        if rank == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            export_io.write_classes_file(os.path.join(out_dir, "classes.jsonl"), records,
+                                         export_io.class_names((settings or {}).get("dataset", getattr(args, "dataset", None)), C))
+            if records and all(r["given"] is not None for r in records):
+                class_summary = export_io.classification_figures([r["row"] for r in records], [r["given"] for r in records])
     if rank == 0:
         info = {"split": getattr(data_loader.dataset, "split", None) if hasattr(data_loader, "dataset") else None,
                 "products": list(products), "high_thre": high_thre, "low_thre": low_thre, "ignore_index": ignore_index,
@@ -461,10 +532,22 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 "num_classes": args.num_classes, "world_size": world}
         if par_mask:
             info["par"] = {"num_iter": seg_helper.PAR_NUM_ITER, "dilations": list(seg_helper.PAR_DILATIONS), "downscale": par_downscale}
+        if classes is not None:                     # (unset: the manifest keeps today's keys)
+            info["classes"] = classes
+        if predicted:
+            info.update({"cls_thre": float(cls_thre), "cls_min": int(cls_min)})
+            if class_summary is not None:
+                info["classes_vs_given"] = class_summary
+        if overlay:
+            info["overlay_alpha"] = float(overlay_alpha)
         info.update(settings or {})
         export_io.write_manifest_file(out_dir, info, images)
     res = {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,
            "bytes_written": writer.bytes_written}
     if scores:
         res["scores"] = score_summary
+    if predicted:
+        res["class_wait_seconds"] = class_wait
+        if class_summary is not None:
+            res["classes"] = class_summary
     return res

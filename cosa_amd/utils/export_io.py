@@ -5,9 +5,12 @@ Pure numpy / PIL: nothing here touches the GPU.  `evaluation_engine.export_predi
 
     <out_dir>/seg|seg_crf|pseudo|pseudo_aux|pseudo_par|pseudo_aux_par/<name>.png
                                                             palette PNGs (mode P) with the PASCAL VOC colour map
+    <out_dir>/overlay/<name>.png                            RGB PNGs: the written `seg` map painted over the image (cosa_export_overlay)
     <out_dir>/camraw|camraw_aux/<name>.npy                  a pickled dict {0-based class index: float32 [H,W]} (np.load(...,
                                                             allow_pickle=True).item()), as the reference's save_cam_npv2 writes it;
                                                             an image without any present class gets no file
+    <out_dir>/classes.jsonl                                 with classes="predicted": one line per image, the class row the model's own
+                                                            head gave it and the logits behind it (write_classes_file)
     <out_dir>/manifest.json                                 settings + (name, H, W) per image, written LAST: a directory that has a
                                                             manifest is complete
 """
@@ -21,7 +24,49 @@ from PIL import Image
 
 MAX_WRITERS = 8                      # a GPU job has 16 CPUs: loader workers and the main thread need the rest
 PNG_PRODUCTS = ("seg", "seg_crf", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par")
+RGB_PRODUCTS = ("overlay",)
 NPY_DIRS = {"rawcam": "camraw", "rawcam_aux": "camraw_aux"}
+IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png")
+VOC_CLASSES = ("aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog", "horse", "motorbike",
+               "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
+COCO_CLASSES = ("person", "bicycle", "car", "motorcycle", "airplane", "bus", "train", "truck", "boat", "traffic light", "fire hydrant", "stop sign",
+                "parking meter", "bench", "bird", "cat", "dog", "horse", "sheep", "cow", "elephant", "bear", "zebra", "giraffe", "backpack",
+                "umbrella", "handbag", "tie", "suitcase", "frisbee", "skis", "snowboard", "sports ball", "kite", "baseball bat", "baseball glove",
+                "skateboard", "surfboard", "tennis racket", "bottle", "wine glass", "cup", "fork", "knife", "spoon", "bowl", "banana", "apple",
+                "sandwich", "orange", "broccoli", "carrot", "hot dog", "pizza", "donut", "cake", "chair", "couch", "potted plant", "bed",
+                "dining table", "toilet", "tv", "laptop", "mouse", "remote", "keyboard", "cell phone", "microwave", "oven", "toaster", "sink",
+                "refrigerator", "book", "clock", "vase", "scissors", "teddy bear", "hair drier", "toothbrush")
+
+
+def class_names(dataset, C):
+    """the names of classes 1..C: the data set's own list when it has exactly C entries, else the 1-based indices as strings"""
+    names = {"VOC12": VOC_CLASSES, "COCO": COCO_CLASSES}.get(dataset, ())
+    return list(names) if len(names) == int(C) else [str(c + 1) for c in range(int(C))]
+
+
+def list_images(source):
+    """`--images`: a directory (its *.jpg / *.jpeg / *.png files, any letter case, not its sub-directories) or a text file with one image
+    path per line (relative paths from the file's own directory).  -> [(name, path)] sorted by file name, name = the stem.  An empty
+    source and two items with one stem are ValueErrors."""
+    source = str(source)
+    if os.path.isdir(source):
+        paths = [os.path.join(source, f) for f in sorted(os.listdir(source))
+                 if f.lower().endswith(IMAGE_SUFFIXES) and os.path.isfile(os.path.join(source, f))]
+    elif os.path.isfile(source):
+        with open(source) as f:
+            lines = [ln.strip() for ln in f]
+        paths = [ln if os.path.isabs(ln) else os.path.join(os.path.dirname(os.path.abspath(source)), ln) for ln in lines if ln]
+    else:
+        raise ValueError(f"{source}: neither a directory nor a text file")
+    items = [(os.path.splitext(os.path.basename(p))[0], p) for p in paths]
+    if not items:
+        raise ValueError(f"{source}: no images (*.jpg, *.jpeg, *.png)")
+    seen = {}
+    for name, p in items:
+        if name in seen:
+            raise ValueError(f"{source}: two images are named {name!r} ({seen[name]}, {p}): their files would overwrite each other")
+        seen[name] = p
+    return items
 
 
 def voc_colormap(n=256):
@@ -65,6 +110,59 @@ def write_png(path, label_map):
     return os.path.getsize(path)
 
 
+def write_png_rgb(path, rgb):
+    a = np.ascontiguousarray(rgb)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"write_png_rgb: uint8 [H,W,3] expected, got {a.dtype} {a.shape}")
+    Image.fromarray(a, mode="RGB").save(path, format="PNG")
+    return os.path.getsize(path)
+
+
+def class_record(name, logits, row, k_live, nonfinite):
+    """one image of classes.jsonl (host data only): float32 logits [C], its {0, 1} row, and the kernel's two counts"""
+    return {"name": str(name), "logits": np.asarray(logits, dtype=np.float32).copy(), "row": np.asarray(row).astype(bool).copy(),
+            "k_live": int(k_live), "nonfinite": int(nonfinite)}
+
+
+def write_classes_file(path, records, names):
+    """one line per image: name, classes (1-based, as scores.jsonl's `present`), class_names, logits (every float32 by its repr: the
+    shortest decimal that reads back as the same float32; NaN / Infinity as Python's json writes them), prob (the float64 sigmoid),
+    k_live, nonfinite"""
+    lines = []
+    for rec in records:
+        x = rec["logits"]
+        with np.errstate(over="ignore"):
+            prob = 1.0 / (1.0 + np.exp(-x.astype(np.float64)))
+        idx = np.nonzero(rec["row"])[0]
+        head = json.dumps({"name": rec["name"], "classes": [int(c) + 1 for c in idx], "class_names": [names[c] for c in idx]})
+        logits = "[" + ", ".join(_float_repr(np.float32(v)) for v in x) + "]"
+        tail = json.dumps({"prob": [float(v) for v in prob], "k_live": rec["k_live"], "nonfinite": rec["nonfinite"]})
+        lines.append(head[:-1] + ', "logits": ' + logits + ", " + tail[1:])
+    with open(path, "w") as f:
+        f.write("".join(ln + "\n" for ln in lines))
+
+
+def _float_repr(v):
+    if v != v:
+        return "NaN"
+    if np.isinf(v):
+        return "Infinity" if v > 0 else "-Infinity"
+    return repr(float(str(v)))                    # str(np.float32) is the float32's shortest repr; through float() it becomes a JSON number
+
+
+def classification_figures(predicted, given):
+    """predicted / given: {0, 1} rows [N, C].  -> integer counts and, from them, the exact-match share and micro precision / recall / F1
+    (None where a denominator is zero)"""
+    p, g = np.asarray(predicted).astype(bool).reshape(len(predicted), -1), np.asarray(given).astype(bool).reshape(len(given), -1)
+    if p.shape != g.shape:
+        raise ValueError(f"classification_figures: {p.shape} against {g.shape}")
+    tp, fp, fn = int((p & g).sum()), int((p & ~g).sum()), int((~p & g).sum())
+    exact, n = int((p == g).all(axis=1).sum()), int(p.shape[0])
+    div = lambda a, b: a / b if b else None
+    return {"images": n, "exact": exact, "tp": tp, "fp": fp, "fn": fn, "exact_match": div(exact, n), "precision": div(tp, tp + fp),
+            "recall": div(tp, tp + fn), "f1": div(2 * tp, 2 * tp + fp + fn)}
+
+
 def write_cam_npy(path, planes, class_idx):
     """planes float32 [K,H,W], class_idx int [K] -> {class index: [H,W]}; K == 0 writes nothing (returns 0)"""
     if len(class_idx) == 0:
@@ -83,7 +181,7 @@ class PredictionWriter:
     def __init__(self, out_dir, products, writers=4):
         self.out_dir = str(out_dir)
         self.writers = check_writers(writers)
-        unknown = [p for p in products if p not in PNG_PRODUCTS and p not in NPY_DIRS]
+        unknown = [p for p in products if p not in PNG_PRODUCTS and p not in NPY_DIRS and p not in RGB_PRODUCTS]
         if unknown:
             raise ValueError(f"unknown export products {unknown}")
         self.products = tuple(products)
@@ -105,6 +203,8 @@ class PredictionWriter:
                     n += write_cam_npy(os.path.join(self.out_dir, NPY_DIRS[key], name + ".npy"), planes, idx)
                 elif key in PNG_PRODUCTS:
                     n += write_png(os.path.join(self.out_dir, key, name + ".png"), val)
+                elif key in RGB_PRODUCTS:
+                    n += write_png_rgb(os.path.join(self.out_dir, key, name + ".png"), val)
                 else:
                     raise ValueError(f"unknown export product {key!r}")
             with self.lock:

@@ -1238,6 +1238,79 @@ def export_refine(image, cam, cam_aux, cls_label, what, high_thre, low_thre, ign
     return {k: out[o:o + H * W].reshape(H, W) for k, o in offs.items() if k in ("pseudo_par", "pseudo_aux_par")}
 
 
+PREDICT_MAX_CLASSES = 256                                # COSA_PREDICT_MAX_CLASSES
+
+
+def cls_threshold_logit(cls_thre):
+    """the logit L a class must reach for a probability threshold t in (0, 1): float32(log(t / (1 - t))), formed in float64 on the host"""
+    t = float(cls_thre)
+    if not 0.0 < t < 1.0:
+        raise ValueError(f"cls_thre must lie in (0, 1), got {cls_thre}")
+    return float(np.float32(np.log(np.float64(t) / (np.float64(1.0) - np.float64(t)))))
+
+
+def predict_classes(logits, cls_thre=0.5, cls_min=1, out=None):
+    """The image-level class rows from the classification logits [G, C] (cosa_predict_classes): class c is present
+    iff logit_c >= cls_threshold_logit(cls_thre); with fewer than `cls_min` present, the largest remaining logits are added (equal ones
+    in index order; never a NaN or -inf).  -> (rows [G, C] fp32 in {0, 1}, k_live [G] int32, nonfinite [G] int32: the NaN / +-inf logits).
+    `out`: the three tensors to write into (a caller that keeps them between calls).  No host wait."""
+    _C.require_cuda(logits)
+    if logits.dim() != 2:
+        raise ValueError(f"predict_classes: logits must be [G, C], got {tuple(logits.shape)}")
+    L = cls_threshold_logit(cls_thre)
+    x = logits.contiguous().float()
+    G, C = int(x.shape[0]), int(x.shape[1])
+    if out is None:
+        out = (torch.empty((G, C), device=x.device, dtype=torch.float32), torch.empty(G, device=x.device, dtype=torch.int32),
+               torch.empty(G, device=x.device, dtype=torch.int32))
+    rows, k_live, nonfinite = out
+    _C.require_cuda(rows, k_live, nonfinite)
+    if (rows.dtype, k_live.dtype, nonfinite.dtype) != (torch.float32, torch.int32, torch.int32) or rows.shape != (G, C) or \
+            k_live.numel() != G or nonfinite.numel() != G or not (rows.is_contiguous() and k_live.is_contiguous() and nonfinite.is_contiguous()):
+        raise ValueError("predict_classes: `out` must be contiguous (fp32 [G, C], int32 [G], int32 [G])")
+    _C.check(_C.lib().cosa_predict_classes(_C.ptr(x), G, C, L, int(cls_min), _C.ptr(rows), _C.ptr(k_live), _C.ptr(nonfinite), _C.stream_ptr()),
+             "cosa_predict_classes")
+    return rows, k_live, nonfinite
+
+
+_OVERLAY_PALETTE = {}                                    # str(device) -> the 256 x 3 colour map there
+
+
+def overlay_alpha256(alpha):
+    a = float(alpha)
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"overlay alpha must lie in [0, 1], got {alpha}")
+    return int(round(a * 256))
+
+
+def export_overlay(image, seg, alpha=0.5, out=None, palette=None):
+    """The label map `seg` (uint8 [H,W] or its H W bytes, e.g. a record's seg slot) painted over its image [3,H,W] / [1,3,H,W] (normalised
+    fp32, as the loaders give it) with the colours of export_io.voc_colormap: label 0 keeps the image's byte, label l > 0 gives
+    (a pal[l] + (256 - a) img + 128) >> 8 with a = round(alpha 256) (cosa_export_overlay).  `out`: 3 H W uint8 bytes to write into (a
+    slice of the image's record).  -> uint8 [H, W, 3], a view of `out`."""
+    _C.require_cuda(image, seg, out, palette)
+    if image.dim() not in (3, 4) or image.shape[-3] != 3 or image.numel() != 3 * image.shape[-2] * image.shape[-1]:
+        raise ValueError(f"export_overlay: image must be one image's [3,H,W], got {tuple(image.shape)}")
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    image = image.contiguous().float()
+    if seg.dtype != torch.uint8 or seg.numel() != H * W or not seg.is_contiguous():
+        raise ValueError(f"export_overlay: seg must be contiguous uint8 with {H * W} elements, got {seg.dtype} {tuple(seg.shape)}")
+    if palette is None:
+        palette = _OVERLAY_PALETTE.get(str(image.device))
+        if palette is None:
+            from .export_io import voc_colormap
+            palette = _OVERLAY_PALETTE[str(image.device)] = torch.from_numpy(voc_colormap()).to(image.device)
+    if palette.dtype != torch.uint8 or palette.numel() != 768 or not palette.is_contiguous():
+        raise ValueError("export_overlay: the palette is 256 x 3 contiguous uint8")
+    if out is None:
+        out = torch.empty(3 * H * W, device=image.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < 3 * H * W:
+        raise ValueError(f"export_overlay: `out` must be contiguous uint8 of at least {3 * H * W} bytes")
+    _C.check(_C.lib().cosa_export_overlay(_C.ptr(image), _C.ptr(seg), _C.ptr(palette), H, W, overlay_alpha256(alpha), _C.ptr(out),
+                                          _C.stream_ptr()), "cosa_export_overlay")
+    return out.reshape(-1)[:3 * H * W].reshape(H, W, 3)
+
+
 # --------------------------------------------------------------------------------------------
 # cam_validation / cam2mask  (utils/seg_helper.py:547-551, 721-797)
 # --------------------------------------------------------------------------------------------

@@ -766,6 +766,32 @@ int cosa_export_refine(const float *image, const float *cam, const float *cam_au
                        int K_live, unsigned what, float high_thre, float low_thre, int ignore_index, int downscale,
                        const int *dilations, int n_dil, int par_iters, void *record, size_t record_bytes, void *workspace,
                        size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Label-free export (csrc/predict_kernels.hip).
+ * cosa_predict_classes: the image-level class rows of G images from their classification logits [G, C] (fp32; the summed
+ *   `cls_final` of the multi-scale pass).  Class c is present iff logit_c >= L (the host passes L = float32(log(t / (1 - t)))
+ *   for a probability threshold t); a NaN is never present.  If fewer than cls_min classes are present, the classes with the
+ *   largest remaining logits are added, one per round, equal logits in index order, until cls_min are present or nothing is
+ *   left to add: a NaN and -inf are never added (+inf is >= L, so present).  rows [G, C] fp32 in {0, 1}; k_live [G] int32
+ *   = the row's sum; nonfinite [G] int32 = the image's NaN and +-inf logits.  One wavefront per image, classes on the lanes;
+ *   plain stores, no atomics, no workspace, one launch.  Envelope: non-NULL pointers, 1 <= C <= COSA_PREDICT_MAX_CLASSES,
+ *   1 <= G <= 65535, 0 <= cls_min <= C, L not NaN; anything else is COSA_EINVAL, nothing is launched, the outputs are untouched.
+ * cosa_export_overlay: the label map `seg` [H, W] (uint8, e.g. the SEG slot of an export record) painted over the image it
+ *   belongs to.  image: [3, H, W] fp32, normalised as the loaders give it ((byte - mean_c) / std_c, mean 123.675, 116.28,
+ *   103.53, std 58.395, 57.12, 57.375); per pixel and channel img = clamp(rint(x * std_c + mean_c), 0, 255) (product and sum
+ *   rounded separately); label 0 keeps img, label l > 0 gives (alpha256 * palette[l][c] + (256 - alpha256) * img + 128) >> 8.
+ *   palette: 256 x 3 bytes on the device.  out: 3 H W bytes, interleaved R G B per pixel (the engine appends them to the
+ *   image's record behind every slot of cosa_export_record_layout, which does not know them).  Integer blending: the same
+ *   bytes on every run.  Four pixels per thread by one dwordx4 per colour plane where image is 16-byte and seg / out are
+ *   4-byte aligned, the H W % 4 last pixels (else all) one per thread.  Envelope: non-NULL pointers, H, W > 0, H W < 2^29,
+ *   0 <= alpha256 <= 256; anything else is COSA_EINVAL, nothing is launched.  One launch, no workspace.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_PREDICT_MAX_CLASSES 256
+int cosa_predict_classes(const float *logits, int G, int C, float L, int cls_min, float *rows, int *k_live, int *nonfinite,
+                         void *stream);
+int cosa_export_overlay(const float *image, const uint8_t *seg, const uint8_t *palette, int H, int W, int alpha256, uint8_t *out,
+                        void *stream);
 /* ---------------------------------------------------------------------------------------
  * Per-step pseudo-label statistics and the teacher finite check: one reduction over tensors the
  * training step already holds, accumulated on the device in a vector of uint64 counters.

@@ -1,6 +1,7 @@
 """Rate of prediction export next to evaluate() on the same loader.
 
-    python tools/bench_export.py --mode evaluate|seg|all_crf|pseudo|pseudo_par|refine_time [--writers N] [--items 200] [--out FILE]
+    python tools/bench_export.py --mode evaluate|seg|all_crf|pseudo|pseudo_par|refine_time|given|predicted|predicted_overlay|kernel_time \
+        [--writers N] [--items 200] [--out FILE]
 
 One mode per process (run each under its own time limit); the result is merged into the JSON file under the key `evaluate` or
 `<mode>_w<writers>`.  The loader is synthetic: `--items` images of VOC-like sizes (around 375 x 500, both orientations) with two
@@ -9,7 +10,9 @@ maps folded into confusion matrices on the device instead of being copied out an
 `pseudo` (seg,pseudo,pseudo_aux) and `pseudo_par` (seg,pseudo_par,pseudo_aux_par) are the pair that shows what PAR refinement costs an
 export run.  `refine_time` is no export run: the device time per image of `seg_helper.export_refine` (both CAM sets) against the generic
 way to the same two maps -- two `_cam2mask_generic(..., refine_model=PAR(...))` calls on resized, validated CAMs -- interleaved in one
-process after warm-up, HIP events around each call, median over `--reps` repetitions per size."""
+process after warm-up, HIP events around each call, median over `--reps` repetitions per size.
+`given`, `predicted` and `predicted_overlay` are `seg` with the class row given, taken from the model's own head, and that plus the
+overlay product; `kernel_time` times `cosa_predict_classes` and `cosa_export_overlay` alone."""
 import argparse
 import json
 import os
@@ -86,14 +89,48 @@ def refine_time(reps, warmup=5):
                     "waits for the device inside the interval, as it does in use"}
 
 
+def kernel_time(reps, warmup=10):
+    """median device ms of the two kernels of label-free export at the sizes an export run gives them: the class rows of one group
+    (G = 4 images, C = 20) and the overlay of one image per VOC-like size"""
+    from cosa_amd.utils import seg_helper
+    rng = np.random.default_rng(0)
+
+    def timed(fn):
+        ts = []
+        for r in range(warmup + reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if r >= warmup:
+                ts.append(a.elapsed_time(b))
+        return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts))}
+
+    logits = torch.from_numpy(rng.standard_normal((4, 20)).astype(np.float32) - 2).cuda()
+    out = seg_helper.predict_classes(logits)
+    res = {"reps": reps, "warmup": warmup, "predict_classes_G4_C20": timed(lambda: seg_helper.predict_classes(logits, 0.5, 1, out=out)),
+           "predict_classes_G4_C20_cls_min20": timed(lambda: seg_helper.predict_classes(logits - 50, 0.5, 20, out=out)), "overlay": [],
+           "note": "HIP events around the Python wrapper on the launch stream: launch overhead included"}
+    for (H, W) in sorted(set(SIZES)):
+        img = torch.from_numpy(rng.standard_normal((3, H, W)).astype(np.float32)).cuda()
+        seg = torch.from_numpy(rng.integers(0, 21, (H, W)).astype(np.uint8)).cuda()
+        rgb = torch.empty(3 * H * W, device="cuda", dtype=torch.uint8)
+        res["overlay"].append(dict(timed(lambda: seg_helper.export_overlay(img, seg, 0.5, out=rgb)), H=H, W=W, bytes_moved=H * W * (12 + 1 + 3)))
+    return res
+
+
 PAR_WHAT = ("pseudo_par", "pseudo_aux_par")
 EXPORT_MODES = {"seg": (("seg",), False), "all_crf": (ALL, True), "pseudo": (("seg", "pseudo", "pseudo_aux"), False),
-                "pseudo_par": (("seg",) + PAR_WHAT, False)}
+                "pseudo_par": (("seg",) + PAR_WHAT, False),
+                # where the class row comes from (DESIGN.md section 23): `given` is `seg` with the argument spelled out
+                "given": (("seg",), False), "predicted": (("seg",), False), "predicted_overlay": (("seg", "overlay"), False)}
+CLASSES = {"given": "given", "predicted": "predicted", "predicted_overlay": "predicted"}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("evaluate",) + tuple(EXPORT_MODES) + ("refine_time",), required=True)
+    ap.add_argument("--mode", choices=("evaluate",) + tuple(EXPORT_MODES) + ("refine_time", "kernel_time"), required=True)
     ap.add_argument("--reps", type=int, default=30, help="refine_time: timed repetitions per size")
     ap.add_argument("--writers", type=int, default=4)
     ap.add_argument("--items", type=int, default=200)
@@ -106,6 +143,11 @@ def main():
         res = refine_time(opt.reps)
         res["device"] = torch.cuda.get_device_name(0)
         merge(opt.out, "refine_time", res)
+        return
+    if opt.mode == "kernel_time":
+        res = kernel_time(opt.reps)
+        res["device"] = torch.cuda.get_device_name(0)
+        merge(opt.out, "kernel_time", res)
         return
     torch.manual_seed(0)
     args = default_args("VOC12", crop_size=448, batch_size=1)
@@ -124,8 +166,9 @@ def main():
             res, key = {"images": len(items), "seconds": dt, "img_per_s": len(items) / dt}, "evaluate"
         else:
             what, crf = EXPORT_MODES[opt.mode]
-            ee.export_predictions(model, warm, args, os.path.join(tmp, "warm"), what=what, getcrf=crf, writers=opt.writers)
-            res = ee.export_predictions(model, items, args, os.path.join(tmp, "run"), what=what, getcrf=crf, writers=opt.writers)
+            kw = {"classes": CLASSES[opt.mode]} if opt.mode in CLASSES else {}
+            ee.export_predictions(model, warm, args, os.path.join(tmp, "warm"), what=what, getcrf=crf, writers=opt.writers, **kw)
+            res = ee.export_predictions(model, items, args, os.path.join(tmp, "run"), what=what, getcrf=crf, writers=opt.writers, **kw)
             res["writers"], key = opt.writers, f"{opt.mode}_w{opt.writers}"
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
