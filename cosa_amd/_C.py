@@ -68,6 +68,12 @@ _SIGS = {
     "cosa_seg_loss_backward_w": (c_int, [c_void_p] * 9 + [c_float] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
     "cosa_cam_loss_targets_m": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p,
                                 c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "cosa_cam_lossv2_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cosa_cam_lossv2": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
+    "cosa_cam_lossv3_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cosa_cam_lossv3": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "cosa_cam_label": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
+                       c_int, c_int, c_int, c_float, c_float, c_int, c_void_p]),
     "cosa_optim_record_bytes": (c_size_t, []),
     "cosa_optim_chunk_elems": (c_int, []),
     "cosa_fused_adamw_ema": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float, c_void_p]),

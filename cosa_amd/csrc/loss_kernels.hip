@@ -942,3 +942,478 @@ extern "C" int cosa_patch_wgrad_bf16(const void *dY, const void *X, float *dW, f
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }
+
+// ---- cam_loss v2 / v3 (the reference's --camloss_version v2 | v3, utils/seg_helper.py:604-653) ----------------------------------------
+// Both normalise every CAM plane first: r = relu(x), mn = min r, mx = max r, d2 = mx + 1e-4, n = (r - mn) / d2, with the gradient flowing
+// through mn and mx (adaptive_max_pool2d routes it to the FIRST position of the extremum in row-major order).  With g = dL/dn,
+// G = sum_plane g and Gn = sum_plane g (r - mn):   dL/dr_i = g_i / d2 - [i == argmin] G / d2 - [i == argmax] Gn / d2^2,   dL/dx = dL/dr [x > 0].
+//   v2: L = multilabel_soft_margin(n, y): element-wise, g = (sigmoid(n) - y) / (B h w C): value and gradient from one launch per plane.
+//   v3: cam_mix = cat(1 - max_c n, n) [B,K,h,w], L = class-balanced CE (weights 0.5 / 0.5, ignore 255) of its bilinear up-sampling against one
+//       label map [B,S,S]: the CE runs on the seg-loss scheme above (LDS tile of the low-resolution planes, taps, 64-bit fixed-point cells),
+//       so nothing of size [B,K,S,S] exists; g_n[c] = g_mix[c + 1] - [c == first argmax_c n] g_mix[0].
+// One workgroup owns one (b, c) plane, held in LDS.  Every reduction has a fixed order (strided per-thread sums, xor butterflies, the four
+// waves in wave order) or is an integer sum: the same bytes every run.  No float atomics.
+namespace cosa {
+namespace {
+
+constexpr int kCamPlaneMax = 6400;       // h w of one CAM plane: 80 x 80 (a 1280-pixel crop of the 16-pixel-patch encoder)
+
+// (value, index) extrema, ties to the lower index: a total order, so the merge order does not matter
+__device__ __forceinline__ void mm_merge(float &mn, int &imn, float &mx, int &imx, float omn, int oimn, float omx, int oimx)
+{
+    if (omn < mn || (omn == mn && oimn < imn)) { mn = omn; imn = oimn; }
+    if (omx > mx || (omx == mx && oimx < imx)) { mx = omx; imx = oimx; }
+}
+
+// r[i] = relu(x[i]) into LDS (a NaN stays one); min / max of the plane with their first positions, in every thread
+__device__ __forceinline__ void plane_minmax(const float *__restrict__ x, float *r, int HW, float (*redf)[2], int (*redi)[2], float &mn, int &imn,
+                                             float &mx, int &imx)
+{
+    const int tid = threadIdx.x;
+    mn = INFINITY; mx = -INFINITY; imn = imx = 0x7fffffff;
+    for (int i = tid; i < HW; i += 256) {
+        const float xv = x[i];
+        const float v = xv > 0.f ? xv : (xv != xv ? xv : 0.f);
+        r[i] = v;
+        if (v < mn) { mn = v; imn = i; }
+        if (v > mx) { mx = v; imx = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float omn = __shfl_xor(mn, o, 64), omx = __shfl_xor(mx, o, 64);
+        const int oimn = __shfl_xor(imn, o, 64), oimx = __shfl_xor(imx, o, 64);
+        mm_merge(mn, imn, mx, imx, omn, oimn, omx, oimx);
+    }
+    if ((tid & 63) == 0) { redf[tid >> 6][0] = mn; redf[tid >> 6][1] = mx; redi[tid >> 6][0] = imn; redi[tid >> 6][1] = imx; }
+    __syncthreads();
+    mn = redf[0][0]; mx = redf[0][1]; imn = redi[0][0]; imx = redi[0][1];
+#pragma unroll
+    for (int wv = 1; wv < 4; wv++) mm_merge(mn, imn, mx, imx, redf[wv][0], redi[wv][0], redf[wv][1], redi[wv][1]);
+}
+
+// NV per-thread doubles -> their plane sums in every thread: butterfly inside the wave, then the four waves in wave order
+template <int NV>
+__device__ __forceinline__ void plane_sums(double *v, double (*red)[NV])
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
+        if ((tid & 63) == 0) red[tid >> 6][j] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; j++) v[j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+}
+
+// the normalisation's adjoint for element i of a plane (see the head of this section)
+__device__ __forceinline__ float norm_adjoint(float g, float xv, int i, int imn, int imx, double d2, double G, double Gn)
+{
+    if (!(xv > 0.f)) return 0.f;
+    double d = (double)g / d2;
+    if (i == imn) d -= G / d2;
+    if (i == imx) d -= Gn / (d2 * d2);
+    return (float)d;
+}
+
+// v2: one plane per workgroup -- grad[plane] complete, part[plane] = the plane's sum of loss terms
+__global__ __launch_bounds__(256) void cam_v2_plane_kernel(const float *__restrict__ x, const float *__restrict__ y, float *__restrict__ grad,
+                                                          double *__restrict__ part, int HW, float inv_n)
+{
+    __shared__ float r[kCamPlaneMax], gl[kCamPlaneMax];
+    __shared__ float redf[4][2];
+    __shared__ int redi[4][2];
+    __shared__ double redd[4][3];
+    const size_t base = (size_t)blockIdx.x * HW;
+    const int tid = threadIdx.x;
+    float mn, mx;
+    int imn, imx;
+    plane_minmax(x + base, r, HW, redf, redi, mn, imn, mx, imx);
+    const float d2 = mx + 1e-4f;
+    double s[3] = {0.0, 0.0, 0.0};       // loss terms, G, Gn
+    for (int i = tid; i < HW; i += 256) {
+        const float rm = r[i] - mn, v = rm / d2, yv = y[base + i];
+        const float e = __expf(-fabsf(v));
+        const float ls = fminf(v, 0.f) - log1pf(e);                    // log sigmoid(v)
+        const float sg = v >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);   // sigmoid(v)
+        const float g = (sg - yv) * inv_n;
+        gl[i] = g;
+        s[0] += (double)((1.f - yv) * v - ls);
+        s[1] += (double)g;
+        s[2] += (double)g * (double)rm;
+    }
+    plane_sums<3>(s, redd);
+    for (int i = tid; i < HW; i += 256) grad[base + i] = norm_adjoint(gl[i], x[base + i], i, imn, imx, (double)d2, s[1], s[2]);
+    if (tid == 0) part[blockIdx.x] = s[0];
+}
+
+// v3 (a): n of plane (b, c) into channel c + 1 of cam_mix [B,C+1,h,w]; stats[plane] = {mn, d2}, idx[plane] = {argmin, argmax}
+__global__ __launch_bounds__(256) void cam_v3_plane_kernel(const float *__restrict__ x, float *__restrict__ mix, float *__restrict__ stats,
+                                                          int *__restrict__ idx, int C, int HW)
+{
+    __shared__ float r[kCamPlaneMax];
+    __shared__ float redf[4][2];
+    __shared__ int redi[4][2];
+    const int plane = blockIdx.x, b = plane / C, c = plane - b * C;
+    float mn, mx;
+    int imn, imx;
+    plane_minmax(x + (size_t)plane * HW, r, HW, redf, redi, mn, imn, mx, imx);
+    const float d2 = mx + 1e-4f;
+    float *o = mix + ((size_t)b * (C + 1) + c + 1) * HW;
+    for (int i = threadIdx.x; i < HW; i += 256) o[i] = (r[i] - mn) / d2;
+    if (threadIdx.x == 0) { stats[2 * plane] = mn; stats[2 * plane + 1] = d2; idx[2 * plane] = imn; idx[2 * plane + 1] = imx; }
+}
+
+// v3 (a), the cells: channel 0 of cam_mix = 1 - max_c n, arg = the first channel of that maximum
+__global__ __launch_bounds__(256) void cam_v3_bg_kernel(float *__restrict__ mix, int *__restrict__ arg, int B, int C, int HW)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= B * HW) return;
+    const int b = t / HW, i = t - b * HW;
+    float *p = mix + (size_t)b * (C + 1) * HW + i;
+    float m = p[HW];
+    int a = 0;
+    for (int c = 1; c < C; c++) {
+        const float v = p[(size_t)(c + 1) * HW];
+        if (v > m) { m = v; a = c; }
+    }
+    p[0] = 1.f - m;
+    arg[t] = a;
+}
+
+// v3 (b), forward: class-balanced CE sums of the up-sampled planes against one label map (bytes; 255 and anything >= K: ignored).
+// sums: 64 shards of {bg_sum, bg_cnt, fg_sum, fg_cnt} in fix32.
+__global__ __launch_bounds__(256) void cam_ce_fwd_kernel(const float *__restrict__ lr, const unsigned char *__restrict__ label,
+                                                        unsigned long long *__restrict__ sums, unsigned long long *__restrict__ flag,
+                                                        int K, int hs, int ws, int S, float sy, float sx)
+{
+    extern __shared__ __attribute__((aligned(16))) float tile[];
+    __shared__ float red[4][4];
+    const int b = blockIdx.z;
+    const QuadCtx c = setup(lr, tile, K, hs, ws, S, sy, sx, b);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c.valid) {
+        const size_t SS = (size_t)S * S;
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            float mx = -INFINITY;
+            for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, c.t[p]));
+            float se = 0.f;
+            for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, c.t[p]) - mx);
+            const float lse = mx + __logf(se);
+            const int la = (int)label[(size_t)b * SS + (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1)];
+            if (la == 0) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
+            else if (la < K) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
+        }
+    }
+    const int tid = threadIdx.y * 16 + threadIdx.x, wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const float v = wave_sum(acc[i]);
+        if (lane == 0) red[wave][i] = v;
+    }
+    __syncthreads();
+    const unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (tid < 4) atomicAdd(&sums[(wg & 63u) * 4 + tid], fix32(red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid], flag));
+}
+
+// sums[4] in fp32 and the loss 0.5 bg_sum / (bg_cnt + 1e-6) + 0.5 fg_sum / (fg_cnt + 1e-6)
+__global__ void cam_ce_sums_kernel(const unsigned long long *__restrict__ fix, const unsigned long long *__restrict__ flag, float *__restrict__ sums,
+                                   float *__restrict__ loss)
+{
+    __shared__ float s[4];
+    if (threadIdx.x < 4) {
+        unsigned long long t = 0;
+        for (int sh = 0; sh < 64; sh++) t += fix[sh * 4 + threadIdx.x];
+        s[threadIdx.x] = sums[threadIdx.x] = *flag ? __builtin_nanf("") : (float)((double)(long long)t * (1.0 / 4294967296.0));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) loss[0] = 0.5f * (s[0] / (s[1] + 1e-6f)) + 0.5f * (s[2] / (s[3] + 1e-6f));
+}
+
+// v3 (b), backward for a unit upstream gradient: d/dz_k(pixel) = c(pix) (p_k - [k == label]), c = 0.5 / (count + 1e-6) of the pixel's group;
+// scattered into the low-resolution cells as seg_loss_bwd_kernel does (a cell pre-sums at most all pixels once: |v| <= W g with W = 1, g = 1)
+__global__ __launch_bounds__(256) void cam_ce_bwd_kernel(const float *__restrict__ lr, const unsigned char *__restrict__ label,
+                                                        const float *__restrict__ sums, unsigned long long *__restrict__ grad,
+                                                        unsigned long long *__restrict__ flag, int K, int hs, int ws, int S, float sy, float sx)
+{
+    extern __shared__ __attribute__((aligned(16))) float tile[];       // [K][TC][TC] planes, then [K][TC][TC] gradient cells (64-bit fixed point)
+    const int b = blockIdx.z;
+    const QuadCtx c = setup(lr, tile, K, hs, ws, S, sy, sx, b);
+    unsigned long long *gt = reinterpret_cast<unsigned long long *>(tile + ((K * TC * TC + 1) & ~1));
+    const int tid = threadIdx.y * 16 + threadIdx.x;
+    for (int e = tid; e < K * TC * TC; e += 256) gt[e] = 0ull;
+    __syncthreads();
+    // (the wave-level grouping of seg_loss_bwd_kernel: 4 x 4 quads that read the same four cells are summed by butterflies, one lane adds)
+    const bool same = c.t[0].o00 == c.t[3].o00 && c.t[0].o11 == c.t[3].o11 && c.t[0].o01 == c.t[3].o01 && c.t[0].o10 == c.t[3].o10;
+    bool grp_ok = c.valid && same;
+#pragma unroll
+    for (int sft = 0; sft < 4; sft++) {
+        const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
+        grp_ok = grp_ok && __shfl_xor(c.t[0].o00, x, 64) == c.t[0].o00 && __shfl_xor(c.t[0].o11, x, 64) == c.t[0].o11;
+    }
+    const bool grouped = __all(grp_ok) != 0;
+    if (c.valid) {
+        const size_t SS = (size_t)S * S;
+        const float cbg = 0.5f / (sums[1] + 1e-6f), cfg = 0.5f / (sums[3] + 1e-6f);
+        float m[4], inv[4], ca[4];
+        int la[4];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            float mx = -INFINITY;
+            for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, c.t[p]));
+            float se = 0.f;
+            for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, c.t[p]) - mx);
+            m[p] = mx;
+            inv[p] = 1.0f / se;
+            la[p] = (int)label[(size_t)b * SS + (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1)];
+            ca[p] = la[p] == 0 ? cbg : (la[p] < K ? cfg : 0.f);
+        }
+        for (int k = 0; k < K; k++) {
+            const float *pl = tile + k * TC * TC;
+            float dz[4];
+#pragma unroll
+            for (int p = 0; p < 4; p++) dz[p] = ca[p] * (__expf(tap(pl, c.t[p]) - m[p]) * inv[p] - (la[p] == k ? 1.f : 0.f));
+            unsigned long long *gp = gt + k * TC * TC;
+            if (grouped || same) {
+                float v00 = dz[0] * c.t[0].w00 + dz[1] * c.t[1].w00 + dz[2] * c.t[2].w00 + dz[3] * c.t[3].w00;
+                float v01 = dz[0] * c.t[0].w01 + dz[1] * c.t[1].w01 + dz[2] * c.t[2].w01 + dz[3] * c.t[3].w01;
+                float v10 = dz[0] * c.t[0].w10 + dz[1] * c.t[1].w10 + dz[2] * c.t[2].w10 + dz[3] * c.t[3].w10;
+                float v11 = dz[0] * c.t[0].w11 + dz[1] * c.t[1].w11 + dz[2] * c.t[2].w11 + dz[3] * c.t[3].w11;
+                if (grouped) {
+#pragma unroll
+                    for (int sft = 0; sft < 4; sft++) {
+                        const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
+                        v00 += __shfl_xor(v00, x, 64);
+                        v01 += __shfl_xor(v01, x, 64);
+                        v10 += __shfl_xor(v10, x, 64);
+                        v11 += __shfl_xor(v11, x, 64);
+                    }
+                }
+                if (!grouped || (tid & 0x33) == 0) {
+                    atomicAdd(gp + c.t[0].o00, fix52(v00, flag));
+                    atomicAdd(gp + c.t[0].o01, fix52(v01, flag));
+                    atomicAdd(gp + c.t[0].o10, fix52(v10, flag));
+                    atomicAdd(gp + c.t[0].o11, fix52(v11, flag));
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    atomicAdd(gp + c.t[p].o00, fix52(dz[p] * c.t[p].w00, flag));
+                    atomicAdd(gp + c.t[p].o01, fix52(dz[p] * c.t[p].w01, flag));
+                    atomicAdd(gp + c.t[p].o10, fix52(dz[p] * c.t[p].w10, flag));
+                    atomicAdd(gp + c.t[p].o11, fix52(dz[p] * c.t[p].w11, flag));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < K * TC * TC; e += 256) {
+        const unsigned long long v = gt[e];
+        if (v != 0ull) {
+            const int k = e / (TC * TC), r = e - k * TC * TC;
+            const int cy = c.cy0 + r / TC, cx = c.cx0 + r % TC;
+            if (cy < hs && cx < ws) atomicAdd(&grad[(((size_t)b * K + k) * hs + cy) * ws + cx], v);
+        }
+    }
+}
+
+// v3 (c): the fixed-point cells of d L / d cam_mix -> d L / d x of plane (b, c)
+__global__ __launch_bounds__(256) void cam_v3_adjoint_kernel(const float *__restrict__ x, const unsigned long long *__restrict__ gfix,
+                                                            const unsigned long long *__restrict__ flag, const int *__restrict__ arg,
+                                                            const float *__restrict__ stats, const int *__restrict__ idx, float *__restrict__ grad,
+                                                            int C, int HW)
+{
+    __shared__ float gl[kCamPlaneMax];
+    __shared__ double redd[4][2];
+    const int plane = blockIdx.x, b = plane / C, c = plane - b * C, tid = threadIdx.x;
+    const float mn = stats[2 * plane], d2 = stats[2 * plane + 1];
+    const int imn = idx[2 * plane], imx = idx[2 * plane + 1];
+    const unsigned long long *g0 = gfix + (size_t)b * (C + 1) * HW, *g1 = g0 + (size_t)(c + 1) * HW;
+    const int *ar = arg + (size_t)b * HW;
+    const float *xp = x + (size_t)plane * HW;
+    const bool bad = *flag != 0ull;
+    double s[2] = {0.0, 0.0};            // G, Gn
+    for (int i = tid; i < HW; i += 256) {
+        float g = (float)((double)(long long)g1[i] * (1.0 / kFixGrad));
+        if (ar[i] == c) g -= (float)((double)(long long)g0[i] * (1.0 / kFixGrad));
+        const float xv = xp[i];
+        const float rm = (xv > 0.f ? xv : (xv != xv ? xv : 0.f)) - mn;
+        gl[i] = g;
+        s[0] += (double)g;
+        s[1] += (double)g * (double)rm;
+    }
+    plane_sums<2>(s, redd);
+    float *o = grad + (size_t)plane * HW;
+    for (int i = tid; i < HW; i += 256) o[i] = bad ? __builtin_nanf("") : norm_adjoint(gl[i], xp[i], i, imn, imx, (double)d2, s[0], s[1]);
+}
+
+// v3 (d): the label map of cam_lossv3_wrap straight from the per-scale low-resolution teacher segs, one thread per pixel of [B,S,S]:
+// z_k = sum over scales of (original half + un-flipped flipped half), as cam_target_kernel evaluates them; an online max / sum-exp over k.
+//   AFTER = false: label = first argmax of the masked z (absent classes at -1e5), maximum probability 1 / sum_k exp((z_k - z_max) / T)
+//   AFTER = true:  softmax over all K; argmax and maximum over the present classes (background included)
+// label = 255 where the maximum probability is not above `thre`.
+template <bool AFTER>
+__global__ __launch_bounds__(256) void cam_label_kernel(SegScales sc, const float *__restrict__ labels, unsigned char *__restrict__ out,
+                                                       int B, int K, int S, float inv_temp, float thre)
+{
+    const int px = blockIdx.x * 64 + (threadIdx.x & 63), py = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
+    if (px >= S || py >= S) return;
+    int y0[4], y1[4], x0[4], x1[4], f0[4], f1[4];
+    float ly0[4], ly1[4], lx0[4], lx1[4], fl0[4], fl1[4];
+#pragma unroll
+    for (int s2 = 0; s2 < 4; s2++)
+        if (s2 < sc.n) {
+            const int h = sc.h[s2], w = sc.w[s2];
+            src_index(py, h, (float)h / (float)S, y0[s2], y1[s2], ly0[s2], ly1[s2]);
+            src_index(px, w, (float)w / (float)S, x0[s2], x1[s2], lx0[s2], lx1[s2]);
+            src_index(S - 1 - px, w, (float)w / (float)S, f0[s2], f1[s2], fl0[s2], fl1[s2]);
+        }
+    const int C = K - 1;
+    float m = -INFINITY, se = 0.f, best = -INFINITY;
+    int bk = 0;
+    for (int k = 0; k < K; k++) {
+        const bool present = k == 0 || labels[(size_t)b * C + k - 1] != 0.0f;
+        float acc = 0.f;
+#pragma unroll
+        for (int s2 = 0; s2 < 4; s2++)
+            if (s2 < sc.n) {
+                const int h = sc.h[s2], w = sc.w[s2];
+                const float *a = sc.p[s2] + ((size_t)b * K + k) * h * w;
+                const float *f = sc.p[s2] + ((size_t)(b + B) * K + k) * h * w;
+                const float v = bilerp_fma(a, w, y0[s2], y1[s2], x0[s2], x1[s2], ly0[s2], ly1[s2], lx0[s2], lx1[s2]) +
+                                bilerp_fma(f, w, y0[s2], y1[s2], f0[s2], f1[s2], ly0[s2], ly1[s2], fl0[s2], fl1[s2]);
+                acc = s2 == 0 ? v : acc + v;
+            }
+        const float z = (AFTER || present) ? acc : -1e5f;
+        // (the max is kept on the summed logits and the DIFFERENCE is divided by T: no rounding of z / T itself)
+        if (z > m) { se = se * expf((m - z) * inv_temp) + 1.f; m = z; }
+        else se += expf((z - m) * inv_temp);
+        if ((!AFTER || present) && z > best) { best = z; bk = k; }
+    }
+    const float maxp = expf((best - m) * inv_temp) / se;
+    out[((size_t)b * S + py) * S + px] = maxp > thre ? (unsigned char)bk : (unsigned char)255;
+}
+
+size_t cam_v3_ws_layout(int B, int C, int HW, size_t *o_mix, size_t *o_arg, size_t *o_stats, size_t *o_idx, size_t *o_sums)
+{
+    const size_t cells = (size_t)B * (C + 1) * HW, planes = (size_t)B * C;
+    size_t off = (64 * 4 + cells + 1) * sizeof(unsigned long long);      // CE sums (64 shards), gradient cells, the sticky flag
+    *o_mix = off;   off += cells * sizeof(float);
+    *o_arg = off;   off += (size_t)B * HW * sizeof(int);
+    *o_stats = off; off += 2 * planes * sizeof(float);
+    *o_idx = off;   off += 2 * planes * sizeof(int);
+    *o_sums = off;  off += 4 * sizeof(float);
+    return align_up(off, 256);
+}
+
+int cam_plane_shapes(const char *who, int B, int C, int h, int w)
+{
+    COSA_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0 && B <= 65535, "%s: bad shape", who);
+    COSA_REQUIRE(C + 1 <= 128, "%s: at most 128 classes, background included (got %d)", who, C + 1);
+    COSA_REQUIRE((long long)h * w <= kCamPlaneMax, "%s: a %d x %d plane is outside the envelope (h w <= %d)", who, h, w, kCamPlaneMax);
+    return COSA_OK;
+}
+
+}  // namespace
+}  // namespace cosa
+
+/* cam_lossv2 on targets already at the CAM's size: cam / targets / grad fp32 [B,C,h,w], loss one float; grad is d loss / d cam for a unit
+ * upstream gradient.  workspace: cosa_cam_lossv2_workspace_bytes(B, C) bytes (one double per plane). */
+extern "C" size_t cosa_cam_lossv2_workspace_bytes(int B, int C)
+{
+    if (B <= 0 || C <= 0) return 0;
+    return cosa::align_up((size_t)B * C * sizeof(double), 256);
+}
+
+extern "C" int cosa_cam_lossv2(const float *cam, const float *targets, float *grad, float *loss, int B, int C, int h, int w, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    COSA_REQUIRE(cam && targets && grad && loss && workspace, "cosa_cam_lossv2: null pointer");
+    int rc = cam_plane_shapes("cosa_cam_lossv2", B, C, h, w);
+    if (rc) return rc;
+    COSA_REQUIRE(workspace_bytes >= cosa_cam_lossv2_workspace_bytes(B, C), "cosa_cam_lossv2: workspace too small (size it with cosa_cam_lossv2_workspace_bytes)");
+    const int HW = h * w, planes = B * C;
+    const float inv_n = (float)(1.0 / ((double)planes * (double)HW));
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(cam_v2_plane_kernel, dim3(planes), dim3(256), 0, st, cam, targets, grad, static_cast<double *>(workspace), HW, inv_n);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(msm_loss_finalize_kernel, dim3(1), dim3(256), 0, st, static_cast<const double *>(workspace), planes, loss, inv_n);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+/* cam_lossv3 (cambgmax): cam / grad fp32 [B,C,h,w], label bytes [B,S,S] (0 background, 1..C, 255 -- and anything above C -- ignored), loss one
+ * float; grad is d loss / d cam for a unit upstream gradient.  S even, S >= 8 h, S >= 8 w. */
+extern "C" size_t cosa_cam_lossv3_workspace_bytes(int B, int C, int h, int w)
+{
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0) return 0;
+    size_t o[5];
+    return cosa::cam_v3_ws_layout(B, C, h * w, o, o + 1, o + 2, o + 3, o + 4);
+}
+
+extern "C" int cosa_cam_lossv3(const float *cam, const uint8_t *label, float *grad, float *loss, int B, int C, int h, int w, int S, void *workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    COSA_REQUIRE(cam && label && grad && loss && workspace, "cosa_cam_lossv3: null pointer");
+    int rc = cam_plane_shapes("cosa_cam_lossv3", B, C, h, w);
+    if (rc) return rc;
+    COSA_REQUIRE(S > 0 && (S & 1) == 0, "cosa_cam_lossv3: the label map's size must be even (got %d)", S);
+    COSA_REQUIRE(S >= 8 * h && S >= 8 * w, "cosa_cam_lossv3: needs an up-sampling factor >= 8 (got %d x %d -> %d)", h, w, S);
+    COSA_REQUIRE(workspace_bytes >= cosa_cam_lossv3_workspace_bytes(B, C, h, w), "cosa_cam_lossv3: workspace too small (size it with cosa_cam_lossv3_workspace_bytes)");
+    const int HW = h * w, K = C + 1, planes = B * C;
+    size_t o_mix, o_arg, o_stats, o_idx, o_sums;
+    cam_v3_ws_layout(B, C, HW, &o_mix, &o_arg, &o_stats, &o_idx, &o_sums);
+    char *base = static_cast<char *>(workspace);
+    const size_t cells = (size_t)B * K * HW;
+    unsigned long long *fsum = reinterpret_cast<unsigned long long *>(base), *gfix = fsum + 64 * 4, *flag = gfix + cells;
+    float *mix = reinterpret_cast<float *>(base + o_mix), *stats = reinterpret_cast<float *>(base + o_stats), *sums = reinterpret_cast<float *>(base + o_sums);
+    int *arg = reinterpret_cast<int *>(base + o_arg), *idx = reinterpret_cast<int *>(base + o_idx);
+    hipStream_t st = as_stream(stream);
+    COSA_HIP_CHECK(hipMemsetAsync(fsum, 0, (64 * 4 + cells + 1) * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(cam_v3_plane_kernel, dim3(planes), dim3(256), 0, st, cam, mix, stats, idx, C, HW);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cam_v3_bg_kernel, dim3((B * HW + 255) / 256), dim3(256), 0, st, mix, arg, B, C, HW);
+    COSA_LAUNCH_CHECK();
+    const dim3 grid((S + 31) / 32, (S + 31) / 32, B), blk(16, 16);
+    const float sy = (float)h / (float)S, sx = (float)w / (float)S;
+    hipLaunchKernelGGL(cam_ce_fwd_kernel, grid, blk, (size_t)K * TC * TC * sizeof(float), st, mix, label, fsum, flag, K, h, w, S, sy, sx);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cam_ce_sums_kernel, dim3(1), dim3(64), 0, st, fsum, flag, sums, loss);
+    COSA_LAUNCH_CHECK();
+    const size_t lds = (size_t)((K * TC * TC + 1) & ~1) * sizeof(float) + (size_t)K * TC * TC * sizeof(unsigned long long);     // K <= 128: 55 KB
+    hipLaunchKernelGGL(cam_ce_bwd_kernel, grid, blk, lds, st, mix, label, sums, gfix, flag, K, h, w, S, sy, sx);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cam_v3_adjoint_kernel, dim3(planes), dim3(256), 0, st, cam, gfix, flag, arg, stats, idx, grad, C, HW);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+/* the label map of cam_lossv3_wrap from the per-scale low-resolution teacher segs (cosa_cam_loss_targets_m's inputs): out bytes [B,S,S] */
+extern "C" int cosa_cam_label(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels, uint8_t *out,
+                              int B, int K, int S, float temperature, float segconf_thre, int after_softmax, void *stream)
+{
+    COSA_REQUIRE(seg_scales && hs && ws && labels && out, "cosa_cam_label: null pointer");
+    COSA_REQUIRE(n_scales >= 1 && n_scales <= 4, "cosa_cam_label: 1 to 4 scales (got %d)", n_scales);
+    COSA_REQUIRE(B > 0 && B <= 65535 && K > 1 && S > 0, "cosa_cam_label: bad shape");
+    COSA_REQUIRE(K <= 128, "cosa_cam_label: at most 128 classes (got %d)", K);
+    COSA_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "cosa_cam_label: the temperature must be finite and positive (got %g)", (double)temperature);
+    COSA_REQUIRE(std::isfinite(segconf_thre), "cosa_cam_label: segconf_thre must be finite (got %g)", (double)segconf_thre);
+    COSA_REQUIRE(after_softmax == 0 || after_softmax == 1, "cosa_cam_label: after_softmax must be 0 or 1 (got %d)", after_softmax);
+    SegScales sc;
+    sc.n = n_scales;
+    for (int i = 0; i < 4; i++) {
+        COSA_REQUIRE(i >= n_scales || (seg_scales[i] && hs[i] > 0 && ws[i] > 0), "cosa_cam_label: scale %d is null or empty", i);
+        sc.p[i] = i < n_scales ? seg_scales[i] : nullptr;
+        sc.h[i] = i < n_scales ? hs[i] : 1;
+        sc.w[i] = i < n_scales ? ws[i] : 1;
+    }
+    const dim3 grid((S + 63) / 64, (S + 3) / 4, B);
+    if (after_softmax)
+        hipLaunchKernelGGL(cam_label_kernel<true>, grid, dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, 1.0f / temperature, segconf_thre);
+    else
+        hipLaunchKernelGGL(cam_label_kernel<false>, grid, dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, 1.0f / temperature, segconf_thre);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}

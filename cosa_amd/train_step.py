@@ -42,7 +42,7 @@ def default_args(dataset="VOC12", **over):
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
              clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
              teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None,
-             act_stats_iters=0)
+             act_stats_iters=0, camloss_version='v1', segconf_thre=0.25)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -50,6 +50,19 @@ def default_args(dataset="VOC12", **over):
     a.update(over)
     a["dataset"] = dataset
     return SimpleNamespace(**a)
+
+
+CAMLOSS_VERSIONS = ("v1", "v2", "v3")          # --camloss_version (main.py:216-224)
+
+
+def camloss_version(args):
+    """--camloss_version of `args` ("v1" where the field is missing); an unknown one is refused"""
+    v = str(getattr(args, "camloss_version", "v1") or "v1")
+    if v not in CAMLOSS_VERSIONS:
+        raise ValueError(f"camloss_version {v!r}: one of {', '.join(CAMLOSS_VERSIONS)}")
+    if v == "v3" and not math.isfinite(float(getattr(args, "segconf_thre", 0.25))):
+        raise ValueError(f"segconf_thre {getattr(args, 'segconf_thre')!r}: a finite probability threshold")
+    return v
 
 
 NOGRAD_PRECISIONS = ("bf16", "fp16", "fp32", "fp64", "bf16x3", "fp16x3", "fp16c8", "fp16c4")     # VITNetwork.set_nograd_precision's base names
@@ -142,6 +155,7 @@ class CoSATrainer:
     def __init__(self, args, device, ddp=False, seed=0):
         self.args = args
         self.device = device
+        self.camloss_version = camloss_version(args)      # (before anything is built: an unknown version costs nothing)
         torch_helper.setup_seed(seed)
         self.model_ON = build_model(args).to(device)
         self.model_AN = build_model(args).to(device)
@@ -493,6 +507,8 @@ class CoSATrainer:
                 if mask_aux is not None:
                     l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
                 cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
+            if self.camloss_version != "v1":               # (ctx["tgt"]: v2's targets, v3's label map)
+                cam_l = self._cam_loss_fn(ctx["tgt"])
             l_cam = cam_l(cam_b)
             if args.aux_seg2cam:
                 l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
@@ -626,7 +642,9 @@ class CoSATrainer:
             reg_loss = seg_helper.get_energy_loss(img=simg, logit=seg_pred, label=refine_mask_label, img_box=img_box,
                                                   loss_layer=self.reg_layer)
         check_tgt = None
-        if self.fused_losses:
+        if self.camloss_version != "v1":
+            cam_loss, check_tgt, check_tgt_s = self._cam_loss_v23(seg_ps, cls_label, wimg.shape[-1], cam_pred, cam_aux_pred)
+        elif self.fused_losses:
             with torch.no_grad():      # seg_ps is the list of per-scale low-res teacher segs here
                 tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:], args.seg_softmaxtemp,
                                                   after_softmax=args.after_softmax)
@@ -671,6 +689,44 @@ class CoSATrainer:
         return loss, dict(overall_loss=overall, cls_loss=cls_loss.detach(), cls_aux_loss=cls_loss_aux.detach(),
                           seg_loss=seg_loss.detach(), cam_loss=cam_loss.detach(), reg_loss=reg_loss.detach(),
                           mask=refine_mask_label, cls_logits=cls_final.detach(), cls_aux_logits=cls_aux.detach())
+
+    def _cam_loss_fn(self, tgt):
+        """cam -> the selected --camloss_version v2 | v3 against `tgt` (v2: targets at the CAM's size on the fused path, the refined teacher
+        probabilities on the torch one; v3: the label map), by the path this trainer takes; the step and the student check share it"""
+        v3 = self.camloss_version == "v3"
+        if self.fused_losses:
+            return (lambda c: seg_helper.cam_lossv3(c, tgt)) if v3 else (lambda c: seg_helper.cam_lossv2_from_targets(c, tgt))
+        if v3:
+            return lambda c: seg_helper._cam_lossv3_torch(c, tgt)
+        return lambda c: seg_helper._cam_lossv2_torch(c, F.interpolate(tgt[:, 1:], size=list(c.shape[-2:]), mode='bilinear', align_corners=False))
+
+    def _cam_loss_v23(self, seg_ps, cls_label, S, cam_pred, cam_aux_pred):
+        """--camloss_version v2 | v3 (main.py:216-224) -> (cam loss, the teacher check's targets | None, the student check's target).  The
+        targets / the label map are made here, outside the captured teacher pass, as cam_loss_targets is: the graph is the same for every
+        version.  `cam_label_last` keeps v3's label map."""
+        args = self.args
+        v3 = self.camloss_version == "v3"
+        with torch.no_grad():
+            if self.fused_losses:      # seg_ps is the list of per-scale low-res teacher segs here
+                if v3:
+                    tgt = seg_helper.cam_label_from_scales(seg_ps, cls_label, S, args.seg_softmaxtemp, args.segconf_thre,
+                                                           after_softmax=args.after_softmax)
+                else:
+                    tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, S, cam_pred.shape[-2:], args.seg_softmaxtemp,
+                                                      after_softmax=args.after_softmax)
+                check_tgt = None if v3 else tgt
+            else:
+                tgt = seg_helper.seg_refine_by_label(seg_ps, cls_label, softmaxtemp=args.seg_softmaxtemp, after_softmax=args.after_softmax)
+                if v3:
+                    tgt = seg_helper._cam_label_torch(tgt, args.segconf_thre)
+                check_tgt = None
+        if v3:
+            self.cam_label_last = tgt
+        fn = self._cam_loss_fn(tgt)
+        cam_loss = fn(cam_pred)
+        if args.aux_seg2cam:
+            cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + args.aux_seg2cam_alpha * fn(cam_aux_pred)
+        return cam_loss, check_tgt, tgt
 
     def prepare_ddp(self, wimg, cls_label):
         """first step under data parallelism on the GPU: warm up and CAPTURE the teacher pass, then wrap the student (see __init__)"""

@@ -1922,6 +1922,145 @@ def cam_loss(cam, seg_ps, is_relu=True):
 
 
 # --------------------------------------------------------------------------------------------
+# cam_lossv2 / cam_lossv3 / cam_lossv3_wrap  (utils/seg_helper.py:604-653, --camloss_version v2 | v3)
+# --------------------------------------------------------------------------------------------
+CAM_PLANE_MAX = 6400        # h w of one CAM plane the kernels hold in LDS (csrc/loss_kernels.hip: kCamPlaneMax)
+CAM_UPSAMPLE_MIN = 8        # the least up-sampling factor of the cross-entropy's LDS tile (csrc/loss_kernels.hip: TC)
+
+
+def _cam_minmax_norm(cam, detach=False):
+    """(relu(cam) - min) / (max + 1e-4) per plane; the extrema through adaptive_max_pool2d, which routes the gradient to the first position
+    of each (a plain amin / amax would spread it over ties)"""
+    r = F.relu(cam.float())
+    lo, hi = F.adaptive_max_pool2d(-r, (1, 1)), F.adaptive_max_pool2d(r, (1, 1)) + 1e-4
+    if detach:
+        lo, hi = lo.detach(), hi.detach()
+    return (r + lo) / hi
+
+
+def _cam_lossv2_torch(cam, targets, detach=False):
+    """cam_lossv2 given targets at the CAM's size, op by op: the composition the kernels are checked against (fused_losses=False, host
+    tensors, detach=True, shapes outside the kernels' envelope)"""
+    B, C, H, W = cam.shape
+    n = _cam_minmax_norm(cam, detach)
+    return F.multilabel_soft_margin_loss(n.permute(0, 2, 3, 1).reshape(B * H * W, C), targets.permute(0, 2, 3, 1).reshape(B * H * W, C))
+
+
+def _cam_lossv3_torch(cam, seg_label, detach=False, cambgmax=True):
+    """cam_lossv3 op by op (see _cam_lossv2_torch): the class-balanced cross-entropy of the up-sampled [background, n] planes"""
+    n = _cam_minmax_norm(cam, detach)
+    bg = 1 - (torch.max(n, dim=1, keepdim=True)[0] if cambgmax else torch.mean(n, dim=1, keepdim=True))
+    mix = F.interpolate(torch.cat([bg, n], dim=1), size=list(seg_label.shape[-2:]), mode='bilinear', align_corners=False)
+    return seg_loss(mix, seg_label)
+
+
+def _cam_label_torch(seg_ps, seg_confident_thre):
+    """cam_lossv3_wrap's label map: the class of the largest probability (lowest index at a tie), 255 where it is not above the threshold"""
+    value, label = torch.max(seg_ps, dim=1)
+    return torch.where(value <= seg_confident_thre, torch.full_like(label, 255), label)
+
+
+def _cam_kernel_ok(cam, S=None):
+    """fp32 device CAMs inside the plane kernels' envelope (and, for v3, a label map the cross-entropy's tile can serve)"""
+    if not (cam.is_cuda and cam.dtype == torch.float32 and cam.dim() == 4):
+        return False
+    B, C, h, w = cam.shape
+    if not (0 < B <= 65535 and 0 < C < 128 and 0 < h * w <= CAM_PLANE_MAX):
+        return False
+    return S is None or (S[0] == S[1] and S[0] % 2 == 0 and S[0] >= CAM_UPSAMPLE_MIN * h and S[0] >= CAM_UPSAMPLE_MIN * w)
+
+
+class _CamLossV2Fn(torch.autograd.Function):
+    """cam_lossv2 on targets at the CAM's size, value and gradient from one launch per plane (cosa_cam_lossv2)"""
+
+    @staticmethod
+    def forward(ctx, cam, targets):
+        cam = cam.contiguous()
+        targets = targets.contiguous().float()
+        B, C, h, w = cam.shape
+        grad = torch.empty_like(cam)
+        loss = torch.empty(1, device=cam.device, dtype=torch.float32)
+        L = _C.lib()
+        ws = _C.workspace(L.cosa_cam_lossv2_workspace_bytes(B, C), cam.device, "cam_lossv2")
+        _C.check(L.cosa_cam_lossv2(_C.ptr(cam), _C.ptr(targets), _C.ptr(grad), _C.ptr(loss), B, C, h, w, _C.ptr(ws), ws.numel(), _C.stream_ptr()),
+                 "cosa_cam_lossv2")
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None
+
+
+class _CamLossV3Fn(torch.autograd.Function):
+    """cam_lossv3 against a byte label map [B,S,S], value and gradient from one call (cosa_cam_lossv3); nothing of size [B,K,S,S] is written"""
+
+    @staticmethod
+    def forward(ctx, cam, label):
+        cam = cam.contiguous()
+        B, C, h, w = cam.shape
+        grad = torch.empty_like(cam)
+        loss = torch.empty(1, device=cam.device, dtype=torch.float32)
+        L = _C.lib()
+        ws = _C.workspace(L.cosa_cam_lossv3_workspace_bytes(B, C, h, w), cam.device, "cam_lossv3")
+        _C.check(L.cosa_cam_lossv3(_C.ptr(cam), _C.ptr(label), _C.ptr(grad), _C.ptr(loss), B, C, h, w, label.shape[-1], _C.ptr(ws), ws.numel(),
+                                   _C.stream_ptr()), "cosa_cam_lossv3")
+        ctx.save_for_backward(grad)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None
+
+
+def cam_lossv2_from_targets(cam, targets):
+    """cam_lossv2 (seg_helper.py:604-624) given pre-resized targets [B,C,H,W] (cam_loss_targets): the fused kernel for fp32 device CAMs
+    inside its envelope, the torch composition otherwise"""
+    if _cam_kernel_ok(cam) and targets.is_cuda and targets.shape == cam.shape:
+        return _CamLossV2Fn.apply(cam, targets)
+    return _cam_lossv2_torch(cam, targets)
+
+
+def cam_lossv2(cam, seg_ps, detach=False):
+    B, C, H, W = cam.shape
+    targets = F.interpolate(seg_ps[:, 1:, ...], size=[H, W], mode='bilinear', align_corners=False)
+    if detach:
+        return _cam_lossv2_torch(cam, targets, detach=True)
+    return cam_lossv2_from_targets(cam, targets)
+
+
+def cam_lossv3(cam, seg_label, detach=False, cambgmax=True):
+    """seg_label [B,H,W]: 0 background, 1..C, 255 ignored (any integer dtype, or the bytes cam_label_from_scales writes)"""
+    if not detach and cambgmax and seg_label.is_cuda and seg_label.dim() == 3 and _cam_kernel_ok(cam, tuple(seg_label.shape[-2:])) \
+            and seg_label.shape[0] == cam.shape[0]:
+        lab = seg_label if seg_label.dtype == torch.uint8 else seg_label.to(torch.uint8)
+        return _CamLossV3Fn.apply(cam, lab.contiguous())
+    return _cam_lossv3_torch(cam, seg_label, detach=detach, cambgmax=cambgmax)
+
+
+def cam_lossv3_wrap(cam, seg_ps, seg_confident_thre=0.25):
+    return cam_lossv3(cam, _cam_label_torch(seg_ps, seg_confident_thre))
+
+
+def cam_label_from_scales(seg_scales, cls_label, S, softmaxtemp, segconf_thre, after_softmax=False):
+    """cam_lossv3_wrap's label map, bytes [B,S,S], from the per-scale low-res teacher segs (cam_loss_targets' inputs) without building the
+    [b,K,S,S] tensor: argmax of seg_refine_by_label(sum_scales seg, T, after_softmax), 255 where its maximum is not above segconf_thre"""
+    b2, K = seg_scales[0].shape[:2]
+    B = b2 // 2
+    out = torch.empty((B, int(S), int(S)), device=seg_scales[0].device, dtype=torch.uint8)
+    n = len(seg_scales)
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in seg_scales])
+    hs = _C.int_array([t.shape[2] for t in seg_scales])
+    ws = _C.int_array([t.shape[3] for t in seg_scales])
+    lab = cls_label.contiguous().float()
+    _C.check(_C.lib().cosa_cam_label(ptrs, hs, ws, n, _C.ptr(lab), _C.ptr(out), B, K, int(S), float(softmaxtemp), float(segconf_thre),
+                                     int(bool(after_softmax)), _C.stream_ptr()), "cosa_cam_label")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # dense-CRF post-processing of the final evaluation  (utils/seg_helper.py:961-996)
 # --------------------------------------------------------------------------------------------
 class DenseCRF(object):

@@ -574,6 +574,27 @@ int cosa_cam_loss_targets(const float *const *seg_scales, const int *hs, const i
  * sum_scales / T over all K channels and sets the channels of absent classes to zero afterwards; 0 is the call above, bit for bit.      */
 int cosa_cam_loss_targets_m(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
                             float *out, int B, int K, int S, int oh, int ow, float temperature, int after_softmax, void *stream);
+/* --camloss_version v2 | v3 (utils/seg_helper.py:604-653).  Both normalise every plane of relu(cam) to n = (r - min r) / (max r + 1e-4) with
+ * the gradient flowing through the minimum and the maximum (to the FIRST position of each, as adaptive_max_pool2d routes it).
+ *   cam / grad fp32 [B,C,h,w], loss one float, grad = d loss / d cam for a unit upstream gradient (value and gradient from one call).
+ *   One workgroup per plane: h w <= 6400 (80 x 80), C + 1 <= 128; fixed-order reductions and integer sums -- the same bytes every run.
+ * cosa_cam_lossv2: multilabel_soft_margin(n, targets), targets fp32 [B,C,h,w] already at the CAM's size (cosa_cam_loss_targets_m's output).
+ * cosa_cam_lossv3: cam_mix = cat(1 - max_c n, n); class-balanced cross-entropy (0.5 background + 0.5 foreground, each a mean over its pixels)
+ *   of bilinear_up(cam_mix, S) against label bytes [B,S,S]: 0 background, 1..C, 255 (and anything above C) ignored.  S even, S >= 8 h and
+ *   S >= 8 w.  The up-sampled tensor is never written: the cross-entropy runs on the cosa_seg_loss_* scheme.  At equal n the lowest channel
+ *   takes the background's gradient.
+ * cosa_cam_label: the label map of cam_lossv3_wrap from cosa_cam_loss_targets_m's inputs at every pixel: the argmax (lowest index at a tie)
+ *   of seg_refine_by_label(sum of scales, T, after_softmax), 255 where its maximum probability is not above segconf_thre.  out bytes [B,S,S].
+ * A refused call (COSA_EINVAL: null pointer, more than 128 classes, a plane outside the envelope, an up-sampling factor below 8, a
+ * non-finite temperature or threshold, a short workspace) launches nothing.                                                              */
+size_t cosa_cam_lossv2_workspace_bytes(int B, int C);
+int cosa_cam_lossv2(const float *cam, const float *targets, float *grad, float *loss, int B, int C, int h, int w, void *workspace,
+                    size_t workspace_bytes, void *stream);
+size_t cosa_cam_lossv3_workspace_bytes(int B, int C, int h, int w);
+int cosa_cam_lossv3(const float *cam, const uint8_t *label, float *grad, float *loss, int B, int C, int h, int w, int S, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int cosa_cam_label(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels, uint8_t *out,
+                   int B, int K, int S, float temperature, float segconf_thre, int after_softmax, void *stream);
 /* utils/seg_helper.py:210-230 (get_energy_loss: F.softmax over the classes of the full-resolution logits) + :199-203 (DenseEnergyLoss.forward:
  * bilinear resize of the probabilities by 0.5 = the mean of each 2x2 quad) in one pass, and the backward of the pair:
  *   logit [B,K,H,W] (H, W even)   out / grad_out [B,K,H/2,W/2]   grad_logit [B,K,H,W]                                                     */
