@@ -211,6 +211,10 @@ _SIGS.update({
     # label-free export (csrc/predict_kernels.hip)
     "cosa_predict_classes": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cosa_export_overlay": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # the --grad_check_iters check (csrc/grad_check_kernels.hip)
+    "cosa_grad_check_workspace_bytes": (c_size_t, [c_int]),
+    "cosa_grad_check_norms": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cosa_grad_check_perturb": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

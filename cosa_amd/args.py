@@ -95,6 +95,14 @@ EXTRA = [
                                              # weak images and reduces, per block, the range of q / k / v / o / h / x (bits of headroom under fp16's 65504)
                                              # and per head the attention logits' magnitude and row entropy; logged and written to
                                              # <output_dir>/act_stats.jsonl every log_iters; training is untouched
+    # the gradient check; 0: nothing changes
+    ("grad_check_iters", int, 0),            # every N-th optimizer step differences the step's objective along the step's own raw gradient on a
+                                             # no-grad network of its own (four perturbed weight sets per direction, written on the device) and reports
+                                             # r = <grad L, g> / <g, g>: 1 for an exact gradient; logged with the next log line and written to
+                                             # <output_dir>/grad_check.jsonl; training is untouched; a world of one only
+    ("grad_check_mode", str, "fp64"),        # fp64 | fp32: the arithmetic of the differenced forward (a 16-bit one is rounding noise: refused)
+    ("grad_check_dirs", str, "all"),         # all: one direction, every tensor with a gradient; sites: plus embed, block<i>, norm, decoder, heads
+    ("grad_check_rho", float, 1e-5),         # the relative step |s g| / |w| of the difference (utils/grad_check.py: DEFAULT_RHO)
     # per-image evaluation scores; off: nothing changes
     ("image_scores", str2bool, False),       # every evaluate() of the run also counts each image's label maps against its ground truth on the
                                              # device and writes <output_dir>/<iteration>/image_scores_<s|t>.jsonl and iou_dic_<s|t>.pth (the

@@ -57,6 +57,7 @@ SOURCES = {
     "image_scores_kernels.hip": EXACT,
     # label-free export: the class row from the logits (comparisons only) and the overlay (x * std + mean rounded twice, integer blend)
     "predict_kernels.hip": EXACT,
+    "grad_check_kernels.hip": EXACT,      # (--grad_check_iters: w + fl32(s g) in two roundings, double sums in a fixed order)
 }
 
 

@@ -27,6 +27,7 @@ from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
 from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher
+from .utils import grad_check as gcheck
 from .utils import torch_helper
 
 
@@ -71,8 +72,12 @@ def check_supported(args):
     get_backbone(args.backbone)                                   # NotImplementedError listing the built encoders
     if getattr(args, "accum_steps", 1) < 1:
         raise ValueError(f"--accum_steps {args.accum_steps}: a positive number of micro-batches per optimizer step")
-    for which in ("teacher", "student", "act_stats"):
+    for which in ("teacher", "student", "act_stats", "grad"):
         check_iters(args, which, flag="--")
+    if check_iters(args, "grad") > 0:
+        gcheck.check_mode(getattr(args, "grad_check_mode", "fp64"))
+        gcheck.check_dirs(getattr(args, "grad_check_dirs", "all"))
+        gcheck.check_rho(getattr(args, "grad_check_rho", gcheck.DEFAULT_RHO))
     refuse_fp64_teacher(getattr(args, "teacher_precision", "auto"), flag="--")
     notes = []
     if not args.find_unused:
@@ -103,6 +108,17 @@ def read_interval(acc, log_iters, monitors):
         m.zero(t)
         at += n
     return vals[:acc.numel()], host
+
+
+def grad_check_record(summary, n_iter, targs):
+    """one line of <output_dir>/grad_check.jsonl: the iteration, mode and rho of a check and its directions (utils.grad_check.summarize)"""
+    import json
+    return json.dumps(gcheck.jsonable(dict(iters=int(n_iter), mode=targs.grad_check_mode, rho=float(targs.grad_check_rho), dirs=summary)))
+
+
+def append_grad_check(output_dir, summary, n_iter, targs):
+    with (Path(output_dir) / "grad_check.jsonl").open("a") as f:
+        f.write(grad_check_record(summary, n_iter, targs) + "\n")
 
 
 def next_batch(it, new_iter, pos):
@@ -181,6 +197,7 @@ def main(args):
         loss_df = {k: list(resumed["loss_df"][k]) for k in loss_df}
     tstats_on = bool(getattr(args, "tensor_stats", False))                        # per-tensor diagnostics
     n_micro = int(getattr(args, "accum_steps", 1))                                # micro-batches per optimizer step
+    gcheck_on, gcheck_line = check_iters(args, "grad") > 0, ""                    # the gradient check
     for n_iter in range(first_iter, args.max_iters):
         if tstats_on and (n_iter + 1) % args.log_iters == 0:
             trainer.request_tensor_stats()                                         # this step closes the interval: it samples the table
@@ -194,6 +211,11 @@ def main(args):
                 acc += torch.stack([t.reshape(()).double() for t in (
                     logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
                     (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
+        if gcheck_on and (n_iter + 1) % args.grad_check_iters == 0:              # a check step: its record is read here (the check's one sync)
+            gsum = trainer.pop_grad_check()
+            if gsum is not None and is_main:
+                append_grad_check(output_dir, gsum, n_iter + 1, targs)
+                gcheck_line = gcheck.line(gsum, targs.grad_check_mode)
         if (n_iter + 1) % args.log_iters == 0:
             vals, host = read_interval(acc, args.log_iters * n_micro, monitors.active(trainer))   # the one host sync of the interval
             now = time.time()
@@ -214,6 +236,7 @@ def main(args):
                             line += m.line(summary, targs)
                             if m.record_extra is not None:
                                 monitors.append_monitor(output_dir, m, summary, n_iter + 1, targs)
+                line, gcheck_line = line + gcheck_line, ""                                 # (the last check since the previous line, if any)
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             score_kw = {"image_scores": True} if args.image_scores else {}           # (off: the calls as ever)

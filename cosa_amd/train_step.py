@@ -24,6 +24,7 @@ from .models import build_model
 from .models.PAR import PAR
 from .models.vit import ActProbe
 from . import _C
+from .utils import grad_check as gcheck
 from .utils import seg_helper, torch_helper
 
 IMAGENET_MEAN = (123.675, 116.28, 103.53)
@@ -42,7 +43,8 @@ def default_args(dataset="VOC12", **over):
              queue_update_ratio=100, compute_dtype=torch.bfloat16, teacher_precision="auto", teacher_graph=True, teacher_async=True, lattice_async=False, fused_losses=True, fused_optimizer=True,
              clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
              teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None,
-             act_stats_iters=0, camloss_version='v1', segconf_thre=0.25)
+             act_stats_iters=0, camloss_version='v1', segconf_thre=0.25,
+             grad_check_iters=0, grad_check_mode='fp64', grad_check_dirs='all', grad_check_rho=gcheck.DEFAULT_RHO)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -116,7 +118,7 @@ def resolve_teacher_check_mode(mode, teacher_precision):
 
 
 def check_iters(args, which, flag=""):
-    """--<which>_check_iters of `args` (which: "teacher" / "student"), or --act_stats_iters (which: "act_stats"), as an int; a negative one is
+    """--<which>_check_iters of `args` (which: "teacher" / "student" / "grad"), or --act_stats_iters (which: "act_stats"), as an int; a negative one is
     refused, here for the trainer and, with flag="--", for the launcher's check_supported"""
     name = "act_stats_iters" if which == "act_stats" else which + "_check_iters"
     n = int(getattr(args, name, 0) or 0)
@@ -156,6 +158,14 @@ class CoSATrainer:
         self.args = args
         self.device = device
         self.camloss_version = camloss_version(args)      # (before anything is built: an unknown version costs nothing)
+        if check_iters(args, "grad") > 0:                 # (--grad_check_iters, DESIGN.md section 25: refused before anything is built too)
+            args.grad_check_mode = gcheck.check_mode(getattr(args, "grad_check_mode", "fp64"))
+            args.grad_check_dirs = gcheck.check_dirs(getattr(args, "grad_check_dirs", "all"))
+            args.grad_check_rho = gcheck.check_rho(getattr(args, "grad_check_rho", gcheck.DEFAULT_RHO))
+            if ddp:
+                raise NotImplementedError("grad_check_iters under data parallelism: the reduced gradient belongs to the mean of all ranks' "
+                                          "losses, and averaging the check's loss slots across ranks is not built; run the check in a "
+                                          "world of one (tools/grad_check.py)")
         torch_helper.setup_seed(seed)
         self.model_ON = build_model(args).to(device)
         self.model_AN = build_model(args).to(device)
@@ -288,7 +298,7 @@ class CoSATrainer:
         # that moment, and scores the two passes against each other.  The counters are state of the run (`teacher_check.counters` of
         # extra_state); model_CK is not: every check overwrites it
         self.teacher_check_state = self.model_CK = None
-        self._check_iters = {which: check_iters(args, which) for which in ("teacher", "student", "act_stats")}
+        self._check_iters = {which: check_iters(args, which) for which in ("teacher", "student", "act_stats", "grad")}
         if self._check_iters["teacher"] > 0:
             cm = resolve_teacher_check_mode(getattr(args, "teacher_check_mode", "auto"), tp)
             args.teacher_check_mode = cm
@@ -338,6 +348,17 @@ class CoSATrainer:
                 assert len(self._ak_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ak_params, self._ema_pairs[0]))
                 self.model_AK.encoder.act_probe = ActProbe(*self.act_stats_shape, table=seg_helper.act_stats_table(self.act_stats_state, *self.act_stats_shape))
                 self._ak_buffers = {}                                             # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
+        # the gradient check: off (None) unless --grad_check_iters N > 0.  Every N-th optimizer step differences the
+        # step's objective along the step's own raw gradient on `model_GK`, a network of its own in --grad_check_mode (fp32 | fp64) whose
+        # fp32 parameters the perturb kernel writes.  Nothing accumulates: `grad_check_state` is the record of ONE check (overwritten by the
+        # next), so the check is no row of monitors.MONITORS and no entry of a state file
+        self.grad_check_state = self.model_GK = self._gcheck_ctx = self._gk_pending = self.grad_check_last = None
+        if self._check_iters["grad"] > 0:
+            self.student.check_nograd_precision(args.grad_check_mode)
+            if device.type == "cuda" and not on:
+                raise NotImplementedError("grad_check_iters: the check runs the no-grad fp32 / fp64 path of the HIP encoder; this trainer's "
+                                          "compute dtype has none")
+            self._build_grad_check()
         if on:
             for sh in (self._teacher_shadows, self._student_shadows):
                 if sh is not None:
@@ -436,8 +457,38 @@ class CoSATrainer:
         ck = ck.to(self.device)
         for p in ck.parameters():
             p.requires_grad = False
-        ck.set_nograd_precision(mode)
+        if self.device.type == "cuda" or hasattr(ck, "set_nograd_precision"):      # (a host trainer's toy network has torch operators only)
+            ck.set_nograd_precision(mode)
         return ck
+
+    def _build_grad_check(self):
+        """model_GK and the check's buffers.  `_gk_params`: the fp32 tensors the perturbed weights are written to, in _ema_pairs[1]'s order
+        -- model_GK's own parameters, which the fp32 / fp64 families read as they are; a host trainer in mode fp64 runs model_GK in
+        torch.float64 and loads it from fp32 staging copies"""
+        args, dev = self.args, self.device
+        net = self._new_check_network(args.grad_check_mode)
+        params = list(net.parameters())
+        assert len(params) == len(self._ema_pairs[1]) and all(a.shape == b.shape for a, b in zip(params, self._ema_pairs[1]))
+        self._gk_stage = dev.type != "cuda" and args.grad_check_mode == "fp64"
+        if self._gk_stage:
+            net = net.double()
+            params = [torch.empty_like(p, dtype=torch.float32) for p in net.parameters()]
+        self.model_GK, self._gk_params = net, params
+        self._gk_names = [n for n, _ in self.student.named_parameters()]
+        self._gk_dirs = self._gk_plan = self._gk_tables = None                       # (made by the first check: which tensors hold a gradient)
+        self.grad_check_state = True                                              # (the record itself: allocated with the plan)
+
+    def _gk_make_plan(self, grads):
+        args, dev = self.args, self.device
+        self._gk_dirs, self._gk_plan = gcheck.plan(self._gk_names, [g is not None for g in grads], args.grad_check_dirs)
+        self.grad_check_state = torch.zeros((len(self._gk_dirs), gcheck.RECORD), dtype=torch.float64, device=dev)
+        self._gk_tables = None
+        if dev.type == "cuda":
+            sizes = [int(p.numel()) for p in self._ema_pairs[1]]
+            self._gk_tables = [gcheck.Table(sizes, dev) for _ in self._gk_plan]     # (one per pass: a pinned table is read by an async copy)
+            self._gk_host = torch.empty_like(self.grad_check_state, device="cpu").pin_memory()
+            self._gk_event = torch.cuda.Event()
+        self._gk_has_grad = [g is not None for g in grads]
 
     def _build_check(self, which):
         """model_CK, the --teacher_check network, or model_SK, the --student_check one (_new_check_network on args.<which>_check_mode): two
@@ -489,34 +540,129 @@ class CoSATrainer:
         and operand buffers are its own, the library workspaces it needs are slots of their own (_C.workspace_scope), and the backward
         that read the training forward's workspaces has already run.  `student_check_last` keeps what went into the reduction."""
         ctx, self._scheck_ctx = self._scheck_ctx, None
-        args = self.args
         torch._foreach_copy_(self._sk_params, self._ema_pairs[1])                  # (the unwrapped student's parameters, not DDP's)
-        lab, simg, (mask, mask_aux) = ctx["cls_label"], ctx["simg"], ctx["masks"]
+        lab = ctx["cls_label"]
         with self._check_pass("student_check"):
-            cls_b, clsaux_b, _feat, seg_b, cam_b, aux_b = self.model_SK(simg, cam_only=False, detach='none')
-            cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
-            l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
-            l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
-            if self.fused_losses:
-                l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
-                                                         aux_alpha=args.aux_cam2seg_alpha)
-                cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
-            else:
-                up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
-                l_seg = seg_helper.seg_loss(up, mask, fg_alpha=args.segfg_alpha)
-                if mask_aux is not None:
-                    l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
-                cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
-            if self.camloss_version != "v1":               # (ctx["tgt"]: v2's targets, v3's label map)
-                cam_l = self._cam_loss_fn(ctx["tgt"])
-            l_cam = cam_l(cam_b)
-            if args.aux_seg2cam:
-                l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
-            loss_b = torch.stack([t.reshape(()).float() for t in (l_cls, l_cls_aux, l_seg, l_cam)])
+            b, four = self._check_forward_losses(self.model_SK, ctx)
+            loss_b = torch.stack([t.reshape(()).float() for t in four])
         a, loss_a = ctx["outputs"], torch.stack([t.reshape(()).float() for t in ctx["losses"]])
-        b = dict(seg=seg_b, cam=cam_b, cam_aux=aux_b, cls=cls_b, cls_aux=clsaux_b)
         seg_helper.student_check(*[(a[k], b[k]) for k in seg_helper.STUDENT_CHECK_TENSORS], (loss_a, loss_b), lab, self.student_check_state)
         self.student_check_last = dict(a=a, b=b, loss_a=loss_a, loss_b=loss_b, cls_label=lab)
+
+    def _check_forward_losses(self, net, ctx):
+        """`net`'s full no-grad forward over the step's strong images and the step's four dense / classification losses on its outputs,
+        forward kernels only, against what `ctx` kept of the step (label maps, cam-loss targets or v3's label map, labels, boxes) and the
+        step's blend weights -> ({seg, cam, cam_aux, cls, cls_aux} as contiguous fp32, (cls, cls_aux, seg, cam) losses).  Both checks
+        (_student_check, _grad_check) call it, inside their own _check_pass."""
+        args = self.args
+        lab, simg, (mask, mask_aux) = ctx["cls_label"], ctx["simg"], ctx["masks"]
+        cls_b, clsaux_b, _feat, seg_b, cam_b, aux_b = net(simg, cam_only=False, detach='none')
+        cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
+        l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
+        l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
+        if self.fused_losses:
+            l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
+                                                     aux_alpha=args.aux_cam2seg_alpha)
+            cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
+        else:
+            up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
+            l_seg = seg_helper.seg_loss(up, mask, fg_alpha=args.segfg_alpha)
+            if mask_aux is not None:
+                l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
+            cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
+        if self.camloss_version != "v1":               # (ctx["tgt"]: v2's targets, v3's label map)
+            cam_l = self._cam_loss_fn(ctx["tgt"])
+        l_cam = cam_l(cam_b)
+        if args.aux_seg2cam:
+            l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
+        return dict(seg=seg_b, cam=cam_b, cam_aux=aux_b, cls=cls_b, cls_aux=clsaux_b), (l_cls, l_cls_aux, l_seg, l_cam)
+
+    def _check_objective(self, net, ctx):
+        """the five float32 terms (cls, cls_aux, seg, cam, reg) of the step's objective on `net`, forward only, inside the caller's
+        _check_pass.  The regulariser is get_energy_loss on this pass's up-sampled seg logits: its lattice is rebuilt from the same image
+        (the training step's lattice state has been consumed by the backward)."""
+        outs, four = self._check_forward_losses(net, ctx)
+        mask = ctx["masks"][0]
+        up = F.interpolate(outs["seg"], size=mask.shape[1:], mode='bilinear', align_corners=False)
+        reg = seg_helper.get_energy_loss(img=ctx["simg"], logit=up, label=mask, img_box=ctx["img_box"], loss_layer=self.reg_layer)
+        return torch.stack([t.reshape(()).float() for t in four + (reg,)])
+
+    @torch.no_grad()
+    def _grad_check(self):
+        """One check, eagerly on the current stream AFTER the step's backward and BEFORE the weights move (with
+        --accum_steps: before the closing micro-batch's gradient is folded): per direction the norms and the step length s (one reduction
+        over the masters and their raw .grad), four perturbed weight sets w + fl32(c s g), c = +1, -1, +1/2, -1/2, written into model_GK by
+        the perturb kernel (s is read on the device), and the step's objective evaluated forward-only at w and at each set.  The record
+        [n_dirs][RECORD] is complete on the device when this returns and is on its way to the host; grad_check() waits for it -- the check's
+        one sync.  No RNG, and nothing the training path reads is written: model_GK's weights and operand buffers are its own, the
+        library workspaces it needs are slots of their own (_C.workspace_scope)."""
+        ctx, self._gcheck_ctx = self._gcheck_ctx, None
+        args, rho, host = self.args, self.args.grad_check_rho, self.device.type != "cuda"
+        ws = self._ema_pairs[1]                                                      # (the unwrapped student's parameters)
+        grads = [p.grad if p.requires_grad else None for p in ws]
+        if self._gk_plan is None or self._gk_has_grad != [g is not None for g in grads]:
+            self._gk_make_plan(grads)
+        rec = self.grad_check_state
+        rec.zero_()
+
+        def objective():
+            if self._gk_stage:
+                torch._foreach_copy_(list(self.model_GK.parameters()), self._gk_params)
+            with self._check_pass("grad_check"):
+                return self._check_objective(self.model_GK, ctx).double()
+
+        torch._foreach_copy_(self._gk_params, ws)
+        rec[:, gcheck.LOSS:gcheck.LOSS + 5] = objective()
+        for p, (row0, n_dirs, dirs) in enumerate(self._gk_plan):
+            rows = rec[row0:row0 + n_dirs]
+            if host:
+                gcheck.norms_torch(ws, grads, dirs, n_dirs, rho, rows)
+            else:
+                table = self._gk_tables[p].fill(ws, grads, self._gk_params, dirs)
+                gcheck.norms(table, n_dirs, rho, rows)
+            for d in range(n_dirs):
+                for k, c in enumerate(gcheck.STEPS):
+                    if host:
+                        gcheck.perturb_torch(ws, grads, self._gk_params, dirs, d, c, k, rows)
+                    else:
+                        gcheck.perturb(table, n_dirs, d, c, k, rows)
+                    at = gcheck.LOSS + 5 * (k + 1)
+                    rows[d, at:at + 5] = objective()
+        if host:
+            self._gk_pending = rec.clone()
+        else:
+            self._gk_host.copy_(rec, non_blocking=True)
+            self._gk_event.record()
+            self._gk_pending = self._gk_host
+        self._gk_weights = list(ctx["weights"])
+
+    def grad_check(self):
+        """the summary (utils.grad_check.summarize: one dict per direction) of the last check; waits for its record, the check's one sync.
+        None when the check is off or none has run"""
+        if self._gk_pending is not None:
+            if self.device.type == "cuda":
+                self._gk_event.synchronize()
+            self.grad_check_last = gcheck.summarize(self._gk_pending.tolist(), self._gk_dirs, self._gk_weights)
+            self.grad_check_record = self._gk_pending.clone()
+            self._gk_pending = None
+        return self.grad_check_last
+
+    def grad_check_batch(self, wimg, simg, cls_label, img_box, n_iter, gt=None):
+        """forward, backward and one check on a batch WITHOUT an optimizer update (the weights never move) -> the check's summary.  For
+        tools/grad_check.py: a trainer built with grad_check_iters=1, so that every step is a check step."""
+        if self.model_GK is None or self._check_iters["grad"] != 1 or self._accum_steps != 1:
+            raise RuntimeError("grad_check_batch: build the trainer with grad_check_iters=1 and accum_steps=1")
+        loss, _logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.device.type == "cuda" and self._student_shadows is not None:
+            nn_ops.wgrad_arena_begin(self.device)
+        loss.backward()
+        self._grad_check()
+        return self.grad_check()
+
+    def pop_grad_check(self):
+        """grad_check() of a check that has not been read yet, else None: what the launcher asks after a check step"""
+        return self.grad_check() if self._gk_pending is not None else None
 
     def student_check(self):
         """_summary_of --student_check_iters' counters (seg_helper.student_check_summary)"""
@@ -679,6 +825,12 @@ class CoSATrainer:
         if wvec is None:
             wl = [1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight]
             wvec = self._loss_weights[wkey] = torch.tensor(wl, device=cls_loss.device, dtype=torch.float32)
+        if self.model_GK is not None and self._is_check_step(n_iter, "grad"):
+            # what the check after this step's backward (_grad_check) reads: detached references and the loss weights as the dot product
+            # below rounds them (fp32), nothing is copied or computed here
+            wl32 = [float(np.float32(v)) for v in ([1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight])]
+            self._gcheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux),
+                                    tgt=check_tgt_s, weights=wl32)
         loss = torch.dot(torch.stack([cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(),
                                       reg_loss.reshape(()).float()]), wvec)
         overall = loss.detach()
@@ -755,6 +907,8 @@ class CoSATrainer:
         loss.backward()
         if self._scheck_ctx is not None:                 # (--student_check_iters: after the backward, before the weights move)
             self._student_check()
+        if self._gcheck_ctx is not None:                 # (--grad_check_iters: likewise)
+            self._grad_check()
         return self._apply_gradients(logs)
 
     def _apply_gradients(self, logs):
@@ -787,6 +941,8 @@ class CoSATrainer:
         if self.device.type == "cuda" and self._student_shadows is not None:
             nn_ops.wgrad_arena_begin(self.device)        # this micro-step's weight gradients: consumed by accumulate() below
         loss.backward()
+        if self._gcheck_ctx is not None:                 # (--grad_check_iters: the closing micro-batch's own gradient against its own loss, before it is folded)
+            self._grad_check()
         if self._fused_step is not None:
             self._fused_step.accumulate(k)
         else:

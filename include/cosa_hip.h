@@ -1017,6 +1017,55 @@ int cosa_range_stats_f32(const float *x, long long rows, int cols, long long ld,
 int cosa_attn_stats_f32(const float *qkv, int B, int N, int H, int head_dim, float scale, long long ldq, int64_t *out /* [H][7] */,
                         void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The --grad_check_iters check (csrc/grad_check_kernels.hip): the step's raw fp32 gradient g against
+ * central differences of the loss along g itself.  These two entry points are the streams over the parameters; the losses
+ * are evaluated by the caller between them.
+ * The table: n_tensors records {const float *w; const float *g; float *dst; int64 n; int32 dir; int32 pad}
+ *   (COSA_GRAD_CHECK_RECORD_BYTES each) followed at once by n_chunks {int32 tensor; int32 chunk}: every chunk of
+ *   COSA_GRAD_CHECK_CHUNK elements of every tensor once, tensors ascending, a tensor's chunks from 0.  dir: the direction the
+ *   tensor belongs to, -1 for none (g may then be NULL).  The table is passed twice: `table_host`, on which the envelope is
+ *   checked, and `table_dev`, the device copy of the same bytes the kernels read.
+ * The record: n_dirs rows of COSA_GRAD_CHECK_RECORD doubles --
+ *   COSA_GRAD_CHECK_G2 sum g^2;  _W2 sum w^2 (both in double over the direction's tensors);  _S the step length
+ *   float(rho sqrt(W2 / G2)) as a double;  _FLAGS the OR of COSA_GRAD_CHECK_FLAG_* (s is 0 whenever one is set);
+ *   _T + k, k < COSA_GRAD_CHECK_STEPS, the realised step sum (dst - w) g of perturb's slot k;  _LOSS + 5 j + i the caller's:
+ *   loss term i at evaluation j (0: at w, 1 + k: at slot k's weights);  _BAD_G, _BAD_W the non-finite elements counted.
+ * cosa_grad_check_norms    writes G2, W2, S, FLAGS, BAD_G, BAD_W of every row.  rho finite and > 0.
+ * cosa_grad_check_perturb  reads row `dir`'s S on the device (no host sync) and writes, for EVERY tensor of the table,
+ *                          dst = w + fl32(fl32(c S) g) inside direction `dir` -- the product and the sum rounded separately
+ *                          -- and dst = w outside it or with S = 0; then row `dir`'s T + slot.  c finite.
+ * Sums: each thread adds its strided elements in double, a wavefront's sums meet in an xor butterfly, the wavefronts in wave
+ *   order, one partial per chunk, the partials lane-strided in chunk order: no atomics, the same bytes on every run.  dwordx4
+ *   accesses where w, g and dst are 16-byte aligned, single elements otherwise.  Two launches each, no host sync.
+ * Workspace: cosa_grad_check_workspace_bytes(n_chunks) serves both.
+ * Refused with COSA_EINVAL, nothing launched and nothing written: a NULL table, record or workspace, counts < 1, a record
+ *   with n < 0, dir outside [-1, n_dirs), a NULL or misaligned w / dst, a direction's tensor without g, a chunk list that is
+ *   not exactly the tensors' chunks in order, a short workspace, a non-finite or non-positive rho, a non-finite c, `dir`
+ *   outside [0, n_dirs), `slot` outside [0, COSA_GRAD_CHECK_STEPS).
+ * ------------------------------------------------------------------------------------- */
+#define COSA_GRAD_CHECK_CHUNK 16384
+#define COSA_GRAD_CHECK_RECORD_BYTES 40
+#define COSA_GRAD_CHECK_RECORD 36
+#define COSA_GRAD_CHECK_STEPS 4
+#define COSA_GRAD_CHECK_G2 0
+#define COSA_GRAD_CHECK_W2 1
+#define COSA_GRAD_CHECK_S 2
+#define COSA_GRAD_CHECK_FLAGS 3
+#define COSA_GRAD_CHECK_T 4
+#define COSA_GRAD_CHECK_LOSS 8
+#define COSA_GRAD_CHECK_BAD_G 33
+#define COSA_GRAD_CHECK_BAD_W 34
+#define COSA_GRAD_CHECK_FLAG_ZERO_GRAD 1   /* G2 == 0 (or the direction is empty)                     */
+#define COSA_GRAD_CHECK_FLAG_BAD_GRAD 2    /* a non-finite gradient element or a non-finite G2        */
+#define COSA_GRAD_CHECK_FLAG_BAD_WEIGHT 4  /* a non-finite weight or a non-finite W2                  */
+#define COSA_GRAD_CHECK_FLAG_NO_STEP 8     /* rho sqrt(W2 / G2) is 0 or outside fp32                  */
+size_t cosa_grad_check_workspace_bytes(int n_chunks);
+int cosa_grad_check_norms(const void *table_host, const void *table_dev, int n_tensors, int n_chunks, int n_dirs, double rho,
+                          double *record, void *workspace, size_t workspace_bytes, void *stream);
+int cosa_grad_check_perturb(const void *table_host, const void *table_dev, int n_tensors, int n_chunks, int n_dirs, int dir,
+                            float c, int slot, double *record, void *workspace, size_t workspace_bytes, void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
