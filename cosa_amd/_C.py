@@ -208,6 +208,9 @@ _SIGS.update({
     # per-image evaluation counters (csrc/image_scores_kernels.hip)
     "cosa_image_scores_words": (c_size_t, [c_int, c_int]),
     "cosa_image_scores": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_size_t, c_int, c_void_p, c_void_p]),
+    # the same row over band pixels, Boundary IoU (csrc/boundary_scores_kernels.hip)
+    "cosa_boundary_scores_words": (c_size_t, [c_int, c_int]),
+    "cosa_boundary_scores": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     # label-free export (csrc/predict_kernels.hip)
     "cosa_predict_classes": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cosa_export_overlay": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -107,6 +107,11 @@ EXTRA = [
     ("image_scores", str2bool, False),       # every evaluate() of the run also counts each image's label maps against its ground truth on the
                                              # device and writes <output_dir>/<iteration>/image_scores_<s|t>.jsonl and iou_dic_<s|t>.pth (the
                                              # reference's iou_dic.pth); read them with tools/image_scores.py
+    # per-image Boundary IoU counters; off: nothing changes
+    ("boundary_scores", str2bool, False),    # every evaluate() of the run also counts the same maps over the pixels within d of each map's own
+                                             # contours and writes <output_dir>/<iteration>/boundary_scores_<s|t>.jsonl (the same format)
+    ("boundary_ratio", float, 0.02),         # d = max(1, round(ratio * the image's diagonal)), in (0, 1)
+    ("boundary_d", int, 0),                  # a fixed d in pixels, 1..64; 0: use the ratio
 ]
 
 

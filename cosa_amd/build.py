@@ -55,6 +55,8 @@ SOURCES = {
     "act_stats_kernels.hip": EXACT,
     # per-image evaluation counters: integer byte work
     "image_scores_kernels.hip": EXACT,
+    # the same row over band pixels (Boundary IoU): integer byte work through LDS tiles
+    "boundary_scores_kernels.hip": EXACT,
     # label-free export: the class row from the logits (comparisons only) and the overlay (x * std + mean rounded twice, integer blend)
     "predict_kernels.hip": EXACT,
     "grad_check_kernels.hip": EXACT,      # (--grad_check_iters: w + fl32(s g) in two roundings, double sums in a fixed order)

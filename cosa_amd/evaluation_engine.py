@@ -66,10 +66,14 @@ class _GraphedCamSeg:
 
 
 def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=False, epoch=None, threshold_filters=None, getcrf=False,
-             s_or_t='t', get_camiou=False, isfinal=False, class_list=None, use_graph=True, eval_group=4, image_scores=None):
+             s_or_t='t', get_camiou=False, isfinal=False, class_list=None, use_graph=True, eval_group=4, image_scores=None,
+             boundary_scores=None):
     """`image_scores`: None (default) adds nothing.  A directory, or True for args.output_dir/<epoch, five digits>/, scores every label map
     this call produces against the ground truth per image on the device (evaluation.ImageScores: one launch per image, one copy at the
-    end) and has rank 0 write image_scores_<s_or_t>.jsonl and iou_dic_<s_or_t>.pth there."""
+    end) and has rank 0 write image_scores_<s_or_t>.jsonl and iou_dic_<s_or_t>.pth there.
+    `boundary_scores`: None or False (default) adds nothing.  A directory or True, as above: the same maps, counted over the pixels within
+    d of each map's own contours (evaluation.BoundaryScores: Boundary IoU; d from args.boundary_ratio, default 0.02 of the image's diagonal,
+    or a fixed args.boundary_d > 0), into boundary_scores_<s_or_t>.jsonl.  Independent of `image_scores`."""
     if save_result or save_rawcam:
         raise NotImplementedError("evaluate: save_result / save_rawcam (image dumps) are not part of the device path of evaluate(); "
                                   "files are written by evaluation_engine.export_predictions / python -m cosa_amd.predict")
@@ -94,6 +98,14 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
         except TypeError:
             capacity = 64
         scores = evaluation.ImageScores(nc, list(meters), [m.pseudo for m in meters.values()], capacity, device)
+    bscores, bscore_meta = None, []                   # the same maps over band pixels (off: nothing is built)
+    if boundary_scores is not None and boundary_scores is not False:
+        try:
+            capacity = len(data_loader)
+        except TypeError:
+            capacity = 64
+        bscores = evaluation.BoundaryScores(nc, list(meters), [m.pseudo for m in meters.values()], capacity, device,
+                                            ratio=getattr(args, "boundary_ratio", 0.02), d=getattr(args, "boundary_d", 0))
     ap_sum = torch.zeros(2, device=device, dtype=torch.float64)          # sums of per-batch mean AP (cls, cls_aux) ...
     ap_cnt = 0                                                           # ... over the batches (AverageMeter semantics, :86-92)
     was_training = model.training
@@ -153,6 +165,9 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
             if scores is not None:                    # every map of this image exists: one launch (per eight maps), no host wait
                 scores.add(len(score_meta), gt, [maps[k] for k in meters])
                 score_meta.append(meta + (int(size[0]), int(size[1])))
+            if bscores is not None:
+                bscores.add(len(bscore_meta), gt.reshape(size), [maps[k].reshape(size) for k in meters])
+                bscore_meta.append(meta + (int(size[0]), int(size[1])))
 
     with torch.no_grad():
         group = []
@@ -185,6 +200,13 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
         local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(torch.as_tensor(cl).reshape(-1)).reshape(-1) + 1).tolist(),
                                                             rows[k])) for k, (nm, cl, h, w) in enumerate(score_meta)]
         score_records = evaluation.gather_records(local)
+    bscore_records = None
+    if bscores is not None:
+        world = dist.get_world_size() if distributed else 1
+        rows = bscores.rows(len(bscore_meta))
+        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(torch.as_tensor(cl).reshape(-1)).reshape(-1) + 1).tolist(),
+                                                            rows[k], bscores.widths[k])) for k, (nm, cl, h, w) in enumerate(bscore_meta)]
+        bscore_records = evaluation.gather_records(local)
     if heads_before is not None:
         net.batch_invariant_heads = heads_before
         net.decoder.batch_invariant = heads_before
@@ -206,6 +228,13 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
             a = evaluation.assist_from_row(rec["row"], nc, vd, cl)
             iou_dic[rec["name"]] = {k: (float(v) if k in ("miou", "wmiou") else v) for k, v in a.items()}
         torch.save(iou_dic, out_dir / f"iou_dic_{s_or_t}.pth")
+    if bscores is not None:
+        out_dir = Path(args.output_dir) / str(epoch).zfill(5) if boundary_scores is True else Path(boundary_scores)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        settings = {"maps": bscores.map_names, "pseudo": bscores.pseudo_flags, "num_classes": nc, "epoch": epoch, "s_or_t": s_or_t,
+                    "world_size": dist.get_world_size() if distributed else 1, "checkpoint": getattr(args, "checkpoint", None),
+                    "boundary": bscores.settings()}
+        evaluation.write_score_file(out_dir / f"boundary_scores_{s_or_t}.jsonl", settings, bscore_records)
     cam_score, cam_aux_score, seg_vd_score = meters["cam"].scores(), meters["cam_aux"].scores(), meters["seg_vd"].scores()
     metrics, names = [cam_score, cam_aux_score, seg_vd_score], ["CAM", "aux_CAM", "Seg_vd"]
     if isfinal:
@@ -288,7 +317,8 @@ def _sharded(data_loader, rank, world):
 
 
 def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=False, high_thre=None, low_thre=None, eval_group=4,
-                       use_graph=True, writers=4, settings=None, scores=False, classes=None, cls_thre=0.5, cls_min=1, overlay_alpha=0.5):
+                       use_graph=True, writers=4, settings=None, scores=False, classes=None, cls_thre=0.5, cls_min=1, overlay_alpha=0.5,
+                       boundary=False, boundary_ratio=0.02, boundary_d=None):
     """Write the predictions of `model` over `data_loader` (items `(name, image [1,3,H,W], labels, cls_label [1,C])` as the evaluation
     loaders give them; an item without a label row -- `cls_label` None or not 2-D, the `test` stage -- can only give `seg`) into
     `out_dir` (layout: utils/export_io.py).  The forward is evaluate()'s: resize to crop_size, the captured multi-scale pass, groups of
@@ -299,6 +329,9 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     `scores=True` (items must carry their ground-truth map as third element): every uint8 product of an image -- seg, pseudo*, pseudo*_par,
     seg_crf -- is scored against it straight from the device record (evaluation.ImageScores; pseudo* maps with pseudo=1), rank 0 writes
     `scores.jsonl` and the result gains "scores": {product: {"miou", "labelled"}}; off: nothing changes.
+    `boundary=True` (independent of `scores`, the same demands on the items): the same maps counted over the pixels within d of each map's
+    own contours (evaluation.BoundaryScores; `boundary_ratio` of the image's diagonal or a fixed `boundary_d`), rank 0 writes
+    `boundary_scores.jsonl`, the result gains "boundary": {product: {"miou"}} and the manifest the settings.
     `classes`: where an image's class row comes from.  None (default): what the items carry -- their row, or none
     (`seg` only).  "given": the same, but an item without a row is an error.  "none": no row even where the items carry one.  "predicted":
     the model's own head -- per group one `seg_helper.predict_classes` launch on the pass's `cls_final` logits (`cls_thre`, `cls_min`) and
@@ -353,6 +386,17 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         except TypeError:
             capacity = 64
         table = evaluation.ImageScores(args.num_classes, score_names, [p.startswith("pseudo") for p in score_names], capacity, device)
+    band_names = [p for p in products if p in SCORED_PRODUCTS] if boundary else []
+    btable, bscore_meta = None, []
+    if boundary:
+        if not band_names:
+            raise ValueError(f"export_predictions: boundary=True needs a label-map product (one of {list(SCORED_PRODUCTS)}), got {list(products)}")
+        try:
+            capacity = len(data_loader) // world + 1
+        except TypeError:
+            capacity = 64
+        btable = evaluation.BoundaryScores(args.num_classes, band_names, [p.startswith("pseudo") for p in band_names], capacity, device,
+                                           ratio=boundary_ratio, d=boundary_d)
     was_training = model.training
     model.eval()
     net = model.module if hasattr(model, "module") else model
@@ -451,6 +495,12 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 offs = dict(seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0], seg_crf=crf_off)
                 table.add(len(score_meta), gt, [slot.dev[offs[p]:offs[p] + H * W] for p in score_names])
                 score_meta.append((name, cls_host if cls_host is not None or not predicted else torch.from_numpy(rows_h[i]), H, W))
+            if btable is not None:
+                if item_mask != mask or gt is None or gt.numel() != H * W:
+                    raise ValueError(f"export_predictions: boundary=True needs the label row and a ground-truth map of the image's size ({name!r})")
+                offs = dict(seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0], seg_crf=crf_off)
+                btable.add(len(bscore_meta), gt.reshape(H, W), [slot.dev[offs[p]:offs[p] + H * W].view(H, W) for p in band_names])
+                bscore_meta.append((name, cls_host if cls_host is not None or not predicted else torch.from_numpy(rows_h[i]), H, W))
             slot.host[:total].copy_(slot.dev[:total], non_blocking=True)          # the one device-to-host copy of the image
             slot.event.record()
             slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off, ov_off))
@@ -472,7 +522,7 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 cls_dev = cls_label.to(device, non_blocking=True).float() if use_cls else None
                 img_org = img_org.to(device, non_blocking=True)
                 inputs = F.interpolate(img_org, size=[args.crop_size, args.crop_size], mode='bilinear', align_corners=False)
-                gts = labels.to(device, non_blocking=True).to(torch.uint8) if scores and torch.is_tensor(labels) else None
+                gts = labels.to(device, non_blocking=True).to(torch.uint8) if (scores or boundary) and torch.is_tensor(labels) else None
                 for i in range(inputs.shape[0]):
                     group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if use_cls else None, int(k_lives[i]),
                                   img_org[i:i + 1], gts[i] if gts is not None and gts.dim() == 3 else None, cls_label[i] if has_cls else None))
@@ -516,6 +566,20 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                                          "checkpoint": (settings or {}).get("checkpoint")}, records)
             ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), args.num_classes) if records else []
             score_summary = {p: {"miou": evaluation.nan_to_none(d["miou"]), "labelled": evaluation.nan_to_none(d["labelled"])} for p, d in zip(score_names, ds)}
+    band_summary = None
+    if btable is not None:
+        rows = btable.rows(len(bscore_meta))
+        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(cl.reshape(-1)).reshape(-1) + 1).tolist(), rows[k],
+                                                            btable.widths[k])) for k, (nm, cl, h, w) in enumerate(bscore_meta)]
+        records = evaluation.gather_records(local)
+        if rank == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            evaluation.write_score_file(os.path.join(out_dir, "boundary_scores.jsonl"),
+                                        {"maps": band_names, "pseudo": btable.pseudo_flags, "num_classes": args.num_classes, "epoch": None,
+                                         "s_or_t": (settings or {}).get("s_or_t"), "world_size": world,
+                                         "checkpoint": (settings or {}).get("checkpoint"), "boundary": btable.settings()}, records)
+            ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), args.num_classes) if records else []
+            band_summary = {p: {"miou": evaluation.nan_to_none(d["miou"])} for p, d in zip(band_names, ds)}
     class_summary = None
     if predicted:                                   # gathered as the score records are: dataset order, rank 0 writes
         records = evaluation.gather_records(class_records)
@@ -540,12 +604,16 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 info["classes_vs_given"] = class_summary
         if overlay:
             info["overlay_alpha"] = float(overlay_alpha)
+        if btable is not None:
+            info["boundary"] = btable.settings()
         info.update(settings or {})
         export_io.write_manifest_file(out_dir, info, images)
     res = {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,
            "bytes_written": writer.bytes_written}
     if scores:
         res["scores"] = score_summary
+    if boundary:
+        res["boundary"] = band_summary
     if predicted:
         res["class_wait_seconds"] = class_wait
         if class_summary is not None:

@@ -27,6 +27,7 @@ from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
 from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher
+from .utils import evaluation
 from .utils import grad_check as gcheck
 from .utils import torch_helper
 
@@ -88,6 +89,7 @@ def check_supported(args):
                                                  (args.voc12_root if args.dataset == 'VOC12' else args.coco_root)):
         raise ValueError("--gt_stats true needs the ground-truth maps of the training images: give the dataset root (--voc12_root / "
                          "--coco_root: its SegmentationClassAug / SegmentationClass/train2014) or --gt_dir")
+    evaluation.check_boundary_settings(getattr(args, "boundary_ratio", 0.02), getattr(args, "boundary_d", 0))      # or a ValueError
     for n in notes:
         print("note:", n, flush=True)
 
@@ -240,6 +242,8 @@ def main(args):
                 log(line)
         if (n_iter + 1) % args.eval_iters == 0:                                   # main.py:313-383
             score_kw = {"image_scores": True} if args.image_scores else {}           # (off: the calls as ever)
+            if getattr(args, "boundary_scores", False):
+                score_kw["boundary_scores"] = True
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,
                              threshold_filters=args.eval_threshold_filters, **score_kw)
             if is_main:
@@ -295,7 +299,8 @@ def finaleval(args):
     torch_helper.load_best(model, args.bestseg_path, strict=True)
     model = model.to(device)
     res = evaluate(model, build_test_loader(args), args, df=None, epoch='best1', isfinal=True, getcrf=True,   # main.py:414-425
-                   threshold_filters=None, **({"image_scores": output_dir / "best1"} if getattr(args, "image_scores", False) else {}))
+                   threshold_filters=None, **({"image_scores": output_dir / "best1"} if getattr(args, "image_scores", False) else {}),
+                   **({"boundary_scores": output_dir / "best1"} if getattr(args, "boundary_scores", False) else {}))
     if getattr(args, "rank", 0) == 0:
         print('Final Model Result:\n' + res[0], flush=True)
         with (output_dir / "log_val.txt").open("a") as f:

@@ -2,7 +2,7 @@
 
     python -m cosa_amd.predict NAME --checkpoint best_seg.pth --dataset VOC12 --voc12_root $VOC --split val|test|train|train_aug \
         --out DIR --what seg[,pseudo,pseudo_aux,pseudo_par,pseudo_aux_par,rawcam,rawcam_aux] [--crf] [--high_thre H --low_thre L] [--writers N] \
-        [--scores]
+        [--scores] [--boundary [--boundary_ratio R | --boundary_d N]]
 
 Segmentation PNGs of `val` / `test` (what the VOC evaluation server takes), pseudo-label PNGs of `train_aug` / `train` for a second-stage
 network (`pseudo`: thresholds only; `pseudo_par`: refined by PAR(num_iter=10, dilations=[1,2,4,8,12,24]) at `--par_downscale` 2 or 0, the
@@ -13,6 +13,9 @@ Under `torchrun` the images are sharded over the ranks (`index % world == rank`)
 `manifest.json` last.  Prints the engine's result as one JSON line.  `--scores` (splits with ground-truth maps on disk: val, train,
 train_aug) also reads each image's mask, scores every exported label map against it on the device and writes `scores.jsonl` (per-image
 integer counters; read it with tools/image_scores.py); the result line gains the products' mIoU and labelled share.
+`--boundary` (the same splits, with or without `--scores`) counts the same maps over the pixels within d of each map's own contours --
+Boundary IoU, d = `--boundary_ratio` (0.02) of the image's diagonal or a fixed `--boundary_d` -- into `boundary_scores.jsonl` (the same
+format); the result line gains the products' boundary mIoU and the manifest the settings.
 
 Any folder of pictures:
 
@@ -58,6 +61,9 @@ def get_parser():
     p.add_argument("--what", type=str, default="seg", help="comma-separated products out of " + ", ".join(PRODUCTS))
     p.add_argument("--crf", action="store_true", help="also write seg_crf/ (dense-CRF post-processing, as finaleval scores it)")
     p.add_argument("--scores", action="store_true", help="score every exported label map against the ground-truth mask: scores.jsonl")
+    p.add_argument("--boundary", action="store_true",
+                   help="Boundary IoU counters of every exported label map against the ground-truth mask: boundary_scores.jsonl "
+                        "(--boundary_ratio of the diagonal, or a fixed --boundary_d)")
     p.add_argument("--writers", type=int, default=4, help=f"PNG / npy writer threads (1..{MAX_WRITERS})")
     p.add_argument("--eval_group", type=int, default=4)
     p.add_argument("--trust_checkpoint", action="store_true",
@@ -79,6 +85,8 @@ def parse(argv=None):
             parser.error("--images replaces the data set's split: give one of --images and --split")
         if args.scores:
             parser.error("--scores needs ground-truth maps: --images has none")
+        if args.boundary:
+            parser.error("--boundary needs ground-truth maps: --images has none")
         if args.classes == "given":
             parser.error("--classes given: --images has no image-level label rows (use predicted or none)")
         try:
@@ -105,6 +113,16 @@ def parse(argv=None):
         parser.error("--scores needs ground-truth maps: --split test has none")
     if args.scores and not (args.crf or any(w in ("seg",) or w.startswith("pseudo") for w in what)):
         parser.error(f"--scores needs a label-map product (seg, pseudo*, --crf), got --what {args.what}")
+    if args.boundary and args.split == "test":
+        parser.error("--boundary needs ground-truth maps: --split test has none")
+    if args.boundary and not (args.crf or any(w in ("seg",) or w.startswith("pseudo") for w in what)):
+        parser.error(f"--boundary needs a label-map product (seg, pseudo*, --crf), got --what {args.what}")
+    if args.boundary:
+        from .utils import evaluation
+        try:
+            evaluation.check_boundary_settings(args.boundary_ratio, args.boundary_d)
+        except ValueError as e:
+            parser.error(str(e))
     if not 1 <= args.writers <= MAX_WRITERS:
         parser.error(f"--writers must be in 1..{MAX_WRITERS} (got {args.writers})")
     if args.usepar:
@@ -202,12 +220,14 @@ def main(argv=None):
     if args.image_items is not None:
         dataset = _ImageFiles(args.image_items)
     else:
-        dataset = build_dataset(args)             # (its items read the ground-truth mask: only --scores wants it)
-        dataset = dataset if args.scores else _ImagesOnly(dataset)
+        dataset = build_dataset(args)             # (its items read the ground-truth mask: only --scores / --boundary want it)
+        dataset = dataset if args.scores or args.boundary else _ImagesOnly(dataset)
     loader = DataLoader(dataset=dataset, batch_size=1, shuffle=False, num_workers=args.num_workers, pin_memory=False)
     settings = {"checkpoint": os.path.abspath(args.checkpoint), "checkpoint_epoch": ckpt.get("epoch"), "s_or_t": ckpt.get("s_or_t"),
                 "dataset": args.dataset, "split": args.split, "crf": bool(args.crf)}
     extra = {"scores": True} if args.scores else {}
+    if args.boundary:
+        extra.update({"boundary": True, "boundary_ratio": args.boundary_ratio, "boundary_d": args.boundary_d})
     if args.images is not None:
         settings.update({"split": None, "images": os.path.abspath(args.images)})
     if args.classes is not None or args.images is not None:           # unset on a split: the engine's defaults, nothing new in the manifest

@@ -6,6 +6,7 @@ is the streaming form the evaluation engine uses: device-resident accumulation o
 ranks at the end (the reference gathers every prediction map on rank 0 through temp files, evaluation_engine.py:203-216).
 """
 import json
+import math
 import warnings
 
 import numpy as np
@@ -96,29 +97,38 @@ class ImageScores:
     More than eight maps go in chunks of eight, each launch re-reading the ground truth; a chunk's launch writes its own [n, n_valid]
     in front of its maps, so the table keeps one such pair per chunk and `rows()` drops all but the first."""
 
+    _entry = "cosa_image_scores"                  # the C entry that fills a chunk's words; `<entry>_words` sizes them
+
     def __init__(self, num_classes, map_names, pseudo_flags, capacity, device=None):
+        who = type(self).__name__
         device = torch.device(device if device is not None else "cuda")
         if device.type != "cuda":
-            raise RuntimeError("ImageScores counts on the GPU (cosa_image_scores); no CPU path")
+            raise RuntimeError(f"{who} counts on the GPU ({self._entry}); no CPU path")
         self.num_classes, self.map_names = int(num_classes), [str(m) for m in map_names]
         self.pseudo_flags = [int(bool(p)) for p in pseudo_flags]
         if len(self.pseudo_flags) != len(self.map_names) or not self.map_names or len(set(self.map_names)) != len(self.map_names):
-            raise ValueError("ImageScores: one pseudo flag per map, at least one map, every name once")
+            raise ValueError(f"{who}: one pseudo flag per map, at least one map, every name once")
         self._chunks, off = [], 0                 # (first map, maps, word offset in the table's row)
         for first in range(0, len(self.map_names), MAX_MAPS):
             k = min(MAX_MAPS, len(self.map_names) - first)
-            words = _C.lib().cosa_image_scores_words(self.num_classes, k)
+            words = getattr(_C.lib(), self._entry + "_words")(self.num_classes, k)
             if not words:
-                _C.check(1, "cosa_image_scores_words")
+                _C.check(1, self._entry + "_words")
             self._chunks.append((first, k, off))
             off += words
         self.table = torch.zeros((max(int(capacity), 1), off), device=device, dtype=torch.int64)
 
+    def _launch(self, gt, ptrs, first, k, row, stream):
+        """one chunk of maps of one image into the words at `row`"""
+        return _C.lib().cosa_image_scores(_C.ptr(gt), ptrs, _C.int_array(self.pseudo_flags[first:first + k]), k, gt.numel(), self.num_classes,
+                                          row, stream)
+
     def add(self, index, gt, preds):
         """score the uint8 device maps `preds` (one per map name) of one image against its uint8 ground truth into row `index`"""
+        who = type(self).__name__
         index = int(index)
         if len(preds) != len(self.map_names):
-            raise ValueError(f"ImageScores.add: {len(self.map_names)} maps expected, got {len(preds)}")
+            raise ValueError(f"{who}.add: {len(self.map_names)} maps expected, got {len(preds)}")
         if index < 0:
             raise IndexError(index)
         if index >= self.table.shape[0]:             # a loader that did not tell its length: grow on the device, no host wait
@@ -130,14 +140,14 @@ class ImageScores:
         maps = []
         for p in preds:
             if p.dtype != torch.uint8 or gt.dtype != torch.uint8 or p.numel() != n:
-                raise ValueError("ImageScores.add: uint8 maps of the ground truth's size")
+                raise ValueError(f"{who}.add: uint8 maps of the ground truth's size")
             maps.append(p.contiguous())
         gt = gt.contiguous()
-        fn, st = _C.lib().cosa_image_scores, _C.stream_ptr()
+        st = _C.stream_ptr()
         for first, k, off in self._chunks:
             ptrs = (_C.c_void_p * k)(*[m.data_ptr() for m in maps[first:first + k]])
             row = _C.c_void_p(self.table.data_ptr() + 8 * (index * self.table.shape[1] + off))
-            _C.check(fn(_C.ptr(gt), ptrs, _C.int_array(self.pseudo_flags[first:first + k]), k, n, self.num_classes, row, st), "cosa_image_scores")
+            _C.check(self._launch(gt, ptrs, first, k, row, st), self._entry)
 
     def rows(self, count=None):
         """-> numpy [count or capacity, 2 + maps * num_classes * 4] int64: the single device-to-host copy"""
@@ -148,6 +158,57 @@ class ImageScores:
         for _, k, off in self._chunks:
             parts.append(t[:, off + 2:off + 2 + k * self.num_classes * 4])
         return np.ascontiguousarray(np.concatenate(parts, axis=1))
+
+
+MAX_BOUNDARY_D = 64                               # cosa_boundary_scores' envelope: 2 % of a 3200-pixel diagonal
+
+
+def boundary_width(h, w, ratio=0.02, d=None):
+    """the band's width in pixels for an h x w image: a fixed `d`, or `ratio` of the diagonal (Boundary IoU: 0.02), at least 1"""
+    if d:
+        return int(d)
+    return max(1, int(round(ratio * math.sqrt(h * h + w * w))))
+
+
+def check_boundary_settings(ratio, d):
+    """-> (ratio, fixed d or None) or a ValueError: a ratio in (0, 1), a fixed d in 1..64 (0 / None: use the ratio)"""
+    ratio, d = float(ratio), int(d or 0)
+    if not 0.0 < ratio < 1.0:
+        raise ValueError(f"boundary scores: the ratio must be in (0, 1) (got {ratio})")
+    if not 0 <= d <= MAX_BOUNDARY_D:
+        raise ValueError(f"boundary scores: a fixed d must be in 0..{MAX_BOUNDARY_D}, 0 for the ratio (got {d})")
+    return ratio, (d or None)
+
+
+class BoundaryScores(ImageScores):
+    """ImageScores' table over BAND pixels (cosa_boundary_scores): row `index` = [n, n_valid, then for map m, class
+    c: I, P, G, A] counted over the pixels within `d` of each map's own contours; Boundary IoU of a class is I / (P + G - I), the dataset
+    figure `dataset_scores` of the rows.  `add` takes 2-D maps, forms d = boundary_width(H, W, ratio, d) on the host from the shape alone
+    and launches; `widths` keeps each row's d for the files.  `pseudo_flags` are recorded for the files only."""
+    _entry = "cosa_boundary_scores"
+
+    def __init__(self, num_classes, map_names, pseudo_flags, capacity, device=None, ratio=0.02, d=None):
+        self.ratio, self.d = check_boundary_settings(ratio, d)
+        self.widths = {}                          # row index -> the d its maps were scored with
+        super().__init__(num_classes, map_names, pseudo_flags, capacity, device)
+
+    def _launch(self, gt, ptrs, first, k, row, stream):
+        return _C.lib().cosa_boundary_scores(_C.ptr(gt), ptrs, k, self._shape[0], self._shape[1], self._width, self.num_classes, row, stream)
+
+    def add(self, index, gt, preds):
+        if gt.dim() != 2 or any(p.dim() != 2 or p.shape != gt.shape for p in preds):
+            raise ValueError("BoundaryScores.add: 2-D uint8 maps [H, W] of one size")
+        self._shape = (int(gt.shape[0]), int(gt.shape[1]))
+        width = boundary_width(*self._shape, ratio=self.ratio, d=self.d)
+        self._width = min(width, max(self._shape))                       # no pixel is interior from max(H, W) on: the same row
+        if self._width > MAX_BOUNDARY_D:
+            raise ValueError(f"BoundaryScores.add: d = {width} for a {self._shape[0]} x {self._shape[1]} image is beyond the kernel's {MAX_BOUNDARY_D}")
+        super().add(index, gt, preds)
+        self.widths[int(index)] = width
+
+    def settings(self):
+        """the `boundary` entry of a score file's settings line"""
+        return {"ratio": self.ratio, "d": self.d}
 
 
 def split_row(row, num_classes):
@@ -211,9 +272,13 @@ def nan_to_none(x):
     return None if x != x else x                 # NaN is written as null
 
 
-def score_record(name, h, w, present, row):
-    """one image of a score file (host data only): `present` = the class ids of cls_label (1-based), `row` its counters"""
-    return {"name": str(name), "h": int(h), "w": int(w), "present": [int(c) for c in present], "row": np.asarray(row, dtype=np.int64)}
+def score_record(name, h, w, present, row, d=None):
+    """one image of a score file (host data only): `present` = the class ids of cls_label (1-based), `row` its counters; `d`: the band's
+    width where the row is a boundary row (BoundaryScores), else the record has no such key"""
+    rec = {"name": str(name), "h": int(h), "w": int(w), "present": [int(c) for c in present], "row": np.asarray(row, dtype=np.int64)}
+    if d is not None:
+        rec["d"] = int(d)
+    return rec
 
 
 def merge_records(shards):
@@ -240,8 +305,8 @@ def write_score_file(path, settings, records):
             a = assist_from_counts(cnt[m][:, 0], cnt[m][:, 3], cnt[m][:, 2], n, cls_label)
             per_map[name] = {"classes": {str(c): [int(v) for v in cnt[m][c]] for c in range(nc) if cnt[m][c].any()},
                              "miou": nan_to_none(a["miou"]), "wmiou": nan_to_none(a["wmiou"])}
-        lines.append(json.dumps({"name": rec["name"], "h": rec["h"], "w": rec["w"], "n": n, "n_valid": n_valid, "present": rec["present"],
-                                 "maps": per_map}))
+        lines.append(json.dumps(dict({"name": rec["name"], "h": rec["h"], "w": rec["w"], "n": n, "n_valid": n_valid, "present": rec["present"],
+                                      "maps": per_map}, **({"d": rec["d"]} if "d" in rec else {}))))
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
 
@@ -260,7 +325,7 @@ def read_score_file(path):
         for m, name in enumerate(maps):
             for c, v in d["maps"][name]["classes"].items():
                 cnt[m, int(c)] = v
-        records.append(score_record(d["name"], d["h"], d["w"], d["present"], row))
+        records.append(score_record(d["name"], d["h"], d["w"], d["present"], row, d.get("d")))
     return settings, records
 
 

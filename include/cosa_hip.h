@@ -740,6 +740,27 @@ int cosa_image_scores(const uint8_t *gt, const uint8_t *const *preds, const int 
                       int num_classes, unsigned long long *row, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Per-image Boundary IoU counters (Cheng et al., CVPR 2021): cosa_image_scores' row over BAND pixels.
+ * A label map is uint8 [H, W]; a value < num_classes is a class, any other value (255 included) is no class.  For d >= 1 a
+ * class pixel is INTERIOR iff its whole (2d+1) x (2d+1) window lies inside the image and every pixel of it holds the pixel's
+ * own label; a class pixel that is not interior is a BAND pixel of its class; a pixel that is no class is in no band (d
+ * erosions of the class's mask on a zero border, mask minus eroded, for every class at once).  One call scores ONE image: gt
+ * and n_maps maps of it ADD into a caller-zeroed row of cosa_boundary_scores_words(num_classes, n_maps) uint64 words
+ *   row = [ n, n_valid, then for map m, class c: I, P, G, A ]            (= cosa_image_scores_words)
+ * n = H * W, n_valid = #{gt < num_classes}.  A pixel is counted for map m under cosa_image_scores' rule on the maps
+ * themselves: gt < num_classes and pred_m < num_classes.  Over counted pixels I = #{gt band c and pred band c},
+ * P = #{pred band c}, G = #{gt band c}; A = #{pred band c} over all n pixels.  Boundary IoU of class c is I / (P + G - I).
+ * Any d >= max(H, W) leaves no pixel interior: the row is then cosa_image_scores' row word for word.  Integer atomics only:
+ * the row holds the same bytes on every run and for any grid.  preds is a HOST array of n_maps device pointers of any byte
+ * alignment; the maps are dense H x W.  Envelope: gt, preds, every preds[m] and row non-NULL, row 8-byte aligned,
+ * 1 <= num_classes <= 255, 1 <= n_maps <= COSA_IMAGE_SCORES_MAX_MAPS, H, W >= 1, H * W < 2^32, 1 <= d <= 64; anything else is
+ * COSA_EINVAL, nothing is launched and the row is untouched.  One launch, no workspace, no host sync.
+ * ------------------------------------------------------------------------------------- */
+size_t cosa_boundary_scores_words(int num_classes, int n_maps);   /* uint64 words of one row; 0 on bad arguments */
+int cosa_boundary_scores(const uint8_t *gt, const uint8_t *const *preds, int n_maps, int H, int W, int d,
+                         int num_classes, unsigned long long *row, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Export: every file product of ONE image, at the image's own (generally non-square) H x W, in one
  * packed record, from what multi_scale_camsegv3 returns for it: cam / cam_aux [C,S,S], seg [C+1,S,S], cls_label [C] or
  * NULL (no image-level labels: seg only, plain argmax).  `what` is a mask of COSA_EXPORT_* bits:

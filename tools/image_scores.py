@@ -1,5 +1,7 @@
 """Read per-image score files: `image_scores_<s|t>.jsonl` of `--image_scores true` / evaluate(image_scores=...) and
-`scores.jsonl` of `python -m cosa_amd.predict --scores`.  numpy only, no GPU.
+`scores.jsonl` of `python -m cosa_amd.predict --scores`; and the boundary files in the same format:
+`boundary_scores_<s|t>.jsonl` of `--boundary_scores true` and `boundary_scores.jsonl` of `predict --boundary`, whose counters are taken
+over the pixels within d of each map's own contours, so that every IoU below is then a Boundary IoU.  numpy only, no GPU.
 
     python tools/image_scores.py summary FILE [--json]
     python tools/image_scores.py worst FILE --map seg_vd [-n 20] [--json]
@@ -56,7 +58,7 @@ def _map_index(settings, name, path):
 
 
 def summary(path):
-    settings, names, counts, _ = read(path)
+    settings, names, counts, lines = read(path)
     total = counts.sum(axis=0)
     iu, _ = iou_from_counts(total)
     out = {"file": path, "images": len(names), "num_classes": int(settings["num_classes"]), "maps": {}}
@@ -64,6 +66,9 @@ def summary(path):
         valid = total[m, :, 2] > 0                       # the mean exactly as the confusion-matrix scores take it: nanmean over G > 0
         miou = float(np.nanmean(iu[m][valid])) if valid.any() else float("nan")
         out["maps"][name] = {"iou": [None if v != v else float(v) for v in iu[m]], "miou": None if miou != miou else miou}
+    if "boundary" in settings:                           # a boundary file: the band's settings and the widths the images were scored with
+        ds = sorted({int(d["d"]) for d in lines if "d" in d})
+        out["boundary"] = dict(settings["boundary"], d_min=ds[0] if ds else None, d_max=ds[-1] if ds else None)
     return out
 
 
@@ -137,6 +142,10 @@ def main(argv=None):
     if a.cmd == "summary":
         res = summary(a.file)
         text = [f"{a.file}: {res['images']} images"]
+        if "boundary" in res:
+            b = res["boundary"]
+            text[0] += (f", Boundary IoU: band of d = {b['d']} pixels" if b["d"] else f", Boundary IoU: band of {b['ratio']} of the diagonal") + \
+                f" (d {b['d_min']}..{b['d_max']})"
         for name, d in res["maps"].items():
             text.append(f"{name:>14s}  mIoU {_pct(d['miou'])}  | " + " ".join(_pct(v).strip() for v in d["iou"]))
     elif a.cmd == "worst":
