@@ -214,6 +214,9 @@ _SIGS.update({
     # label-free export (csrc/predict_kernels.hip)
     "cosa_predict_classes": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cosa_export_overlay": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # the CAM pictures of export (csrc/heat_kernels.hip)
+    "cosa_export_camheat": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "cosa_export_panel": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     # the --grad_check_iters check (csrc/grad_check_kernels.hip)
     "cosa_grad_check_workspace_bytes": (c_size_t, [c_int]),
     "cosa_grad_check_norms": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -59,7 +59,9 @@ SOURCES = {
     "boundary_scores_kernels.hip": EXACT,
     # label-free export: the class row from the logits (comparisons only) and the overlay (x * std + mean rounded twice, integer blend)
     "predict_kernels.hip": EXACT,
-    "grad_check_kernels.hip": EXACT,      # (--grad_check_iters: w + fl32(s g) in two roundings, double sums in a fixed order)
+    # the CAM heat maps and panels of export: x * std + mean and 255 * m each rounded once, integers from there
+    "heat_kernels.hip": EXACT,
+    "grad_check_kernels.hip": EXACT,     # (--grad_check_iters: w + fl32(s g) in two roundings, double sums in a fixed order)
 }
 
 

@@ -271,6 +271,7 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
 # ---------------------------------------------------------------------------------------------------------------------------------
 EXPORT_PRODUCTS = tuple(seg_helper.EXPORT_BITS)                   # seg, pseudo, pseudo_aux, rawcam, rawcam_aux, pseudo_par, pseudo_aux_par
 CAM_PRODUCTS = tuple(p for p in EXPORT_PRODUCTS if p != "seg")    # these need the image-level label row
+PICTURE_PRODUCTS = ("camheat", "camheat_aux", "panel")             # one RGB picture per present class, behind the record's slots (section 27)
 SCORED_PRODUCTS = ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par", "seg_crf")      # the uint8 label maps: scores=True
 
 
@@ -338,12 +339,26 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     one small copy that the loop waits for (k_live sizes the records); every product is then made as with a given row, rank 0 writes
     `classes.jsonl`, and where the items carry rows too the result gains "classes": predicted against given, from integer counts.
     `what` may also name `overlay`: the written `seg` map over the image (`overlay_alpha`), RGB bytes behind the record's other slots.
+    `camheat` / `camheat_aux` / `panel` (they need a class row): per present class the `rawcam` / `rawcam_aux` plane
+    as a heat map over the image, and the panel heat map | seg == class | ground truth == class | image (the ground-truth column where
+    the item carries a map of the image's size).  Their slots (`rawcam`, `rawcam_aux`; `seg` and `rawcam` for the panel) are computed even
+    where no file of them is asked for; the pictures lie behind the overlay's bytes and ride in the same copy.
     Returns {"images", "seconds", "img_per_s", "bytes_written"} of this process."""
     what = tuple(what)
     overlay = "overlay" in what
-    if what.count("overlay") > 1:
-        raise ValueError(f"export_predictions: `overlay` named twice in {list(what)}")
-    mask = seg_helper.export_what_mask(tuple(w for w in what if w != "overlay")) if what != ("overlay",) else 0
+    for extra in ("overlay",) + PICTURE_PRODUCTS:
+        if what.count(extra) > 1:
+            raise ValueError(f"export_predictions: `{extra}` named twice in {list(what)}")
+    pictures = tuple(p for p in PICTURE_PRODUCTS if p in what)
+    panel = "panel" in pictures
+    slot_names = tuple(w for w in what if w != "overlay" and w not in PICTURE_PRODUCTS)
+    mask = seg_helper.export_what_mask(slot_names) if slot_names or not what else 0
+    if "camheat" in pictures or panel:              # a picture shows the numbers of the rawcam slot: computed even where no .npy is asked for
+        mask |= seg_helper.EXPORT_BITS["rawcam"]
+    if "camheat_aux" in pictures:
+        mask |= seg_helper.EXPORT_BITS["rawcam_aux"]
+    if panel:
+        mask |= seg_helper.EXPORT_BITS["seg"]
     if overlay:                                     # the overlay shows the seg map: its slot is computed even where no seg file is asked for
         mask |= seg_helper.EXPORT_BITS["seg"]
         seg_helper.overlay_alpha256(overlay_alpha)  # [0, 1], or a ValueError before anything runs
@@ -413,19 +428,24 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         pack_host = torch.empty(gmax * (2 * C + 2), dtype=torch.float32).pin_memory()
         pack_event = torch.cuda.Event()
 
-    def host_products(slot, H, W, k_live, item_mask, crf_off, ov_off):
+    picture_names = export_io.class_names((settings or {}).get("dataset", getattr(args, "dataset", None)), C) if pictures else None
+
+    def host_products(slot, H, W, k_live, item_mask, crf_off, ov_off, pic_off):
         def get():
             slot.event.synchronize()                # in the writer thread: the loop itself never waits for a copy
             rec = slot.host.numpy()
             v = seg_helper.export_record_views(rec, C, H, W, k_live, item_mask)
             out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par") if p in v and p in products}
             for p in ("rawcam", "rawcam_aux"):
-                if p in v:
+                if p in v and p in products:
                     out[p] = (v[p], v[p + "_idx"])
             if crf_off is not None:
                 out["seg_crf"] = rec[crf_off:crf_off + H * W].reshape(H, W)
             if ov_off is not None:
                 out["overlay"] = rec[ov_off:ov_off + 3 * H * W].reshape(H, W, 3)
+            for p, (off, cols) in pic_off.items():  # one picture per present class, named by the class
+                idx = v["rawcam_aux_idx" if p == "camheat_aux" else "rawcam_idx"]
+                out[p] = (rec[off:off + 3 * k_live * H * cols * W].reshape(k_live, H, cols * W, 3), [picture_names[c] for c in idx])
             return out
         return get
 
@@ -470,8 +490,19 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 crf_off, total = nbytes, nbytes + ((H * W + 15) & ~15)
             if overlay:                             # behind every other slot, seg_crf included
                 ov_off, total = total, total + ((3 * H * W + 15) & ~15)
+            pic_off, heat_off = {}, {}              # the pictures: behind the overlay; without a present class there is none
+            if pictures and k_live:
+                heat_bytes = (3 * k_live * H * W + 15) & ~15
+                for p in ("camheat", "camheat_aux"):
+                    if p in pictures:
+                        pic_off[p], heat_off[p], total = (total, 1), total, total + heat_bytes
+                if panel:
+                    gt_panel = gt if gt is not None and gt.numel() == H * W else None
+                    cols = 4 if gt_panel is not None else 3
+                    pic_off["panel"], total = (total, cols), total + ((3 * k_live * H * cols * W + 15) & ~15)
+                    heat_off.setdefault("camheat", total)        # no camheat files: the panel's first column is made behind what is copied
             slot = slots[count % len(slots)]
-            slot.reserve(total)
+            slot.reserve(max([total] + [o + (3 * k_live * H * W) for o in heat_off.values()]))
             maps_mask = item_mask & seg_helper.EXPORT_MAPS_MASK
             if maps_mask:
                 seg_helper.export_maps(cams[i] if maps_mask & 0x0a else None, cams_aux[i] if maps_mask & 0x14 else None, seg_ps[i], cls_dev, (H, W),
@@ -483,6 +514,14 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
             if overlay:                             # the seg slot as just written, over the still normalised image (the CRF lines below rescale it in place)
                 seg_off = seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0]["seg"]
                 seg_helper.export_overlay(img_org, slot.dev[seg_off:seg_off + H * W], overlay_alpha, out=slot.dev[ov_off:ov_off + 3 * H * W])
+            if pic_off:                             # from the record's slots as just written, before the CRF lines rescale the image
+                dv = seg_helper.export_record_views(slot.dev, C, H, W, k_live, item_mask)
+                heat = {p: seg_helper.export_camheat(dv["rawcam" if p == "camheat" else "rawcam_aux"], img_org,
+                                                     out=slot.dev[o:o + 3 * k_live * H * W]) for p, o in heat_off.items()}
+                if panel:
+                    o, cols = pic_off["panel"]
+                    seg_helper.export_panel(heat["camheat"], dv["seg"], dv["rawcam_idx"], img_org, gt=gt_panel,
+                                            out=slot.dev[o:o + 3 * k_live * H * cols * W])
             if getcrf:                              # evaluate()'s Seg_crf lines
                 rs = F.interpolate(seg_ps[i:i + 1], size=(H, W), mode='bilinear', align_corners=False)
                 vd = seg_helper.seg_validation(rs, cls_dev).softmax(dim=1)[0]
@@ -503,7 +542,7 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 bscore_meta.append((name, cls_host if cls_host is not None or not predicted else torch.from_numpy(rows_h[i]), H, W))
             slot.host[:total].copy_(slot.dev[:total], non_blocking=True)          # the one device-to-host copy of the image
             slot.event.record()
-            slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off, ov_off))
+            slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off, ov_off, pic_off))
             count += 1
 
     t0 = time.perf_counter()
@@ -522,7 +561,7 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
                 cls_dev = cls_label.to(device, non_blocking=True).float() if use_cls else None
                 img_org = img_org.to(device, non_blocking=True)
                 inputs = F.interpolate(img_org, size=[args.crop_size, args.crop_size], mode='bilinear', align_corners=False)
-                gts = labels.to(device, non_blocking=True).to(torch.uint8) if (scores or boundary) and torch.is_tensor(labels) else None
+                gts = labels.to(device, non_blocking=True).to(torch.uint8) if (scores or boundary or panel) and torch.is_tensor(labels) else None
                 for i in range(inputs.shape[0]):
                     group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if use_cls else None, int(k_lives[i]),
                                   img_org[i:i + 1], gts[i] if gts is not None and gts.dim() == 3 else None, cls_label[i] if has_cls else None))
@@ -606,6 +645,8 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
             info["overlay_alpha"] = float(overlay_alpha)
         if btable is not None:
             info["boundary"] = btable.settings()
+        if pictures:
+            info["camheat"] = {"ramp": "jet-int", "panel_colour": list(seg_helper.PANEL_COLOUR)}
         info.update(settings or {})
         export_io.write_manifest_file(out_dir, info, images)
     res = {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,

@@ -31,7 +31,13 @@ for `test`, and `predicted` with `--images`.  Predicted rows go through the same
 unlabelled images, `test` keeps the class validation of `Seg_vd`, and `classes.jsonl` lists each image's classes, logits and
 probabilities.  On a labelled split `--classes predicted` may be combined with `--scores`; the result line then also compares the
 predicted rows with the given ones (exact-match share, micro precision / recall / F1).  `--what overlay` writes `overlay/<name>.png`:
-the `seg` map as written, in the VOC colours, blended over the image with weight `--overlay_alpha`."""
+the `seg` map as written, in the VOC colours, blended over the image with weight `--overlay_alpha`.
+
+The CAM pictures (they need a class row, given or predicted): `--what camheat` writes `cam/<name>_<class>.png`
+for every present class -- the class's `rawcam` plane as a jet heat map over the image, in exact integers -- `camheat_aux` the same for
+the auxiliary CAM into `camaux/`, and `panel` writes `merged/<name>_<class>.png`: heat map | the `seg` map's pixels of the class | the
+ground truth's (on `val` / `train`, where the masks are on disk; left out elsewhere) | the image.  `<class>` is the data set's class name
+with spaces as `_`, or the 1-based index where the head has another number of classes."""
 import json
 import os
 import sys
@@ -39,7 +45,7 @@ import sys
 from . import args as cosa_args
 from .utils.export_io import MAX_WRITERS
 
-PRODUCTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "pseudo_par", "pseudo_aux_par", "overlay")
+PRODUCTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "pseudo_par", "pseudo_aux_par", "overlay", "camheat", "camheat_aux", "panel")
 CLASS_SOURCES = ("given", "predicted", "none")
 SPLITS = ("val", "test", "train", "train_aug")
 
@@ -220,8 +226,9 @@ def main(argv=None):
     if args.image_items is not None:
         dataset = _ImageFiles(args.image_items)
     else:
-        dataset = build_dataset(args)             # (its items read the ground-truth mask: only --scores / --boundary want it)
-        dataset = dataset if args.scores or args.boundary else _ImagesOnly(dataset)
+        dataset = build_dataset(args)             # (its items read the ground-truth mask: only --scores / --boundary / panel want it)
+        wants_gt = args.scores or args.boundary or ("panel" in what and args.split in ("val", "train"))    # the panel's ground-truth column
+        dataset = dataset if wants_gt else _ImagesOnly(dataset)
     loader = DataLoader(dataset=dataset, batch_size=1, shuffle=False, num_workers=args.num_workers, pin_memory=False)
     settings = {"checkpoint": os.path.abspath(args.checkpoint), "checkpoint_epoch": ckpt.get("epoch"), "s_or_t": ckpt.get("s_or_t"),
                 "dataset": args.dataset, "split": args.split, "crf": bool(args.crf)}

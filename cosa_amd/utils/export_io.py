@@ -6,6 +6,10 @@ Pure numpy / PIL: nothing here touches the GPU.  `evaluation_engine.export_predi
     <out_dir>/seg|seg_crf|pseudo|pseudo_aux|pseudo_par|pseudo_aux_par/<name>.png
                                                             palette PNGs (mode P) with the PASCAL VOC colour map
     <out_dir>/overlay/<name>.png                            RGB PNGs: the written `seg` map painted over the image (cosa_export_overlay)
+    <out_dir>/cam|camaux/<name>_<class>.png                 RGB PNGs, one per present class: the main / auxiliary CAM plane as a heat map over
+                                                            the image (products camheat / camheat_aux; cosa_export_camheat)
+    <out_dir>/merged/<name>_<class>.png                     RGB PNGs, one per present class: heat map | seg == class | ground truth == class
+                                                            (where the item has one) | image (product panel; cosa_export_panel)
     <out_dir>/camraw|camraw_aux/<name>.npy                  a pickled dict {0-based class index: float32 [H,W]} (np.load(...,
                                                             allow_pickle=True).item()), as the reference's save_cam_npv2 writes it;
                                                             an image without any present class gets no file
@@ -26,6 +30,7 @@ MAX_WRITERS = 8                      # a GPU job has 16 CPUs: loader workers and
 PNG_PRODUCTS = ("seg", "seg_crf", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par")
 RGB_PRODUCTS = ("overlay",)
 NPY_DIRS = {"rawcam": "camraw", "rawcam_aux": "camraw_aux"}
+CLASS_RGB_DIRS = {"camheat": "cam", "camheat_aux": "camaux", "panel": "merged"}      # one RGB PNG per present class; the reference's directory names
 IMAGE_SUFFIXES = (".jpg", ".jpeg", ".png")
 VOC_CLASSES = ("aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog", "horse", "motorbike",
                "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
@@ -42,6 +47,11 @@ def class_names(dataset, C):
     """the names of classes 1..C: the data set's own list when it has exactly C entries, else the 1-based indices as strings"""
     names = {"VOC12": VOC_CLASSES, "COCO": COCO_CLASSES}.get(dataset, ())
     return list(names) if len(names) == int(C) else [str(c + 1) for c in range(int(C))]
+
+
+def class_file_name(name, class_name):
+    """<name>_<class>: the file stem of a per-class picture; the class name with every space replaced by `_`"""
+    return f"{name}_{str(class_name).replace(' ', '_')}"
 
 
 def list_images(source):
@@ -181,12 +191,12 @@ class PredictionWriter:
     def __init__(self, out_dir, products, writers=4):
         self.out_dir = str(out_dir)
         self.writers = check_writers(writers)
-        unknown = [p for p in products if p not in PNG_PRODUCTS and p not in NPY_DIRS and p not in RGB_PRODUCTS]
+        unknown = [p for p in products if p not in PNG_PRODUCTS and p not in NPY_DIRS and p not in RGB_PRODUCTS and p not in CLASS_RGB_DIRS]
         if unknown:
             raise ValueError(f"unknown export products {unknown}")
         self.products = tuple(products)
         for p in self.products:
-            os.makedirs(os.path.join(self.out_dir, NPY_DIRS.get(p, p)), exist_ok=True)
+            os.makedirs(os.path.join(self.out_dir, NPY_DIRS.get(p, CLASS_RGB_DIRS.get(p, p))), exist_ok=True)
         self.pool = ThreadPoolExecutor(max_workers=self.writers, thread_name_prefix="cosa-export")
         self.lock = threading.Lock()
         self.bytes_written = 0
@@ -205,6 +215,10 @@ class PredictionWriter:
                     n += write_png(os.path.join(self.out_dir, key, name + ".png"), val)
                 elif key in RGB_PRODUCTS:
                     n += write_png_rgb(os.path.join(self.out_dir, key, name + ".png"), val)
+                elif key in CLASS_RGB_DIRS:
+                    pictures, names = val
+                    for picture, cls in zip(pictures, names):
+                        n += write_png_rgb(os.path.join(self.out_dir, CLASS_RGB_DIRS[key], class_file_name(name, cls) + ".png"), picture)
                 else:
                     raise ValueError(f"unknown export product {key!r}")
             with self.lock:
@@ -224,9 +238,11 @@ class PredictionWriter:
         self.futures = keep
 
     def submit(self, name, H, W, products, release=None):
-        """products: {product: uint8 [H,W]} / {"rawcam"|"rawcam_aux": (float32 [K,H,W], int [K])}, or a callable returning that dict (run
-        inside the job: the engine waits there for the record's copy).  The arrays must stay valid until the job is done; `release` is
-        called then, whether the job succeeded or not.  Returns the job's future."""
+        """products: {product: uint8 [H,W]} / {"rawcam"|"rawcam_aux": (float32 [K,H,W], int [K])} /
+        {"camheat"|"camheat_aux"|"panel": (uint8 [k,H,cols*W,3], class names [k])} (cols: 1 for the heat maps, 3 or 4 for the panel; one
+        file per class), or a callable returning that dict (run inside the job: the engine waits there for the record's copy).  The
+        arrays must stay valid until the job is done; `release` is called then, whether the job succeeded or not.  Returns the job's
+        future."""
         if self.closed:
             raise RuntimeError("PredictionWriter is closed")
         self._raise_finished()

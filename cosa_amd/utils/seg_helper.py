@@ -1311,6 +1311,68 @@ def export_overlay(image, seg, alpha=0.5, out=None, palette=None):
     return out.reshape(-1)[:3 * H * W].reshape(H, W, 3)
 
 
+CAMHEAT_MAX_CLASSES = 256                                # COSA_CAMHEAT_MAX_CLASSES
+PANEL_COLOUR = (10, 186, 181)                            # the panel's region colour (csrc/heat_kernels.hip)
+
+
+def _one_image(image, who):
+    if image.dim() not in (3, 4) or image.shape[-3] != 3 or image.numel() != 3 * image.shape[-2] * image.shape[-1]:
+        raise ValueError(f"{who}: image must be one image's [3,H,W], got {tuple(image.shape)}")
+    return int(image.shape[-2]), int(image.shape[-1]), image.contiguous().float()
+
+
+def export_camheat(planes, image, out=None):
+    """The class planes `planes` (fp32 [k,H,W], e.g. a record's rawcam / rawcam_aux slot) as k heat maps over their image [3,H,W] /
+    [1,3,H,W] (normalised fp32, as the loaders give it), in integers (cosa_export_camheat): idx = trunc(255 m)
+    clamped to 0..255, the ramp (clamp(765 - |8 idx - k_c|, 0, 510) + 1) >> 1, plus the image's byte, times 255 over the picture's
+    maximum.  `out`: at least 3 k H W uint8 bytes to write into (a slice of the image's record).  Two launches whatever k is, no host
+    wait.  -> uint8 [k, H, W, 3], a view of `out`."""
+    _C.require_cuda(planes, image, out)
+    H, W, image = _one_image(image, "export_camheat")
+    if planes.dtype != torch.float32 or planes.dim() != 3 or tuple(planes.shape[1:]) != (H, W) or not planes.is_contiguous():
+        raise ValueError(f"export_camheat: planes must be contiguous fp32 [k,{H},{W}], got {planes.dtype} {tuple(planes.shape)}")
+    k = int(planes.shape[0])
+    if not 1 <= k <= CAMHEAT_MAX_CLASSES:
+        raise ValueError(f"export_camheat: k must be in 1..{CAMHEAT_MAX_CLASSES} (got {k})")
+    n = 3 * k * H * W
+    if out is None:
+        out = torch.empty(n, device=image.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < n:
+        raise ValueError(f"export_camheat: `out` must be contiguous uint8 of at least {n} bytes")
+    ws = _C.workspace(4 * k, image.device, "camheat")
+    _C.check(_C.lib().cosa_export_camheat(_C.ptr(planes), _C.ptr(image), k, H, W, _C.ptr(out), out.numel(), _C.ptr(ws), ws.numel(),
+                                          _C.stream_ptr()), "cosa_export_camheat")
+    return out.reshape(-1)[:n].reshape(k, H, W, 3)
+
+
+def export_panel(heat, seg, class_idx, image, gt=None, out=None):
+    """One comparison panel per class (cosa_export_panel), columns left to right: heat[j] (uint8 [k,H,W,3],
+    export_camheat's pictures) | PANEL_COLOUR where seg == class_idx[j] + 1 | the same for gt (left out when `gt` is None; a gt of 255
+    never matches) | the image.  seg, gt: contiguous uint8 with H W elements; class_idx: int32 [k] on the device, 0-based (a record's
+    rawcam_idx slot).  `out`: at least 3 k H cols W bytes.  One launch.  -> uint8 [k, H, cols W, 3], cols = 4 with gt, else 3."""
+    _C.require_cuda(heat, seg, class_idx, image, gt, out)
+    H, W, image = _one_image(image, "export_panel")
+    if heat.dtype != torch.uint8 or heat.dim() != 4 or tuple(heat.shape[1:]) != (H, W, 3) or not heat.is_contiguous():
+        raise ValueError(f"export_panel: heat must be contiguous uint8 [k,{H},{W},3], got {heat.dtype} {tuple(heat.shape)}")
+    k = int(heat.shape[0])
+    if not 1 <= k <= CAMHEAT_MAX_CLASSES:
+        raise ValueError(f"export_panel: k must be in 1..{CAMHEAT_MAX_CLASSES} (got {k})")
+    for t, nm in ((seg, "seg"), (gt, "gt")):
+        if t is not None and (t.dtype != torch.uint8 or t.numel() != H * W or not t.is_contiguous()):
+            raise ValueError(f"export_panel: {nm} must be contiguous uint8 with {H * W} elements, got {t.dtype} {tuple(t.shape)}")
+    if class_idx.dtype != torch.int32 or class_idx.numel() != k or not class_idx.is_contiguous():
+        raise ValueError(f"export_panel: class_idx must be contiguous int32 [{k}], got {class_idx.dtype} {tuple(class_idx.shape)}")
+    cols = 4 if gt is not None else 3
+    n = 3 * k * H * cols * W
+    if out is None:
+        out = torch.empty(n, device=image.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < n:
+        raise ValueError(f"export_panel: `out` must be contiguous uint8 of at least {n} bytes")
+    _C.check(_C.lib().cosa_export_panel(_C.ptr(heat), _C.ptr(seg), _C.ptr(gt), _C.ptr(class_idx), _C.ptr(image), k, H, W, _C.ptr(out),
+                                        out.numel(), _C.stream_ptr()), "cosa_export_panel")
+    return out.reshape(-1)[:n].reshape(k, H, cols * W, 3)
+
+
 # --------------------------------------------------------------------------------------------
 # cam_validation / cam2mask  (utils/seg_helper.py:547-551, 721-797)
 # --------------------------------------------------------------------------------------------

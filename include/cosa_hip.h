@@ -834,6 +834,32 @@ int cosa_predict_classes(const float *logits, int G, int C, float L, int cls_min
                          void *stream);
 int cosa_export_overlay(const float *image, const uint8_t *seg, const uint8_t *palette, int H, int W, int alpha256, uint8_t *out,
                         void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The CAM pictures of prediction export (csrc/heat_kernels.hip).
+ * cosa_export_camheat: k class planes [k, H, W] fp32 (the RAWCAM or RAWCAM_AUX slot of an export record) as k heat maps over
+ *   the image [3, H, W] (fp32, normalised as for cosa_export_overlay).  Per picture, pixel and colour c, in integers:
+ *     idx = trunc(255 m) clamped to 0..255 (a NaN gives 0);
+ *     jet[idx][c] = (clamp(765 - |8 idx - k_c|, 0, 510) + 1) >> 1, k = 1530, 1020, 510 for R, G, B;
+ *     s = jet[idx][c] + img (img as in cosa_export_overlay); M = max of s over the picture's 3 H W values (>= 128);
+ *     byte = 255 s / M (integer division).
+ *   out: [k, H, W, 3] uint8, dense.  Two launches whatever k is: the k maxima by 32-bit integer atomics into `workspace`
+ *   (4 k bytes, 4-byte aligned; zeroed here, on the stream), then the bytes.  No float
+ *   atomics, no host sync: the same bytes on every run.  Four pixels per thread by one dwordx4 per plane (unaligned where
+ *   H W % 4 != 0 moves a plane off the 16-byte grid), the H W % 4 last pixels one per thread.
+ * cosa_export_panel: per class j one picture [H, cols W, 3] of column blocks, left to right: heat[j] ([k, H, W, 3], what
+ *   cosa_export_camheat wrote); (10,186,181) where seg == class_idx[j] + 1, else black; the same for gt (a gt of 255 never
+ *   matches); the image's bytes.  gt may be NULL: the block is then left out, cols = 3, else 4.  seg, gt: uint8 [H, W];
+ *   class_idx: int32 [k] on the device, 0-based (a record's RAWCAM index slot).  One launch.
+ * Envelope of both: non-NULL pointers (gt excepted), H, W > 0, H W < 2^29, 1 <= k <= COSA_CAMHEAT_MAX_CLASSES, out_bytes
+ *   (workspace_bytes) at least what is written, float / int32 arrays 4-byte aligned; anything else is COSA_EINVAL and nothing
+ *   is launched.
+ * ------------------------------------------------------------------------------------- */
+#define COSA_CAMHEAT_MAX_CLASSES 256
+int cosa_export_camheat(const float *planes, const float *image, int k, int H, int W, uint8_t *out, size_t out_bytes,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int cosa_export_panel(const uint8_t *heat, const uint8_t *seg, const uint8_t *gt, const int *class_idx, const float *image, int k,
+                      int H, int W, uint8_t *out, size_t out_bytes, void *stream);
 /* ---------------------------------------------------------------------------------------
  * Per-step pseudo-label statistics and the teacher finite check: one reduction over tensors the
  * training step already holds, accumulated on the device in a vector of uint64 counters.

@@ -1,6 +1,6 @@
 """Rate of prediction export next to evaluate() on the same loader.
 
-    python tools/bench_export.py --mode evaluate|seg|all_crf|pseudo|pseudo_par|refine_time|given|predicted|predicted_overlay|kernel_time \
+    python tools/bench_export.py --mode evaluate|seg|all_crf|pseudo|pseudo_par|refine_time|given|predicted|predicted_overlay|camheat|kernel_time \
         [--writers N] [--items 200] [--out FILE]
 
 One mode per process (run each under its own time limit); the result is merged into the JSON file under the key `evaluate` or
@@ -12,7 +12,8 @@ export run.  `refine_time` is no export run: the device time per image of `seg_h
 way to the same two maps -- two `_cam2mask_generic(..., refine_model=PAR(...))` calls on resized, validated CAMs -- interleaved in one
 process after warm-up, HIP events around each call, median over `--reps` repetitions per size.
 `given`, `predicted` and `predicted_overlay` are `seg` with the class row given, taken from the model's own head, and that plus the
-overlay product; `kernel_time` times `cosa_predict_classes` and `cosa_export_overlay` alone."""
+overlay product; `kernel_time` times `cosa_predict_classes` and `cosa_export_overlay` alone.
+`camheat` is seg,camheat,panel: per item two heat maps and two four-column panels on top of `seg`."""
 import argparse
 import json
 import os
@@ -124,6 +125,7 @@ PAR_WHAT = ("pseudo_par", "pseudo_aux_par")
 EXPORT_MODES = {"seg": (("seg",), False), "all_crf": (ALL, True), "pseudo": (("seg", "pseudo", "pseudo_aux"), False),
                 "pseudo_par": (("seg",) + PAR_WHAT, False),
                 # where the class row comes from: `given` is `seg` with the argument spelled out
+                "camheat": (("seg", "camheat", "panel"), False),         # the CAM pictures
                 "given": (("seg",), False), "predicted": (("seg",), False), "predicted_overlay": (("seg", "overlay"), False)}
 CLASSES = {"given": "given", "predicted": "predicted", "predicted_overlay": "predicted"}
 
