@@ -18,13 +18,19 @@ softmax -> one mean-field step of the dense CRF (`seg_helper.crf_inference_infv2
 argmax, scored as the row `Seg_crf`.  Parity of that row with pydensecrf is unpinned (see seg_helper.DenseCRF).
 
 `evaluate` writes no image files (`save_result`, `save_rawcam` raise NotImplementedError) -- only, with `image_scores=...`, the per-image score
-files of DESIGN.md section 22 (off by default: nothing changes); `export_predictions` below does: the same
-forward, one `cosa_export_maps` record per image at the image's own size, one asynchronous copy to pinned memory, a pool of writer
-threads (command line: `python -m cosa_amd.predict`).
+files of DESIGN.md section 22 (off by default: nothing changes); `export_predictions` below does: the same forward, one packed record per
+image at the image's own size, one asynchronous copy to pinned memory, a pool of writer threads (command line:
+`python -m cosa_amd.predict`).  The two share `_eval_pass` (model state and the captured pass), `_seg_crf_map` and `evaluation.ScoreLog`
+(a score table from the first image to its file); the export's host logic is `check_export_request` (every refusal before the device is
+touched) and `_RecordPlan` (every byte offset of an image's record, computed once).
 """
+import contextlib
+import functools
+import math
 import os
 import time
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -65,6 +71,49 @@ class _GraphedCamSeg:
         return self.outs
 
 
+@contextlib.contextmanager
+def _eval_pass(model, use_graph):
+    """The state both passes below run in: eval mode, no grad, and the heads and the decoder batch-invariant (the narrow heads on their own
+    kernel), so that grouped items reproduce the one-at-a-time bits.  Yields the multi-scale pass; flags and mode come back on every path."""
+    was_training = model.training
+    net = model.module if hasattr(model, "module") else model
+    heads_before = getattr(net, "batch_invariant_heads", None)
+    model.eval()
+    if heads_before is not None:
+        net.batch_invariant_heads = True
+        net.decoder.batch_invariant = True
+    try:
+        with torch.no_grad():
+            yield _GraphedCamSeg(model, EVAL_SCALES, enabled=use_graph and getattr(model, "can_forward_multi", None) is not None)
+    finally:
+        if heads_before is not None:
+            net.batch_invariant_heads = heads_before
+            net.decoder.batch_invariant = heads_before
+        if was_training:
+            model.train()
+
+
+def _seg_crf_map(seg_logits, cls_row, img_org, size):
+    """The Seg_crf label map of one image (evaluation_engine.py:204-211): softmax of the validated logits [1,C+1,S,S] at the ground truth's
+    size, the de-normalised uint8 image, one mean-field step, argmax -> uint8 [1,H,W].  `img_org` is de-normalised IN PLACE: whatever reads
+    the normalised image comes before this."""
+    rs = F.interpolate(seg_logits, size=size, mode='bilinear', align_corners=False)
+    vd = seg_helper.seg_validation(rs, cls_row).softmax(dim=1)[0]
+    ori = torch_helper.denormalize_img_(img_org)[0].permute(1, 2, 0)
+    q = seg_helper.crf_inference_infv2(ori, vd.contiguous())
+    return q.argmax(dim=0, keepdim=True).to(torch.uint8)
+
+
+def _write_iou_dic(path, records, num_classes, map_index):
+    """the reference's iou_dic.pth (evaluation_engine.py:160-168,282-283) of one map of the score records; means as Python floats"""
+    iou_dic = {}
+    for rec in records:
+        cl = [1 if c + 1 in rec["present"] else 0 for c in range(num_classes - 1)]
+        a = evaluation.assist_from_row(rec["row"], num_classes, map_index, cl)
+        iou_dic[rec["name"]] = {k: (float(v) if k in ("miou", "wmiou") else v) for k, v in a.items()}
+    torch.save(iou_dic, path)
+
+
 def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=False, epoch=None, threshold_filters=None, getcrf=False,
              s_or_t='t', get_camiou=False, isfinal=False, class_list=None, use_graph=True, eval_group=4, image_scores=None,
              boundary_scores=None):
@@ -91,31 +140,14 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
     for thre in threshold_filters:                    # pseudo_scores' relabelling: a prediction of 255 drops the pixel (utils/evaluation.py:43-46)
         meters[f"cam_{thre}"] = evaluation.ConfusionMeter(nc, device, pseudo=True)
         meters[f"camaux_{thre}"] = evaluation.ConfusionMeter(nc, device, pseudo=True)
-    scores, score_meta = None, []                     # per-image counters of the same maps, in the meters' order (off: nothing is built)
-    if image_scores is not None and image_scores is not False:
-        try:
-            capacity = len(data_loader)
-        except TypeError:
-            capacity = 64
-        scores = evaluation.ImageScores(nc, list(meters), [m.pseudo for m in meters.values()], capacity, device)
-    bscores, bscore_meta = None, []                   # the same maps over band pixels (off: nothing is built)
-    if boundary_scores is not None and boundary_scores is not False:
-        try:
-            capacity = len(data_loader)
-        except TypeError:
-            capacity = 64
-        bscores = evaluation.BoundaryScores(nc, list(meters), [m.pseudo for m in meters.values()], capacity, device,
-                                            ratio=getattr(args, "boundary_ratio", 0.02), d=getattr(args, "boundary_d", 0))
+    world = dist.get_world_size() if distributed else 1
+    logs = {}                                         # per-image counters of the same maps, in the meters' order (off: nothing is built)
+    for kind, where, band in (("image", image_scores, None),
+                              ("boundary", boundary_scores, (getattr(args, "boundary_ratio", 0.02), getattr(args, "boundary_d", 0)))):
+        if where is not None and where is not False:  # the loader is this rank's share already
+            logs[kind] = (where, evaluation.ScoreLog(nc, list(meters), [m.pseudo for m in meters.values()], data_loader, 1, device, band))
     ap_sum = torch.zeros(2, device=device, dtype=torch.float64)          # sums of per-batch mean AP (cls, cls_aux) ...
     ap_cnt = 0                                                           # ... over the batches (AverageMeter semantics, :86-92)
-    was_training = model.training
-    model.eval()
-    net = model.module if hasattr(model, "module") else model
-    heads_before = getattr(net, "batch_invariant_heads", None)
-    if heads_before is not None:                       # grouped items must reproduce the one-at-a-time bits: narrow heads on own kernel
-        net.batch_invariant_heads = True
-        net.decoder.batch_invariant = True
-    camseg = _GraphedCamSeg(model, EVAL_SCALES, enabled=use_graph and getattr(model, "can_forward_multi", None) is not None)
     # Every image is resized to crop_size x crop_size before the network (:82), so `eval_group` loader items share one multi-scale pass
     # (GEMMs with several times the rows instead of ten batch-1 encoder passes per image: 137 -> 242 img/s at 4); label maps, histograms
     # and AP stay per image.  Every kernel on the CAM / seg path (patch projection, encoder, convs, narrow heads, CAM tail) gives a token
@@ -137,20 +169,9 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
             cam_label, pred_ps, pred_vd = seg_helper.eval_label_maps(cams[i:i + 1], seg_ps[i:i + 1], cls_label, size, args.bkg_thre)
             cam_aux_label, _, _ = seg_helper.eval_label_maps(cams_aux[i:i + 1], None, cls_label, size, args.bkg_thre)
             gt = labels.to(torch.uint8)
-            meters["cam"].update(gt, cam_label)
-            meters["cam_aux"].update(gt, cam_aux_label)
-            meters["seg_ps"].update(gt, pred_ps)
-            meters["seg_vd"].update(gt, pred_vd)
             maps = {"cam": cam_label, "cam_aux": cam_aux_label, "seg_ps": pred_ps, "seg_vd": pred_vd}
             if getcrf:
-                # evaluation_engine.py:204-211: softmax of the validated logits at the ground truth's size, the de-normalised uint8 image,
-                # one mean-field step, argmax
-                rs = F.interpolate(seg_ps[i:i + 1], size=size, mode='bilinear', align_corners=False)
-                vd = seg_helper.seg_validation(rs, cls_label).softmax(dim=1)[0]
-                ori = torch_helper.denormalize_img_(img_org)[0].permute(1, 2, 0)
-                q = seg_helper.crf_inference_infv2(ori, vd.contiguous())
-                maps["seg_crf"] = q.argmax(dim=0, keepdim=True).to(torch.uint8)
-                meters["seg_crf"].update(gt, maps["seg_crf"])
+                maps["seg_crf"] = _seg_crf_map(seg_ps[i:i + 1], cls_label, img_org, size)
             if threshold_filters:
                 # evaluation_engine.py:132-152: the CAMs resized to the ground truth's size, validated, then cam2mask with the box
                 # [0, -1, 0, -1] (Python slice semantics: the last row and column stay `ignore`, as in the reference) and no refine model
@@ -161,15 +182,12 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
                         m = seg_helper.cam2mask(images=shape_only, img_boxes=[[0, -1, 0, -1]], cams=seg_helper.cam_validation(rc, cls_label),
                                                 cls_labels=cls_label, threshold_high=1 - thre, threshold_low=thre)
                         maps[key] = m.to(torch.uint8)
-                        meters[key].update(gt, maps[key])
-            if scores is not None:                    # every map of this image exists: one launch (per eight maps), no host wait
-                scores.add(len(score_meta), gt, [maps[k] for k in meters])
-                score_meta.append(meta + (int(size[0]), int(size[1])))
-            if bscores is not None:
-                bscores.add(len(bscore_meta), gt.reshape(size), [maps[k].reshape(size) for k in meters])
-                bscore_meta.append(meta + (int(size[0]), int(size[1])))
+            for key, meter in meters.items():         # every map of this image exists: into its confusion matrix ...
+                meter.update(gt, maps[key])
+            for _, log in logs.values():              # ... and into the per-image tables: one launch (per eight maps), no host wait
+                log.add(*meta, size[0], size[1], gt, [maps[k] for k in meters])
 
-    with torch.no_grad():
+    with _eval_pass(model, use_graph) as camseg:
         group = []
         for data in data_loader:
             name, img_org, labels, cls_label = data
@@ -192,49 +210,15 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
         flush(group)
     for m in meters.values():
         m.all_reduce()
-    score_records = None
-    if scores is not None:
-        # DistributedSampler(shuffle=False) hands rank r the dataset positions r, r + world, ...: the k-th item of this rank is r + k world
-        world = dist.get_world_size() if distributed else 1
-        rows = scores.rows(len(score_meta))
-        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(torch.as_tensor(cl).reshape(-1)).reshape(-1) + 1).tolist(),
-                                                            rows[k])) for k, (nm, cl, h, w) in enumerate(score_meta)]
-        score_records = evaluation.gather_records(local)
-    bscore_records = None
-    if bscores is not None:
-        world = dist.get_world_size() if distributed else 1
-        rows = bscores.rows(len(bscore_meta))
-        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(torch.as_tensor(cl).reshape(-1)).reshape(-1) + 1).tolist(),
-                                                            rows[k], bscores.widths[k])) for k, (nm, cl, h, w) in enumerate(bscore_meta)]
-        bscore_records = evaluation.gather_records(local)
-    if heads_before is not None:
-        net.batch_invariant_heads = heads_before
-        net.decoder.batch_invariant = heads_before
-    if was_training:
-        model.train()
+    for kind, (where, log) in logs.items():           # every rank gathers, rank 0 writes (DESIGN.md sections 22 and 26)
+        out_dir = Path(args.output_dir) / str(epoch).zfill(5) if where is True else Path(where)
+        records = log.write(out_dir / f"{kind}_scores_{s_or_t}.jsonl",
+                            {"epoch": epoch, "s_or_t": s_or_t, "checkpoint": getattr(args, "checkpoint", None)}, rank, world)
+        if rank == 0 and kind == "image":
+            _write_iou_dic(out_dir / f"iou_dic_{s_or_t}.pth", records, nc, list(meters).index("seg_vd"))
     if rank != 0:
         return (None,) * (5 if get_camiou else 4)
 
-    if scores is not None:
-        out_dir = Path(args.output_dir) / str(epoch).zfill(5) if image_scores is True else Path(image_scores)
-        out_dir.mkdir(parents=True, exist_ok=True)
-        settings = {"maps": scores.map_names, "pseudo": scores.pseudo_flags, "num_classes": nc, "epoch": epoch, "s_or_t": s_or_t,
-                    "world_size": dist.get_world_size() if distributed else 1, "checkpoint": getattr(args, "checkpoint", None)}
-        evaluation.write_score_file(out_dir / f"image_scores_{s_or_t}.jsonl", settings, score_records)
-        vd = scores.map_names.index("seg_vd")
-        iou_dic = {}
-        for rec in score_records:                         # the reference's iou_dic.pth (evaluation_engine.py:160-168,282-283); means as Python floats
-            cl = [1 if c + 1 in rec["present"] else 0 for c in range(nc - 1)]
-            a = evaluation.assist_from_row(rec["row"], nc, vd, cl)
-            iou_dic[rec["name"]] = {k: (float(v) if k in ("miou", "wmiou") else v) for k, v in a.items()}
-        torch.save(iou_dic, out_dir / f"iou_dic_{s_or_t}.pth")
-    if bscores is not None:
-        out_dir = Path(args.output_dir) / str(epoch).zfill(5) if boundary_scores is True else Path(boundary_scores)
-        out_dir.mkdir(parents=True, exist_ok=True)
-        settings = {"maps": bscores.map_names, "pseudo": bscores.pseudo_flags, "num_classes": nc, "epoch": epoch, "s_or_t": s_or_t,
-                    "world_size": dist.get_world_size() if distributed else 1, "checkpoint": getattr(args, "checkpoint", None),
-                    "boundary": bscores.settings()}
-        evaluation.write_score_file(out_dir / f"boundary_scores_{s_or_t}.jsonl", settings, bscore_records)
     cam_score, cam_aux_score, seg_vd_score = meters["cam"].scores(), meters["cam_aux"].scores(), meters["seg_vd"].scores()
     metrics, names = [cam_score, cam_aux_score, seg_vd_score], ["CAM", "aux_CAM", "Seg_vd"]
     if isfinal:
@@ -255,8 +239,6 @@ def evaluate(model, data_loader, args, df=None, save_result=False, save_rawcam=F
     df['mIoU'].extend(mioulist)
     df['Metrics'].extend(names)
     df['ST'].extend([s_or_t] * len(names))
-    # (as the reference, evaluation_engine.py:289: the last row, or the one before it with getcrf -- with threshold_filters that is a
-    # `cam_<t>` / `camaux_<t>` row, not Seg_vd)
     # evaluation_engine.py:287-290 of the reference: the "seg" score handed back is the LAST row of the table (second to last with the CRF row).
     # With `threshold_filters` that row is a pseudo-label sweep row (camaux_<t>), not Seg_vd -- the reference's behaviour, kept so that
     # best-checkpoint selection in main.py follows the reference run for run (README: "--eval_threshold_filters").
@@ -317,6 +299,156 @@ def _sharded(data_loader, rank, world):
     return [items[i] for i in export_shard(len(items), rank, world)]
 
 
+_BITS = seg_helper.EXPORT_BITS
+_MAPS_OF_CAM = _BITS["pseudo"] | _BITS["rawcam"]                  # cosa_export_maps reads the main CAMs for these ...
+_MAPS_OF_CAM_AUX = _BITS["pseudo_aux"] | _BITS["rawcam_aux"]      # ... and the auxiliary ones for these
+_HEAT_SOURCE = {"camheat": "rawcam", "camheat_aux": "rawcam_aux"}  # the slot whose planes a heat picture shows
+
+
+def check_export_request(what, classes, cls_thre, cls_min, overlay_alpha, scores, boundary, getcrf, writers, args):
+    """Everything export_predictions refuses before it touches the device (host logic only), and the request read once: -> a namespace of
+    `what`, `products` (what + seg_crf), `mask` (the record's COSA_EXPORT_* slots), `par_mask`, `par_downscale`, `overlay`, `pictures`,
+    `predicted`, `writers` and `scored` (the label-map products that scores=True / boundary=True count)."""
+    what = tuple(what)
+    for extra in ("overlay",) + PICTURE_PRODUCTS:
+        if what.count(extra) > 1:
+            raise ValueError(f"export_predictions: `{extra}` named twice in {list(what)}")
+    overlay = "overlay" in what
+    pictures = tuple(p for p in PICTURE_PRODUCTS if p in what)
+    slot_names = tuple(w for w in what if w != "overlay" and w not in PICTURE_PRODUCTS)
+    mask = seg_helper.export_what_mask(slot_names) if slot_names or not what else 0
+    for p in pictures:                              # a picture shows the numbers of its slots: computed even where no .npy / .png is asked for
+        mask |= _BITS["rawcam"] | _BITS["seg"] if p == "panel" else _BITS[_HEAT_SOURCE[p]]
+    if overlay:                                     # the overlay shows the seg map: its slot is computed even where no seg file is asked for
+        mask |= _BITS["seg"]
+        seg_helper.overlay_alpha256(overlay_alpha)  # [0, 1], or a ValueError before anything runs
+    if classes not in (None, "given", "predicted", "none"):
+        raise ValueError(f"export_predictions: classes must be None, 'given', 'predicted' or 'none' (got {classes!r})")
+    if classes == "none" and (mask & ~_BITS["seg"]):
+        raise ValueError(f"export_predictions: classes='none' leaves only 'seg' (and its overlay) to export (asked for {list(what)})")
+    if classes == "predicted":
+        seg_helper.cls_threshold_logit(cls_thre)    # (0, 1), or a ValueError before anything runs
+        if not 0 <= int(cls_min) <= args.num_classes - 1:
+            raise ValueError(f"export_predictions: cls_min must be in 0..{args.num_classes - 1} (got {cls_min})")
+    writers = export_io.check_writers(writers)
+    if getattr(args, "usepar", False):
+        raise NotImplementedError("export_predictions: `usepar` does not select an export product; the PAR-refined labels are the products "
+                                  "pseudo_par / pseudo_aux_par (--what pseudo_par)")
+    par_mask = mask & seg_helper.EXPORT_PAR_MASK
+    par_downscale = int(getattr(args, "par_downscale", 2) or 0)
+    if par_mask and par_downscale not in (0, 2):
+        raise ValueError(f"export_predictions: pseudo_par / pseudo_aux_par are built for par_downscale 2 and 0 (got {par_downscale})")
+    products = what + (("seg_crf",) if getcrf else ())
+    scored = [p for p in products if p in SCORED_PRODUCTS]
+    for flag, on in (("scores", scores), ("boundary", boundary)):
+        if on and not scored:
+            raise ValueError(f"export_predictions: {flag}=True needs a label-map product (one of {list(SCORED_PRODUCTS)}), got {list(products)}")
+    return SimpleNamespace(what=what, products=products, mask=mask, par_mask=par_mask, par_downscale=par_downscale, overlay=overlay,
+                           pictures=pictures, predicted=classes == "predicted", writers=writers, scored=scored)
+
+
+class _RecordPlan:
+    """Where everything of ONE image lies in its packed record, computed once: `offsets` (slot -> byte offset) are cosa_export_record_layout's
+    and behind them, each on the next 16-byte boundary, seg_crf | overlay | camheat | camheat_aux | panel (one picture per present class: none
+    without one); `copy_bytes` go to the host; `heat_at`: where each heat plane is rendered -- its own slot, or for a panel without camheat
+    files a scratch plane behind the copied bytes; `reserve_bytes`: what the record must hold.  `view` is the only reader of the offsets."""
+
+    def __init__(self, C, H, W, k_live, item_mask, getcrf=False, overlay=False, pictures=(), panel_cols=3):
+        self.mask, self.k_live = item_mask, k_live
+        self.offsets, end = seg_helper.export_record_layout(C, H, W, k_live, item_mask)
+        self.shapes = {p: (k_live,) if p.endswith("_idx") else (k_live, H, W) if p.startswith("rawcam") else (H, W) for p in self.offsets}
+        extra = [("seg_crf", (H, W))] * bool(getcrf) + [("overlay", (H, W, 3))] * bool(overlay)      # bytes, like every slot but rawcam*
+        if k_live:
+            extra += [(p, (k_live, H, W, 3)) for p in _HEAT_SOURCE if p in pictures]
+            extra += [("panel", (k_live, H, panel_cols * W, 3))] * ("panel" in pictures)
+        for p, shape in extra:
+            self.offsets[p], self.shapes[p], end = end, shape, end + ((math.prod(shape) + 15) & ~15)
+        self.copy_bytes = end
+        self.heat_at = {p: self.offsets[p] for p in _HEAT_SOURCE if p in self.offsets}
+        if "panel" in self.offsets:
+            self.heat_at.setdefault("camheat", end)
+        self.heat_bytes = 3 * k_live * H * W
+        self.reserve_bytes = max([end] + [o + self.heat_bytes for o in self.heat_at.values()])
+
+    def view(self, record, slot):
+        """the slot inside `record` (the device record or the host copy's numpy array: uint8, flat): label maps uint8 [H,W], rawcam* float32
+        [k_live,H,W], rawcam*_idx int32 [k_live], overlay uint8 [H,W,3], the pictures uint8 [k_live,H,cols W,3]"""
+        o, shape = self.offsets[slot], self.shapes[slot]
+        if not slot.startswith("rawcam"):
+            return record[o:o + math.prod(shape)].reshape(shape)
+        lib = torch if torch.is_tensor(record) else np       # rawcam*, rawcam*_idx: 4-byte words
+        return record[o:o + 4 * math.prod(shape)].view(lib.int32 if slot.endswith("_idx") else lib.float32).reshape(shape)
+
+
+class _PredictedRows:
+    """classes="predicted" (DESIGN.md section 23): one group's [rows | logits | k_live | nonfinite] in 4-byte words, on the device and
+    pinned; per group one `seg_helper.predict_classes` launch, one small copy and the one host wait of the predicted path."""
+
+    def __init__(self, gmax, C, device, cls_thre, cls_min):
+        self.C, self.cls_thre, self.cls_min, self.wait_seconds = C, cls_thre, cls_min, 0.0
+        self.dev = torch.empty(gmax * (2 * C + 2), device=device, dtype=torch.float32)
+        self.host = torch.empty(gmax * (2 * C + 2), dtype=torch.float32).pin_memory()
+        self.event = torch.cuda.Event()
+
+    def __call__(self, cls_final, G):
+        """-> (rows on the device [G,C], host rows, k_live, nonfinite, logits)"""
+        C = self.C
+        if cls_final.shape != (G, C):
+            raise RuntimeError(f"export_predictions: the pass returned logits {tuple(cls_final.shape)} for {G} images of {C} classes")
+        rows, logits = self.dev[:G * C].view(G, C), self.dev[G * C:2 * G * C].view(G, C)
+        ints = self.dev[2 * G * C:2 * G * C + 2 * G].view(torch.int32)
+        logits.copy_(cls_final)
+        seg_helper.predict_classes(logits, self.cls_thre, self.cls_min, out=(rows, ints[:G], ints[G:]))
+        n = G * (2 * C + 2)
+        self.host[:n].copy_(self.dev[:n], non_blocking=True)
+        self.event.record()
+        t = time.perf_counter()
+        self.event.synchronize()                    # the only host wait of the predicted path: once per group
+        self.wait_seconds += time.perf_counter() - t
+        h = self.host[:n].numpy().copy()
+        hi = h[2 * G * C:].view(np.int32)
+        return rows, h[:G * C].reshape(G, C), hi[:G], hi[G:], h[G * C:2 * G * C].reshape(G, C)
+
+
+def _fill_record(plan, record, cam, cam_aux, seg_logits, cls_row, img_org, gt, req, thresholds, overlay_alpha):
+    """Every slot of one image's `record` on the device, nothing waited for.  cam / cam_aux [C,S,S] and seg_logits [1,C+1,S,S] are the pass's,
+    `img_org` [1,3,H,W] the normalised image, `gt` the ground truth of its size or None (the panel's third column), `thresholds` export_maps'.
+    The order matters: the overlay and the pictures read the slots just written and the image, which the CRF lines then rescale in place."""
+    H, W = img_org.shape[-2:]
+    maps_mask = plan.mask & seg_helper.EXPORT_MAPS_MASK
+    if maps_mask:
+        seg_helper.export_maps(cam if maps_mask & _MAPS_OF_CAM else None, cam_aux if maps_mask & _MAPS_OF_CAM_AUX else None, seg_logits[0],
+                               cls_row, (H, W), maps_mask, out=record, k_live=plan.k_live, **thresholds)
+    if plan.mask & seg_helper.EXPORT_PAR_MASK:      # the PAR slots lie behind the others: the same record, the same one copy
+        seg_helper.export_refine(torch_helper.denormalize_img(img_org), cam if plan.mask & _BITS["pseudo_par"] else None,
+                                 cam_aux if plan.mask & _BITS["pseudo_aux_par"] else None, cls_row, plan.mask, downscale=req.par_downscale,
+                                 out=record, k_live=plan.k_live, **thresholds)
+    if req.overlay:
+        seg_helper.export_overlay(img_org, plan.view(record, "seg"), overlay_alpha, out=plan.view(record, "overlay"))
+    heat = {p: seg_helper.export_camheat(plan.view(record, _HEAT_SOURCE[p]), img_org, out=record[o:o + plan.heat_bytes]) for p, o in plan.heat_at.items()}
+    if "panel" in plan.offsets:
+        seg_helper.export_panel(heat["camheat"], plan.view(record, "seg"), plan.view(record, "rawcam_idx"), img_org, gt=gt,
+                                out=plan.view(record, "panel"))
+    if "seg_crf" in plan.offsets:
+        plan.view(record, "seg_crf").copy_(_seg_crf_map(seg_logits, cls_row, img_org, (H, W))[0])
+
+
+def _host_products(plan, slot, products, picture_names):
+    """In a writer thread: wait for the record's copy (the loop itself never does), then the products asked for as views of the host copy,
+    in the shapes PredictionWriter.submit takes"""
+    slot.event.synchronize()
+    rec = slot.host.numpy()
+    out = {}
+    for p in (p for p in products if p in plan.offsets):      # not there: no label row (seg only), or no present class to picture
+        if p in PICTURE_PRODUCTS:                    # one picture per present class, named by the class
+            out[p] = (plan.view(rec, p), [picture_names[c] for c in plan.view(rec, _HEAT_SOURCE.get(p, "rawcam") + "_idx")])
+        elif p in _HEAT_SOURCE.values():
+            out[p] = (plan.view(rec, p), plan.view(rec, p + "_idx"))
+        else:
+            out[p] = plan.view(rec, p)
+    return out
+
+
 def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=False, high_thre=None, low_thre=None, eval_group=4,
                        use_graph=True, writers=4, settings=None, scores=False, classes=None, cls_thre=0.5, cls_min=1, overlay_alpha=0.5,
                        boundary=False, boundary_ratio=0.02, boundary_d=None):
@@ -344,224 +476,75 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     the item carries a map of the image's size).  Their slots (`rawcam`, `rawcam_aux`; `seg` and `rawcam` for the panel) are computed even
     where no file of them is asked for; the pictures lie behind the overlay's bytes and ride in the same copy.
     Returns {"images", "seconds", "img_per_s", "bytes_written"} of this process."""
-    what = tuple(what)
-    overlay = "overlay" in what
-    for extra in ("overlay",) + PICTURE_PRODUCTS:
-        if what.count(extra) > 1:
-            raise ValueError(f"export_predictions: `{extra}` named twice in {list(what)}")
-    pictures = tuple(p for p in PICTURE_PRODUCTS if p in what)
-    panel = "panel" in pictures
-    slot_names = tuple(w for w in what if w != "overlay" and w not in PICTURE_PRODUCTS)
-    mask = seg_helper.export_what_mask(slot_names) if slot_names or not what else 0
-    if "camheat" in pictures or panel:              # a picture shows the numbers of the rawcam slot: computed even where no .npy is asked for
-        mask |= seg_helper.EXPORT_BITS["rawcam"]
-    if "camheat_aux" in pictures:
-        mask |= seg_helper.EXPORT_BITS["rawcam_aux"]
-    if panel:
-        mask |= seg_helper.EXPORT_BITS["seg"]
-    if overlay:                                     # the overlay shows the seg map: its slot is computed even where no seg file is asked for
-        mask |= seg_helper.EXPORT_BITS["seg"]
-        seg_helper.overlay_alpha256(overlay_alpha)  # [0, 1], or a ValueError before anything runs
-    if classes not in (None, "given", "predicted", "none"):
-        raise ValueError(f"export_predictions: classes must be None, 'given', 'predicted' or 'none' (got {classes!r})")
-    predicted = classes == "predicted"
-    if classes == "none" and (mask & ~seg_helper.EXPORT_BITS["seg"]):
-        raise ValueError(f"export_predictions: classes='none' leaves only 'seg' (and its overlay) to export (asked for {list(what)})")
-    if predicted:
-        seg_helper.cls_threshold_logit(cls_thre)    # (0, 1), or a ValueError before anything runs
-        if not 0 <= int(cls_min) <= args.num_classes - 1:
-            raise ValueError(f"export_predictions: cls_min must be in 0..{args.num_classes - 1} (got {cls_min})")
-    writers = export_io.check_writers(writers)
-    if getattr(args, "usepar", False):
-        raise NotImplementedError("export_predictions: `usepar` does not select an export product; the PAR-refined labels are the products "
-                                  "pseudo_par / pseudo_aux_par (--what pseudo_par)")
-    par_mask = mask & seg_helper.EXPORT_PAR_MASK
-    par_downscale = int(getattr(args, "par_downscale", 2) or 0)
-    if par_mask and par_downscale not in (0, 2):
-        raise ValueError(f"export_predictions: pseudo_par / pseudo_aux_par are built for par_downscale 2 and 0 (got {par_downscale})")
-    high_thre = float(args.high_thre if high_thre is None else high_thre)
-    low_thre = float(args.low_thre if low_thre is None else low_thre)
-    ignore_index = int(getattr(args, "ignore_index", 255))
+    req = check_export_request(what, classes, cls_thre, cls_min, overlay_alpha, scores, boundary, getcrf, writers, args)
+    thresholds = {"high_thre": float(args.high_thre if high_thre is None else high_thre),
+                  "low_thre": float(args.low_thre if low_thre is None else low_thre), "ignore_index": int(getattr(args, "ignore_index", 255))}
     distributed = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if distributed else (0, 1)
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("export_predictions runs on the GPU (HIP kernels); no CPU path")
-    C = args.num_classes - 1
-    products = what + (("seg_crf",) if getcrf else ())
-    writer = export_io.PredictionWriter(out_dir, products, writers)
-    slots = _export_slots(device, writers + 1)
-    score_names = [p for p in products if p in SCORED_PRODUCTS] if scores else []
-    table, score_meta = None, []
-    if scores:
-        if not score_names:
-            raise ValueError(f"export_predictions: scores=True needs a label-map product (one of {list(SCORED_PRODUCTS)}), got {list(products)}")
-        try:
-            capacity = len(data_loader) // world + 1
-        except TypeError:
-            capacity = 64
-        table = evaluation.ImageScores(args.num_classes, score_names, [p.startswith("pseudo") for p in score_names], capacity, device)
-    band_names = [p for p in products if p in SCORED_PRODUCTS] if boundary else []
-    btable, bscore_meta = None, []
-    if boundary:
-        if not band_names:
-            raise ValueError(f"export_predictions: boundary=True needs a label-map product (one of {list(SCORED_PRODUCTS)}), got {list(products)}")
-        try:
-            capacity = len(data_loader) // world + 1
-        except TypeError:
-            capacity = 64
-        btable = evaluation.BoundaryScores(args.num_classes, band_names, [p.startswith("pseudo") for p in band_names], capacity, device,
-                                           ratio=boundary_ratio, d=boundary_d)
-    was_training = model.training
-    model.eval()
-    net = model.module if hasattr(model, "module") else model
-    heads_before = getattr(net, "batch_invariant_heads", None)
-    if heads_before is not None:
-        net.batch_invariant_heads = True
-        net.decoder.batch_invariant = True
-    camseg = _GraphedCamSeg(model, EVAL_SCALES, enabled=use_graph and getattr(model, "can_forward_multi", None) is not None)
-    count = 0
-    class_records, class_wait = [], 0.0             # classes="predicted": (dataset position, record) per image; seconds spent in the group waits
-    if predicted:                                   # one group's [rows | logits | k_live | nonfinite], 4-byte words, on the device and pinned
-        gmax = max(1, int(eval_group))
-        pack_dev = torch.empty(gmax * (2 * C + 2), device=device, dtype=torch.float32)
-        pack_host = torch.empty(gmax * (2 * C + 2), dtype=torch.float32).pin_memory()
-        pack_event = torch.cuda.Event()
-
-    picture_names = export_io.class_names((settings or {}).get("dataset", getattr(args, "dataset", None)), C) if pictures else None
-
-    def host_products(slot, H, W, k_live, item_mask, crf_off, ov_off, pic_off):
-        def get():
-            slot.event.synchronize()                # in the writer thread: the loop itself never waits for a copy
-            rec = slot.host.numpy()
-            v = seg_helper.export_record_views(rec, C, H, W, k_live, item_mask)
-            out = {p: v[p] for p in ("seg", "pseudo", "pseudo_aux", "pseudo_par", "pseudo_aux_par") if p in v and p in products}
-            for p in ("rawcam", "rawcam_aux"):
-                if p in v and p in products:
-                    out[p] = (v[p], v[p + "_idx"])
-            if crf_off is not None:
-                out["seg_crf"] = rec[crf_off:crf_off + H * W].reshape(H, W)
-            if ov_off is not None:
-                out["overlay"] = rec[ov_off:ov_off + 3 * H * W].reshape(H, W, 3)
-            for p, (off, cols) in pic_off.items():  # one picture per present class, named by the class
-                idx = v["rawcam_aux_idx" if p == "camheat_aux" else "rawcam_idx"]
-                out[p] = (rec[off:off + 3 * k_live * H * cols * W].reshape(k_live, H, cols * W, 3), [picture_names[c] for c in idx])
-            return out
-        return get
-
-    def predicted_rows(group, cls_final):
-        """the group's class rows by the kernel, and the one wait for them: -> (rows on the device [G,C], host rows, k_live, nonfinite, logits)"""
-        nonlocal class_wait
-        G = len(group)
-        if cls_final.shape != (G, C):
-            raise RuntimeError(f"export_predictions: the pass returned logits {tuple(cls_final.shape)} for {G} images of {C} classes")
-        rows, logits = pack_dev[:G * C].view(G, C), pack_dev[G * C:2 * G * C].view(G, C)
-        ints = pack_dev[2 * G * C:2 * G * C + 2 * G].view(torch.int32)
-        logits.copy_(cls_final)
-        seg_helper.predict_classes(logits, cls_thre, cls_min, out=(rows, ints[:G], ints[G:]))
-        n = G * (2 * C + 2)
-        pack_host[:n].copy_(pack_dev[:n], non_blocking=True)
-        pack_event.record()
-        t = time.perf_counter()
-        pack_event.synchronize()                    # the only host wait of the predicted path: once per group
-        class_wait += time.perf_counter() - t
-        h = pack_host[:n].numpy().copy()
-        hi = h[2 * G * C:].view(np.int32)
-        return rows, h[:G * C].reshape(G, C), hi[:G], hi[G:], h[G * C:2 * G * C].reshape(G, C)
+    nc, C = args.num_classes, args.num_classes - 1
+    settings = settings or {}
+    writer = export_io.PredictionWriter(out_dir, req.products, req.writers)
+    slots = _export_slots(device, req.writers + 1)
+    logs = {}                                       # scores / boundary -> the table of the label-map products (off: nothing is built)
+    for flag, on, band in (("scores", scores, None), ("boundary", boundary, (boundary_ratio, boundary_d))):
+        if on:
+            logs[flag] = evaluation.ScoreLog(nc, req.scored, [p.startswith("pseudo") for p in req.scored], data_loader, world, device, band)
+    class_names = export_io.class_names(settings.get("dataset", getattr(args, "dataset", None)), C)
+    predict_rows = _PredictedRows(max(1, int(eval_group)), C, device, cls_thre, cls_min) if req.predicted else None
+    class_records, count = [], 0                    # classes="predicted": (dataset position, record) per image
 
     def flush(group):
         nonlocal count
         if not group:
             return
         cams, cams_aux, seg_ps, cls_final, _ = camseg(torch.cat([g[1] for g in group], dim=0))
-        if predicted:
-            rows_dev, rows_h, k_h, nf_h, logits_h = predicted_rows(group, cls_final)
+        if req.predicted:
+            rows_dev, rows_h, k_h, nf_h, logits_h = predict_rows(cls_final, len(group))
         for i, (name, _, cls_dev, k_live, img_org, gt, cls_host) in enumerate(group):
             H, W = int(img_org.shape[-2]), int(img_org.shape[-1])
-            if predicted:
+            if req.predicted:
                 cls_dev, k_live = rows_dev[i:i + 1], int(k_h[i])
                 rec = export_io.class_record(name, logits_h[i], rows_h[i], k_live, nf_h[i])
                 rec["given"] = None if cls_host is None else (cls_host.reshape(-1) != 0).numpy()
                 class_records.append((rank + count * world, rec))
-            item_mask = mask if cls_dev is not None else seg_helper.EXPORT_BITS["seg"]
-            _, nbytes = seg_helper.export_record_layout(C, H, W, k_live, item_mask)
-            crf_off, ov_off, total = None, None, nbytes
-            if getcrf:
-                crf_off, total = nbytes, nbytes + ((H * W + 15) & ~15)
-            if overlay:                             # behind every other slot, seg_crf included
-                ov_off, total = total, total + ((3 * H * W + 15) & ~15)
-            pic_off, heat_off = {}, {}              # the pictures: behind the overlay; without a present class there is none
-            if pictures and k_live:
-                heat_bytes = (3 * k_live * H * W + 15) & ~15
-                for p in ("camheat", "camheat_aux"):
-                    if p in pictures:
-                        pic_off[p], heat_off[p], total = (total, 1), total, total + heat_bytes
-                if panel:
-                    gt_panel = gt if gt is not None and gt.numel() == H * W else None
-                    cols = 4 if gt_panel is not None else 3
-                    pic_off["panel"], total = (total, cols), total + ((3 * k_live * H * cols * W + 15) & ~15)
-                    heat_off.setdefault("camheat", total)        # no camheat files: the panel's first column is made behind what is copied
+                if cls_host is None:                # the score files' `present`: the given row where there is one
+                    cls_host = torch.from_numpy(rows_h[i])
+            if gt is not None and gt.numel() != H * W:
+                gt = None
+            item_mask = req.mask if cls_dev is not None else _BITS["seg"]
+            plan = _RecordPlan(C, H, W, k_live, item_mask, getcrf, req.overlay, req.pictures, 4 if gt is not None else 3)
             slot = slots[count % len(slots)]
-            slot.reserve(max([total] + [o + (3 * k_live * H * W) for o in heat_off.values()]))
-            maps_mask = item_mask & seg_helper.EXPORT_MAPS_MASK
-            if maps_mask:
-                seg_helper.export_maps(cams[i] if maps_mask & 0x0a else None, cams_aux[i] if maps_mask & 0x14 else None, seg_ps[i], cls_dev, (H, W),
-                                       maps_mask, high_thre, low_thre, ignore_index=ignore_index, out=slot.dev, k_live=k_live)
-            if item_mask & seg_helper.EXPORT_PAR_MASK:          # the PAR slots lie behind the others: the same record, the same one copy
-                seg_helper.export_refine(torch_helper.denormalize_img(img_org), cams[i] if item_mask & 0x20 else None,
-                                         cams_aux[i] if item_mask & 0x40 else None, cls_dev, item_mask, high_thre, low_thre,
-                                         ignore_index=ignore_index, downscale=par_downscale, out=slot.dev, k_live=k_live)
-            if overlay:                             # the seg slot as just written, over the still normalised image (the CRF lines below rescale it in place)
-                seg_off = seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0]["seg"]
-                seg_helper.export_overlay(img_org, slot.dev[seg_off:seg_off + H * W], overlay_alpha, out=slot.dev[ov_off:ov_off + 3 * H * W])
-            if pic_off:                             # from the record's slots as just written, before the CRF lines rescale the image
-                dv = seg_helper.export_record_views(slot.dev, C, H, W, k_live, item_mask)
-                heat = {p: seg_helper.export_camheat(dv["rawcam" if p == "camheat" else "rawcam_aux"], img_org,
-                                                     out=slot.dev[o:o + 3 * k_live * H * W]) for p, o in heat_off.items()}
-                if panel:
-                    o, cols = pic_off["panel"]
-                    seg_helper.export_panel(heat["camheat"], dv["seg"], dv["rawcam_idx"], img_org, gt=gt_panel,
-                                            out=slot.dev[o:o + 3 * k_live * H * cols * W])
-            if getcrf:                              # evaluate()'s Seg_crf lines
-                rs = F.interpolate(seg_ps[i:i + 1], size=(H, W), mode='bilinear', align_corners=False)
-                vd = seg_helper.seg_validation(rs, cls_dev).softmax(dim=1)[0]
-                ori = torch_helper.denormalize_img_(img_org)[0].permute(1, 2, 0)
-                q = seg_helper.crf_inference_infv2(ori, vd.contiguous())
-                slot.dev[crf_off:crf_off + H * W].copy_(q.argmax(dim=0).to(torch.uint8).reshape(-1))
-            if table is not None:                   # scored where it lies, before the copy: one launch, no host wait
-                if item_mask != mask or gt is None or gt.numel() != H * W:
-                    raise ValueError(f"export_predictions: scores=True needs the label row and a ground-truth map of the image's size ({name!r})")
-                offs = dict(seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0], seg_crf=crf_off)
-                table.add(len(score_meta), gt, [slot.dev[offs[p]:offs[p] + H * W] for p in score_names])
-                score_meta.append((name, cls_host if cls_host is not None or not predicted else torch.from_numpy(rows_h[i]), H, W))
-            if btable is not None:
-                if item_mask != mask or gt is None or gt.numel() != H * W:
-                    raise ValueError(f"export_predictions: boundary=True needs the label row and a ground-truth map of the image's size ({name!r})")
-                offs = dict(seg_helper.export_record_layout(C, H, W, k_live, item_mask)[0], seg_crf=crf_off)
-                btable.add(len(bscore_meta), gt.reshape(H, W), [slot.dev[offs[p]:offs[p] + H * W].view(H, W) for p in band_names])
-                bscore_meta.append((name, cls_host if cls_host is not None or not predicted else torch.from_numpy(rows_h[i]), H, W))
-            slot.host[:total].copy_(slot.dev[:total], non_blocking=True)          # the one device-to-host copy of the image
+            slot.reserve(plan.reserve_bytes)
+            _fill_record(plan, slot.dev, cams[i], cams_aux[i], seg_ps[i:i + 1], cls_dev, img_org, gt, req, thresholds, overlay_alpha)
+            for flag, log in logs.items():          # scored where they lie, before the copy: one launch each, no host wait
+                if item_mask != req.mask or gt is None:
+                    raise ValueError(f"export_predictions: {flag}=True needs the label row and a ground-truth map of the image's size ({name!r})")
+                log.add(name, cls_host, H, W, gt, [plan.view(slot.dev, p) for p in req.scored])
+            slot.host[:plan.copy_bytes].copy_(slot.dev[:plan.copy_bytes], non_blocking=True)      # the one device-to-host copy of the image
             slot.event.record()
-            slot.job = writer.submit(name, H, W, host_products(slot, H, W, k_live, item_mask, crf_off, ov_off, pic_off))
+            slot.job = writer.submit(name, H, W, functools.partial(_host_products, plan, slot, req.products, class_names))
             count += 1
 
     t0 = time.perf_counter()
     try:
-        with torch.no_grad():
+        with _eval_pass(model, use_graph) as camseg:
             group = []
             for data in _sharded(data_loader, rank, world):
                 names, img_org, labels, cls_label = data
                 names = [names] if isinstance(names, str) else list(names)
                 has_cls = torch.is_tensor(cls_label) and cls_label.dim() == 2
-                if not has_cls and ((mask & ~seg_helper.EXPORT_BITS["seg"]) or classes == "given") and not predicted:
+                if not has_cls and ((req.mask & ~_BITS["seg"]) or classes == "given") and not req.predicted:
                     raise ValueError(f"export_predictions: item {names[0]!r} has no image-level label row; only 'seg' can be exported "
-                                     f"for it (asked for {list(what)})")
+                                     f"for it (asked for {list(req.what)})")
                 use_cls = has_cls and classes in (None, "given")                # predicted rows come per group, in flush
                 k_lives = (cls_label != 0).sum(dim=1).tolist() if use_cls else [0] * len(names)      # the loader's host tensor: no device wait
                 cls_dev = cls_label.to(device, non_blocking=True).float() if use_cls else None
                 img_org = img_org.to(device, non_blocking=True)
                 inputs = F.interpolate(img_org, size=[args.crop_size, args.crop_size], mode='bilinear', align_corners=False)
-                gts = labels.to(device, non_blocking=True).to(torch.uint8) if (scores or boundary or panel) and torch.is_tensor(labels) else None
+                gts = labels.to(device, non_blocking=True).to(torch.uint8) if (logs or "panel" in req.pictures) and torch.is_tensor(labels) else None
                 for i in range(inputs.shape[0]):
                     group.append((str(names[i]), inputs[i:i + 1], cls_dev[i:i + 1] if use_cls else None, int(k_lives[i]),
                                   img_org[i:i + 1], gts[i] if gts is not None and gts.dim() == 3 else None, cls_label[i] if has_cls else None))
@@ -573,11 +556,6 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
     finally:
         for s in slots:
             s.job = None
-        if heads_before is not None:
-            net.batch_invariant_heads = heads_before
-            net.decoder.batch_invariant = heads_before
-        if was_training:
-            model.train()
         if writer.futures:                          # an error on the way: let the threads finish before it propagates
             try:
                 writer.drain()
@@ -591,72 +569,49 @@ def export_predictions(model, data_loader, args, out_dir, what=("seg",), getcrf=
         dist.all_gather_object(gathered, images)
         images = sorted(x for part in gathered for x in part)
         dist.barrier()                              # every rank's files are on disk
-    score_summary = None
-    if table is not None:                           # _sharded: the k-th item of this rank is dataset position rank + k world
-        rows = table.rows(len(score_meta))
-        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(cl.reshape(-1)).reshape(-1) + 1).tolist(), rows[k]))
-                 for k, (nm, cl, h, w) in enumerate(score_meta)]
-        records = evaluation.gather_records(local)
+    summaries = {}                                  # scores / boundary -> {product: dataset figures} on rank 0
+    for flag, log in logs.items():
+        records = log.write(os.path.join(out_dir, "scores.jsonl" if flag == "scores" else "boundary_scores.jsonl"),
+                            {"epoch": None, "s_or_t": settings.get("s_or_t"), "checkpoint": settings.get("checkpoint")}, rank, world)
         if rank == 0:
-            os.makedirs(out_dir, exist_ok=True)
-            evaluation.write_score_file(os.path.join(out_dir, "scores.jsonl"),
-                                        {"maps": score_names, "pseudo": table.pseudo_flags, "num_classes": args.num_classes, "epoch": None,
-                                         "s_or_t": (settings or {}).get("s_or_t"), "world_size": world,
-                                         "checkpoint": (settings or {}).get("checkpoint")}, records)
-            ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), args.num_classes) if records else []
-            score_summary = {p: {"miou": evaluation.nan_to_none(d["miou"]), "labelled": evaluation.nan_to_none(d["labelled"])} for p, d in zip(score_names, ds)}
-    band_summary = None
-    if btable is not None:
-        rows = btable.rows(len(bscore_meta))
-        local = [(rank + k * world, evaluation.score_record(nm, h, w, (torch.nonzero(cl.reshape(-1)).reshape(-1) + 1).tolist(), rows[k],
-                                                            btable.widths[k])) for k, (nm, cl, h, w) in enumerate(bscore_meta)]
-        records = evaluation.gather_records(local)
-        if rank == 0:
-            os.makedirs(out_dir, exist_ok=True)
-            evaluation.write_score_file(os.path.join(out_dir, "boundary_scores.jsonl"),
-                                        {"maps": band_names, "pseudo": btable.pseudo_flags, "num_classes": args.num_classes, "epoch": None,
-                                         "s_or_t": (settings or {}).get("s_or_t"), "world_size": world,
-                                         "checkpoint": (settings or {}).get("checkpoint"), "boundary": btable.settings()}, records)
-            ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), args.num_classes) if records else []
-            band_summary = {p: {"miou": evaluation.nan_to_none(d["miou"])} for p, d in zip(band_names, ds)}
+            ds = evaluation.dataset_scores(np.stack([r["row"] for r in records]), nc) if records else []
+            summaries[flag] = {p: {k: evaluation.nan_to_none(d[k]) for k in (("miou", "labelled") if flag == "scores" else ("miou",))}
+                               for p, d in zip(req.scored, ds)}
     class_summary = None
-    if predicted:                                   # gathered as the score records are: dataset order, rank 0 writes
+    if req.predicted:                               # gathered as the score records are: dataset order, rank 0 writes
         records = evaluation.gather_records(class_records)
         if rank == 0:
             os.makedirs(out_dir, exist_ok=True)
-            export_io.write_classes_file(os.path.join(out_dir, "classes.jsonl"), records,
-                                         export_io.class_names((settings or {}).get("dataset", getattr(args, "dataset", None)), C))
+            export_io.write_classes_file(os.path.join(out_dir, "classes.jsonl"), records, class_names)
             if records and all(r["given"] is not None for r in records):
                 class_summary = export_io.classification_figures([r["row"] for r in records], [r["given"] for r in records])
     if rank == 0:
         info = {"split": getattr(data_loader.dataset, "split", None) if hasattr(data_loader, "dataset") else None,
-                "products": list(products), "high_thre": high_thre, "low_thre": low_thre, "ignore_index": ignore_index,
-                "crop_size": args.crop_size, "scales": EVAL_SCALES, "backbone": getattr(args, "backbone", None),
-                "num_classes": args.num_classes, "world_size": world}
-        if par_mask:
-            info["par"] = {"num_iter": seg_helper.PAR_NUM_ITER, "dilations": list(seg_helper.PAR_DILATIONS), "downscale": par_downscale}
+                "products": list(req.products), "high_thre": thresholds["high_thre"], "low_thre": thresholds["low_thre"],
+                "ignore_index": thresholds["ignore_index"], "crop_size": args.crop_size, "scales": EVAL_SCALES,
+                "backbone": getattr(args, "backbone", None), "num_classes": nc, "world_size": world}
+        if req.par_mask:
+            info["par"] = {"num_iter": seg_helper.PAR_NUM_ITER, "dilations": list(seg_helper.PAR_DILATIONS), "downscale": req.par_downscale}
         if classes is not None:                     # (unset: the manifest keeps today's keys)
             info["classes"] = classes
-        if predicted:
+        if req.predicted:
             info.update({"cls_thre": float(cls_thre), "cls_min": int(cls_min)})
             if class_summary is not None:
                 info["classes_vs_given"] = class_summary
-        if overlay:
+        if req.overlay:
             info["overlay_alpha"] = float(overlay_alpha)
-        if btable is not None:
-            info["boundary"] = btable.settings()
-        if pictures:
+        if "boundary" in logs:
+            info["boundary"] = logs["boundary"].table.settings()
+        if req.pictures:
             info["camheat"] = {"ramp": "jet-int", "panel_colour": list(seg_helper.PANEL_COLOUR)}
-        info.update(settings or {})
+        info.update(settings)
         export_io.write_manifest_file(out_dir, info, images)
     res = {"images": len(writer.images), "seconds": seconds, "img_per_s": len(writer.images) / seconds if seconds > 0 else 0.0,
            "bytes_written": writer.bytes_written}
-    if scores:
-        res["scores"] = score_summary
-    if boundary:
-        res["boundary"] = band_summary
-    if predicted:
-        res["class_wait_seconds"] = class_wait
+    for flag in logs:
+        res[flag] = summaries.get(flag)             # None on the other ranks
+    if req.predicted:
+        res["class_wait_seconds"] = predict_rows.wait_seconds
         if class_summary is not None:
             res["classes"] = class_summary
     return res

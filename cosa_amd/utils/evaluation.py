@@ -7,6 +7,7 @@ ranks at the end (the reference gathers every prediction map on rank 0 through t
 """
 import json
 import math
+import os
 import warnings
 
 import numpy as np
@@ -337,3 +338,43 @@ def gather_records(local):
         dist.all_gather_object(shards, local)
         return merge_records(shards) if dist.get_rank() == 0 else None
     return merge_records([local])
+
+
+def local_score_records(meta, rows, rank, world, widths=None):
+    """This rank's [(dataset position, score_record)] from host data alone.  `meta`: per scored image, in the order it was scored,
+    (name, class row, h, w); `rows`: its counters.  A loader that deals the items round-robin (DistributedSampler(shuffle=False),
+    export_shard) hands rank r the dataset positions r, r + world, ...: the k-th item of this rank is r + k world.  `present` is the class
+    row's non-zero entries as 1-based class ids; `widths` (row index -> d) is given for boundary rows and only then the records carry `d`."""
+    return [(rank + k * world, score_record(name, h, w, (torch.nonzero(torch.as_tensor(cl).reshape(-1)).reshape(-1) + 1).tolist(), rows[k],
+                                            None if widths is None else widths[k])) for k, (name, cl, h, w) in enumerate(meta)]
+
+
+class ScoreLog:
+    """One per-image score table -- ImageScores, or BoundaryScores where `boundary` = (ratio, fixed d) is given -- with the host facts of
+    its rows (name, class row, size), from the first image to the score file.  `add` launches and returns; `write` is the table's one
+    device-to-host copy, the gather over the ranks and rank 0's file."""
+
+    def __init__(self, num_classes, map_names, pseudo_flags, loader, shards, device, boundary=None):
+        try:                                          # a guess, the table grows: this rank's share of the loader's items (shards = 1
+            capacity = len(loader) // max(int(shards), 1) + 1      # where the loader is the rank's own share already)
+        except TypeError:
+            capacity = 64
+        kind, kw = (ImageScores, {}) if boundary is None else (BoundaryScores, {"ratio": boundary[0], "d": boundary[1]})
+        self.table, self.meta = kind(num_classes, map_names, pseudo_flags, capacity, device, **kw), []
+
+    def add(self, name, class_row, H, W, gt, maps):
+        """the uint8 device maps of one image (H W elements each) against its ground truth, no host wait; `class_row`: a HOST tensor"""
+        self.table.add(len(self.meta), gt.reshape(H, W), [m.reshape(H, W) for m in maps])
+        self.meta.append((name, class_row, int(H), int(W)))
+
+    def write(self, path, settings, rank=0, world=1):
+        """-> on rank 0 the records of every rank in dataset order, written to `path` under `settings` plus what the table knows (maps,
+        pseudo, num_classes, world_size, and boundary for a band table); elsewhere None"""
+        widths = getattr(self.table, "widths", None)                    # a band table's d per row
+        records = gather_records(local_score_records(self.meta, self.table.rows(len(self.meta)), rank, world, widths))
+        if rank == 0:
+            settings = dict(settings, maps=self.table.map_names, pseudo=self.table.pseudo_flags, num_classes=self.table.num_classes,
+                            world_size=world, **({} if widths is None else {"boundary": self.table.settings()}))
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            write_score_file(path, settings, records)
+        return records

@@ -241,6 +241,50 @@ def test_second_call_reuses_buffers(tmp_path):
     assert mem[2] <= mem[1], mem
 
 
+EVERYTHING = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "pseudo_par", "pseudo_aux_par", "overlay", "camheat", "camheat_aux", "panel")
+ONE_AT_A_TIME = [(("seg",), dict(getcrf=True, scores=True, boundary=True, boundary_d=2)), (("pseudo", "pseudo_aux", "rawcam", "rawcam_aux"), {}),
+                 (("pseudo_par", "pseudo_aux_par"), {}), (("seg", "overlay"), {}), (("rawcam", "camheat"), {}), (("rawcam_aux", "camheat_aux"), {}),
+                 (("panel",), {}), (("camheat_aux", "panel"), {})]
+NOT_PRODUCTS = ("manifest.json", "scores.jsonl", "boundary_scores.jsonl")
+
+
+@pytest.fixture(scope="module")
+def all_at_once(tmp_path_factory):
+    """three images with two present classes each and one with none (no pictures, k_live 0), every product in one run"""
+    from cosa_amd import evaluation_engine as ee
+    args, model, loader = _model_and_loader(C=4, S=64, n=3)
+    rng = np.random.default_rng(9)
+    img = torch.from_numpy(rng.standard_normal((1, 3, 37, 41)).astype(np.float32))
+    lab = torch.from_numpy(rng.integers(0, 5, (1, 37, 41)).astype(np.int64))
+    loader.append(("img_03", img, lab, torch.zeros(1, 4)))
+    root = tmp_path_factory.mktemp("all_at_once")
+    ee.export_predictions(model, loader, args, root, what=EVERYTHING, getcrf=True, scores=True, boundary=True, boundary_d=2)
+    return args, model, loader, root, {k: b for k, b in _tree(root).items() if k not in NOT_PRODUCTS}
+
+
+@pytest.mark.parametrize("what,kw", ONE_AT_A_TIME, ids=["+".join(w) for w, _ in ONE_AT_A_TIME])
+def test_all_at_once_equals_one_at_a_time(all_at_once, tmp_path, what, kw):
+    """every slot offset of the packed record at once (the pictures behind the overlay behind seg_crf, the panel's heat plane with and
+    without camheat files) against runs that lay out one kind of slot each: the same bytes in every product file, the same counters"""
+    from cosa_amd import evaluation_engine as ee
+    from cosa_amd.utils import evaluation
+    args, model, loader, root, everything = all_at_once
+    ee.export_predictions(model, loader, args, tmp_path, what=what, **kw)
+    files = {k: b for k, b in _tree(tmp_path).items() if k not in NOT_PRODUCTS}
+    dirs = {os.path.dirname(k) for k in files}
+    assert len(dirs) == len(what) + bool(kw.get("getcrf")) and len(files) >= 3 * len(dirs)          # the picture-free image has fewer files
+    for k, b in files.items():
+        assert k in everything and b == everything[k], k
+    for f in ("scores.jsonl", "boundary_scores.jsonl") if kw else ():
+        (st_a, rec_a), (st_b, rec_b) = evaluation.read_score_file(root / f), evaluation.read_score_file(tmp_path / f)
+        assert st_b["maps"] == ["seg", "seg_crf"] and [r["name"] for r in rec_a] == [r["name"] for r in rec_b] == [it[0] for it in loader]
+        for ra, rb in zip(rec_a, rec_b):
+            (na, va, ca), (nb, vb, cb) = evaluation.split_row(ra["row"], args.num_classes), evaluation.split_row(rb["row"], args.num_classes)
+            assert (na, va, ra.get("d")) == (nb, vb, rb.get("d"))
+            for m, name in enumerate(st_b["maps"]):
+                assert np.array_equal(ca[st_a["maps"].index(name)], cb[m]), (f, ra["name"], name)
+
+
 def test_predict_command_line_end_to_end(tmp_path, capsys):
     """python -m cosa_amd.predict on a tiny VOC-shaped tree: checkpoint in the trainer's format, `val` with labels, `test` without"""
     from cosa_amd import predict
