@@ -101,18 +101,102 @@ __device__ __forceinline__ float wave_sum(float v)
 // aux blend b -- the defaults' 4 x 0.25 included --, so |v| < 16 carries every add for every loss weight g < 16; the entry point admits
 // weights in [0, 1] each, W <= 4, so g < 4 there.  The cell total is bounded by the same W g (all pixels once), far inside the 15 integer bits that
 // 1024 adds below 16 could fill (48 + 15 bits + sign).  A larger g may trip the check: the sticky flag then gives NaN, never a wrapped sum.
-// (Round 4 bounded |v| < 1 at 52 fractional bits, which a weight g >= 2 with few foreground pixels could trip: ADVICE r4.  This comment used
-// to give 0.5 g per add and g < 32 for the defaults; summed over all four groups it is g, hence g < 16.)
+// Both backward kernels add into the cells of scatter_begin / scatter_flush below under this one argument: it asks W g < 16, which
+// seg_loss_bwd_kernel meets as above and cam_ce_bwd_kernel with W = g = 1 (two groups of weight 0.5, a unit upstream gradient).
 __device__ __forceinline__ unsigned long long fix32(float v, unsigned long long *flag)
 {
     if (!(__builtin_fabsf(v) < 2147483648.0f)) { atomicOr(flag, 1ull); return 0ull; }
     return (unsigned long long)(long long)__builtin_rint((double)v * 4294967296.0);
 }
 constexpr double kFixGrad = 281474976710656.0;          // 2^48
-__device__ __forceinline__ unsigned long long fix52(float v, unsigned long long *flag)      // (the name is round 3's: 48 fractional bits since round 5)
+__device__ __forceinline__ unsigned long long fix48(float v, unsigned long long *flag)      // a gradient cell's add: 48 fractional bits, |v| < 16
 {
     if (!(__builtin_fabsf(v) < 16.0f)) { atomicOr(flag, 1ull); return 0ull; }
     return (unsigned long long)(long long)__builtin_rint((double)v * kFixGrad);
+}
+
+// ---- the up-sampled cross-entropy's shared pieces: seg_loss_* and cam_ce_* (cam_loss v3, at the end of the file) both run on these ----------
+// softmax of one quad pixel over the tile's K planes, in class order: its max and 1 / sum-exp; returns the log-sum-exp
+__device__ __forceinline__ float pixel_softmax(const float *tile, const Tap &t, int K, float &m, float &inv)
+{
+    float mx = -INFINITY;
+    for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, t));
+    float se = 0.f;
+    for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, t) - mx);
+    m = mx;
+    inv = 1.0f / se;
+    return mx + __logf(se);
+}
+
+// the class-balanced CE's label rule: 0 is background, 0 < la < K foreground, anything else (255, a label outside the classes) is ignored
+__device__ __forceinline__ bool ce_is_bg(int la) { return la == 0; }
+__device__ __forceinline__ bool ce_is_fg(int la, int K) { return la > 0 && la < K; }
+
+// backward: the pixel's coefficient on (p_k - [k == la])
+__device__ __forceinline__ float ce_coef(int la, int K, float cbg, float cfg) { return ce_is_bg(la) ? cbg : (ce_is_fg(la, K) ? cfg : 0.f); }
+
+// forward: the block's N sums -> shard (workgroup number & 63) of sums[64][N].  64 shards: thousands of workgroups adding to the same N addresses
+// serialise at ~20 ns per add; integer addition is associative, so the total does not depend on the sharding either
+template <int N>
+__device__ __forceinline__ void block_sums_to_shard(const float (&acc)[N], unsigned long long *sums, unsigned long long *flag)
+{
+    __shared__ float red[4][N];
+    const int tid = threadIdx.y * 16 + threadIdx.x, wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const float v = wave_sum(acc[i]);
+        if (lane == 0) red[wave][i] = v;
+    }
+    __syncthreads();
+    const unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (tid < N) atomicAdd(&sums[(wg & 63u) * N + tid], fix32(red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid], flag));
+}
+
+// sum i of sums[64][N] back in fp32; NaN if any add was not representable (the sticky flag)
+__device__ __forceinline__ float shard_total(const unsigned long long *fix, const unsigned long long *flag, int N, int i)
+{
+    unsigned long long t = 0;
+    for (int sh = 0; sh < 64; sh++) t += fix[sh * N + i];
+    return *flag ? __builtin_nanf("") : (float)((double)(long long)t * (1.0 / 4294967296.0));
+}
+
+// backward: the gradient cells of the block's tile live in LDS behind the logits, in 64-bit fixed point.  A cell collects 16 x 16 pixels, and
+// per-thread LDS atomics on the same four addresses serialise.  In a wave, the 4 x 4 quads whose lane numbers differ in bits 0, 1 (x) and 4, 5 (y)
+// read the same four cells whenever the up-sampling factor is 16 and the tile origin a multiple of 32 (checked, not assumed): `grouped`, the
+// kernels sum them with four butterfly steps and one lane adds.  `same`: the quad's four pixels share their four cells (always at S = 16 h).
+// The sums of dz x weight themselves stay in each kernel: under -ffp-contract=fast their rounding follows the code around them, and each
+// kernel keeps the form -- and so the bits -- it has always had.
+struct Scatter { unsigned long long *cells; bool grouped, same; };
+
+__device__ __forceinline__ Scatter scatter_begin(float *tile, const QuadCtx &c, int K)
+{
+    Scatter s;
+    s.cells = reinterpret_cast<unsigned long long *>(tile + ((K * TC * TC + 1) & ~1));
+    for (int e = threadIdx.y * 16 + threadIdx.x; e < K * TC * TC; e += 256) s.cells[e] = 0ull;
+    __syncthreads();
+    s.same = c.t[0].o00 == c.t[3].o00 && c.t[0].o11 == c.t[3].o11 && c.t[0].o01 == c.t[3].o01 && c.t[0].o10 == c.t[3].o10;
+    bool grp_ok = c.valid && s.same;
+#pragma unroll
+    for (int sft = 0; sft < 4; sft++) {
+        const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
+        grp_ok = grp_ok && __shfl_xor(c.t[0].o00, x, 64) == c.t[0].o00 && __shfl_xor(c.t[0].o11, x, 64) == c.t[0].o11;
+    }
+    s.grouped = __all(grp_ok) != 0;
+    return s;
+}
+
+// the tile's cells -> the global cells grad[B][K][hs][ws] (every thread of the block)
+__device__ __forceinline__ void scatter_flush(const Scatter &s, const QuadCtx &c, unsigned long long *grad, int b, int K, int hs, int ws)
+{
+    __syncthreads();
+    for (int e = threadIdx.y * 16 + threadIdx.x; e < K * TC * TC; e += 256) {
+        const unsigned long long v = s.cells[e];
+        if (v != 0ull) {
+            const int k = e / (TC * TC), r = e - k * TC * TC;
+            const int cy = c.cy0 + r / TC, cx = c.cx0 + r % TC;
+            if (cy < hs && cx < ws) atomicAdd(&grad[(((size_t)b * K + k) * hs + cy) * ws + cx], v);
+        }
+    }
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------
@@ -127,7 +211,6 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restri
                                                           int K, int hs, int ws, int S, float sy, float sx)
 {
     extern __shared__ __attribute__((aligned(16))) float tile[];
-    __shared__ float red[4][8];
     const int b = blockIdx.z;
     const QuadCtx c = setup(seg_lr, tile, K, hs, ws, S, sy, sx, b);
     const int Sq = S >> 1;
@@ -138,20 +221,14 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restri
         // pass 1+2: per-pixel max and sum-exp; CE terms
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            float mx = -INFINITY;
-            for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, c.t[p]));
-            float se = 0.f;
-            for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, c.t[p]) - mx);
-            m[p] = mx;
-            inv[p] = 1.0f / se;
-            const float lse = mx + __logf(se);
+            const float lse = pixel_softmax(tile, c.t[p], K, m[p], inv[p]);
             const size_t pix = (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1);
             const int la = (int)maskA[(size_t)b * SS + pix], lb = HAS_B ? (int)maskB[(size_t)b * SS + pix] : 255;
-            if (la == 0) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
-            else if (la != 255) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
+            if (ce_is_bg(la)) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
+            else if (ce_is_fg(la, K)) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
             if (HAS_B) {
-                if (lb == 0) { acc[4] += lse - tap(tile, c.t[p]); acc[5] += 1.f; }
-                else if (lb != 255) { acc[6] += lse - tap(tile + lb * TC * TC, c.t[p]); acc[7] += 1.f; }
+                if (ce_is_bg(lb)) { acc[4] += lse - tap(tile, c.t[p]); acc[5] += 1.f; }
+                else if (ce_is_fg(lb, K)) { acc[6] += lse - tap(tile + lb * TC * TC, c.t[p]); acc[7] += 1.f; }
             }
         }
         // pass 3: probabilities, 2x2 mean (the exact x0.5 bilinear), energy-grid outputs
@@ -169,28 +246,15 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restri
         for (int ch = 0; ch < 3; ch++) s_img[((size_t)b * 3 + ch) * QQ + q] = simg[((size_t)b * 3 + ch) * SS + pix0] * sd[ch] + mean[ch];
         const int32_t *bx = boxes + b * 4;
         roi[(size_t)b * QQ + q] = (c.Y >= bx[0] && c.Y < bx[1] && c.X >= bx[2] && c.X < bx[3]) ? 1.0f : 0.0f;
-        unlabel[(size_t)b * QQ + q] = ((int)maskA[(size_t)b * SS + pix0] == 255) ? 1 : 0;
+        const int la0 = (int)maskA[(size_t)b * SS + pix0];
+        unlabel[(size_t)b * QQ + q] = (ce_is_bg(la0) || ce_is_fg(la0, K)) ? 0 : 1;
     }
-    const int tid = threadIdx.y * 16 + threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) red[wave][i] = v;
-    }
-    __syncthreads();
-    // 64 shards of the 8 sums (workgroup number & 63): thousands of workgroups adding to the same 8 addresses serialise at ~20 ns per add;
-    // integer addition is associative, so the total does not depend on the sharding either
-    const unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (tid < 8) atomicAdd(&sums[(wg & 63u) * 8 + tid], fix32(red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid], flag));
+    block_sums_to_shard<8>(acc, sums, flag);
 }
 
 __global__ void seg_loss_sums_kernel(const unsigned long long *__restrict__ fix, const unsigned long long *__restrict__ flag, float *__restrict__ sums)
 {
-    if (threadIdx.x < 8) {
-        unsigned long long t = 0;
-        for (int sh = 0; sh < 64; sh++) t += fix[sh * 8 + threadIdx.x];
-        sums[threadIdx.x] = *flag ? __builtin_nanf("") : (float)((double)(long long)t * (1.0 / 4294967296.0));
-    }
+    if (threadIdx.x < 8) sums[threadIdx.x] = shard_total(fix, flag, 8, threadIdx.x);
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------
@@ -211,20 +275,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
     extern __shared__ __attribute__((aligned(16))) float tile[];       // [K][TC][TC] logits, then [K][TC][TC] gradient cells (64-bit fixed point)
     const int b = blockIdx.z;
     const QuadCtx c = setup(seg_lr, tile, K, hs, ws, S, sy, sx, b);
-    unsigned long long *gt = reinterpret_cast<unsigned long long *>(tile + ((K * TC * TC + 1) & ~1));
-    const int tid = threadIdx.y * 16 + threadIdx.x;
-    for (int e = tid; e < K * TC * TC; e += 256) gt[e] = 0ull;
-    __syncthreads();
-    // The gradient of a low-res cell collects 16 x 16 pixels: per-thread LDS atomics on the same four addresses serialise.  In a wave, the
-    // 4 x 4 quads whose lane numbers differ in bits 0, 1 (x) and 4, 5 (y) read the same four cells whenever the up-sampling factor is 16
-    // and the tile origin a multiple of 32 (checked, not assumed); then they are summed with four butterfly steps and one lane adds.
-    bool grp_ok = c.valid && c.t[0].o00 == c.t[3].o00 && c.t[0].o11 == c.t[3].o11 && c.t[0].o01 == c.t[3].o01 && c.t[0].o10 == c.t[3].o10;
-#pragma unroll
-    for (int sft = 0; sft < 4; sft++) {
-        const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
-        grp_ok = grp_ok && __shfl_xor(c.t[0].o00, x, 64) == c.t[0].o00 && __shfl_xor(c.t[0].o11, x, 64) == c.t[0].o11;
-    }
-    const bool grouped = __all(grp_ok) != 0;
+    const Scatter sc = scatter_begin(tile, c, K);
     if (c.valid) {
         const size_t SS = (size_t)S * S;
         const int Sq = S >> 1;
@@ -238,17 +289,12 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
         int la[4], lb[4];
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            float mx = -INFINITY;
-            for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, c.t[p]));
-            float se = 0.f;
-            for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, c.t[p]) - mx);
-            m[p] = mx;
-            inv[p] = 1.0f / se;
+            pixel_softmax(tile, c.t[p], K, m[p], inv[p]);
             const size_t pix = (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1);
             la[p] = (int)maskA[(size_t)b * SS + pix];
             lb[p] = HAS_B ? (int)maskB[(size_t)b * SS + pix] : 255;
-            ca[p] = la[p] == 0 ? cbgA : (la[p] != 255 ? cfgA : 0.f);
-            cb[p] = lb[p] == 0 ? cbgB : (lb[p] != 255 ? cfgB : 0.f);
+            ca[p] = ce_coef(la[p], K, cbgA, cfgA);
+            cb[p] = ce_coef(lb[p], K, cbgB, cfgB);
             dot[p] = 0.f;
         }
         if (ge != 0.f) {
@@ -259,7 +305,6 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
                 for (int p = 0; p < 4; p++) dot[p] += __expf(tap(pl, c.t[p]) - m[p]) * inv[p] * dP;
             }
         }
-        const bool same = c.t[0].o00 == c.t[3].o00 && c.t[0].o11 == c.t[3].o11 && c.t[0].o01 == c.t[3].o01 && c.t[0].o10 == c.t[3].o10;
         for (int k = 0; k < K; k++) {
             const float *pl = tile + k * TC * TC;
             const float dP = ge != 0.f ? ge * AS[((size_t)b * K + k) * QQ + q] : 0.f;
@@ -270,8 +315,8 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
                 if (HAS_B) dz[p] = ca[p] * (pk - (la[p] == k ? 1.f : 0.f)) + cb[p] * (pk - (lb[p] == k ? 1.f : 0.f)) + pk * (dP - dot[p]);
                 else dz[p] = ca[p] * (pk - (la[p] == k ? 1.f : 0.f)) + pk * (dP - dot[p]);
             }
-            unsigned long long *gp = gt + k * TC * TC;
-            if (grouped) {    // 4 x 4 quads (lanes differing in bits 0, 1, 4, 5) share their four cells: one lane adds the sum of all sixteen
+            unsigned long long *gp = sc.cells + k * TC * TC;
+            if (sc.grouped) {    // 4 x 4 quads (lanes differing in bits 0, 1, 4, 5) share their four cells: one lane adds the sum of all sixteen
                 float v00 = dz[0] * c.t[0].w00 + dz[1] * c.t[1].w00 + dz[2] * c.t[2].w00 + dz[3] * c.t[3].w00;
                 float v01 = dz[0] * c.t[0].w01 + dz[1] * c.t[1].w01 + dz[2] * c.t[2].w01 + dz[3] * c.t[3].w01;
                 float v10 = dz[0] * c.t[0].w10 + dz[1] * c.t[1].w10 + dz[2] * c.t[2].w10 + dz[3] * c.t[3].w10;
@@ -285,36 +330,28 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
                     v11 += __shfl_xor(v11, x, 64);
                 }
                 if (((threadIdx.y * 16 + threadIdx.x) & 0x33) == 0) {
-                    atomicAdd(gp + c.t[0].o00, fix52(v00, flag));
-                    atomicAdd(gp + c.t[0].o01, fix52(v01, flag));
-                    atomicAdd(gp + c.t[0].o10, fix52(v10, flag));
-                    atomicAdd(gp + c.t[0].o11, fix52(v11, flag));
+                    atomicAdd(gp + c.t[0].o00, fix48(v00, flag));
+                    atomicAdd(gp + c.t[0].o01, fix48(v01, flag));
+                    atomicAdd(gp + c.t[0].o10, fix48(v10, flag));
+                    atomicAdd(gp + c.t[0].o11, fix48(v11, flag));
                 }
-            } else if (same) {       // the quad's four pixels share their four low-res cells (always true for S = 16 h)
-                atomicAdd(gp + c.t[0].o00, fix52(dz[0] * c.t[0].w00 + dz[1] * c.t[1].w00 + dz[2] * c.t[2].w00 + dz[3] * c.t[3].w00, flag));
-                atomicAdd(gp + c.t[0].o01, fix52(dz[0] * c.t[0].w01 + dz[1] * c.t[1].w01 + dz[2] * c.t[2].w01 + dz[3] * c.t[3].w01, flag));
-                atomicAdd(gp + c.t[0].o10, fix52(dz[0] * c.t[0].w10 + dz[1] * c.t[1].w10 + dz[2] * c.t[2].w10 + dz[3] * c.t[3].w10, flag));
-                atomicAdd(gp + c.t[0].o11, fix52(dz[0] * c.t[0].w11 + dz[1] * c.t[1].w11 + dz[2] * c.t[2].w11 + dz[3] * c.t[3].w11, flag));
+            } else if (sc.same) {       // the quad's four pixels share their four low-res cells (always true for S = 16 h)
+                atomicAdd(gp + c.t[0].o00, fix48(dz[0] * c.t[0].w00 + dz[1] * c.t[1].w00 + dz[2] * c.t[2].w00 + dz[3] * c.t[3].w00, flag));
+                atomicAdd(gp + c.t[0].o01, fix48(dz[0] * c.t[0].w01 + dz[1] * c.t[1].w01 + dz[2] * c.t[2].w01 + dz[3] * c.t[3].w01, flag));
+                atomicAdd(gp + c.t[0].o10, fix48(dz[0] * c.t[0].w10 + dz[1] * c.t[1].w10 + dz[2] * c.t[2].w10 + dz[3] * c.t[3].w10, flag));
+                atomicAdd(gp + c.t[0].o11, fix48(dz[0] * c.t[0].w11 + dz[1] * c.t[1].w11 + dz[2] * c.t[2].w11 + dz[3] * c.t[3].w11, flag));
             } else {
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
-                    atomicAdd(gp + c.t[p].o00, fix52(dz[p] * c.t[p].w00, flag));
-                    atomicAdd(gp + c.t[p].o01, fix52(dz[p] * c.t[p].w01, flag));
-                    atomicAdd(gp + c.t[p].o10, fix52(dz[p] * c.t[p].w10, flag));
-                    atomicAdd(gp + c.t[p].o11, fix52(dz[p] * c.t[p].w11, flag));
+                    atomicAdd(gp + c.t[p].o00, fix48(dz[p] * c.t[p].w00, flag));
+                    atomicAdd(gp + c.t[p].o01, fix48(dz[p] * c.t[p].w01, flag));
+                    atomicAdd(gp + c.t[p].o10, fix48(dz[p] * c.t[p].w10, flag));
+                    atomicAdd(gp + c.t[p].o11, fix48(dz[p] * c.t[p].w11, flag));
                 }
             }
         }
     }
-    __syncthreads();
-    for (int e = tid; e < K * TC * TC; e += 256) {
-        const unsigned long long v = gt[e];
-        if (v != 0ull) {
-            const int k = e / (TC * TC), r = e - k * TC * TC;
-            const int cy = c.cy0 + r / TC, cx = c.cx0 + r % TC;
-            if (cy < hs && cx < ws) atomicAdd(&grad[(((size_t)b * K + k) * hs + cy) * ws + cx], v);
-        }
-    }
+    scatter_flush(sc, c, grad, b, K, hs, ws);
 }
 
 __global__ __launch_bounds__(256) void seg_loss_grad_kernel(const unsigned long long *__restrict__ fix, const unsigned long long *__restrict__ flag,
@@ -389,6 +426,27 @@ __device__ __forceinline__ float bilerp_fma(const float *pl, int w, int y0, int 
     return __builtin_fmaf(r0, ly0, r1 * ly1);
 }
 
+// the bilinear taps of full-resolution pixel (py, px) in one h x w scale: rows, columns, and the columns of the mirrored pixel (the flipped half)
+struct ScaleTaps { int h, w, y0, y1, x0, x1, f0, f1; float ly0, ly1, lx0, lx1, fl0, fl1; };
+
+__device__ __forceinline__ ScaleTaps scale_taps(int py, int px, int h, int w, int S)
+{
+    ScaleTaps t;
+    t.h = h; t.w = w;
+    src_index(py, h, (float)h / (float)S, t.y0, t.y1, t.ly0, t.ly1);
+    src_index(px, w, (float)w / (float)S, t.x0, t.x1, t.lx0, t.lx1);
+    src_index(S - 1 - px, w, (float)w / (float)S, t.f0, t.f1, t.fl0, t.fl1);
+    return t;
+}
+
+// class k of image b at that pixel in scale `p` [2B,K,h,w]: the original half plus the un-flipped flipped half
+__device__ __forceinline__ float scale_value(const float *p, const ScaleTaps &t, int b, int B, int K, int k)
+{
+    const float *a = p + ((size_t)b * K + k) * t.h * t.w;
+    const float *f = p + ((size_t)(b + B) * K + k) * t.h * t.w;
+    return bilerp_fma(a, t.w, t.y0, t.y1, t.x0, t.x1, t.ly0, t.ly1, t.lx0, t.lx1) + bilerp_fma(f, t.w, t.y0, t.y1, t.f0, t.f1, t.ly0, t.ly1, t.fl0, t.fl1);
+}
+
 // One WAVE per output cell, the class index on the lane (k = lane, lane + 64): every summed logit is evaluated once (the serial version
 // recomputed it in three passes and ran 12 544 threads in total), max / sum are wave reductions.
 // AFTER = true is the reference's other branch (seg_helper.py:558-561, --after_softmax true): the softmax runs over all K channels of
@@ -425,15 +483,7 @@ __global__ __launch_bounds__(256) void cam_target_kernel(SegScales sc, const flo
                 const int py = Y[p >> 1], px = X[p & 1];
                 float acc = 0.f;
                 for (int s2 = 0; s2 < sc.n; s2++) {
-                    const int h = sc.h[s2], w = sc.w[s2];
-                    int y0, y1, x0, x1, f0, f1;
-                    float ly0, ly1, lx0, lx1, fl0, fl1;
-                    src_index(py, h, (float)h / (float)S, y0, y1, ly0, ly1);
-                    src_index(px, w, (float)w / (float)S, x0, x1, lx0, lx1);
-                    src_index(S - 1 - px, w, (float)w / (float)S, f0, f1, fl0, fl1);
-                    const float *a = sc.p[s2] + ((size_t)b * K + k) * h * w;
-                    const float *f = sc.p[s2] + ((size_t)(b + B) * K + k) * h * w;
-                    const float v = bilerp_fma(a, w, y0, y1, x0, x1, ly0, ly1, lx0, lx1) + bilerp_fma(f, w, y0, y1, f0, f1, ly0, ly1, fl0, fl1);
+                    const float v = scale_value(sc.p[s2], scale_taps(py, px, sc.h[s2], sc.w[s2], S), b, B, K, k);
                     acc = s2 == 0 ? v : acc + v;
                 }
                 zz = ((AFTER || present) ? acc : -1e5f) * inv_temp;
@@ -642,6 +692,33 @@ static int check_shapes(int B, int K, int hs, int ws, int S)
     return COSA_OK;
 }
 
+// the launch geometry of the four tile kernels (seg_loss_fwd / _bwd, cam_ce_fwd / _bwd): a block of 16 x 16 quads per 32 x 32 pixels, the
+// forward's LDS (the logits tile) and the backward's (the tile, then its 64-bit gradient cells)
+struct TileLaunch { dim3 grid, blk; float sy, sx; size_t lds_fwd, lds_bwd; };
+
+static TileLaunch tile_launch(int B, int K, int hs, int ws, int S)
+{
+    // lds_bwd is 432 bytes per class: above 64 KB from K = 152, where seg_loss_bwd_kernel's entry point raises the kernel's limit;
+    // cam_ce_bwd_kernel has K <= 128 (54 KB) and needs no such step
+    return {dim3((S + 31) / 32, (S + 31) / 32, B), dim3(16, 16), (float)hs / (float)S, (float)ws / (float)S, (size_t)K * TC * TC * sizeof(float),
+            (size_t)((K * TC * TC + 1) & ~1) * sizeof(float) + (size_t)K * TC * TC * sizeof(unsigned long long)};
+}
+
+// the per-scale teacher segs of cosa_cam_loss_targets_m / cosa_cam_label as the kernels take them: 1 to 4 scales, none null or empty
+static int pack_scales(const char *who, const float *const *seg_scales, const int *hs, const int *ws, int n_scales, SegScales *sc)
+{
+    COSA_REQUIRE(seg_scales && hs && ws, "%s: null pointer", who);
+    COSA_REQUIRE(n_scales >= 1 && n_scales <= 4, "%s: 1 to 4 scales (got %d)", who, n_scales);
+    sc->n = n_scales;
+    for (int i = 0; i < 4; i++) {
+        COSA_REQUIRE(i >= n_scales || (seg_scales[i] && hs[i] > 0 && ws[i] > 0), "%s: scale %d is null or empty", who, i);
+        sc->p[i] = i < n_scales ? seg_scales[i] : nullptr;
+        sc->h[i] = i < n_scales ? hs[i] : 1;
+        sc->w[i] = i < n_scales ? ws[i] : 1;
+    }
+    return COSA_OK;
+}
+
 /* scratch of the two entry points below: the 64-bit fixed-point sums (8 of the forward, B*K*hs*ws gradient cells of the backward) */
 extern "C" size_t cosa_seg_loss_workspace_bytes(int B, int K, int hs, int ws)
 {
@@ -667,14 +744,10 @@ extern "C" int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, 
     unsigned long long *flag = fix + 64 * 8 + (size_t)B * K * hs * ws;            // reset here, read by both conversions (a forward always precedes its backward)
     COSA_HIP_CHECK(hipMemsetAsync(fix, 0, 64 * 8 * sizeof(unsigned long long), st));
     COSA_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned long long), st));
-    const dim3 grid((S + 31) / 32, (S + 31) / 32, B), blk(16, 16);
-    const size_t lds = (size_t)K * TC * TC * sizeof(float);
-    if (maskB)
-        hipLaunchKernelGGL(seg_loss_fwd_kernel<true>, grid, blk, lds, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K,
-                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
-    else
-        hipLaunchKernelGGL(seg_loss_fwd_kernel<false>, grid, blk, lds, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K,
-                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
+    const TileLaunch t = tile_launch(B, K, hs, ws, S);
+    const auto kern = maskB ? seg_loss_fwd_kernel<true> : seg_loss_fwd_kernel<false>;
+    hipLaunchKernelGGL(kern, t.grid, t.blk, t.lds_fwd, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K, hs, ws, S,
+                       t.sy, t.sx);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_loss_sums_kernel, dim3(1), dim3(64), 0, st, fix, flag, sums);
     COSA_LAUNCH_CHECK();
@@ -711,22 +784,17 @@ extern "C" int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA,
     unsigned long long *fix = static_cast<unsigned long long *>(workspace) + 64 * 8;
     unsigned long long *flag = fix + n;
     COSA_HIP_CHECK(hipMemsetAsync(fix, 0, n * sizeof(unsigned long long), st));
-    const dim3 grid((S + 31) / 32, (S + 31) / 32, B), blk(16, 16);
-    const size_t lds = (size_t)((K * TC * TC + 1) & ~1) * sizeof(float) + (size_t)K * TC * TC * sizeof(unsigned long long);
+    const TileLaunch t = tile_launch(B, K, hs, ws, S);
     static size_t lds_set[2] = {0, 0};
     const int hb = maskB ? 1 : 0;
-    if (lds > 65536 && lds > lds_set[hb]) {
-        const void *fn = hb ? (const void *)seg_loss_bwd_kernel<true> : (const void *)seg_loss_bwd_kernel<false>;
-        COSA_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set[hb] = lds;
+    const auto kern = hb ? seg_loss_bwd_kernel<true> : seg_loss_bwd_kernel<false>;
+    if (t.lds_bwd > 65536 && t.lds_bwd > lds_set[hb]) {
+        COSA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bwd));
+        lds_set[hb] = t.lds_bwd;
     }
     const SegWeights wt = {wA_bg, wA_fg, wB_bg, wB_fg};
-    if (hb)
-        hipLaunchKernelGGL(seg_loss_bwd_kernel<true>, grid, blk, lds, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K,
-                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
-    else
-        hipLaunchKernelGGL(seg_loss_bwd_kernel<false>, grid, blk, lds, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K,
-                           hs, ws, S, (float)hs / (float)S, (float)ws / (float)S);
+    hipLaunchKernelGGL(kern, t.grid, t.blk, t.lds_bwd, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K, hs, ws, S, t.sy,
+                       t.sx);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_loss_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fix, flag, grad_seg_lr, n);
     COSA_LAUNCH_CHECK();
@@ -762,24 +830,16 @@ extern "C" int cosa_msm_loss(const float *x, const float *y, float *grad, float 
 extern "C" int cosa_cam_loss_targets_m(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
                                        float *out, int B, int K, int S, int oh, int ow, float temperature, int after_softmax, void *stream)
 {
-    COSA_REQUIRE(seg_scales && hs && ws && labels && out && n_scales >= 1 && n_scales <= 4, "cosa_cam_loss_targets: bad arguments");
+    COSA_REQUIRE(labels && out, "cosa_cam_loss_targets: null pointer");
     COSA_REQUIRE(B > 0 && K > 1 && S > 0 && oh > 0 && ow > 0 && temperature > 0.f, "cosa_cam_loss_targets: bad shape");
     COSA_REQUIRE(after_softmax == 0 || after_softmax == 1, "cosa_cam_loss_targets: after_softmax must be 0 or 1 (got %d)", after_softmax);
-    SegScales sc;
-    sc.n = n_scales;
-    for (int i = 0; i < 4; i++) {
-        sc.p[i] = i < n_scales ? seg_scales[i] : nullptr;
-        sc.h[i] = i < n_scales ? hs[i] : 1;
-        sc.w[i] = i < n_scales ? ws[i] : 1;
-    }
     COSA_REQUIRE(K <= 128, "cosa_cam_loss_targets: at most 128 classes (got %d)", K);
+    SegScales sc;
+    int rc = pack_scales("cosa_cam_loss_targets", seg_scales, hs, ws, n_scales, &sc);
+    if (rc) return rc;
     const int total = B * oh * ow;
-    if (after_softmax)
-        hipLaunchKernelGGL(cam_target_kernel<true>, dim3((total + 3) / 4), dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, oh, ow,
-                           1.0f / temperature);
-    else
-        hipLaunchKernelGGL(cam_target_kernel<false>, dim3((total + 3) / 4), dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, oh, ow,
-                           1.0f / temperature);
+    const auto kern = after_softmax ? cam_target_kernel<true> : cam_target_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((total + 3) / 4), dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, oh, ow, 1.0f / temperature);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }
@@ -1089,7 +1149,6 @@ __global__ __launch_bounds__(256) void cam_ce_fwd_kernel(const float *__restrict
                                                         int K, int hs, int ws, int S, float sy, float sx)
 {
     extern __shared__ __attribute__((aligned(16))) float tile[];
-    __shared__ float red[4][4];
     const int b = blockIdx.z;
     const QuadCtx c = setup(lr, tile, K, hs, ws, S, sy, sx, b);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1097,25 +1156,14 @@ __global__ __launch_bounds__(256) void cam_ce_fwd_kernel(const float *__restrict
         const size_t SS = (size_t)S * S;
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            float mx = -INFINITY;
-            for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, c.t[p]));
-            float se = 0.f;
-            for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, c.t[p]) - mx);
-            const float lse = mx + __logf(se);
+            float m, inv;
+            const float lse = pixel_softmax(tile, c.t[p], K, m, inv);
             const int la = (int)label[(size_t)b * SS + (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1)];
-            if (la == 0) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
-            else if (la < K) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
+            if (ce_is_bg(la)) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
+            else if (ce_is_fg(la, K)) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
         }
     }
-    const int tid = threadIdx.y * 16 + threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) red[wave][i] = v;
-    }
-    __syncthreads();
-    const unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (tid < 4) atomicAdd(&sums[(wg & 63u) * 4 + tid], fix32(red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid], flag));
+    block_sums_to_shard<4>(acc, sums, flag);
 }
 
 // sums[4] in fp32 and the loss 0.5 bg_sum / (bg_cnt + 1e-6) + 0.5 fg_sum / (fg_cnt + 1e-6)
@@ -1123,11 +1171,7 @@ __global__ void cam_ce_sums_kernel(const unsigned long long *__restrict__ fix, c
                                    float *__restrict__ loss)
 {
     __shared__ float s[4];
-    if (threadIdx.x < 4) {
-        unsigned long long t = 0;
-        for (int sh = 0; sh < 64; sh++) t += fix[sh * 4 + threadIdx.x];
-        s[threadIdx.x] = sums[threadIdx.x] = *flag ? __builtin_nanf("") : (float)((double)(long long)t * (1.0 / 4294967296.0));
-    }
+    if (threadIdx.x < 4) s[threadIdx.x] = sums[threadIdx.x] = shard_total(fix, flag, 4, threadIdx.x);
     __syncthreads();
     if (threadIdx.x == 0) loss[0] = 0.5f * (s[0] / (s[1] + 1e-6f)) + 0.5f * (s[2] / (s[3] + 1e-6f));
 }
@@ -1141,19 +1185,7 @@ __global__ __launch_bounds__(256) void cam_ce_bwd_kernel(const float *__restrict
     extern __shared__ __attribute__((aligned(16))) float tile[];       // [K][TC][TC] planes, then [K][TC][TC] gradient cells (64-bit fixed point)
     const int b = blockIdx.z;
     const QuadCtx c = setup(lr, tile, K, hs, ws, S, sy, sx, b);
-    unsigned long long *gt = reinterpret_cast<unsigned long long *>(tile + ((K * TC * TC + 1) & ~1));
-    const int tid = threadIdx.y * 16 + threadIdx.x;
-    for (int e = tid; e < K * TC * TC; e += 256) gt[e] = 0ull;
-    __syncthreads();
-    // (the wave-level grouping of seg_loss_bwd_kernel: 4 x 4 quads that read the same four cells are summed by butterflies, one lane adds)
-    const bool same = c.t[0].o00 == c.t[3].o00 && c.t[0].o11 == c.t[3].o11 && c.t[0].o01 == c.t[3].o01 && c.t[0].o10 == c.t[3].o10;
-    bool grp_ok = c.valid && same;
-#pragma unroll
-    for (int sft = 0; sft < 4; sft++) {
-        const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
-        grp_ok = grp_ok && __shfl_xor(c.t[0].o00, x, 64) == c.t[0].o00 && __shfl_xor(c.t[0].o11, x, 64) == c.t[0].o11;
-    }
-    const bool grouped = __all(grp_ok) != 0;
+    const Scatter sc = scatter_begin(tile, c, K);
     if (c.valid) {
         const size_t SS = (size_t)S * S;
         const float cbg = 0.5f / (sums[1] + 1e-6f), cfg = 0.5f / (sums[3] + 1e-6f);
@@ -1161,27 +1193,22 @@ __global__ __launch_bounds__(256) void cam_ce_bwd_kernel(const float *__restrict
         int la[4];
 #pragma unroll
         for (int p = 0; p < 4; p++) {
-            float mx = -INFINITY;
-            for (int k = 0; k < K; k++) mx = fmaxf(mx, tap(tile + k * TC * TC, c.t[p]));
-            float se = 0.f;
-            for (int k = 0; k < K; k++) se += __expf(tap(tile + k * TC * TC, c.t[p]) - mx);
-            m[p] = mx;
-            inv[p] = 1.0f / se;
+            pixel_softmax(tile, c.t[p], K, m[p], inv[p]);
             la[p] = (int)label[(size_t)b * SS + (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1)];
-            ca[p] = la[p] == 0 ? cbg : (la[p] < K ? cfg : 0.f);
+            ca[p] = ce_coef(la[p], K, cbg, cfg);
         }
         for (int k = 0; k < K; k++) {
             const float *pl = tile + k * TC * TC;
             float dz[4];
 #pragma unroll
             for (int p = 0; p < 4; p++) dz[p] = ca[p] * (__expf(tap(pl, c.t[p]) - m[p]) * inv[p] - (la[p] == k ? 1.f : 0.f));
-            unsigned long long *gp = gt + k * TC * TC;
-            if (grouped || same) {
+            unsigned long long *gp = sc.cells + k * TC * TC;
+            if (sc.grouped || sc.same) {
                 float v00 = dz[0] * c.t[0].w00 + dz[1] * c.t[1].w00 + dz[2] * c.t[2].w00 + dz[3] * c.t[3].w00;
                 float v01 = dz[0] * c.t[0].w01 + dz[1] * c.t[1].w01 + dz[2] * c.t[2].w01 + dz[3] * c.t[3].w01;
                 float v10 = dz[0] * c.t[0].w10 + dz[1] * c.t[1].w10 + dz[2] * c.t[2].w10 + dz[3] * c.t[3].w10;
                 float v11 = dz[0] * c.t[0].w11 + dz[1] * c.t[1].w11 + dz[2] * c.t[2].w11 + dz[3] * c.t[3].w11;
-                if (grouped) {
+                if (sc.grouped) {
 #pragma unroll
                     for (int sft = 0; sft < 4; sft++) {
                         const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
@@ -1191,32 +1218,24 @@ __global__ __launch_bounds__(256) void cam_ce_bwd_kernel(const float *__restrict
                         v11 += __shfl_xor(v11, x, 64);
                     }
                 }
-                if (!grouped || (tid & 0x33) == 0) {
-                    atomicAdd(gp + c.t[0].o00, fix52(v00, flag));
-                    atomicAdd(gp + c.t[0].o01, fix52(v01, flag));
-                    atomicAdd(gp + c.t[0].o10, fix52(v10, flag));
-                    atomicAdd(gp + c.t[0].o11, fix52(v11, flag));
+                if (!sc.grouped || ((threadIdx.y * 16 + threadIdx.x) & 0x33) == 0) {
+                    atomicAdd(gp + c.t[0].o00, fix48(v00, flag));
+                    atomicAdd(gp + c.t[0].o01, fix48(v01, flag));
+                    atomicAdd(gp + c.t[0].o10, fix48(v10, flag));
+                    atomicAdd(gp + c.t[0].o11, fix48(v11, flag));
                 }
             } else {
 #pragma unroll
                 for (int p = 0; p < 4; p++) {
-                    atomicAdd(gp + c.t[p].o00, fix52(dz[p] * c.t[p].w00, flag));
-                    atomicAdd(gp + c.t[p].o01, fix52(dz[p] * c.t[p].w01, flag));
-                    atomicAdd(gp + c.t[p].o10, fix52(dz[p] * c.t[p].w10, flag));
-                    atomicAdd(gp + c.t[p].o11, fix52(dz[p] * c.t[p].w11, flag));
+                    atomicAdd(gp + c.t[p].o00, fix48(dz[p] * c.t[p].w00, flag));
+                    atomicAdd(gp + c.t[p].o01, fix48(dz[p] * c.t[p].w01, flag));
+                    atomicAdd(gp + c.t[p].o10, fix48(dz[p] * c.t[p].w10, flag));
+                    atomicAdd(gp + c.t[p].o11, fix48(dz[p] * c.t[p].w11, flag));
                 }
             }
         }
     }
-    __syncthreads();
-    for (int e = tid; e < K * TC * TC; e += 256) {
-        const unsigned long long v = gt[e];
-        if (v != 0ull) {
-            const int k = e / (TC * TC), r = e - k * TC * TC;
-            const int cy = c.cy0 + r / TC, cx = c.cx0 + r % TC;
-            if (cy < hs && cx < ws) atomicAdd(&grad[(((size_t)b * K + k) * hs + cy) * ws + cx], v);
-        }
-    }
+    scatter_flush(sc, c, grad, b, K, hs, ws);
 }
 
 // v3 (c): the fixed-point cells of d L / d cam_mix -> d L / d x of plane (b, c)
@@ -1250,7 +1269,7 @@ __global__ __launch_bounds__(256) void cam_v3_adjoint_kernel(const float *__rest
 }
 
 // v3 (d): the label map of cam_lossv3_wrap straight from the per-scale low-resolution teacher segs, one thread per pixel of [B,S,S]:
-// z_k = sum over scales of (original half + un-flipped flipped half), as cam_target_kernel evaluates them; an online max / sum-exp over k.
+// z_k = sum over scales of scale_value (original half + un-flipped flipped half), what cam_target_kernel sums; an online max / sum-exp over k.
 //   AFTER = false: label = first argmax of the masked z (absent classes at -1e5), maximum probability 1 / sum_k exp((z_k - z_max) / T)
 //   AFTER = true:  softmax over all K; argmax and maximum over the present classes (background included)
 // label = 255 where the maximum probability is not above `thre`.
@@ -1260,16 +1279,10 @@ __global__ __launch_bounds__(256) void cam_label_kernel(SegScales sc, const floa
 {
     const int px = blockIdx.x * 64 + (threadIdx.x & 63), py = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
     if (px >= S || py >= S) return;
-    int y0[4], y1[4], x0[4], x1[4], f0[4], f1[4];
-    float ly0[4], ly1[4], lx0[4], lx1[4], fl0[4], fl1[4];
+    ScaleTaps t[4];
 #pragma unroll
     for (int s2 = 0; s2 < 4; s2++)
-        if (s2 < sc.n) {
-            const int h = sc.h[s2], w = sc.w[s2];
-            src_index(py, h, (float)h / (float)S, y0[s2], y1[s2], ly0[s2], ly1[s2]);
-            src_index(px, w, (float)w / (float)S, x0[s2], x1[s2], lx0[s2], lx1[s2]);
-            src_index(S - 1 - px, w, (float)w / (float)S, f0[s2], f1[s2], fl0[s2], fl1[s2]);
-        }
+        if (s2 < sc.n) t[s2] = scale_taps(py, px, sc.h[s2], sc.w[s2], S);
     const int C = K - 1;
     float m = -INFINITY, se = 0.f, best = -INFINITY;
     int bk = 0;
@@ -1279,11 +1292,7 @@ __global__ __launch_bounds__(256) void cam_label_kernel(SegScales sc, const floa
 #pragma unroll
         for (int s2 = 0; s2 < 4; s2++)
             if (s2 < sc.n) {
-                const int h = sc.h[s2], w = sc.w[s2];
-                const float *a = sc.p[s2] + ((size_t)b * K + k) * h * w;
-                const float *f = sc.p[s2] + ((size_t)(b + B) * K + k) * h * w;
-                const float v = bilerp_fma(a, w, y0[s2], y1[s2], x0[s2], x1[s2], ly0[s2], ly1[s2], lx0[s2], lx1[s2]) +
-                                bilerp_fma(f, w, y0[s2], y1[s2], f0[s2], f1[s2], ly0[s2], ly1[s2], fl0[s2], fl1[s2]);
+                const float v = scale_value(sc.p[s2], t[s2], b, B, K, k);
                 acc = s2 == 0 ? v : acc + v;
             }
         const float z = (AFTER || present) ? acc : -1e5f;
@@ -1376,14 +1385,12 @@ extern "C" int cosa_cam_lossv3(const float *cam, const uint8_t *label, float *gr
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(cam_v3_bg_kernel, dim3((B * HW + 255) / 256), dim3(256), 0, st, mix, arg, B, C, HW);
     COSA_LAUNCH_CHECK();
-    const dim3 grid((S + 31) / 32, (S + 31) / 32, B), blk(16, 16);
-    const float sy = (float)h / (float)S, sx = (float)w / (float)S;
-    hipLaunchKernelGGL(cam_ce_fwd_kernel, grid, blk, (size_t)K * TC * TC * sizeof(float), st, mix, label, fsum, flag, K, h, w, S, sy, sx);
+    const TileLaunch t = tile_launch(B, K, h, w, S);
+    hipLaunchKernelGGL(cam_ce_fwd_kernel, t.grid, t.blk, t.lds_fwd, st, mix, label, fsum, flag, K, h, w, S, t.sy, t.sx);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(cam_ce_sums_kernel, dim3(1), dim3(64), 0, st, fsum, flag, sums, loss);
     COSA_LAUNCH_CHECK();
-    const size_t lds = (size_t)((K * TC * TC + 1) & ~1) * sizeof(float) + (size_t)K * TC * TC * sizeof(unsigned long long);     // K <= 128: 55 KB
-    hipLaunchKernelGGL(cam_ce_bwd_kernel, grid, blk, lds, st, mix, label, sums, gfix, flag, K, h, w, S, sy, sx);
+    hipLaunchKernelGGL(cam_ce_bwd_kernel, t.grid, t.blk, t.lds_bwd, st, mix, label, sums, gfix, flag, K, h, w, S, t.sy, t.sx);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(cam_v3_adjoint_kernel, dim3(planes), dim3(256), 0, st, cam, gfix, flag, arg, stats, idx, grad, C, HW);
     COSA_LAUNCH_CHECK();
@@ -1394,26 +1401,18 @@ extern "C" int cosa_cam_lossv3(const float *cam, const uint8_t *label, float *gr
 extern "C" int cosa_cam_label(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels, uint8_t *out,
                               int B, int K, int S, float temperature, float segconf_thre, int after_softmax, void *stream)
 {
-    COSA_REQUIRE(seg_scales && hs && ws && labels && out, "cosa_cam_label: null pointer");
-    COSA_REQUIRE(n_scales >= 1 && n_scales <= 4, "cosa_cam_label: 1 to 4 scales (got %d)", n_scales);
+    COSA_REQUIRE(labels && out, "cosa_cam_label: null pointer");
     COSA_REQUIRE(B > 0 && B <= 65535 && K > 1 && S > 0, "cosa_cam_label: bad shape");
     COSA_REQUIRE(K <= 128, "cosa_cam_label: at most 128 classes (got %d)", K);
     COSA_REQUIRE(std::isfinite(temperature) && temperature > 0.f, "cosa_cam_label: the temperature must be finite and positive (got %g)", (double)temperature);
     COSA_REQUIRE(std::isfinite(segconf_thre), "cosa_cam_label: segconf_thre must be finite (got %g)", (double)segconf_thre);
     COSA_REQUIRE(after_softmax == 0 || after_softmax == 1, "cosa_cam_label: after_softmax must be 0 or 1 (got %d)", after_softmax);
     SegScales sc;
-    sc.n = n_scales;
-    for (int i = 0; i < 4; i++) {
-        COSA_REQUIRE(i >= n_scales || (seg_scales[i] && hs[i] > 0 && ws[i] > 0), "cosa_cam_label: scale %d is null or empty", i);
-        sc.p[i] = i < n_scales ? seg_scales[i] : nullptr;
-        sc.h[i] = i < n_scales ? hs[i] : 1;
-        sc.w[i] = i < n_scales ? ws[i] : 1;
-    }
+    int rc = pack_scales("cosa_cam_label", seg_scales, hs, ws, n_scales, &sc);
+    if (rc) return rc;
     const dim3 grid((S + 63) / 64, (S + 3) / 4, B);
-    if (after_softmax)
-        hipLaunchKernelGGL(cam_label_kernel<true>, grid, dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, 1.0f / temperature, segconf_thre);
-    else
-        hipLaunchKernelGGL(cam_label_kernel<false>, grid, dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, 1.0f / temperature, segconf_thre);
+    const auto kern = after_softmax ? cam_label_kernel<true> : cam_label_kernel<false>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, as_stream(stream), sc, labels, out, B, K, S, 1.0f / temperature, segconf_thre);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }

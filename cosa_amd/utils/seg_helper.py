@@ -1904,29 +1904,53 @@ def seg_refine_by_label(seg, cls_label, softmaxtemp, after_softmax=False):
     return F.softmax(valid_seg / softmaxtemp, dim=1)
 
 
-def cam_loss_targets(seg_scales, cls_label, S, out_hw, softmaxtemp, after_softmax=False):
-    """seg_refine_by_label(sum_scales seg, T, after_softmax)[:, 1:] bilinearly resized to `out_hw` (main.py:227-228, seg_helper.py:553-568,
-    595-597), computed from the per-scale low-res teacher segs without building the [b,K,S,S] tensor."""
-    b2, K = seg_scales[0].shape[:2]
-    B = b2 // 2
-    oh, ow = out_hw
-    out = torch.empty((B, K - 1, oh, ow), device=seg_scales[0].device, dtype=torch.float32)
+def _scale_args(seg_scales):
+    """the per-scale low-res teacher segs [2B,K,h_i,w_i] as cosa_cam_loss_targets_m / cosa_cam_label take them -> (ptrs, hs, ws, n, B, K)"""
     n = len(seg_scales)
     ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in seg_scales])
     hs = _C.int_array([t.shape[2] for t in seg_scales])
     ws = _C.int_array([t.shape[3] for t in seg_scales])
+    b2, K = seg_scales[0].shape[:2]
+    return ptrs, hs, ws, n, b2 // 2, K
+
+
+def cam_loss_targets(seg_scales, cls_label, S, out_hw, softmaxtemp, after_softmax=False):
+    """seg_refine_by_label(sum_scales seg, T, after_softmax)[:, 1:] bilinearly resized to `out_hw` (main.py:227-228, seg_helper.py:553-568,
+    595-597), computed from the per-scale low-res teacher segs without building the [b,K,S,S] tensor."""
+    ptrs, hs, ws, n, B, K = _scale_args(seg_scales)
+    oh, ow = out_hw
+    out = torch.empty((B, K - 1, oh, ow), device=seg_scales[0].device, dtype=torch.float32)
     lab = cls_label.contiguous().float()
     _C.check(_C.lib().cosa_cam_loss_targets_m(ptrs, hs, ws, n, _C.ptr(lab), _C.ptr(out), B, K, int(S), oh, ow, float(softmaxtemp),
                                               int(bool(after_softmax)), _C.stream_ptr()), "cosa_cam_loss_targets_m")
     return out
 
 
-class _MultilabelSoftMarginFn(torch.autograd.Function):
+class _ValueAndGradFn(torch.autograd.Function):
+    """a scalar loss whose kernel writes the value and d loss / d x (for a unit upstream gradient) in one call: forward saves the gradient,
+    backward scales it.  A subclass gives `launch(x, grad, loss, *rest)`, the kernel call on a contiguous x; `rest` receives no gradient."""
+
+    @classmethod
+    def forward(cls, ctx, x, *rest):
+        x = x.contiguous()
+        grad = torch.empty_like(x)
+        loss = torch.empty(1, device=x.device, dtype=torch.float32)
+        cls.launch(x, grad, loss, *rest)
+        ctx.save_for_backward(grad)
+        ctx.n_rest = len(rest)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * ctx.n_rest
+
+
+class _MultilabelSoftMarginFn(_ValueAndGradFn):
     """F.multilabel_soft_margin_loss(v, y), v = x or relu(x), value and gradient from one kernel pass (cosa_msm_loss)"""
 
     @staticmethod
-    def forward(ctx, x, y, relu):
-        x = x.contiguous()
+    def launch(x, grad, loss, y, relu):
         y = y.contiguous().float()
         if x.dim() == 4:
             B, C, H, W = x.shape
@@ -1934,18 +1958,9 @@ class _MultilabelSoftMarginFn(torch.autograd.Function):
         else:
             R, C = x.shape
             HW = 1
-        grad = torch.empty_like(x)
-        loss = torch.empty(1, device=x.device, dtype=torch.float32)
         ws = torch.empty((R + 255) // 256, device=x.device, dtype=torch.float64)
         _C.check(_C.lib().cosa_msm_loss(_C.ptr(x), _C.ptr(y), _C.ptr(grad), _C.ptr(loss), _C.ptr(ws), R, C, HW, int(relu), _C.stream_ptr()),
                  "cosa_msm_loss")
-        ctx.save_for_backward(grad)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None
 
 
 def multilabel_soft_margin(x, y, relu=False):
@@ -2032,49 +2047,29 @@ def _cam_kernel_ok(cam, S=None):
     return S is None or (S[0] == S[1] and S[0] % 2 == 0 and S[0] >= CAM_UPSAMPLE_MIN * h and S[0] >= CAM_UPSAMPLE_MIN * w)
 
 
-class _CamLossV2Fn(torch.autograd.Function):
+class _CamLossV2Fn(_ValueAndGradFn):
     """cam_lossv2 on targets at the CAM's size, value and gradient from one launch per plane (cosa_cam_lossv2)"""
 
     @staticmethod
-    def forward(ctx, cam, targets):
-        cam = cam.contiguous()
+    def launch(cam, grad, loss, targets):
         targets = targets.contiguous().float()
         B, C, h, w = cam.shape
-        grad = torch.empty_like(cam)
-        loss = torch.empty(1, device=cam.device, dtype=torch.float32)
         L = _C.lib()
         ws = _C.workspace(L.cosa_cam_lossv2_workspace_bytes(B, C), cam.device, "cam_lossv2")
         _C.check(L.cosa_cam_lossv2(_C.ptr(cam), _C.ptr(targets), _C.ptr(grad), _C.ptr(loss), B, C, h, w, _C.ptr(ws), ws.numel(), _C.stream_ptr()),
                  "cosa_cam_lossv2")
-        ctx.save_for_backward(grad)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None
 
 
-class _CamLossV3Fn(torch.autograd.Function):
+class _CamLossV3Fn(_ValueAndGradFn):
     """cam_lossv3 against a byte label map [B,S,S], value and gradient from one call (cosa_cam_lossv3); nothing of size [B,K,S,S] is written"""
 
     @staticmethod
-    def forward(ctx, cam, label):
-        cam = cam.contiguous()
+    def launch(cam, grad, loss, label):
         B, C, h, w = cam.shape
-        grad = torch.empty_like(cam)
-        loss = torch.empty(1, device=cam.device, dtype=torch.float32)
         L = _C.lib()
         ws = _C.workspace(L.cosa_cam_lossv3_workspace_bytes(B, C, h, w), cam.device, "cam_lossv3")
         _C.check(L.cosa_cam_lossv3(_C.ptr(cam), _C.ptr(label), _C.ptr(grad), _C.ptr(loss), B, C, h, w, label.shape[-1], _C.ptr(ws), ws.numel(),
                                    _C.stream_ptr()), "cosa_cam_lossv3")
-        ctx.save_for_backward(grad)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None
 
 
 def cam_lossv2_from_targets(cam, targets):
@@ -2109,13 +2104,8 @@ def cam_lossv3_wrap(cam, seg_ps, seg_confident_thre=0.25):
 def cam_label_from_scales(seg_scales, cls_label, S, softmaxtemp, segconf_thre, after_softmax=False):
     """cam_lossv3_wrap's label map, bytes [B,S,S], from the per-scale low-res teacher segs (cam_loss_targets' inputs) without building the
     [b,K,S,S] tensor: argmax of seg_refine_by_label(sum_scales seg, T, after_softmax), 255 where its maximum is not above segconf_thre"""
-    b2, K = seg_scales[0].shape[:2]
-    B = b2 // 2
+    ptrs, hs, ws, n, B, K = _scale_args(seg_scales)
     out = torch.empty((B, int(S), int(S)), device=seg_scales[0].device, dtype=torch.uint8)
-    n = len(seg_scales)
-    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in seg_scales])
-    hs = _C.int_array([t.shape[2] for t in seg_scales])
-    ws = _C.int_array([t.shape[3] for t in seg_scales])
     lab = cls_label.contiguous().float()
     _C.check(_C.lib().cosa_cam_label(ptrs, hs, ws, n, _C.ptr(lab), _C.ptr(out), B, K, int(S), float(softmaxtemp), float(segconf_thre),
                                      int(bool(after_softmax)), _C.stream_ptr()), "cosa_cam_label")

@@ -550,7 +550,9 @@ int cosa_seg_loss_backward(const float *seg_lr, const float *maskA, const float 
  *   weight must lie in [0, 1] (non-finite ones are refused too): COSA_EINVAL, nothing is launched.  The entry points above are these with
  *   both maps and 0.25 x 4 -- same kernels, same bits.  Fixed-point range of the gradient cells: every value is carried while
  *   g_seg (wA_bg + wA_fg + wB_bg + wB_fg) < 16, i.e. g_seg < 16 for the table above; beyond it the result may be NaN (sticky flag), never a
- *   wrapped sum. */
+ *   wrapped sum.
+ *   Labels: 0 is background, 0 < label < K foreground, every other value is ignored -- 255 (K <= 255 keeps it free) and, exactly as 255 is,
+ *   a label in [K, 255): it enters no sum, no count and no gradient, and its quad counts as unlabelled in `unlabel`. */
 int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
                             const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
                             int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream);
@@ -571,7 +573,9 @@ int cosa_msm_loss(const float *x, const float *y, float *grad, float *loss, void
 int cosa_cam_loss_targets(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
                           float *out, int B, int K, int S, int oh, int ow, float temperature, void *stream);
 /* ... with the reference's other branch (seg_helper.py:558-561, --after_softmax true) selectable: after_softmax = 1 takes the softmax of
- * sum_scales / T over all K channels and sets the channels of absent classes to zero afterwards; 0 is the call above, bit for bit.      */
+ * sum_scales / T over all K channels and sets the channels of absent classes to zero afterwards; 0 is the call above, bit for bit.
+ * 1 to 4 scales; a null or empty scale (seg_scales[i] NULL, hs[i] or ws[i] <= 0) is refused as cosa_cam_label refuses it: COSA_EINVAL,
+ * nothing is launched.                                                                                                              */
 int cosa_cam_loss_targets_m(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels,
                             float *out, int B, int K, int S, int oh, int ow, float temperature, int after_softmax, void *stream);
 /* --camloss_version v2 | v3 (utils/seg_helper.py:604-653).  Both normalise every plane of relu(cam) to n = (r - min r) / (max r + 1e-4) with

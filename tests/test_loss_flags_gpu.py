@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(6, 4, 64), (3, 8, 64), (21, 12, 192)]      # factor 16 (butterfly-grouped adds) / factor 8 (per-pixel adds) / several blocks, K = 21
+SHAPES = [(6, 4, 64), (3, 8, 64), (21, 12, 192)]      # factor 16 (butterfly-grouped adds) / factor 8 (each quad's own sum) / several blocks, K = 21
 # (fg_alpha, aux_alpha, auxiliary label map given)
 SETTINGS = [(0.3, 0.5, True), (0.5, 0.25, True), (1.0, 0.5, True), (0.0, 1.0, True), (0.7, 0.0, True), (0.5, 0.5, False), (0.3, 0.5, False)]
 W_SEG, W_REG = 0.1, 0.05
@@ -32,23 +32,23 @@ def _layer():
 
 
 @functools.lru_cache(maxsize=None)
-def _inputs(K, hs, S):
-    """B = 2, one full and one partial box; label maps over {0, some classes, 255}"""
+def _inputs(K, hs, S, ws=None):
+    """B = 2, one full and one partial box; label maps over {0, some classes, 255}; logits hs x hs, or hs x ws"""
     torch.manual_seed(100 + K)
     rng = np.random.default_rng(100 + K)
     B = 2
     vals = [0, 1, K - 1, 255] if K < 8 else [0, 1, 5, K - 1, 255]
     mk = lambda: torch.from_numpy(rng.choice(vals, size=(B, S, S)).astype(np.float32))
-    return dict(B=B, K=K, hs=hs, S=S, seg=torch.randn(B, K, hs, hs) * 2, mA=mk(), mB=mk(), simg=torch.randn(B, 3, S, S),
+    return dict(B=B, K=K, hs=hs, S=S, seg=torch.randn(B, K, hs, ws or hs) * 2, mA=mk(), mB=mk(), simg=torch.randn(B, 3, S, S),
                 box=torch.tensor([[0, S, 0, S], [3, S - 4, 0, S - 14]], dtype=torch.int16),
                 AS=torch.randn(B, K, S // 2, S // 2) * 1e4)
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle_energy(K, hs, S):
+def _oracle_energy(K, hs, S, ws=None):
     """the regulariser does not depend on the flags: value and gradient w.r.t. the low-resolution logits, once per shape"""
     from oracle import torch_oracle as to
-    c = _inputs(K, hs, S)
+    c = _inputs(K, hs, S, ws)
     lr = c["seg"].clone().requires_grad_(True)
     up = F.interpolate(lr, size=(S, S), mode="bilinear", align_corners=False)
     l_reg, g_up = to.energy_loss_and_grad(c["simg"], up.detach(), c["mA"].to(torch.uint8).unsqueeze(1), c["box"].numpy())
@@ -97,6 +97,32 @@ def _check_against_oracle(c, mA, mB, a, b, energy):
 def test_weighted_seg_and_energy_loss_vs_oracle(K, hs, S, a, b, aux):
     c = _inputs(K, hs, S)
     _check_against_oracle(c, c["mA"], c["mB"] if aux else None, a, b, _oracle_energy(K, hs, S))
+
+
+def test_per_pixel_scatter_shape_vs_oracle():
+    """5 x 7 cells under 64 x 64 pixels: factors 12.8 and 9.14, so quads straddle cell borders and their gradient goes through the scatter's
+    per-pixel adds (factor 16 takes the butterfly-grouped adds, factor 8 the quad's own sum).  The bars of the test above."""
+    K, hs, ws, S = 5, 5, 7, 64
+    c = _inputs(K, hs, S, ws)
+    assert c["seg"].shape[-2:] == (hs, ws)
+    _check_against_oracle(c, c["mA"], c["mB"], 0.3, 0.5, _oracle_energy(K, hs, S, ws))
+
+
+def test_labels_outside_the_classes_are_ignored_like_255():
+    """a label in [K, 255) is outside the contract; the kernels ignore it exactly as they ignore 255 (it used to index past the LDS tile):
+    every 255 of both maps rewritten to 200 gives the same bytes in the sums, the energy-grid outputs and the gradient"""
+    c = _inputs(6, 4, 64)
+    assert int((c["mA"] == 255).sum()) > 0 and int((c["mB"] == 255).sum()) > 0
+    other = dict(c, mA=torch.where(c["mA"] == 255, torch.full_like(c["mA"], 200.0), c["mA"]),
+                 mB=torch.where(c["mB"] == 255, torch.full_like(c["mB"], 200.0), c["mB"]))
+    assert int((other["mA"] == 255).sum()) == 0 and int((other["mB"] == 255).sum()) == 0 and int((other["mA"] == 200).sum()) > 0
+    weights = (0.35, 0.15, 0.35, 0.15)
+    ref, out = _raw_seg(c, weights), _raw_seg(other, weights)
+    assert ref["rc_f"] == ref["rc_b"] == out["rc_f"] == out["rc_b"] == 0
+    assert torch.isfinite(ref["grad"]).all() and float(ref["grad"].abs().max()) > 0 and float(ref["sums"][3]) > 0
+    assert int(ref["unl"].sum()) > 0
+    for k in ("sums", "s_seg", "s_img", "roi", "unl", "grad"):
+        assert torch.equal(_bits(ref[k]), _bits(out[k])), k
 
 
 @pytest.mark.parametrize("a,b", [(0.3, 0.5), (1.0, 0.25)])
@@ -227,6 +253,18 @@ def test_refused_null_pointers_and_modes_launch_nothing():
         assert _raw_cam([seg], lab, 64, out, 0.01, mode) == 1
     torch.cuda.synchronize()
     assert bool((out == SENT).all())
+    # a null or an empty scale: refused as cosa_cam_label refuses it, with a message that names the scale
+    two = [seg, torch.randn(4, 6, 4, 4, device="cuda")]
+    n = len(two)
+    hs, ws = _C.int_array([t.shape[2] for t in two]), _C.int_array([t.shape[3] for t in two])
+    targets = lambda ptrs, hs: L.cosa_cam_loss_targets_m(ptrs, hs, ws, n, _C.ptr(lab), _C.ptr(out), 2, 6, 64, 4, 4, 0.01, 0, _C.stream_ptr())
+    assert targets((ctypes.c_void_p * n)(two[0].data_ptr(), None), hs) == 1
+    assert b"scale 1" in L.cosa_last_error()
+    assert targets((ctypes.c_void_p * n)(*[t.data_ptr() for t in two]), _C.int_array([8, 0])) == 1
+    assert b"scale 1" in L.cosa_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == SENT).all())
+    assert targets((ctypes.c_void_p * n)(*[t.data_ptr() for t in two]), hs) == 0
     assert _raw_cam([seg], lab, 64, out, 0.01, 1) == 0 and _raw_cam([seg], lab, 64, out, 0.0, 1) == 1
 
 

@@ -1,6 +1,6 @@
 """A/B of two builds of libcosa_hip.so on the monitor kernels and the fp32 attention forward, INTERLEAVED in one process.
 
-    python tools/ab_monitor_libs.py parent.so new.so [--json profiles/monitor_kernels_ab.json] [--bits-only]
+    python tools/ab_monitor_libs.py parent.so new.so [--json profiles/monitor_kernels_ab.json] [--bits-only] [--cases monitors|losses]
 
 Bits: cosa_attn_fwd_f32 and cosa_attn_stats_f32 at B = 2, H = 2, N in {1, 33, 161} (a single key, a tail tile, two query blocks with six key
 tiles) and cosa_range_stats_f32 at 3 x 7 and 3 x 64: every output byte of the second build against the first's.  Speed: the same entry
@@ -8,7 +8,14 @@ points and cosa_teacher_check / cosa_gt_stats at the workload's shapes (b = 16 x
 HIP event pair per call, the builds taking turns, 5 warm-up and 30 timed calls each, the median per entry point.  The first build is
 loaded a second time from a copy of its file (`again`): what its median differs from the first's by, or the first's own interquartile
 range if that is larger, is this machine's spread, and the second build passes an entry point if its median is not slower by more than
-that.  The counters of the two timed monitors are compared as well.  Exit status 1 if a byte differs or an entry point fails."""
+that.  The counters of the two timed monitors are compared as well.  Exit status 1 if a byte differs or an entry point fails.
+
+--cases losses (-> profiles/loss_kernels_ab.json): the dense losses of csrc/loss_kernels.hip by the same rules.  Their
+sums are integers, so every output is the same bytes whatever the scheduling.  Bits: cosa_seg_loss_forward_w then _backward_w at B = 2 with
+and without the second label map, weights 0.25 x 4 and (0.21, 0.49, 0.09, 0.21), at (K, hs, ws, S) = (6, 4, 4, 64) (factor 16: grouped
+adds), (3, 8, 8, 64) (factor 8), (5, 5, 7, 64) (quads straddle cells: per-pixel adds), (6, 4, 4, 72) (edge blocks) and (21, 12, 12, 192);
+cosa_cam_lossv3 at tests/test_camloss_gpu.py's V3_SHAPES and at a 5 x 7 plane; cosa_cam_loss_targets_m and cosa_cam_label on one and on
+three scales, K = 6 and 70, both after_softmax modes.  Speed: the same entry points at b = 16, K = 21, 28 x 28 -> 448, scales of 28, 14, 42."""
 import argparse, ctypes, json, os, shutil, statistics, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,6 +25,9 @@ P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 SIGS = {"cosa_attn_fwd_f32": [P, P, I, I, I, I, F, I, I, P], "cosa_attn_stats_f32": [P, I, I, I, I, F, L, P, P],
         "cosa_range_stats_f32": [P, L, I, L, P, P], "cosa_gt_stats": [P] * 6 + [I] * 6 + [P, P],
         "cosa_teacher_check": [P] * 12 + [I] * 7 + [F, P, P, Z, P]}
+SIGS.update({"cosa_seg_loss_forward_w": [P] * 10 + [I] * 5 + [P, Z, P], "cosa_seg_loss_backward_w": [P] * 9 + [F] * 4 + [I] * 5 + [P, Z, P],
+             "cosa_cam_lossv3": [P] * 4 + [I] * 5 + [P, Z, P], "cosa_cam_loss_targets_m": [P, P, P, I, P, P] + [I] * 5 + [F, I, P],
+             "cosa_cam_label": [P, P, P, I, P, P, I, I, I, F, F, I, P]})
 WARMUP, TIMED = 5, 30
 
 
@@ -99,6 +109,114 @@ def monitors(B, K, S, h, w, seed):
     return {"cosa_teacher_check": teacher, "cosa_gt_stats": gt_stats}
 
 
+def label_maps(g, n, B, K, S):
+    """n float label maps [B,S,S] of 4 x 4 patches of one class, one patch in K + 1 ignored (255)"""
+    m = torch.randint(0, K + 1, (n, B, S // 4, S // 4), generator=g, device=dev).repeat_interleave(4, 2).repeat_interleave(4, 3)
+    return [t.contiguous() for t in torch.where(m == K, 255, m).float()]
+
+
+def seg_loss(B, K, hs, ws, S, seed, settings):
+    """cosa_seg_loss_forward_w / _backward_w per (second map given, weights): random logits and AS, non-unit upstream gradients, boxes that
+    cut into the image -> {"seg_loss ... <output>": forward then backward, one entry per output} and the two entry points alone (for the clock)"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    Sq = S // 2
+    seg, simg, AS = rand(g, B, K, hs, ws) * 2, rand(g, B, 3, S, S), rand(g, B, K, Sq, Sq) * 1e4
+    mA, mB = label_maps(g, 2, B, K, S)
+    boxes = torch.tensor([[8 * (b % 3), S - 4 * (b % 5), 4 * (b % 4), S - 8 * (b % 2)] for b in range(B)], dtype=torch.int32, device=dev)
+    gs, gr = torch.tensor([0.1], device=dev), torch.tensor([0.05 * 1e-7], device=dev)
+
+    def make(lib, has_b, w, part, which):
+        lib.cosa_seg_loss_workspace_bytes.argtypes, lib.cosa_seg_loss_workspace_bytes.restype = [I] * 4, Z
+        wsp = torch.zeros(lib.cosa_seg_loss_workspace_bytes(B, K, hs, ws), dtype=torch.uint8, device=dev)
+        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
+        out = dict(sums=z(8), s_seg=z(B, K, Sq, Sq), s_img=z(B, 3, Sq, Sq), roi=z(B, Sq, Sq), unlabel=z(B, Sq, Sq, dt=torch.uint8),
+                   grad_seg_lr=z(B, K, hs, ws))
+        b_map = mB if has_b else None
+        fwd = lambda: lib.cosa_seg_loss_forward_w(ptr(seg), ptr(mA), ptr(b_map), ptr(simg), ptr(boxes), ptr(out["sums"]), ptr(out["s_seg"]),
+                                                  ptr(out["s_img"]), ptr(out["roi"]), ptr(out["unlabel"]), B, K, hs, ws, S, ptr(wsp), wsp.numel(),
+                                                  _C.stream_ptr())
+        bwd = lambda: lib.cosa_seg_loss_backward_w(ptr(seg), ptr(mA), ptr(b_map), ptr(out["sums"]), ptr(AS), ptr(out["roi"]), ptr(gs), ptr(gr),
+                                                   ptr(out["grad_seg_lr"]), *w, B, K, hs, ws, S, ptr(wsp), wsp.numel(), _C.stream_ptr())
+        if part == "backward":                                                          # (its inputs are a forward's outputs)
+            assert fwd() == 0
+        return {"both": lambda: fwd() or bwd(), "forward": fwd, "backward": bwd}[part], out[which]
+
+    res = {}
+    for has_b, w in settings:
+        tag = f"{'AB' if has_b else 'A'} {'/'.join(f'{x:g}' for x in w)}"
+        for which in OUTPUTS:                                                           # one entry per output: the record names what differed
+            res[f"seg_loss {tag} {which}"] = lambda lib, has_b=has_b, w=w, which=which: make(lib, has_b, w, "both", which)
+    return res, {"cosa_seg_loss_forward_w": lambda lib: make(lib, *settings[0], "forward", "sums"),
+                 "cosa_seg_loss_backward_w": lambda lib: make(lib, *settings[0], "backward", "grad_seg_lr")}
+
+
+def cam_lossv3(B, C, h, w, S, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    cam = rand(g, B, C, h, w)
+    label = label_maps(g, 1, B, C + 1, S)[0].to(torch.uint8)
+
+    def run(lib, which):
+        lib.cosa_cam_lossv3_workspace_bytes.argtypes, lib.cosa_cam_lossv3_workspace_bytes.restype = [I] * 4, Z
+        wsp = torch.zeros(lib.cosa_cam_lossv3_workspace_bytes(B, C, h, w), dtype=torch.uint8, device=dev)
+        out = dict(loss=torch.zeros(1, device=dev), grad=torch.zeros(B, C, h, w, device=dev))
+        return (lambda: lib.cosa_cam_lossv3(ptr(cam), ptr(label), ptr(out["grad"]), ptr(out["loss"]), B, C, h, w, S, ptr(wsp), wsp.numel(),
+                                            _C.stream_ptr())), out[which]
+
+    return {f"cosa_cam_lossv3 {which}": (lambda lib, which=which: run(lib, which)) for which in ("loss", "grad")}
+
+
+def scale_kernels(B, K, S, cells, oh, temp, thre, after, seed):
+    """cosa_cam_loss_targets_m and cosa_cam_label on per-scale teacher segs [2B,K,c,c] (live flipped halves), a third of the classes present"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    scales = [rand(g, 2 * B, K, c, c) for c in cells]
+    n = len(scales)
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in scales])
+    hw = (ctypes.c_int * n)(*cells)
+    labels = (torch.rand(B, K - 1, generator=g, device=dev) < 0.33).float()
+    labels[:, 0] = 1
+
+    def targets(lib):
+        out = torch.zeros(B, K - 1, oh, oh, device=dev)
+        return (lambda: lib.cosa_cam_loss_targets_m(ptrs, hw, hw, n, ptr(labels), ptr(out), B, K, S, oh, oh, temp, after, _C.stream_ptr())), out
+
+    def label(lib):
+        out = torch.zeros(B, S, S, dtype=torch.uint8, device=dev)
+        return (lambda: lib.cosa_cam_label(ptrs, hw, hw, n, ptr(labels), ptr(out), B, K, S, temp, thre, after, _C.stream_ptr())), out
+
+    targets.keep = label.keep = scales                                                  # (the pointer array does not own the tensors)
+    return {"cosa_cam_loss_targets_m": targets, "cosa_cam_label": label}
+
+
+OUTPUTS = ("sums", "s_seg", "s_img", "roi", "unlabel", "grad_seg_lr")
+SEG_SETTINGS = [(has_b, w) for has_b in (True, False) for w in ((0.25, 0.25, 0.25, 0.25), (0.21, 0.49, 0.09, 0.21))]
+
+
+def loss_cases():
+    """[(key in the record, printed case, makers)] of the bit comparison, and a function that builds the makers of the timed workload"""
+    bits = []
+    for i, (K, hs, ws, S) in enumerate([(6, 4, 4, 64), (3, 8, 8, 64), (5, 5, 7, 64), (6, 4, 4, 72), (21, 12, 12, 192)]):
+        bits.append((f"K={K} {hs}x{ws} S={S}", seg_loss(2, K, hs, ws, S, 20 + i, SEG_SETTINGS)[0]))
+    for i, (C, h, w, S) in enumerate([(5, 4, 4, 64), (2, 8, 8, 64), (20, 12, 12, 192), (4, 5, 7, 64)]):      # V3_SHAPES of tests/test_camloss_gpu.py, + 5 x 7
+        bits.append((f"C={C} {h}x{w} S={S}", cam_lossv3(2, C, h, w, S, 40 + i)))
+    i = 0
+    for cells in ((4,), (4, 2, 6)):
+        for K in (6, 70):                                                               # K = 70: the second class slot of a lane, k >= 64
+            for temp, thre in ((0.01, 0.25), (1.0, 0.5)):                               # LABEL_SETTINGS of tests/camloss_ref.py
+                for after in (0, 1):
+                    bits.append((f"{len(cells)} scales K={K} T={temp:g} after={after}", scale_kernels(2, K, 64, cells, 4, temp, thre, after, 60 + i)))
+                    i += 1
+    work = lambda: {**seg_loss(16, 21, 28, 28, 448, 7, SEG_SETTINGS[:1])[1], "cosa_cam_lossv3": cam_lossv3(16, 20, 28, 28, 448, 8)["cosa_cam_lossv3 grad"],
+                    **scale_kernels(16, 21, 448, (28, 14, 42), 28, 0.01, 0.25, 0, 9)}
+    return [(case, case, makers) for case, makers in bits], work
+
+
+def monitor_cases():
+    bits = [(f"B2 H2 N{N}", f"B=2 H=2 N={N}", attention(2, 2, N, seed=N)) for N in (1, 33, 161)]
+    bits += [(f"{rows}x{cols}", f"{rows} x {cols}", range_stats(rows, cols, seed=cols)) for rows, cols in ((3, 7), (3, 64))]
+    work = lambda: {**attention(32, 12, 785, seed=7), **range_stats(32 * 785, 768, seed=8), **monitors(16, 21, 448, 28, 28, seed=9)}
+    return bits, work
+
+
 def same_bytes(case, makers, libs):
     """one call per build on zeroed outputs -> {entry point: whether every build's output equals the first's byte for byte}"""
     res = {}
@@ -142,22 +260,17 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--json", default=None, help="write the figures there")
     ap.add_argument("--bits-only", action="store_true")
+    ap.add_argument("--cases", choices=("monitors", "losses"), default="monitors")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         again = shutil.copy(a.parent, os.path.join(tmp, "libcosa_hip_again.so"))          # a second code object of the same build
         parent, new, again = load(a.parent), load(a.new), load(again)
-        ok, bits = True, {}
-        for N in (1, 33, 161):
-            bits[f"B2 H2 N{N}"] = same_bytes(f"B=2 H=2 N={N}", attention(2, 2, N, seed=N), (parent, new))
-        for rows, cols in ((3, 7), (3, 64)):
-            bits[f"{rows}x{cols}"] = same_bytes(f"{rows} x {cols}", range_stats(rows, cols, seed=cols), (parent, new))
+        cases, work = monitor_cases() if a.cases == "monitors" else loss_cases()
+        bits = {key: same_bytes(case, makers, (parent, new)) for key, case, makers in cases}
         ok = all(v for case in bits.values() for v in case.values())
         report = {"device": torch.cuda.get_device_name(0), "bits_equal": bits, "warmup": WARMUP, "timed": TIMED, "unit": "us", "speed": {}}
         if not a.bits_only:
-            work = {}
-            work.update(attention(32, 12, 785, seed=7))
-            work.update(range_stats(32 * 785, 768, seed=8))
-            work.update(monitors(16, 21, 448, 28, 28, seed=9))
+            work = work()
             bits["workload"] = same_bytes("workload", work, (parent, new))
             ok = ok and all(bits["workload"].values())
             for name, (tp, tn, ta) in timed(work, (parent, new, again)).items():
