@@ -221,6 +221,12 @@ _SIGS.update({
     "cosa_grad_check_workspace_bytes": (c_size_t, [c_int]),
     "cosa_grad_check_norms": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cosa_grad_check_perturb": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the supervised-contrastive token loss (csrc/tokcon_kernels.hip)
+    "cosa_token_labels": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "cosa_token_contrast_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cosa_token_contrast_fwd": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "cosa_token_contrast_bwd": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "cosa_token_junction_bwd4": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

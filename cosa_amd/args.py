@@ -112,6 +112,11 @@ EXTRA = [
                                              # contours and writes <output_dir>/<iteration>/boundary_scores_<s|t>.jsonl (the same format)
     ("boundary_ratio", float, 0.02),         # d = max(1, round(ratio * the image's diagonal)), in (0, 1)
     ("boundary_d", int, 0),                  # a fixed d in pixels, 1..64; 0: use the ratio
+    # the supervised-contrastive token loss: this build's own objective, beyond the reference; 0: nothing changes
+    ("tokcon_weight", float, 0.0),           # weight of the term on the student's final patch tokens, labelled from the step's main pseudo-label
+                                             # map (0 during warm-up, like seg / cam / reg); > 0 adds `tok_loss` to the log line
+    ("tokcon_temp", float, 0.5),             # its temperature, in [0.01, 10]
+    ("tokcon_purity", float, 1.0),           # the share of a token's pixels one class must hold for the token to take its label, in (0.5, 1]
 ]
 
 

@@ -62,6 +62,8 @@ SOURCES = {
     # the CAM heat maps and panels of export: x * std + mean and 255 * m each rounded once, integers from there
     "heat_kernels.hip": EXACT,
     "grad_check_kernels.hip": EXACT,     # (--grad_check_iters: w + fl32(s g) in two roundings, double sums in a fixed order)
+    # the supervised-contrastive token loss: fp32 operands on the f32-input MFMA, as f32_kernels.hip
+    "tokcon_kernels.hip": EXACT,
 }
 
 

@@ -26,7 +26,7 @@ from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
-from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher
+from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher, tokcon_settings
 from .utils import evaluation
 from .utils import grad_check as gcheck
 from .utils import torch_helper
@@ -80,6 +80,7 @@ def check_supported(args):
         gcheck.check_dirs(getattr(args, "grad_check_dirs", "all"))
         gcheck.check_rho(getattr(args, "grad_check_rho", gcheck.DEFAULT_RHO))
     refuse_fp64_teacher(getattr(args, "teacher_precision", "auto"), flag="--")
+    tokcon_settings(args, flag="--")                              # the token contrast term: ranges, and not together with --grad_check_iters
     notes = []
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
@@ -92,6 +93,45 @@ def check_supported(args):
     evaluation.check_boundary_settings(getattr(args, "boundary_ratio", 0.02), getattr(args, "boundary_d", 0))      # or a ValueError
     for n in notes:
         print("note:", n, flush=True)
+
+
+BASE_KEYS = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
+
+
+def interval_keys(tokcon_on):
+    """the keys of the interval's running sums `acc`, of the log line and of loss_dataframe.pt: the reference's eight, and `tok_loss` after
+    `reg_loss` with the token contrast term on (--tokcon_weight > 0)"""
+    return BASE_KEYS + (('tok_loss',) if tokcon_on else ())
+
+
+def interval_terms(logs, cls_acc, cls_aux_acc, tokcon_on):
+    """one step's contribution to `acc`, in interval_keys' order"""
+    terms = [logs['overall_loss'], logs['cls_loss'], cls_acc, logs['cls_aux_loss'], cls_aux_acc, logs['seg_loss'], logs['cam_loss'], logs['reg_loss']]
+    if tokcon_on:
+        terms.append(logs['tok_loss'])
+    return torch.stack([t.reshape(()).double() for t in terms])
+
+
+def interval_line(head, vals, tokcon_on):
+    """the log line's loss part from interval_keys' values"""
+    line = (" overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, "
+            "reg_loss: %.4f" % tuple(vals[:8]))
+    if tokcon_on:
+        line += ", tok_loss: %.4f" % vals[8]
+    return head + line + " ..."
+
+
+def load_state_checked(trainer, path, tokcon_on):
+    """trainer.load_state(path); a file written under the other on / off setting of the token contrast term differs in the length of
+    `launcher.acc` (8 | 9 sums): that refusal names the flag instead of a shape"""
+    try:
+        return trainer.load_state(path)
+    except ValueError as e:
+        if "launcher.acc" in str(e) and "differs" in str(e):
+            raise ValueError(f"{path}: written with --tokcon_weight {'0 (the term off)' if tokcon_on else '> 0 (the term on)'}, this run has "
+                             f"--tokcon_weight {'> 0' if tokcon_on else '0'}: resume with the setting the file was written under "
+                             f"(its interval sums carry {'eight' if tokcon_on else 'nine'} keys) [{e}]") from e
+        raise
 
 
 def read_interval(acc, log_iters, monitors):
@@ -170,7 +210,8 @@ def main(args):
             train_loader.sampler.set_epoch(pos["epoch"])
         return train_loader.iter_from(skip) if skip else iter(train_loader)
 
-    keys = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
+    tokcon_on = float(getattr(args, "tokcon_weight", 0.0) or 0.0) > 0           # (off: keys, line and `acc` as ever)
+    keys = interval_keys(tokcon_on)
     acc = torch.zeros(len(keys), device=device, dtype=torch.float64)           # running sums of the interval, on the device
     # ... and part of a state file: saved and restored in place, no sync (next to what the trainer keeps there: --label_stats' counters)
     trainer._add_extra_state("launcher.acc", acc)
@@ -179,7 +220,7 @@ def main(args):
         resume = checkpoint.newest_state(output_dir)                                # none: a fresh start
     resumed = None
     if resume:
-        resumed = trainer.load_state(resume)
+        resumed = load_state_checked(trainer, resume, tokcon_on)
         checkpoint.unpack_rng(resumed["loader"]["rng"], device)                     # 1. the states the interrupted run built its iterator from
         it = new_iter(skip=int(resumed["loader"]["consumed"]))                      # 2./3. same sampler epoch, the consumed batches drawn and dropped
         assert pos["epoch"] == resumed["loader"]["epoch"], "the sampler epoch of the resumed iterator differs from the saved one"
@@ -210,9 +251,7 @@ def main(args):
             with torch.no_grad():                                                 # main.py:257-268, without the per-iteration .item() syncs
                 ap, ok = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_logits"].float()))
                 apa, oka = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_aux_logits"].float()))
-                acc += torch.stack([t.reshape(()).double() for t in (
-                    logs['overall_loss'], logs['cls_loss'], (ap * ok).sum() / ok.sum().clamp_min(1), logs['cls_aux_loss'],
-                    (apa * oka).sum() / oka.sum().clamp_min(1), logs['seg_loss'], logs['cam_loss'], logs['reg_loss'])])
+                acc += interval_terms(logs, (ap * ok).sum() / ok.sum().clamp_min(1), (apa * oka).sum() / oka.sum().clamp_min(1), tokcon_on)
         if gcheck_on and (n_iter + 1) % args.grad_check_iters == 0:              # a check step: its record is read here (the check's one sync)
             gsum = trainer.pop_grad_check()
             if gsum is not None and is_main:
@@ -228,9 +267,9 @@ def main(args):
                 for k, v in zip(keys, vals):
                     loss_df[k].append(v)
                 loss_df['iters'].append(n_iter + 1)
-                line = ("Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  "
-                        "cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, reg_loss: %.4f ..."
-                        % ((n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr']) + tuple(vals)))
+                head = "Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n" % (
+                    n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr'])
+                line = interval_line(head, vals, tokcon_on)
                 for m in monitors.MONITORS:                                                # (a monitor that is off: the line as ever)
                     if m.name in host:
                         summary = host[m.name] if m.summary is None else m.summary(trainer, args, host[m.name])

@@ -242,7 +242,7 @@ class VITNetwork(nn.Module):
         h, w = x.shape[-2] // p, x.shape[-1] // p
         # (patch tokens only: the class token feeds no head.  The returned feature map x4 gets a view of its own: as a view of the decoder's
         # input its gradient would meet the decoder's in bf16 before the fp32 junction -- ADVICE r4; no loss of the reference differentiates
-        # through it, and the junction kernel adds at most three live gradients: a fourth raises instead of rounding silently)
+        # through it; the token contrast term (tokcon_weight > 0) does, and its gradient is the junction's fourth)
         t_dec, t_cam, t_cls, t_x4 = nn_ops.patch_fanout_bf16(feats.final, 4)
         a_cam, a_cls = nn_ops.patch_fanout_bf16(feats.aux, 2)
         x4 = t_x4.reshape(B, h, w, -1).permute(0, 3, 1, 2)

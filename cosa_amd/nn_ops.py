@@ -1382,10 +1382,13 @@ class PatchFanoutFn(Function):
         B, N, D = ctx.shape
         gs = [g.contiguous() if g is not None else None for g in gs]
         live = [g for g in gs if g is not None]
-        if not (1 <= len(live) <= 3 and all(g.dtype == torch.bfloat16 and g.shape == (B, N - 1, D) for g in live)):      # (not an assert: python -O must not strip it)
-            raise _C.CosaError(f"PatchFanoutFn.backward: {len(live)} live gradients (the junction kernel sums at most three bf16 [B, N-1, 768] maps)")
-        live += [None] * (3 - len(live))
+        if not (1 <= len(live) <= 4 and all(g.dtype == torch.bfloat16 and g.shape == (B, N - 1, D) for g in live)):      # (not an assert: python -O must not strip it)
+            raise _C.CosaError(f"PatchFanoutFn.backward: {len(live)} live gradients (the junction kernels sum at most four bf16 [B, N-1, 768] maps)")
         dx = torch.empty((B, N, D), device=live[0].device, dtype=torch.float32)
+        if len(live) == 4:          # the feature map's gradient too (the token contrast term): the four-pointer entry, the same fp32 adds in consumer order
+            _C.check(_C.lib().cosa_token_junction_bwd4(*[_C.ptr(g) for g in live], _C.ptr(dx), B, N, D, _C.stream_ptr()), "cosa_token_junction_bwd4")
+            return dx, None
+        live += [None] * (3 - len(live))
         _C.check(_C.lib().cosa_token_junction_bwd(_C.ptr(live[0]), _C.ptr(live[1]), _C.ptr(live[2]), _C.ptr(dx), B, N, D, _C.stream_ptr()),
                  "cosa_token_junction_bwd")
         return dx, None

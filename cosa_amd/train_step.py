@@ -44,7 +44,8 @@ def default_args(dataset="VOC12", **over):
              clip_grad_norm=0.0, skip_nonfinite=False, label_stats=False, tensor_stats=False, accum_steps=1,
              teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None,
              act_stats_iters=0, camloss_version='v1', segconf_thre=0.25,
-             grad_check_iters=0, grad_check_mode='fp64', grad_check_dirs='all', grad_check_rho=gcheck.DEFAULT_RHO)
+             grad_check_iters=0, grad_check_mode='fp64', grad_check_dirs='all', grad_check_rho=gcheck.DEFAULT_RHO,
+             tokcon_weight=0.0, tokcon_temp=0.5, tokcon_purity=1.0)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -117,6 +118,18 @@ def resolve_teacher_check_mode(mode, teacher_precision):
     return "bf16x3" if teacher_precision == "fp16x3" else "fp16x3"
 
 
+def tokcon_settings(args, flag=""):
+    """(weight, temp, purity) of the token contrast term from `args` (off where the fields are missing), refused when
+    one is outside its range or when the term meets --grad_check_iters, whose five forward-only evaluators do not know a sixth term; here for
+    the trainer and, with flag="--", for the launcher's check_supported"""
+    w, t, p = (getattr(args, "tokcon_weight", 0.0) or 0.0, getattr(args, "tokcon_temp", 0.5), getattr(args, "tokcon_purity", 1.0))
+    seg_helper.check_tokcon_settings(w, t, p, flag=flag)
+    if float(w) > 0 and int(getattr(args, "grad_check_iters", 0) or 0) > 0:
+        raise ValueError(f"{flag}tokcon_weight {w!r} with {flag}grad_check_iters: the gradient check differences the five terms of the "
+                         f"reference's objective and has no evaluator for the token contrast term; run the check with {flag}tokcon_weight 0")
+    return float(w), float(t), float(p)
+
+
 def check_iters(args, which, flag=""):
     """--<which>_check_iters of `args` (which: "teacher" / "student" / "grad"), or --act_stats_iters (which: "act_stats"), as an int; a negative one is
     refused, here for the trainer and, with flag="--", for the launcher's check_supported"""
@@ -158,6 +171,7 @@ class CoSATrainer:
         self.args = args
         self.device = device
         self.camloss_version = camloss_version(args)      # (before anything is built: an unknown version costs nothing)
+        self._tokcon = tokcon_settings(args)              # (likewise: the token contrast term; weight 0: off)
         if check_iters(args, "grad") > 0:                 # (--grad_check_iters, DESIGN.md section 25: refused before anything is built too)
             args.grad_check_mode = gcheck.check_mode(getattr(args, "grad_check_mode", "fp64"))
             args.grad_check_dirs = gcheck.check_dirs(getattr(args, "grad_check_dirs", "all"))
@@ -819,11 +833,16 @@ class CoSATrainer:
                                     outputs=dict(seg=seg_lr.detach(), cam=cam_pred.detach(), cam_aux=cam_aux_pred.detach(),
                                                  cls=cls_final.detach(), cls_aux=cls_aux.detach()),
                                     losses=tuple(t.detach() for t in (cls_loss, cls_loss_aux, seg_loss, cam_loss)))
+        tok_on = self._tokcon[0] > 0
+        if tok_on:
+            tok_loss = self._token_contrast(_feat, refine_mask_label)
         # main.py:230-236: the weighted sum of the five losses (warm-up: classification losses only) as one dot product
         wkey = n_iter <= args.warmup_iters
         wvec = self._loss_weights.get(wkey)
         if wvec is None:
             wl = [1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight]
+            if tok_on:                      # the sixth element: the token contrast term, 0 during warm-up like seg / cam / reg
+                wl.append(0.0 if wkey else self._tokcon[0])
             wvec = self._loss_weights[wkey] = torch.tensor(wl, device=cls_loss.device, dtype=torch.float32)
         if self.model_GK is not None and self._is_check_step(n_iter, "grad"):
             # what the check after this step's backward (_grad_check) reads: detached references and the loss weights as the dot product
@@ -831,16 +850,35 @@ class CoSATrainer:
             wl32 = [float(np.float32(v)) for v in ([1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight])]
             self._gcheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux),
                                     tgt=check_tgt_s, weights=wl32)
-        loss = torch.dot(torch.stack([cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(),
-                                      reg_loss.reshape(()).float()]), wvec)
+        terms = [cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(), reg_loss.reshape(()).float()]
+        if tok_on:
+            terms.append(tok_loss.reshape(()).float())
+        loss = torch.dot(torch.stack(terms), wvec)
         overall = loss.detach()
         if self.label_stats_state is not None and self._skip_nonfinite:
             # teacher refusal: step_scale is 1.0f (an exact product: the bits of the step without it) or, when this step's CAMs held a
             # non-finite element, NaN -- every gradient is then NaN and the gradient guard refuses the step (under DDP on every rank)
             loss = loss * self._step_scale.reshape(())
-        return loss, dict(overall_loss=overall, cls_loss=cls_loss.detach(), cls_aux_loss=cls_loss_aux.detach(),
-                          seg_loss=seg_loss.detach(), cam_loss=cam_loss.detach(), reg_loss=reg_loss.detach(),
-                          mask=refine_mask_label, cls_logits=cls_final.detach(), cls_aux_logits=cls_aux.detach())
+        logs = dict(overall_loss=overall, cls_loss=cls_loss.detach(), cls_aux_loss=cls_loss_aux.detach(),
+                    seg_loss=seg_loss.detach(), cam_loss=cam_loss.detach(), reg_loss=reg_loss.detach(),
+                    mask=refine_mask_label, cls_logits=cls_final.detach(), cls_aux_logits=cls_aux.detach())
+        if tok_on:
+            logs["tok_loss"] = tok_loss.detach()
+        return loss, logs
+
+    def _token_contrast(self, feat, mask):
+        """the token contrast term of the step: the returned feature map [B,768,h,w] taken back to its tokens
+        [B,n,768] as a view, labelled from the step's main pseudo-label map, on the HIP kernels (fused_losses) or the torch composition"""
+        _, temp, purity = self._tokcon
+        if getattr(self.student.encoder, "residual_stream", "fp32") == "bf16":
+            raise ValueError('tokcon_weight > 0 with encoder.residual_stream = "bf16": the feature map then has no fanout view of its own, and '
+                             "its gradient would meet the decoder's in bf16; leave the stream fp32 or set tokcon_weight 0")
+        B, D, h, w = feat.shape
+        tokens = feat.permute(0, 2, 3, 1).reshape(B, h * w, D)
+        with torch.no_grad():
+            labels = seg_helper.token_labels(mask, mask.shape[-1] // h, purity)
+        fn = seg_helper.token_contrast_loss if self.fused_losses else seg_helper._token_contrast_torch
+        return fn(tokens, labels, temp)
 
     def _cam_loss_fn(self, tgt):
         """cam -> the selected --camloss_version v2 | v3 against `tgt` (v2: targets at the CAM's size on the fused path, the refined teacher

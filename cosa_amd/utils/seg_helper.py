@@ -2113,6 +2113,136 @@ def cam_label_from_scales(seg_scales, cls_label, S, softmaxtemp, segconf_thre, a
 
 
 # --------------------------------------------------------------------------------------------
+# the supervised-contrastive token loss: this project's own objective, not the reference's
+# --------------------------------------------------------------------------------------------
+TOKCON_DIM = 768            # the kernels' envelope (csrc/tokcon_kernels.hip): bf16 device tokens of this width ...
+TOKCON_MAX_N = 4096         # ... 2 <= n <= this many per image ...
+TOKCON_TEMP = (0.01, 10.0)  # ... and a temperature in this range
+TOKCON_IGNORE = 255
+
+
+def check_tokcon_settings(weight, temp, purity, flag=""):
+    """the term's three settings (trainer: flag "", launcher: flag "--"), or a ValueError naming the one outside its range"""
+    if not (math.isfinite(float(weight)) and float(weight) >= 0):
+        raise ValueError(f"{flag}tokcon_weight {weight!r}: 0 (off) or a positive weight")
+    if not TOKCON_TEMP[0] <= float(temp) <= TOKCON_TEMP[1]:
+        raise ValueError(f"{flag}tokcon_temp {temp!r}: a temperature in [{TOKCON_TEMP[0]}, {TOKCON_TEMP[1]}]")
+    if not 0.5 < float(purity) <= 1.0:
+        raise ValueError(f"{flag}tokcon_purity {purity!r}: a share of the cell's pixels in (0.5, 1]")
+
+
+def token_need(patch, purity=1.0):
+    """ceil(purity * patch^2) as an integer: the pixels of a cell one class must hold for the token to take its label"""
+    if not 0.5 < float(purity) <= 1.0:
+        raise ValueError(f"purity {purity!r}: a share of the cell's pixels in (0.5, 1]")
+    pp = int(patch) * int(patch)
+    return min(max(int(math.ceil(float(purity) * pp)), pp // 2 + 1), pp)          # (the clamp: a no-op for a purity in range)
+
+
+def _token_labels_torch(mask, patch, need):
+    B, S = mask.shape[0], mask.shape[-1]
+    g = S // patch
+    cells = mask.reshape(B, g, patch, g, patch).permute(0, 1, 3, 2, 4).reshape(B, g * g, patch * patch).long()
+    mode = cells.mode(dim=-1).values
+    cnt = (cells == mode.unsqueeze(-1)).sum(-1)
+    return torch.where((cnt >= need) & (mode != TOKCON_IGNORE), mode, torch.full_like(mode, TOKCON_IGNORE)).to(torch.uint8)
+
+
+def token_labels(mask, patch, purity=1.0):
+    """label map [B,S,S] (any integer dtype, values 0..255, 255 = ignore) -> uint8 [B,(S/patch)^2]: token (r, c) takes the class that holds at
+    least ceil(purity * patch^2) of the pixels of its cell, 255 when none does (background is a class like any other).  One kernel of
+    byte loads and integer counts for device maps (cosa_token_labels), torch for host maps."""
+    patch = int(patch)
+    if mask.dim() != 3 or mask.shape[1] != mask.shape[2] or patch < 1 or mask.shape[-1] % patch != 0:
+        raise ValueError(f"token_labels: a square label map [B,S,S] whose side the patch size divides (got {tuple(mask.shape)}, patch {patch})")
+    need = token_need(patch, purity)
+    if not mask.is_cuda:
+        return _token_labels_torch(mask, patch, need)
+    if mask.dtype not in (torch.uint8, torch.int64):
+        mask = mask.to(torch.int64)
+    mask = mask.contiguous()
+    B, S = mask.shape[0], mask.shape[-1]
+    out = torch.empty((B, (S // patch) ** 2), device=mask.device, dtype=torch.uint8)
+    _C.check(_C.lib().cosa_token_labels(_C.ptr(mask), mask.element_size(), _C.ptr(out), B, S, patch, need, _C.stream_ptr()), "cosa_token_labels")
+    return out
+
+
+def _token_contrast_torch(tokens, labels, temp, return_count=False):
+    """the term op by op in torch (float32 for 16-bit tokens, else the tokens' own dtype): what the kernels are checked against, and the path
+    of host tensors, other dtypes, shapes outside the envelope and fused_losses=False.  -> loss, or (loss, M) with return_count"""
+    x = tokens.float() if tokens.dtype in (torch.bfloat16, torch.float16) else tokens
+    y = labels.long()
+    n = x.shape[1]
+    z = x / x.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    s = torch.matmul(z, z.transpose(1, 2)) / temp
+    valid = y != TOKCON_IGNORE
+    off = ~torch.eye(n, dtype=torch.bool, device=x.device)
+    A = valid.unsqueeze(1) & off                                              # [B, i, j]: j in A(i)
+    P = A & valid.unsqueeze(2) & (y.unsqueeze(2) == y.unsqueeze(1))
+    npos = P.sum(-1)
+    anchor = npos >= 1
+    # (only anchor rows are masked: a row of -inf alone would put NaN into the backward of the rows torch.where drops)
+    lse = torch.logsumexp(s.masked_fill(~A & anchor.unsqueeze(2), float("-inf")), dim=-1)
+    pos = (s * P.to(s.dtype)).sum(-1) / npos.clamp_min(1).to(s.dtype)
+    M = anchor.sum()
+    loss = torch.where(anchor, lse - pos, torch.zeros_like(lse)).sum() / M.clamp_min(1).to(s.dtype)
+    return (loss, M) if return_count else loss
+
+
+def _tokcon_kernel_ok(tokens, labels, temp):
+    return (tokens.is_cuda and labels.is_cuda and tokens.dtype == torch.bfloat16 and tokens.dim() == 3 and tokens.shape[2] == TOKCON_DIM
+            and 2 <= tokens.shape[1] <= TOKCON_MAX_N and 1 <= tokens.shape[0] <= 65535 and TOKCON_TEMP[0] <= float(temp) <= TOKCON_TEMP[1])
+
+
+class _TokenContrastFn(Function):
+    """value and saved statistics (per-token log-sum-exp and positive sum, per-image class counts, M) from one forward call
+    (cosa_token_contrast_fwd), the bf16 gradient from one backward call (cosa_token_contrast_bwd)"""
+
+    @staticmethod
+    def forward(ctx, tokens, labels, temp):
+        B, n, D = tokens.shape
+        L = _C.lib()
+        rows = torch.empty((2, B, n), device=tokens.device, dtype=torch.float32)
+        counts = torch.empty(B * 256 + 1, device=tokens.device, dtype=torch.int32)
+        loss = torch.empty(1, device=tokens.device, dtype=torch.float32)
+        ws = _C.workspace(L.cosa_token_contrast_workspace_bytes(B, n), tokens.device, "token_contrast")
+        _C.check(L.cosa_token_contrast_fwd(_C.ptr(tokens), _C.ptr(labels), _C.ptr(rows), _C.ptr(counts), _C.ptr(loss), B, n, D, float(temp),
+                                           _C.ptr(ws), ws.numel(), _C.stream_ptr()), "cosa_token_contrast_fwd")
+        ctx.save_for_backward(tokens, labels, rows, counts)
+        ctx.temp = float(temp)
+        ctx.mark_non_differentiable(counts)
+        return loss[0], counts
+
+    @staticmethod
+    def backward(ctx, g, _g_counts):
+        tokens, labels, rows, counts = ctx.saved_tensors
+        B, n, D = tokens.shape
+        L = _C.lib()
+        up = g.detach().reshape(1).float().contiguous()
+        dx = torch.empty_like(tokens)
+        ws = _C.workspace(L.cosa_token_contrast_workspace_bytes(B, n), tokens.device, "token_contrast")
+        _C.check(L.cosa_token_contrast_bwd(_C.ptr(tokens), _C.ptr(labels), _C.ptr(rows), _C.ptr(counts), _C.ptr(up), _C.ptr(dx), B, n, D,
+                                           ctx.temp, _C.ptr(ws), ws.numel(), _C.stream_ptr()), "cosa_token_contrast_bwd")
+        return dx, None, None
+
+
+def token_contrast_loss(tokens, labels, temp, return_count=False):
+    """The supervised-contrastive token loss (the form of Khosla et al. 2020) of tokens [B,n,D] under token labels [B,n] (255 = unlabelled),
+    each image on its own: with z_i = x_i / max(|x_i|, 1e-12), s_ij = z_i . z_j / temp, A(i) the labelled j != i, P(i) those of i's label,
+    anchors the labelled i with |P(i)| >= 1 and M their number over the batch,
+        L = (1/M) sum_anchors (log sum_{A(i)} exp s_ia - (1/|P(i)|) sum_{P(i)} s_ij);   M = 0: L = 0 exactly and a zero gradient.
+    Both sides of every pair carry gradient.  bf16 device tokens of width 768 with 2 <= n <= 4096 and 0.01 <= temp <= 10 run on the HIP kernels
+    (csrc/tokcon_kernels.hip), anything else on the torch composition.  -> loss (fp32 scalar), or (loss, M) with return_count; no host sync."""
+    if labels.shape != tokens.shape[:2]:
+        raise ValueError(f"token_contrast_loss: labels {tuple(labels.shape)} for tokens {tuple(tokens.shape)}")
+    if _tokcon_kernel_ok(tokens, labels, temp):
+        lab = labels if labels.dtype == torch.uint8 else labels.to(torch.uint8)
+        loss, counts = _TokenContrastFn.apply(tokens.contiguous(), lab.contiguous(), float(temp))
+        return (loss, counts[-1]) if return_count else loss
+    return _token_contrast_torch(tokens, labels, temp, return_count=return_count)
+
+
+# --------------------------------------------------------------------------------------------
 # dense-CRF post-processing of the final evaluation  (utils/seg_helper.py:961-996)
 # --------------------------------------------------------------------------------------------
 class DenseCRF(object):

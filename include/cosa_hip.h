@@ -1117,6 +1117,36 @@ int cosa_grad_check_norms(const void *table_host, const void *table_dev, int n_t
 int cosa_grad_check_perturb(const void *table_host, const void *table_dev, int n_tensors, int n_chunks, int n_dirs, int dir,
                             float c, int slot, double *record, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The supervised-contrastive token loss (csrc/tokcon_kernels.hip): this project's own objective on the
+ * student's final patch tokens, off by default.
+ * cosa_token_labels   label map [B,S,S] (uint8 or int64 elements of value 0..255, elem_bytes 1 | 8; the low byte is read) ->
+ *                     labels uint8 [B,(S/p)^2]: the class holding >= need of the token's p x p pixels, else 255.  need in
+ *                     (p^2 / 2, p^2], so at most one class qualifies.  Byte loads and integer counts; one launch.
+ * cosa_token_contrast_fwd   tokens bf16 [B,n,768] contiguous, labels uint8 [B,n], tau.  Per image z = x / max(|x|, 1e-12) in
+ *                     fp32, s_ij = z_i . z_j / tau on the f32-input MFMA, A(i) = labelled j != i, P(i) = those with y_i's
+ *                     label, anchors = labelled i with |P(i)| >= 1, M their number over the batch;
+ *                     loss = (1/M) sum_anchors (log sum_A exp s_ia - (1/|P(i)|) sum_P s_ij), an exact 0 with M = 0.
+ *                     Writes rows float [2][B][n] (lse_i, sum_P s_ij), counts int32 [B*256 + 1] (per-image class counts,
+ *                     then M) and loss float [1].  Nothing of size n^2 is written; no float atomics, no host sync.
+ * cosa_token_contrast_bwd   dx bf16 [B,n,768] = upstream[0] * dL/dx from the same tokens / labels and the forward's rows and
+ *                     counts: per image W = G + G^T into scratch (G_ij = (1/M)(exp(s_ij - lse_i)[j in A(i)] - [j in
+ *                     P(i)]/|P(i)|) on anchor rows), dZ = W Z on the f32-input MFMA, then per row
+ *                     (dZ_i - (dZ_i . z_i) z_i) upstream / (tau max(|x_i|, 1e-12)) rounded once.  upstream: a device float.
+ * Envelope of both: dim == 768, 1 <= B <= 65535, 2 <= n <= 4096, 0.01 <= tau <= 10, 16-byte aligned tokens / dx /
+ * workspace of cosa_token_contrast_workspace_bytes(B, n) bytes (at most 256 MiB unless one image needs more: the batch is
+ * walked in image chunks, which moves no bit).  Anything else is COSA_EINVAL and nothing is launched.
+ * cosa_token_junction_bwd4  cosa_token_junction_bwd for four consumers: dx fp32 [B,N,768] = 0 in the class-token row,
+ *                     g0 + g1 + g2 + g3 elsewhere (fp32 adds in that order, absent ones null); g bf16 [B,N-1,768].
+ * ------------------------------------------------------------------------------------- */
+int cosa_token_labels(const void *mask, int elem_bytes, uint8_t *labels, int B, int S, int p, int need, void *stream);
+size_t cosa_token_contrast_workspace_bytes(int B, int n);
+int cosa_token_contrast_fwd(const void *tokens, const uint8_t *labels, float *rows, int32_t *counts, float *loss, int B, int n, int dim,
+                            float tau, void *workspace, size_t workspace_bytes, void *stream);
+int cosa_token_contrast_bwd(const void *tokens, const uint8_t *labels, const float *rows, const int32_t *counts, const float *upstream,
+                            void *dx, int B, int n, int dim, float tau, void *workspace, size_t workspace_bytes, void *stream);
+int cosa_token_junction_bwd4(const void *g0, const void *g1, const void *g2, const void *g3, float *dx, int B, int N, int dim, void *stream);
+
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
 
