@@ -227,6 +227,12 @@ _SIGS.update({
     "cosa_token_contrast_fwd": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p, c_size_t, c_void_p]),
     "cosa_token_contrast_bwd": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float, c_void_p, c_size_t, c_void_p]),
     "cosa_token_junction_bwd4": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    # the reliability-weighted seg loss (csrc/reliability_kernels.hip, and the _rw pair of csrc/loss_kernels.hip)
+    "cosa_label_reliability": (c_int, [ctypes.POINTER(c_void_p), c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                       ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
+                                       c_void_p, c_void_p]),
+    "cosa_seg_loss_forward_rw": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p] + [c_void_p] * 2),
+    "cosa_seg_loss_backward_rw": (c_int, [c_void_p] * 9 + [c_float] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p] + [c_void_p] * 2),
 })
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose

@@ -117,6 +117,11 @@ EXTRA = [
                                              # map (0 during warm-up, like seg / cam / reg); > 0 adds `tok_loss` to the log line
     ("tokcon_temp", float, 0.5),             # its temperature, in [0.01, 10]
     ("tokcon_purity", float, 1.0),           # the share of a token's pixels one class must hold for the token to take its label, in (0.5, 1]
+    # the reliability-weighted seg loss: the reference's seg_weightloss under this build's own weight; off: nothing changes
+    ("seg_reliability", str2bool, False),    # weigh each pseudo-labelled pixel's seg loss by how far its CAM lies from the threshold it passed,
+                                             # raised to the reference's --camweight_beta (in [0, 8]; read with this switch on only); the mean
+                                             # weights are logged and written to <output_dir>/seg_reliability.jsonl at each evaluation
+    ("seg_reliability_floor", float, 0.0),   # the weight of a pixel the CAM does not support (w = floor + (1 - floor) r^beta), in [0, 1)
 ]
 
 

@@ -64,6 +64,8 @@ SOURCES = {
     "grad_check_kernels.hip": EXACT,     # (--grad_check_iters: w + fl32(s g) in two roundings, double sums in a fixed order)
     # the supervised-contrastive token loss: fp32 operands on the f32-input MFMA, as f32_kernels.hip
     "tokcon_kernels.hip": EXACT,
+    # the per-pixel weight of the reliability-weighted seg loss: a formula stated operation by operation
+    "reliability_kernels.hip": EXACT,
 }
 
 

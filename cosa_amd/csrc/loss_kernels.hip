@@ -135,6 +135,14 @@ __device__ __forceinline__ bool ce_is_fg(int la, int K) { return la > 0 && la < 
 // backward: the pixel's coefficient on (p_k - [k == la])
 __device__ __forceinline__ float ce_coef(int la, int K, float cbg, float cfg) { return ce_is_bg(la) ? cbg : (ce_is_fg(la, K) ? cfg : 0.f); }
 
+// a pixel's weight from a weight map (the _rw entry points): in [0, 1]; anything else -- a NaN too -- counts 0 and sets the sticky flag: NaN out
+__device__ __forceinline__ float pixel_weight(const float *__restrict__ rel, size_t at, unsigned long long *flag)
+{
+    const float w = rel[at];
+    if (!(w >= 0.f && w <= 1.f)) { atomicOr(flag, 1ull); return 0.f; }
+    return w;
+}
+
 // forward: the block's N sums -> shard (workgroup number & 63) of sums[64][N].  64 shards: thousands of workgroups adding to the same N addresses
 // serialise at ~20 ns per add; integer addition is associative, so the total does not depend on the sharding either
 template <int N>
@@ -202,9 +210,13 @@ __device__ __forceinline__ void scatter_flush(const Scatter &s, const QuadCtx &c
 // ---- forward ---------------------------------------------------------------------------------------------------
 // sums[8] = {bgA_sum, bgA_cnt, fgA_sum, fgA_cnt, bgB_sum, bgB_cnt, fgB_sum, fgB_cnt}
 // HAS_B = false: no second label map -- nothing of it is loaded and sums[4..7] stay zero (--aux_cam2seg false)
-template <bool HAS_B>
+// HAS_W = true (cosa_seg_loss_forward_rw): a per-pixel weight map beside each label map multiplies the pixel's cross-entropy term
+// (utils/seg_helper.py:823-835, seg_weightloss); the counts stay the plain counts.  The term is formed as ever and multiplied afterwards: the
+// HAS_W = false instantiations are the code they have always been, and a weight of 1.0f changes no bit (x * 1 and fma(x, 1, acc) are exact).
+template <bool HAS_B, bool HAS_W>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restrict__ seg_lr, const float *__restrict__ maskA,
-                                                          const float *__restrict__ maskB, const float *__restrict__ simg,
+                                                          const float *__restrict__ maskB, const float *__restrict__ relA,
+                                                          const float *__restrict__ relB, const float *__restrict__ simg,
                                                           const int32_t *__restrict__ boxes, unsigned long long *__restrict__ sums,
                                                           unsigned long long *__restrict__ flag, float *__restrict__ s_seg, float *__restrict__ s_img,
                                                           float *__restrict__ roi, unsigned char *__restrict__ unlabel,
@@ -224,11 +236,22 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float *__restri
             const float lse = pixel_softmax(tile, c.t[p], K, m[p], inv[p]);
             const size_t pix = (size_t)(c.Y + (p >> 1)) * S + c.X + (p & 1);
             const int la = (int)maskA[(size_t)b * SS + pix], lb = HAS_B ? (int)maskB[(size_t)b * SS + pix] : 255;
-            if (ce_is_bg(la)) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
-            else if (ce_is_fg(la, K)) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
-            if (HAS_B) {
-                if (ce_is_bg(lb)) { acc[4] += lse - tap(tile, c.t[p]); acc[5] += 1.f; }
-                else if (ce_is_fg(lb, K)) { acc[6] += lse - tap(tile + lb * TC * TC, c.t[p]); acc[7] += 1.f; }
+            if (!HAS_W) {
+                if (ce_is_bg(la)) { acc[0] += lse - tap(tile, c.t[p]); acc[1] += 1.f; }
+                else if (ce_is_fg(la, K)) { acc[2] += lse - tap(tile + la * TC * TC, c.t[p]); acc[3] += 1.f; }
+                if (HAS_B) {
+                    if (ce_is_bg(lb)) { acc[4] += lse - tap(tile, c.t[p]); acc[5] += 1.f; }
+                    else if (ce_is_fg(lb, K)) { acc[6] += lse - tap(tile + lb * TC * TC, c.t[p]); acc[7] += 1.f; }
+                }
+            } else {
+                const float wa = pixel_weight(relA, (size_t)b * SS + pix, flag);
+                if (ce_is_bg(la)) { const float ce = lse - tap(tile, c.t[p]); acc[0] += ce * wa; acc[1] += 1.f; }
+                else if (ce_is_fg(la, K)) { const float ce = lse - tap(tile + la * TC * TC, c.t[p]); acc[2] += ce * wa; acc[3] += 1.f; }
+                if (HAS_B) {
+                    const float wb = pixel_weight(relB, (size_t)b * SS + pix, flag);
+                    if (ce_is_bg(lb)) { const float ce = lse - tap(tile, c.t[p]); acc[4] += ce * wb; acc[5] += 1.f; }
+                    else if (ce_is_fg(lb, K)) { const float ce = lse - tap(tile + lb * TC * TC, c.t[p]); acc[6] += ce * wb; acc[7] += 1.f; }
+                }
             }
         }
         // pass 3: probabilities, 2x2 mean (the exact x0.5 bilinear), energy-grid outputs
@@ -264,9 +287,11 @@ __global__ void seg_loss_sums_kernel(const unsigned long long *__restrict__ fix,
 // SegWeights: the four blend weights of main.py:200-203 x seg_helper.py:813 (fg_alpha a, aux blend b): A = ((1-b)(1-a), (1-b)a), B = (b(1-a), ba)
 struct SegWeights { float a_bg, a_fg, b_bg, b_fg; };
 
-template <bool HAS_B>
+// HAS_W = true (cosa_seg_loss_backward_rw): the pixel's coefficient, formed as ever, times its weight
+template <bool HAS_B, bool HAS_W>
 __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restrict__ seg_lr, const float *__restrict__ maskA,
-                                                          const float *__restrict__ maskB, const float *__restrict__ sums,
+                                                          const float *__restrict__ maskB, const float *__restrict__ relA,
+                                                          const float *__restrict__ relB, const float *__restrict__ sums,
                                                           const float *__restrict__ AS, const float *__restrict__ roi,
                                                           const float *__restrict__ g_seg, const float *__restrict__ g_regw,
                                                           unsigned long long *__restrict__ grad, unsigned long long *__restrict__ flag,
@@ -295,6 +320,10 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float *__restri
             lb[p] = HAS_B ? (int)maskB[(size_t)b * SS + pix] : 255;
             ca[p] = ce_coef(la[p], K, cbgA, cfgA);
             cb[p] = ce_coef(lb[p], K, cbgB, cfgB);
+            if (HAS_W) {
+                ca[p] *= pixel_weight(relA, (size_t)b * SS + pix, flag);
+                if (HAS_B) cb[p] *= pixel_weight(relB, (size_t)b * SS + pix, flag);
+            }
             dot[p] = 0.f;
         }
         if (ge != 0.f) {
@@ -727,10 +756,19 @@ extern "C" size_t cosa_seg_loss_workspace_bytes(int B, int K, int hs, int ws)
     return align_up((size_t)B * K * hs * ws * sizeof(unsigned long long) + (64 * 8 + 1) * sizeof(unsigned long long), 256);
 }
 
-/* the general forms: maskB may be NULL (no second label map), four blend weights; the entry points without a suffix are these with both maps and 0.25 x 4 */
-extern "C" int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
-                                       const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
-                                       int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+/* the weight maps of the _rw entry points: relA beside maskA always, relB exactly when there is a maskB */
+static int check_weight_maps(const char *who, const float *maskB, const float *relA, const float *relB)
+{
+    COSA_REQUIRE(relA, "%s: null weight map", who);
+    COSA_REQUIRE((relB != nullptr) == (maskB != nullptr), "%s: a second weight map goes with a second label map, and only with one", who);
+    return COSA_OK;
+}
+
+/* the general forms: maskB may be NULL (no second label map), four blend weights; the entry points without a suffix are these with both maps and 0.25 x 4.
+ * relA / relB: the _rw entry points' weight maps, NULL for every other one */
+static int seg_loss_forward_any(const float *seg_lr, const float *maskA, const float *maskB, const float *relA, const float *relB, const float *simg,
+                                const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                                int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
 {
     COSA_REQUIRE(seg_lr && maskA && simg && boxes && sums && s_seg && s_img && roi && unlabel && workspace, "cosa_seg_loss_forward: null pointer");
     int rc = check_shapes(B, K, hs, ws, S);
@@ -745,13 +783,33 @@ extern "C" int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, 
     COSA_HIP_CHECK(hipMemsetAsync(fix, 0, 64 * 8 * sizeof(unsigned long long), st));
     COSA_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned long long), st));
     const TileLaunch t = tile_launch(B, K, hs, ws, S);
-    const auto kern = maskB ? seg_loss_fwd_kernel<true> : seg_loss_fwd_kernel<false>;
-    hipLaunchKernelGGL(kern, t.grid, t.blk, t.lds_fwd, st, seg_lr, maskA, maskB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K, hs, ws, S,
-                       t.sy, t.sx);
+    const auto kern = relA ? (maskB ? seg_loss_fwd_kernel<true, true> : seg_loss_fwd_kernel<false, true>)
+                           : (maskB ? seg_loss_fwd_kernel<true, false> : seg_loss_fwd_kernel<false, false>);
+    hipLaunchKernelGGL(kern, t.grid, t.blk, t.lds_fwd, st, seg_lr, maskA, maskB, relA, relB, simg, boxes, fix, flag, s_seg, s_img, roi, unlabel, K,
+                       hs, ws, S, t.sy, t.sx);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_loss_sums_kernel, dim3(1), dim3(64), 0, st, fix, flag, sums);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
+}
+
+extern "C" int cosa_seg_loss_forward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
+                                       const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                                       int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return seg_loss_forward_any(seg_lr, maskA, maskB, nullptr, nullptr, simg, boxes, sums, s_seg, s_img, roi, unlabel, B, K, hs, ws, S, workspace,
+                                workspace_bytes, stream);
+}
+
+/* cosa_seg_loss_forward_w with a weight in [0, 1] per pixel of each label map (seg_weightloss, utils/seg_helper.py:823-835) */
+extern "C" int cosa_seg_loss_forward_rw(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
+                                        const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                                        int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream,
+                                        const float *relA, const float *relB)
+{
+    if (int rc = check_weight_maps("cosa_seg_loss_forward_rw", maskB, relA, relB)) return rc;
+    return seg_loss_forward_any(seg_lr, maskA, maskB, relA, relB, simg, boxes, sums, s_seg, s_img, roi, unlabel, B, K, hs, ws, S, workspace,
+                                workspace_bytes, stream);
 }
 
 extern "C" int cosa_seg_loss_forward(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
@@ -763,10 +821,10 @@ extern "C" int cosa_seg_loss_forward(const float *seg_lr, const float *maskA, co
                                    stream);
 }
 
-extern "C" int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
-                                        const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
-                                        float wA_bg, float wA_fg, float wB_bg, float wB_fg,
-                                        int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+static int seg_loss_backward_any(const float *seg_lr, const float *maskA, const float *maskB, const float *relA, const float *relB,
+                                 const float *sums, const float *AS, const float *roi, const float *g_seg, const float *g_regw,
+                                 float *grad_seg_lr, float wA_bg, float wA_fg, float wB_bg, float wB_fg,
+                                 int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
 {
     COSA_REQUIRE(seg_lr && maskA && sums && AS && roi && g_seg && g_regw && grad_seg_lr && workspace, "cosa_seg_loss_backward: null pointer");
     // (a NaN fails every comparison: refused here as well)
@@ -785,20 +843,42 @@ extern "C" int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA,
     unsigned long long *flag = fix + n;
     COSA_HIP_CHECK(hipMemsetAsync(fix, 0, n * sizeof(unsigned long long), st));
     const TileLaunch t = tile_launch(B, K, hs, ws, S);
-    static size_t lds_set[2] = {0, 0};
-    const int hb = maskB ? 1 : 0;
-    const auto kern = hb ? seg_loss_bwd_kernel<true> : seg_loss_bwd_kernel<false>;
-    if (t.lds_bwd > 65536 && t.lds_bwd > lds_set[hb]) {
+    static size_t lds_set[4] = {0, 0, 0, 0};
+    const int hb = maskB ? 1 : 0, inst = hb + (relA ? 2 : 0);
+    const auto kern = relA ? (hb ? seg_loss_bwd_kernel<true, true> : seg_loss_bwd_kernel<false, true>)
+                           : (hb ? seg_loss_bwd_kernel<true, false> : seg_loss_bwd_kernel<false, false>);
+    if (t.lds_bwd > 65536 && t.lds_bwd > lds_set[inst]) {
         COSA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bwd));
-        lds_set[hb] = t.lds_bwd;
+        lds_set[inst] = t.lds_bwd;
     }
     const SegWeights wt = {wA_bg, wA_fg, wB_bg, wB_fg};
-    hipLaunchKernelGGL(kern, t.grid, t.blk, t.lds_bwd, st, seg_lr, maskA, maskB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K, hs, ws, S, t.sy,
-                       t.sx);
+    hipLaunchKernelGGL(kern, t.grid, t.blk, t.lds_bwd, st, seg_lr, maskA, maskB, relA, relB, sums, AS, roi, g_seg, g_regw, fix, flag, wt, B, K, hs,
+                       ws, S, t.sy, t.sx);
     COSA_LAUNCH_CHECK();
     hipLaunchKernelGGL(seg_loss_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fix, flag, grad_seg_lr, n);
     COSA_LAUNCH_CHECK();
     return COSA_OK;
+}
+
+extern "C" int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
+                                        const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
+                                        float wA_bg, float wA_fg, float wB_bg, float wB_fg,
+                                        int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return seg_loss_backward_any(seg_lr, maskA, maskB, nullptr, nullptr, sums, AS, roi, g_seg, g_regw, grad_seg_lr, wA_bg, wA_fg, wB_bg, wB_fg, B, K,
+                                 hs, ws, S, workspace, workspace_bytes, stream);
+}
+
+/* cosa_seg_loss_backward_w with the forward's weight maps: the pixel's coefficient times its weight (the counts in `sums` are the plain ones) */
+extern "C" int cosa_seg_loss_backward_rw(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
+                                         const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
+                                         float wA_bg, float wA_fg, float wB_bg, float wB_fg,
+                                         int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream,
+                                         const float *relA, const float *relB)
+{
+    if (int rc = check_weight_maps("cosa_seg_loss_backward_rw", maskB, relA, relB)) return rc;
+    return seg_loss_backward_any(seg_lr, maskA, maskB, relA, relB, sums, AS, roi, g_seg, g_regw, grad_seg_lr, wA_bg, wA_fg, wB_bg, wB_fg, B, K, hs,
+                                 ws, S, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cosa_seg_loss_backward(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,

@@ -26,7 +26,7 @@ from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
-from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher, tokcon_settings
+from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher, reliability_settings, tokcon_settings
 from .utils import evaluation
 from .utils import grad_check as gcheck
 from .utils import torch_helper
@@ -81,7 +81,10 @@ def check_supported(args):
         gcheck.check_rho(getattr(args, "grad_check_rho", gcheck.DEFAULT_RHO))
     refuse_fp64_teacher(getattr(args, "teacher_precision", "auto"), flag="--")
     tokcon_settings(args, flag="--")                              # the token contrast term: ranges, and not together with --grad_check_iters
+    rel_on, rel_beta, _ = reliability_settings(args, flag="--")       # the reliability-weighted seg loss: ranges
     notes = []
+    if not rel_on and rel_beta != 1.0:
+        notes.append("--camweight_beta: only read with --seg_reliability true")
     if not args.find_unused:
         notes.append("--find_unused false: no effect (DDP runs without find_unused_parameters; the unused ImageNet head is frozen)")
     if args.segconf_thre != 0.25:
@@ -161,6 +164,25 @@ def grad_check_record(summary, n_iter, targs):
 def append_grad_check(output_dir, summary, n_iter, targs):
     with (Path(output_dir) / "grad_check.jsonl").open("a") as f:
         f.write(grad_check_record(summary, n_iter, targs) + "\n")
+
+
+SEG_REL_SETS = ("main", "aux")
+
+
+def seg_rel_line(summary):
+    """the evaluation's fragment of --seg_reliability (trainer.seg_reliability(): one dict per CAM set): ' seg_rel: main bg 0.612 fg 0.371,
+    aux bg ... fg ...'; a group without a pixel prints '-'"""
+    f = lambda v: "-" if v is None else "%.3f" % v
+    return " seg_rel: " + ", ".join("%s bg %s fg %s" % (n, f(s["bg"]), f(s["fg"])) for n, s in zip(SEG_REL_SETS, summary))
+
+
+def append_seg_reliability(output_dir, summary, n_iter, targs):
+    """one line of <output_dir>/seg_reliability.jsonl: the iteration, the weight's settings and the mean weights since the last evaluation"""
+    import json
+    rec = dict(iters=int(n_iter), beta=float(targs.camweight_beta), floor=float(targs.seg_reliability_floor),
+               **{n: s for n, s in zip(SEG_REL_SETS, summary)})
+    with (Path(output_dir) / "seg_reliability.jsonl").open("a") as f:
+        f.write(json.dumps(rec) + "\n")
 
 
 def next_batch(it, new_iter, pos):
@@ -283,6 +305,10 @@ def main(args):
             score_kw = {"image_scores": True} if args.image_scores else {}           # (off: the calls as ever)
             if getattr(args, "boundary_scores", False):
                 score_kw["boundary_scores"] = True
+            rel_summary = trainer.seg_reliability()                                 # (--seg_reliability; None with the switch off: nothing printed)
+            if rel_summary is not None and is_main:
+                log(seg_rel_line(rel_summary))
+                append_seg_reliability(output_dir, rel_summary, n_iter + 1, targs)
             res_o = evaluate(trainer.student, val_loader, args, df=df, epoch=n_iter + 1, s_or_t='s', get_camiou=True,
                              threshold_filters=args.eval_threshold_filters, **score_kw)
             if is_main:

@@ -45,7 +45,8 @@ def default_args(dataset="VOC12", **over):
              teacher_check_iters=0, teacher_check_mode="auto", student_check_iters=0, student_check_mode="fp32", gt_stats=False, gt_dir=None,
              act_stats_iters=0, camloss_version='v1', segconf_thre=0.25,
              grad_check_iters=0, grad_check_mode='fp64', grad_check_dirs='all', grad_check_rho=gcheck.DEFAULT_RHO,
-             tokcon_weight=0.0, tokcon_temp=0.5, tokcon_purity=1.0)
+             tokcon_weight=0.0, tokcon_temp=0.5, tokcon_purity=1.0,
+             seg_reliability=False, seg_reliability_floor=0.0, camweight_beta=1.0)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -130,6 +131,17 @@ def tokcon_settings(args, flag=""):
     return float(w), float(t), float(p)
 
 
+def reliability_settings(args, flag=""):
+    """(on, beta, floor) of the reliability-weighted seg loss from `args` (off where the fields are missing): the
+    switch, the reference's --camweight_beta and the floor, refused when one is outside its range -- with the switch off too, so that a
+    typo does not wait for the run that turns it on; here for the trainer and, with flag="--", for the launcher's check_supported"""
+    beta = getattr(args, "camweight_beta", 1.0)
+    floor = getattr(args, "seg_reliability_floor", 0.0)
+    beta, floor = (1.0 if beta is None else beta), (0.0 if floor is None else floor)
+    seg_helper.check_reliability_settings(beta, floor, flag=flag)
+    return bool(getattr(args, "seg_reliability", False)), float(beta), float(floor)
+
+
 def check_iters(args, which, flag=""):
     """--<which>_check_iters of `args` (which: "teacher" / "student" / "grad"), or --act_stats_iters (which: "act_stats"), as an int; a negative one is
     refused, here for the trainer and, with flag="--", for the launcher's check_supported"""
@@ -172,6 +184,9 @@ class CoSATrainer:
         self.device = device
         self.camloss_version = camloss_version(args)      # (before anything is built: an unknown version costs nothing)
         self._tokcon = tokcon_settings(args)              # (likewise: the token contrast term; weight 0: off)
+        self._seg_rel = reliability_settings(args)        # (likewise: the reliability-weighted seg loss)
+        # its counters, int64 [G][4] (seg_helper.new_reliability_stats): the run's, read and zeroed by seg_reliability(); None: the switch is off
+        self.seg_rel_state = seg_helper.new_reliability_stats(2 if args.aux_cam2seg else 1, device) if self._seg_rel[0] else None
         if check_iters(args, "grad") > 0:                 # (--grad_check_iters, DESIGN.md section 25: refused before anything is built too)
             args.grad_check_mode = gcheck.check_mode(getattr(args, "grad_check_mode", "fp64"))
             args.grad_check_dirs = gcheck.check_dirs(getattr(args, "grad_check_dirs", "all"))
@@ -574,15 +589,16 @@ class CoSATrainer:
         cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
         l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
         l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
+        rel_main, rel_aux = ctx.get("rel", (None, None))      # (--seg_reliability: the step's weight maps, so the checks see the weighted term)
         if self.fused_losses:
             l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
-                                                     aux_alpha=args.aux_cam2seg_alpha)
+                                                     aux_alpha=args.aux_cam2seg_alpha, **self._rel_kw(rel_main, rel_aux))
             cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
         else:
             up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
-            l_seg = seg_helper.seg_loss(up, mask, fg_alpha=args.segfg_alpha)
+            l_seg = self._seg_loss_torch(up, mask, rel_main)
             if mask_aux is not None:
-                l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * seg_helper.seg_loss(up, mask_aux, fg_alpha=args.segfg_alpha)
+                l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * self._seg_loss_torch(up, mask_aux, rel_aux)
             cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
         if self.camloss_version != "v1":               # (ctx["tgt"]: v2's targets, v3's label map)
             cam_l = self._cam_loss_fn(ctx["tgt"])
@@ -783,6 +799,17 @@ class CoSATrainer:
                 refine_mask_label = seg_helper.cam2mask(img_denorm, img_box, cam_ps, cls_label, threhigh, threlow,
                                                         refine_model=self.refine_model, downscale=args.par_downscale,
                                                         _fold_validation=True)
+            rel_main = rel_aux = None
+            if self._seg_rel[0]:
+                # --seg_reliability: one weight map per label map from the CAMs, thresholds and labels cam2mask just
+                # read and wrote -- one launch for both sets, thresholds still on the device under --usegmm
+                aux_on = bool(args.aux_cam2seg)
+                rels = (seg_helper.label_reliability if fused else seg_helper._label_reliability_torch)(
+                    [cam_ps, cam_aux_ps] if aux_on else [cam_ps], cls_label,
+                    [refine_mask_label, refine_mask_label_aux] if aux_on else [refine_mask_label],
+                    [threhigh, auxthrehigh] if aux_on else [threhigh], [threlow, auxthrelow] if aux_on else [threlow],
+                    beta=self._seg_rel[1], floor=self._seg_rel[2], stats=self.seg_rel_state)
+                rel_main, rel_aux = rels[0], (rels[1] if aux_on else None)
             if self.label_stats_state is not None:
                 self.update_label_stats(refine_mask_label, refine_mask_label_aux, seg_pred, cls_label, img_box,
                                         cam_ps, cam_aux_ps if args.aux_cam2seg else None)
@@ -792,12 +819,13 @@ class CoSATrainer:
             # one forward + one backward kernel instead of ~10 full-resolution passes (same maths, main.py:167-212)
             seg_loss, reg_loss = seg_helper.fused_seg_and_energy_loss(seg_pred, refine_mask_label, refine_mask_label_aux, simg,
                                                                       img_box, self.reg_layer, prepared=self._lattice,
-                                                                      fg_alpha=args.segfg_alpha, aux_alpha=args.aux_cam2seg_alpha)
+                                                                      fg_alpha=args.segfg_alpha, aux_alpha=args.aux_cam2seg_alpha,
+                                                                      **self._rel_kw(rel_main, rel_aux))
         else:
             seg_pred = F.interpolate(seg_pred, size=refine_mask_label.shape[1:], mode='bilinear', align_corners=False)
-            seg_loss = seg_helper.seg_loss(seg_pred, refine_mask_label, fg_alpha=args.segfg_alpha)
+            seg_loss = self._seg_loss_torch(seg_pred, refine_mask_label, rel_main)
             if args.aux_cam2seg:
-                seg_loss_aux = seg_helper.seg_loss(seg_pred, refine_mask_label_aux, fg_alpha=args.segfg_alpha)
+                seg_loss_aux = self._seg_loss_torch(seg_pred, refine_mask_label_aux, rel_aux)
                 seg_loss = (1 - args.aux_cam2seg_alpha) * seg_loss + args.aux_cam2seg_alpha * seg_loss_aux
             reg_loss = seg_helper.get_energy_loss(img=simg, logit=seg_pred, label=refine_mask_label, img_box=img_box,
                                                   loss_layer=self.reg_layer)
@@ -830,6 +858,7 @@ class CoSATrainer:
         if self.model_SK is not None and self._is_check_step(n_iter, "student"):
             # what the check after this step's backward (_student_check) reads: detached references, nothing is copied or computed here
             self._scheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux), tgt=check_tgt_s,
+                                    rel=(rel_main, rel_aux),
                                     outputs=dict(seg=seg_lr.detach(), cam=cam_pred.detach(), cam_aux=cam_aux_pred.detach(),
                                                  cls=cls_final.detach(), cls_aux=cls_aux.detach()),
                                     losses=tuple(t.detach() for t in (cls_loss, cls_loss_aux, seg_loss, cam_loss)))
@@ -849,7 +878,7 @@ class CoSATrainer:
             # below rounds them (fp32), nothing is copied or computed here
             wl32 = [float(np.float32(v)) for v in ([1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight])]
             self._gcheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux),
-                                    tgt=check_tgt_s, weights=wl32)
+                                    tgt=check_tgt_s, weights=wl32, rel=(rel_main, rel_aux))
         terms = [cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(), reg_loss.reshape(()).float()]
         if tok_on:
             terms.append(tok_loss.reshape(()).float())
@@ -865,6 +894,27 @@ class CoSATrainer:
         if tok_on:
             logs["tok_loss"] = tok_loss.detach()
         return loss, logs
+
+    @staticmethod
+    def _rel_kw(rel_main, rel_aux):
+        """the weight maps as the fused seg loss's keywords; none with --seg_reliability off: the call is then the one it has always been"""
+        return {} if rel_main is None else dict(rel_main=rel_main, rel_aux=rel_aux)
+
+    def _seg_loss_torch(self, up, mask, rel):
+        """the torch path's seg loss of one label map: seg_loss, or seg_weightloss under its weight map (--seg_reliability)"""
+        if rel is None:
+            return seg_helper.seg_loss(up, mask, fg_alpha=self.args.segfg_alpha)
+        return seg_helper.seg_weightloss(up, mask, rel, fg_alpha=self.args.segfg_alpha)
+
+    def seg_reliability(self):
+        """the mean weights (seg_helper.reliability_summary: one dict per CAM set, main then auxiliary) of --seg_reliability since the last
+        call, and the counters zeroed; None when the switch is off.  Synchronises: call it where a sync already happens (an evaluation).
+        The counters are not part of a state file: what they held since the last call is lost on --resume."""
+        if self.seg_rel_state is None:
+            return None
+        summary = seg_helper.reliability_summary(self.seg_rel_state)
+        self.seg_rel_state.zero_()
+        return summary
 
     def _token_contrast(self, feat, mask):
         """the token contrast term of the step: the returned feature map [B,768,h,w] taken back to its tokens

@@ -1100,12 +1100,14 @@ def act_stats_line(s):
         head, s["smax"], s["smax_at"][0], s["smax_at"][1], s["ent_mean"], s["ent_min"], s["ent_min_at"][0], s["ent_min_at"][1], s["over"])
 
 
-def seg_loss_forward_only(seg_lr, mask_main, mask_aux, img, img_box, fg_alpha=0.5, aux_alpha=0.5):
+def seg_loss_forward_only(seg_lr, mask_main, mask_aux, img, img_box, fg_alpha=0.5, aux_alpha=0.5, rel_main=None, rel_aux=None):
     """the seg-loss half of fused_seg_and_energy_loss by its forward kernel alone (_seg_loss_launch, _seg_loss_value: the same call, the
-    same value): no regulariser, nothing kept for a backward.  For the --student_check pass."""
+    same value): no regulariser, nothing kept for a backward.  For the --student_check pass.  rel_main / rel_aux: the step's weight maps
+    (--seg_reliability), as fused_seg_and_energy_loss takes them."""
     boxes = _boxes_to_device(img_box, seg_lr.device)
     weights = seg_blend_weights(fg_alpha, aux_alpha, mask_aux is not None)
-    return _seg_loss_value(_seg_loss_launch(seg_lr.detach(), mask_main, mask_aux, img, boxes, weights)[0], weights)
+    rel = _rel_pair(rel_main, rel_aux, mask_aux)
+    return _seg_loss_value(_seg_loss_launch(seg_lr.detach(), mask_main, mask_aux, img, boxes, weights, rel)[0], weights)
 
 
 EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16,          # COSA_EXPORT_* of include/cosa_hip.h
@@ -1681,9 +1683,21 @@ def _blend_vec(weights, device):
     return v
 
 
-def _seg_loss_launch(seg_lr, maskA, maskB, simg, boxes, weights):
+def _rel_pair(rel_main, rel_aux, mask_aux):
+    """(relA, relB | None) for the _rw entry points, or None without weight maps: one map per label map"""
+    if rel_main is None:
+        if rel_aux is not None:
+            raise ValueError("seg loss: rel_aux without rel_main")
+        return None
+    if (rel_aux is None) != (mask_aux is None):
+        raise ValueError("seg loss: an auxiliary weight map goes with an auxiliary label map, and only with one")
+    return (rel_main, rel_aux)
+
+
+def _seg_loss_launch(seg_lr, maskA, maskB, simg, boxes, weights, rel=None):
     """the seg-loss forward kernel -> (its eight sums, (seg_lr, maskA, maskB) as the kernel read them, (s_seg, s_img, roi, unlabel): the
-    half-resolution tensors it leaves for the regulariser).  `weights`: FusedSegRegLoss's."""
+    half-resolution tensors it leaves for the regulariser).  `weights`: FusedSegRegLoss's.  `rel` = (relA, relB | None): per-pixel weight
+    maps [B,S,S] fp32 beside the label maps, contiguous on the device -- the call then goes to cosa_seg_loss_forward_rw."""
     _C.require_cuda(seg_lr, maskA, maskB, simg, boxes)
     if maskB is None and (weights is None or weights[2] != 0 or weights[3] != 0):
         raise ValueError("FusedSegRegLoss: no auxiliary label map needs weights with wB_bg = wB_fg = 0")
@@ -1701,11 +1715,19 @@ def _seg_loss_launch(seg_lr, maskA, maskB, simg, boxes, weights):
     maskA, simg = maskA.contiguous().float(), simg.contiguous().float()
     maskB = maskB.contiguous().float() if maskB is not None else None
     wsl = _C.workspace(L.cosa_seg_loss_workspace_bytes(B, K, hs, ws), dev, "seg_loss")
-    fwd, fwd_name = (L.cosa_seg_loss_forward, "cosa_seg_loss_forward") if weights is None else \
-        (L.cosa_seg_loss_forward_w, "cosa_seg_loss_forward_w")
-    _C.check(fwd(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(simg), _C.ptr(boxes), _C.ptr(sums),
-                 _C.ptr(s_seg), _C.ptr(s_img), _C.ptr(roi), _C.ptr(unl), B, K, hs, ws, S, _C.ptr(wsl), wsl.numel(),
-                 _C.stream_ptr()), fwd_name)
+    if rel is None:
+        fwd_name, tail = ("cosa_seg_loss_forward" if weights is None else "cosa_seg_loss_forward_w"), ()
+    else:
+        if weights is None:
+            raise ValueError("FusedSegRegLoss: weight maps need `weights` (the entry points with the defaults built in take none)")
+        _C.require_cuda(*rel)
+        for r, m in zip(rel, (maskA, maskB)):
+            if r is not None and (r.shape != m.shape or r.dtype != torch.float32 or not r.is_contiguous()):
+                raise ValueError("FusedSegRegLoss: a weight map is contiguous fp32 of its label map's shape")
+        fwd_name, tail = "cosa_seg_loss_forward_rw", (_C.ptr(rel[0]), _C.ptr(rel[1]))
+    _C.check(getattr(L, fwd_name)(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(simg), _C.ptr(boxes), _C.ptr(sums),
+                                  _C.ptr(s_seg), _C.ptr(s_img), _C.ptr(roi), _C.ptr(unl), B, K, hs, ws, S, _C.ptr(wsl), wsl.numel(),
+                                  _C.stream_ptr(), *tail), fwd_name)
     return sums, (seg_lr, maskA, maskB), (s_seg, s_img, roi, unl)
 
 
@@ -1726,11 +1748,13 @@ class FusedSegRegLoss(Function):
     kernels re-derive the per-pixel softmax from an LDS tile of the low-res logits.  Returns (seg_loss, reg_loss).
     `weights` = None: fg_alpha = 0.5 and aux_cam2seg_alpha = 0.5 (the reference defaults) through the entry points that have these built in
     (maskB required).  `weights` = seg_blend_weights(...): the general entry points (cosa_seg_loss_*_w); maskB may then be None (no auxiliary
-    label map).  Both give the same bits for the defaults (tests/test_loss_flags_gpu.py)."""
+    label map).  Both give the same bits for the defaults (tests/test_loss_flags_gpu.py).
+    `rel` = (relA, relB | None): per-pixel weight maps beside the label maps (seg_weightloss) through the _rw entry
+    points; None: the calls above, untouched."""
 
     @staticmethod
-    def forward(ctx, seg_lr, maskA, maskB, simg, boxes, weight, sigma_rgb, sigma_xy, prepared=None, weights=None):
-        sums, (seg_lr, maskA, maskB), (s_seg, s_img, roi, unl) = _seg_loss_launch(seg_lr, maskA, maskB, simg, boxes, weights)
+    def forward(ctx, seg_lr, maskA, maskB, simg, boxes, weight, sigma_rgb, sigma_xy, prepared=None, weights=None, rel=None):
+        sums, (seg_lr, maskA, maskB), (s_seg, s_img, roi, unl) = _seg_loss_launch(seg_lr, maskA, maskB, simg, boxes, weights, rel)
         B, K, Sq = s_seg.shape[0], s_seg.shape[1], s_seg.shape[-1]
         S = maskA.shape[-1]
         dev = seg_lr.device
@@ -1749,7 +1773,7 @@ class FusedSegRegLoss(Function):
                                                  Sq, Sq, float(sigma_rgb), float(sigma_xy), _C.ptr(wsb), wsb.numel(), _C.stream_ptr()),
                      "cosa_dense_energy_forward")
         seg_l = _seg_loss_value(sums, weights)      # (after the energy launches, which hide its five small ops: in front of them a step measured 0.27 ms more)
-        ctx.save_for_backward(seg_lr, maskA, maskB, sums, AS, roi)
+        ctx.save_for_backward(seg_lr, maskA, maskB, sums, AS, roi, *(rel if rel is not None else ()))
         ctx.weights = None if weights is None else tuple(float(w) for w in weights)
         ctx.weight = float(weight)
         ctx.S = S
@@ -1757,13 +1781,17 @@ class FusedSegRegLoss(Function):
 
     @staticmethod
     def backward(ctx, g_seg, g_reg):
-        seg_lr, maskA, maskB, sums, AS, roi = ctx.saved_tensors
+        seg_lr, maskA, maskB, sums, AS, roi, *rel = ctx.saved_tensors
         B, K, hs, ws = seg_lr.shape
         grad = torch.empty_like(seg_lr)
         gs = g_seg.reshape(1).float().contiguous()
         gr = (g_reg.reshape(1).float() * ctx.weight).contiguous()
         wsl = _C.workspace(_C.lib().cosa_seg_loss_workspace_bytes(B, K, hs, ws), seg_lr.device, "seg_loss")
-        if ctx.weights is None:
+        if rel:
+            _C.check(_C.lib().cosa_seg_loss_backward_rw(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(sums), _C.ptr(AS), _C.ptr(roi),
+                                                        _C.ptr(gs), _C.ptr(gr), _C.ptr(grad), *ctx.weights, B, K, hs, ws, ctx.S, _C.ptr(wsl),
+                                                        wsl.numel(), _C.stream_ptr(), _C.ptr(rel[0]), _C.ptr(rel[1])), "cosa_seg_loss_backward_rw")
+        elif ctx.weights is None:
             _C.check(_C.lib().cosa_seg_loss_backward(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(sums), _C.ptr(AS), _C.ptr(roi),
                                                      _C.ptr(gs), _C.ptr(gr), _C.ptr(grad), B, K, hs, ws, ctx.S, _C.ptr(wsl), wsl.numel(),
                                                      _C.stream_ptr()), "cosa_seg_loss_backward")
@@ -1771,7 +1799,7 @@ class FusedSegRegLoss(Function):
             _C.check(_C.lib().cosa_seg_loss_backward_w(_C.ptr(seg_lr), _C.ptr(maskA), _C.ptr(maskB), _C.ptr(sums), _C.ptr(AS), _C.ptr(roi),
                                                        _C.ptr(gs), _C.ptr(gr), _C.ptr(grad), *ctx.weights, B, K, hs, ws, ctx.S, _C.ptr(wsl),
                                                        wsl.numel(), _C.stream_ptr()), "cosa_seg_loss_backward_w")
-        return grad, None, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None, None
 
 
 class PreparedLattice:
@@ -1817,13 +1845,15 @@ class PreparedLattice:
 
 
 def fused_seg_and_energy_loss(seg_pred_lr, mask_main, mask_aux, img, img_box, loss_layer, prepared=None, fg_alpha=0.5, aux_alpha=0.5,
-                              _builtin_defaults=False):
+                              _builtin_defaults=False, rel_main=None, rel_aux=None):
     """(seg_loss, reg_loss) of main.py:167-212 for DenseEnergyLoss(scale_factor=0.5):
     (1 - aux_alpha) seg_loss(main, fg_alpha) + aux_alpha seg_loss(aux, fg_alpha), or seg_loss(main, fg_alpha) alone with `mask_aux` = None
     (--aux_cam2seg false), and the regulariser on the main labels.
     `prepared`: a PreparedLattice started on this step's `img` (optional; otherwise the lattice is built here).
     `_builtin_defaults`: the entry points with fg_alpha = aux_alpha = 0.5 built in instead of the weighted ones (same bits; kept for the
-    test of exactly that)."""
+    test of exactly that).
+    `rel_main` / `rel_aux`: per-pixel weight maps [b,S,S] fp32 in [0, 1] beside the label maps (label_reliability): each seg_loss term becomes
+    seg_weightloss with its map, on the _rw entry points.  None: today's calls, untouched."""
     if loss_layer.scale_factor != 0.5:
         raise NotImplementedError("fused losses are built for DenseEnergyLoss(scale_factor=0.5) (main.py:77)")
     boxes = _boxes_to_device(img_box, seg_pred_lr.device)
@@ -1833,7 +1863,7 @@ def fused_seg_and_energy_loss(seg_pred_lr, mask_main, mask_aux, img, img_box, lo
             raise ValueError("_builtin_defaults: the built-in entry points are fg_alpha = aux_alpha = 0.5 with an auxiliary label map")
         weights = None
     return FusedSegRegLoss.apply(seg_pred_lr, mask_main, mask_aux, img, boxes, loss_layer.weight, loss_layer.sigma_rgb,
-                                 loss_layer.sigma_xy * loss_layer.scale_factor, prepared, weights)
+                                 loss_layer.sigma_xy * loss_layer.scale_factor, prepared, weights, _rel_pair(rel_main, rel_aux, mask_aux))
 
 
 def _crop_mask_from_boxes(img_box, b, h, w, device):
@@ -2240,6 +2270,142 @@ def token_contrast_loss(tokens, labels, temp, return_count=False):
         loss, counts = _TokenContrastFn.apply(tokens.contiguous(), lab.contiguous(), float(temp))
         return (loss, counts[-1]) if return_count else loss
     return _token_contrast_torch(tokens, labels, temp, return_count=return_count)
+
+
+# --------------------------------------------------------------------------------------------
+# the reliability-weighted seg loss: the reference's seg_weightloss (utils/seg_helper.py:823-835, called by nothing
+# there) under this project's own weight -- how far the CAM behind a pseudo label lies from the threshold it passed
+# --------------------------------------------------------------------------------------------
+RELIABILITY_BETA = (0.0, 8.0)      # --camweight_beta: the exponent on the distance, in [0, 8]; 0: every labelled pixel weighs 1
+RELIABILITY_MAX_SETS = 4           # the kernel's envelope (csrc/reliability_kernels.hip): CAM sets per launch ...
+RELIABILITY_MAX_C = 255            # ... and classes
+_REL_FIX = 4294967296.0            # the counters' fixed point: rint(w * 2^32)
+
+
+def check_reliability_settings(beta, floor, flag=""):
+    """the weight's two settings (trainer: flag "", launcher: flag "--"), or a ValueError naming the one outside its range"""
+    if not RELIABILITY_BETA[0] <= float(beta) <= RELIABILITY_BETA[1]:
+        raise ValueError(f"{flag}camweight_beta {beta!r}: an exponent in [{RELIABILITY_BETA[0]:g}, {RELIABILITY_BETA[1]:g}]")
+    if not 0.0 <= float(floor) < 1.0:
+        raise ValueError(f"{flag}seg_reliability_floor {floor!r}: the weight of a pixel the CAM does not support, in [0, 1)")
+
+
+def new_reliability_stats(G, device):
+    """zeroed counters int64 [G][4] = {Sum_bg rint(w 2^32), n_bg, Sum_fg rint(w 2^32), n_fg} per CAM set"""
+    return torch.zeros((int(G), 4), device=device, dtype=torch.int64)
+
+
+def _reliability_shapes(cams_list, cls_labels, masks, thresholds_high, thresholds_low, stats):
+    G = len(cams_list)
+    if not (1 <= G <= RELIABILITY_MAX_SETS and len(masks) == G and len(thresholds_high) == G and len(thresholds_low) == G):
+        raise ValueError(f"label_reliability: 1 to {RELIABILITY_MAX_SETS} CAM sets, each with its label map and (high, low) threshold pair")
+    b, C, h, w = cams_list[0].shape
+    if h != w or not 1 <= C <= RELIABILITY_MAX_C or cls_labels.shape != (b, C):
+        raise ValueError(f"label_reliability: cams [b,C,S,S] with 1 <= C <= {RELIABILITY_MAX_C} and cls_labels [b,C] "
+                         f"(got {tuple(cams_list[0].shape)}, {tuple(cls_labels.shape)})")
+    for c, m in zip(cams_list, masks):
+        if c.shape != (b, C, h, w) or m.shape != (b, h, w):
+            raise ValueError("label_reliability: every CAM set [b,C,S,S] with a label map [b,S,S]")
+    if stats is not None and (stats.shape != (G, 4) or stats.dtype != torch.int64 or not stats.is_contiguous()
+                              or stats.device != cams_list[0].device):
+        raise ValueError(f"label_reliability: stats must be contiguous int64 [{G}][4] on the CAMs' device (new_reliability_stats)")
+    return G, b, C, h
+
+
+def _label_reliability_torch(cams_list, cls_labels, masks, thresholds_high, thresholds_low, beta=1.0, floor=0.0, stats=None):
+    """label_reliability op by op in fp32 torch, in the kernel's operation order: what the kernel is checked against, and the path of host
+    tensors and of fused_losses=False"""
+    check_reliability_settings(beta, floor)
+    G, b, C, S = _reliability_shapes(cams_list, cls_labels, masks, thresholds_high, thresholds_low, stats)
+    dev = cams_list[0].device
+    f32 = lambda v: torch.as_tensor(v, device=dev).reshape(()).to(torch.float32)
+    beta, floor = float(np.float32(beta)), float(np.float32(floor))
+    omf = float(np.float32(1.0) - np.float32(floor))
+    y = cls_labels.to(torch.float32)
+    out = []
+    for g in range(G):
+        hi, lo = f32(thresholds_high[g]), f32(thresholds_low[g])
+        cam = cams_list[g].to(torch.float32) * y[:, :, None, None]
+        l = masks[g].to(torch.float32).to(torch.int64)
+        bg, fg = l == 0, (l >= 1) & (l <= C)
+        m = cam.amax(dim=1)
+        v = cam.gather(1, (l - 1).clamp(0, C - 1).unsqueeze(1)).squeeze(1)
+        r = torch.where(bg, (lo - m) / lo, (v - hi) / (1.0 - hi))
+        r = torch.where(r != r, torch.zeros_like(r), r.clamp(0.0, 1.0))
+        if beta == 0.0:
+            u = torch.ones_like(r)
+        elif beta == 1.0:
+            u = r
+        else:
+            u = torch.where(r == 0, torch.zeros_like(r), torch.exp2(beta * torch.log2(r)))
+        w = torch.where(bg | fg, floor + omf * u, torch.zeros_like(u))
+        if stats is not None:
+            q = torch.round(w.double() * _REL_FIX).to(torch.int64)
+            stats[g] += torch.stack([(q * bg).sum(), bg.sum(), (q * fg).sum(), fg.sum()])
+        out.append(w)
+    return out
+
+
+def label_reliability(cams_list, cls_labels, masks, thresholds_high, thresholds_low, beta=1.0, floor=0.0, stats=None):
+    """One weight map [b,S,S] fp32 in [0, 1] per CAM set: how far the CAM behind each pseudo label lies from the threshold it passed.
+    For set g with thresholds (hi, lo) -- floats or device scalars --, label l = masks[g][b,p] and class row y = cls_labels[b], all fp32:
+        l == 0:       m = max_c (y[c] cam[b,c,p]),  r = (lo - m) / lo          (background: how far every present class stays below `lo`)
+        1 <= l <= C:  v = y[l-1] cam[b,l-1,p],      r = (v - hi) / (1 - hi)    (foreground: how far its own class rises above `hi`)
+        otherwise:    w = 0
+        r = 0 where it is NaN, else clamped to [0, 1];  u = r ** beta (beta 0: 1, beta 1: r itself);  w = floor + (1 - floor) u
+    Multiplying by y folds cam_validation in and is idempotent: raw and validated CAMs give the same map.  hi == lo makes it the distance
+    from one threshold; beta = 0 weighs every labelled pixel 1.  A label the CAM does not support -- PAR moved it there, or its class is
+    absent from y -- has r = 0 and weighs `floor`.
+    `stats` (new_reliability_stats(G)): counters the call ADDS to (reliability_summary reads them).
+    Device tensors: one launch for all sets (cosa_label_reliability), no host sync, device thresholds read on the device.  Host tensors:
+    the torch composition (_label_reliability_torch)."""
+    check_reliability_settings(beta, floor)
+    if not cams_list[0].is_cuda:
+        return _label_reliability_torch(cams_list, cls_labels, masks, thresholds_high, thresholds_low, beta, floor, stats)
+    _C.require_cuda(cls_labels, *cams_list, *masks)
+    G, b, C, S = _reliability_shapes(cams_list, cls_labels, masks, thresholds_high, thresholds_low, stats)
+    dev = cams_list[0].device
+    cams_list = [c.contiguous().float() for c in cams_list]
+    masks = [m.contiguous().float() for m in masks]
+    cls_labels = cls_labels.contiguous().float()
+    rel = [torch.empty((b, S, S), device=dev, dtype=torch.float32) for _ in range(G)]
+    ptrs = lambda ts: (ctypes.c_void_p * G)(*[t.data_ptr() for t in ts])
+    if any(torch.is_tensor(t) for t in list(thresholds_high) + list(thresholds_low)):
+        # thresholds that live on the device (adaptive thresholds): [G][hi, lo] float32, read by the kernel -- no host sync
+        tdev = torch.stack([torch.stack([torch.as_tensor(h, device=dev).reshape(()).to(torch.float32),
+                                         torch.as_tensor(l, device=dev).reshape(()).to(torch.float32)])
+                            for h, l in zip(thresholds_high, thresholds_low)]).contiguous()
+        hi = lo = (ctypes.c_float * G)(*([0.0] * G))
+    else:
+        tdev = None
+        hi = (ctypes.c_float * G)(*[float(t) for t in thresholds_high])
+        lo = (ctypes.c_float * G)(*[float(t) for t in thresholds_low])
+    _C.check(_C.lib().cosa_label_reliability(ptrs(cams_list), _C.ptr(cls_labels), ptrs(masks), ptrs(rel), hi, lo, _C.ptr(tdev), G, b, C, S,
+                                             float(beta), float(floor), _C.ptr(stats), _C.stream_ptr()), "cosa_label_reliability")
+    return rel
+
+
+def reliability_summary(stats):
+    """counters [G][4] (label_reliability's `stats`) -> one dict per CAM set: the mean weight of its background and of its foreground pixels
+    (None for a group without a pixel) and the two pixel counts.  Synchronises."""
+    rows = stats.tolist()
+    mean = lambda s, n: (s / _REL_FIX / n) if n else None
+    return [dict(bg=mean(r[0], r[1]), n_bg=r[1], fg=mean(r[2], r[3]), n_fg=r[3]) for r in rows]
+
+
+def seg_weightloss(seg_pred, mask_label, mask_weights, fg_alpha=0.5, ignore_index=255):
+    """utils/seg_helper.py:823-835: seg_loss with every pixel's cross-entropy multiplied by `mask_weights` [b,h,w]; the denominators stay the
+    plain counts of labelled pixels.  One log-softmax pass shared by the two class-balanced terms, as seg_loss."""
+    assert fg_alpha >= 0 and fg_alpha <= 1, "fg_alpha should be in [0,1]"
+    lab = mask_label.long()
+    bg_label = torch.where(lab != 0, torch.full_like(lab, ignore_index), lab)
+    fg_label = torch.where(lab == 0, torch.full_like(lab, ignore_index), lab)
+    logp = F.log_softmax(seg_pred.float(), dim=1)
+    bg_loss_raw = F.nll_loss(logp, bg_label, ignore_index=ignore_index, reduction='none')
+    bg_loss = (bg_loss_raw * mask_weights).sum() / ((bg_label != ignore_index).sum() + 1e-6)
+    fg_loss_raw = F.nll_loss(logp, fg_label, ignore_index=ignore_index, reduction='none')
+    fg_loss = (fg_loss_raw * mask_weights).sum() / ((fg_label != ignore_index).sum() + 1e-6)
+    return (1 - fg_alpha) * bg_loss + fg_alpha * fg_loss
 
 
 # --------------------------------------------------------------------------------------------

@@ -560,6 +560,23 @@ int cosa_seg_loss_backward_w(const float *seg_lr, const float *maskA, const floa
                              const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
                              float wA_bg, float wA_fg, float wB_bg, float wB_fg,
                              int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream);
+/* The same two with a weight per pixel of each label map (utils/seg_helper.py:823-835, seg_weightloss):
+ *   relA [B,S,S] beside maskA (required), relB [B,S,S] beside maskB (NULL exactly when maskB is NULL), each weight in [0, 1].
+ *   The weight multiplies the pixel's cross-entropy term; the denominators stay the plain counts of labelled pixels, so `sums` keeps its
+ *   layout {bgA_wsum, bgA_cnt, fgA_wsum, fgA_cnt, bgB_...} and the host forms the loss from it as above.  In the backward the pixel's
+ *   coefficient is multiplied by its weight.  Energy-grid outputs, the regulariser's share, the scatter and the fixed-point cells are those of
+ *   the _w entry points, and with every weight 1.0f so is every output bit.  Weights in [0, 1] keep the fixed-point range argument as it
+ *   is; a weight outside [0, 1] or a NaN contributes nothing and sets the sticky flag: NaN out, never a wrapped sum.
+ *   relA == NULL, or relB given without maskB (or maskB without relB): COSA_EINVAL, nothing is launched. */
+int cosa_seg_loss_forward_rw(const float *seg_lr, const float *maskA, const float *maskB, const float *simg,
+                             const int32_t *boxes, float *sums, float *s_seg, float *s_img, float *roi, uint8_t *unlabel,
+                             int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream,
+                             const float *relA, const float *relB);
+int cosa_seg_loss_backward_rw(const float *seg_lr, const float *maskA, const float *maskB, const float *sums, const float *AS,
+                              const float *roi, const float *g_seg, const float *g_regw, float *grad_seg_lr,
+                              float wA_bg, float wA_fg, float wB_bg, float wB_fg,
+                              int B, int K, int hs, int ws, int S, void *workspace, size_t workspace_bytes, void *stream,
+                              const float *relA, const float *relB);
 
 /* F.multilabel_soft_margin_loss (main.py:127-128 on the classification logits; seg_helper.py:593-602 on relu(cam) against the resized teacher
  * probabilities) and its gradient in one pass: loss[0] = mean_r mean_c -(y log s(v) + (1-y) log s(-v)), v = relu ? max(x,0) : x;
@@ -1146,6 +1163,26 @@ int cosa_token_contrast_fwd(const void *tokens, const uint8_t *labels, float *ro
 int cosa_token_contrast_bwd(const void *tokens, const uint8_t *labels, const float *rows, const int32_t *counts, const float *upstream,
                             void *dx, int B, int n, int dim, float tau, void *workspace, size_t workspace_bytes, void *stream);
 int cosa_token_junction_bwd4(const void *g0, const void *g1, const void *g2, const void *g3, float *dx, int B, int N, int dim, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The per-pixel weight of the reliability-weighted seg loss (csrc/reliability_kernels.hip): this project's own
+ * weighting, off by default.  For CAM set g with thresholds (hi, lo), image b, pixel p, l = (int)masks[g][b,p], y = labels[b]:
+ *   l == 0        m = max_c (y[c] cams[g][b,c,p]),  r = (lo - m) / lo
+ *   1 <= l <= C   v = y[l-1] cams[g][b,l-1,p],      r = (v - hi) / (1 - hi)
+ *   otherwise     rel = 0, and the pixel enters no statistic
+ *   r = (r != r) ? 0 : min(max(r, 0), 1);  u = 1 (beta == 0) | r (beta == 1) | (r == 0 ? 0 : exp2f(beta log2f(r)))
+ *   rel[g][b,p] = floor + (1 - floor) u            (fp32 in this order, no contraction; floor == 0 gives u exactly)
+ * cams / masks / rel: host arrays of G device pointers ([B,C,S,S] / [B,S,S] / [B,S,S] fp32), labels [B,C] in {0,1}: multiplying by y
+ * folds cam_validation in, so raw and validated CAMs give the same map.  The plane of a class absent from y is never read.
+ * thr_hi / thr_lo: host float[G]; thr_dev (optional): device float[G][2] = (hi, lo) per set, read by the kernel instead -- no host
+ * sync under adaptive thresholds, as cosa_cam2mask_multi.  stats (optional): device int64 [G][4] = {Sum_bg rint(rel 2^32), n_bg,
+ * Sum_fg rint(rel 2^32), n_fg}, ADDED to with integer atomics (no float atomics: the same bytes every run).  One launch for all sets.
+ * Envelope: 1 <= G <= 4, 1 <= C <= 255, 1 <= B <= 65535, 1 <= S <= 32768 (no alignment demand: float4 accesses where S*S % 4 == 0
+ * and the pointers allow, scalar ones elsewhere), 0 <= beta <= 8, 0 <= floor < 1.  Anything else is COSA_EINVAL and nothing is launched.
+ * ------------------------------------------------------------------------------------- */
+int cosa_label_reliability(const float *const *cams, const float *labels, const float *const *masks, float *const *rel,
+                           const float *thr_hi, const float *thr_lo, const float *thr_dev, int G, int B, int C, int S, float beta, float floor,
+                           long long *stats, void *stream);
 
 /* y[i] = the deterministic expf (spec E) as the export translation unit computes it: a test hook */
 int cosa_spec_expf(const float *x, float *y, long long n, void *stream);
