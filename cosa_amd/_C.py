@@ -1,255 +1,90 @@
 """ctypes binding of libcosa_hip.so -- the only way the Python host code reaches the HIP kernels.
 
-The C ABI is declared in include/cosa_hip.h.  Loading FAILS LOUDLY when the shared library is
-missing: there is no CPU or eager-PyTorch fallback anywhere in the product path.
+include/cosa_hip.h is the ONE declaration of the C ABI: every entry point's signature and every integer COSA_* constant the Python side uses
+are parsed from its text (parse_header), nothing is repeated here.  A new entry point is a prototype in the header and its definition in a
+.hip file.  Loading FAILS LOUDLY when the shared library or the header is missing: there is no CPU or eager-PyTorch fallback anywhere in
+the product path.
 """
 import ctypes
+import functools
 import os
+import re
+import types
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcosa_hip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "cosa_hip.h")
 _lib = None
 
 c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+_SCALARS = {"int": c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "long long": ctypes.c_longlong, "size_t": c_size_t,
+            "float": c_float, "double": ctypes.c_double}
 
 
 class CosaError(RuntimeError):
     pass
 
 
-_SIGS = {
-    "cosa_abi_version": (c_int, []),
-    "cosa_last_error": (ctypes.c_char_p, []),
-    "cosa_denormalize_img": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "cosa_cam_minmax_norm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "cosa_cam_minmax_norm_ws": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "cosa_cam_flip_merge_upsample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                     c_void_p]),
-    "cosa_cam_flip_merge_upsample_reuse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                           c_void_p]),
-    "cosa_cam2mask_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "cosa_cam2mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
-                              c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_cam2mask_multi_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "cosa_cam2mask_multi": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, ctypes.POINTER(c_void_p),
-                                    ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    ctypes.POINTER(c_int), c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_augment_record_bytes": (c_int, []),
-    "cosa_augment_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "cosa_augment_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_size_t, c_void_p]),
-    "cosa_augment_labels": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "cosa_gmm_workspace_bytes": (c_size_t, []),
-    "cosa_gmm_fit_thresholds": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_double, ctypes.c_double, c_int,
-                                        c_void_p, c_void_p, c_size_t, c_void_p]),
-    "cosa_par_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "cosa_par_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int,
-                                 c_int, c_void_p, c_size_t, c_void_p]),
-    "bilateralfilter": (None, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_float]),
-    "bilateralfilter_batch": (None, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                     c_float, c_float]),
-    "cosa_bilateral_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "cosa_bilateralfilter_batch_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
-                                               c_void_p, c_void_p, c_size_t, c_void_p]),
-    "cosa_dense_energy_prepare": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_dense_energy_forward_prepared": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                                   c_float, c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_dense_energy_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                          c_int, c_float, c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_dense_energy_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_seg_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "cosa_seg_loss_forward": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_seg_loss_backward": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_cam_loss_targets": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p,
-                              c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "cosa_seg_loss_forward_w": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_seg_loss_backward_w": (c_int, [c_void_p] * 9 + [c_float] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_cam_loss_targets_m": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p,
-                                c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
-    "cosa_cam_lossv2_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "cosa_cam_lossv2": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_cam_lossv3_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "cosa_cam_lossv3": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_cam_label": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_void_p, c_void_p,
-                       c_int, c_int, c_int, c_float, c_float, c_int, c_void_p]),
-    "cosa_optim_record_bytes": (c_size_t, []),
-    "cosa_optim_chunk_elems": (c_int, []),
-    "cosa_fused_adamw_ema": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float, c_void_p]),
-    "cosa_grad_accumulate": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p]),
-    "cosa_grad_guard_bytes": (c_size_t, []),
-    "cosa_grad_norm_workspace_bytes": (c_size_t, [c_int]),
-    "cosa_grad_norm": (c_int, [c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "cosa_fused_adamw_ema_guarded": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_int, c_float, c_void_p, c_void_p]),
-    "cosa_state_record_bytes": (c_size_t, []),
-    "cosa_state_chunk_bytes": (c_size_t, []),
-    "cosa_state_layout": (c_size_t, [c_int, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
-    "cosa_state_snapshot": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "cosa_state_restore": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "cosa_add_layernorm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                       c_float, c_void_p]),
-    "cosa_layernorm_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "cosa_layernorm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                   c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "cosa_layernorm_bwd_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                       c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_eval_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
-                                 c_void_p]),
-    "cosa_cam_to_label": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_float, c_float,
-                                  ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
-    "cosa_confusion_hist": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
-    "cosa_export_record_layout": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_uint, ctypes.POINTER(c_size_t)]),
-    "cosa_export_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_float, c_float,
-                                 c_int, c_void_p, c_size_t, c_void_p]),
-    "cosa_export_refine_workspace_bytes": (c_size_t, [c_int, c_int, c_int, ctypes.c_uint, c_int, c_int]),
-    "cosa_export_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_uint, c_float, c_float,
-                                   c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "cosa_label_stats_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
-    "cosa_label_stats": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "cosa_gt_stats_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
-    "cosa_gt_stats": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p]),
-    "cosa_gt_stats_uses_lds": (c_int, [c_int]),
-    "cosa_teacher_check_layout": (c_size_t, [c_int, ctypes.POINTER(c_size_t)]),
-    "cosa_teacher_check_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "cosa_teacher_check": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "cosa_student_check_counters": (c_size_t, [c_int]),
-    "cosa_student_check": (c_int, [c_void_p] * 14 + [c_int] * 4 + [c_void_p]),
-    "cosa_tensor_stats_layout": (c_size_t, [ctypes.POINTER(c_size_t)]),
-    "cosa_tensor_stats_workspace_bytes": (c_size_t, [c_int]),
-    "cosa_tensor_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "cosa_grad_blame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    "cosa_spec_expf": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
-    "cosa_attn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "cosa_attn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "cosa_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                      c_size_t, c_void_p]),
-    "cosa_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_gemm_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "cosa_gemm_wgrad_batched": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "cosa_gemm_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "cosa_patch_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "cosa_patch_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "cosa_conv3x3_dilated_nhwc": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
-    "cosa_head_gemm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_longlong, c_int, c_int, c_int, c_int,
-                               c_int, c_void_p]),
-    "cosa_im2col_flip": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_im2col_flip_c8_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_im2col_flip_split_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_im2col_flip_split_tokens_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_msm_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_softmax_halfres_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_softmax_halfres_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_embed_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_head_gemm_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "cosa_head_gemm_wgrad_workspace": (c_size_t, [c_int, c_int]),
-    "cosa_head_gemm_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "cosa_conv3x3_dilated_wgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p, c_size_t, c_void_p]),
-    "cosa_gemm_set_variant": (None, [c_int]),
-    "cosa_gemm_set_grid_policy": (None, [c_int]),
-    "cosa_gemm_set_grid_policy_f16": (None, [c_int]),
-    "cosa_token_junction_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "cosa_gemm_set_stamp_slot": (None, [c_void_p]),
-    "cosa_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "cosa_attn_prepare_vt": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "cosa_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p,
-                      c_size_t, c_void_p]),
-}
+def _ctype(fn, ctype, ret=False):
+    """the ctypes type of the C type `ctype` of function `fn`: scalars by value, every pointer a c_void_p (the header's type does not say
+    whether an address is host or device memory), a `const char *` return a c_char_p; anything else is an error, never a guess"""
+    t = " ".join(w for w in ctype.replace("*", " * ").split() if w != "const")
+    if ret and t in ("void", "char *"):
+        return None if t == "void" else ctypes.c_char_p
+    if re.fullmatch(r"[\w ]+( \*)+", t):
+        return c_void_p
+    if t not in _SCALARS:
+        raise CosaError(f"cosa_hip.h: {fn}: unknown type '{ctype}'")
+    return _SCALARS[t]
 
-_SIGS.update({
-    "cosa_gemm_bf16_dual_gelu": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "cosa_pos_resize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "cosa_gelu_backward": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
-    "cosa_transpose_record_bytes": (c_size_t, []),
-    "cosa_transpose_cast_batched": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "cosa_broadcast_rows": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
-    "cosa_resize_bilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_split_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_void_p]),
-    "cosa_layernorm_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "cosa_gemm_bf16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_attn_fwd_bf16x3": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p]),
-    "cosa_lattice_filter_d2_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "cosa_lattice_filter_d2": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_c8_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_void_p]),
-    "cosa_c8_record_bytes": (c_size_t, []),
-    "cosa_c8_rows_batched": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "cosa_layernorm_c8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "cosa_gemm_f16c8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_attn_fwd_f16c8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
-    "cosa_radix_sort_workspace_bytes": (c_size_t, [ctypes.c_longlong]),
-    "cosa_radix_sort_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_size_t, c_void_p]),
-    "cosa_c4_scale_bytes": (c_size_t, [c_int, c_int]),
-    "cosa_c4_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_int, c_void_p]),
-    "cosa_c4_record_bytes": (c_size_t, []),
-    "cosa_c4_rows_batched": (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    "cosa_layernorm_c4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "cosa_attn_fwd_f16c4": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
-    "cosa_gemm_f16c4": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                c_int, c_void_p]),
-    # the "f32" operand family (csrc/f32_kernels.hip; teacher mode "fp32")
-    "cosa_gemm_f32": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
-    "cosa_conv3x3_dilated_f32": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_void_p]),
-    "cosa_attn_fwd_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
-    "cosa_layernorm_f32out": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "cosa_im2col_flip_f32_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    # the "f64" operand family (csrc/f64_kernels.hip; mode "fp64") and the criterion per plane (csrc/conformance_kernels.hip)
-    "cosa_gemm_f64": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
-    "cosa_conv3x3_dilated_f64": (c_int, [c_void_p] * 3 + [c_int] * 10 + [c_void_p]),
-    "cosa_attn_fwd_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_int, c_void_p]),
-    "cosa_layernorm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p]),
-    "cosa_im2col_flip_f64_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_resize_bilinear_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_cam_flip_merge_upsample_f64": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p]),
-    "cosa_cam_minmax_norm_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "cosa_conformance_planes": (c_int, [c_void_p] * 6 + [c_int, c_int] + [ctypes.c_double] * 3 + [c_void_p] * 3),
-    # the --act_stats_iters monitor (csrc/act_stats_kernels.hip)
-    "cosa_range_stats_f32": (c_int, [c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, c_void_p, c_void_p]),
-    "cosa_attn_stats_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, ctypes.c_longlong, c_void_p, c_void_p]),
-    # per-image evaluation counters (csrc/image_scores_kernels.hip)
-    "cosa_image_scores_words": (c_size_t, [c_int, c_int]),
-    "cosa_image_scores": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_size_t, c_int, c_void_p, c_void_p]),
-    # the same row over band pixels, Boundary IoU (csrc/boundary_scores_kernels.hip)
-    "cosa_boundary_scores_words": (c_size_t, [c_int, c_int]),
-    "cosa_boundary_scores": (c_int, [c_void_p, ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    # label-free export (csrc/predict_kernels.hip)
-    "cosa_predict_classes": (c_int, [c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "cosa_export_overlay": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    # the CAM pictures of export (csrc/heat_kernels.hip)
-    "cosa_export_camheat": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "cosa_export_panel": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    # the --grad_check_iters check (csrc/grad_check_kernels.hip)
-    "cosa_grad_check_workspace_bytes": (c_size_t, [c_int]),
-    "cosa_grad_check_norms": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "cosa_grad_check_perturb": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    # the supervised-contrastive token loss (csrc/tokcon_kernels.hip)
-    "cosa_token_labels": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "cosa_token_contrast_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "cosa_token_contrast_fwd": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_token_contrast_bwd": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float, c_void_p, c_size_t, c_void_p]),
-    "cosa_token_junction_bwd4": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
-    # the reliability-weighted seg loss (csrc/reliability_kernels.hip, and the _rw pair of csrc/loss_kernels.hip)
-    "cosa_label_reliability": (c_int, [ctypes.POINTER(c_void_p), c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
-                                       ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
-                                       c_void_p, c_void_p]),
-    "cosa_seg_loss_forward_rw": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p] + [c_void_p] * 2),
-    "cosa_seg_loss_backward_rw": (c_int, [c_void_p] * 9 + [c_float] * 4 + [c_int] * 5 + [c_void_p, c_size_t, c_void_p] + [c_void_p] * 2),
-})
+
+def parse_header(text):
+    """-> ({name: (restype, argtypes)}, {COSA_X: int}) from the text of a C header in the style of include/cosa_hip.h"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(COSA_\w+)[ \t]+(\d+)u?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#[^\n]*|extern\s+"C"\s*\{|typedef\s+struct\b[^{};]*\{[^{}]*\}[^;]*;', " ", text, flags=re.M)
+    sigs = {}
+    for stmt in (" ".join(s.split()) for s in text.split(";")):
+        if stmt in ("", "}"):                                       # (the closing brace of extern "C")
+            continue
+        m = re.fullmatch(r"(.+?)\b(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise CosaError(f"cosa_hip.h: cannot parse '{stmt}'")
+        ret, fn, args = m.groups()
+        params = [] if args.strip() == "void" else [re.fullmatch(r"(.+?)\b\w+", a.strip()) for a in args.split(",")]
+        if not all(params):
+            raise CosaError(f"cosa_hip.h: {fn}: cannot parse the parameters '{args}'")
+        sigs[fn] = (_ctype(fn, ret, ret=True), [_ctype(fn, p[1]) for p in params])
+    return sigs, types.MappingProxyType(consts)
+
+
+@functools.lru_cache(maxsize=None)
+def _header():
+    if not os.path.exists(HEADER_PATH):
+        raise CosaError(f"{HEADER_PATH} is missing: the binding takes every signature and constant from it")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+def declared_symbols():
+    return list(_header()[0])
+
+
+def constant(name):
+    """the integer `#define COSA_...` of include/cosa_hip.h"""
+    return _header()[1][name]
+
 
 # the fp16-operand builds of the GEMM / attention translation units export the same signatures under other names: THE table of the twins whose
 # name is not `name + "_f16"`, plus the attention backward's pair, which is regular but listed so that every 16-bit entry point a test picks
-# by dtype is named in one place (fn16 resolves through it); the other regular ones are listed below for their signatures
+# by dtype is named in one place (fn16 resolves through it)
 _F16_TWIN = {"cosa_gemm_bf16": "cosa_gemm_f16", "cosa_gemm_wgrad_bf16": "cosa_gemm_wgrad_f16",
              # fp16x3 (round 6): the three-term GEMM / attention with fp16 halves
              "cosa_gemm_bf16x3": "cosa_gemm_f16x3", "cosa_attn_fwd_bf16x3": "cosa_attn_fwd_f16x3",
              # the student's attention backward: the fp16 build of the same three kernels
              "cosa_attn_bwd": "cosa_attn_bwd_f16", "cosa_attn_bwd_workspace_bytes": "cosa_attn_bwd_workspace_bytes_f16"}
-for _bf in list(_F16_TWIN) + ["cosa_layernorm", "cosa_conv3x3_dilated_nhwc", "cosa_conv3x3_dilated_wgrad", "cosa_gemm_set_variant",
-                              "cosa_gemm_set_stamp_slot", "cosa_attn_workspace_bytes", "cosa_attn_prepare_vt", "cosa_attn_fwd",
-                              "cosa_split_rows", "cosa_layernorm_split"]:
-    _SIGS[_F16_TWIN.get(_bf, _bf + "_f16")] = _SIGS[_bf]
-
-# entry points added by later translation units register themselves here (vit / gemm / attention)
-EXTRA_SIGS = {}
 
 
 def fn16(name, dtype):
@@ -261,6 +96,22 @@ def fn16(name, dtype):
     raise CosaError(f"{name}: operands must be bfloat16 or float16, got {dtype}")
 
 
+def load(path, strict=True):
+    """Open the library at `path` and give every entry point of the header its restype / argtypes.  A name the library lacks is an error, or
+    with strict=False left unset (an older build in an A/B run)."""
+    L = ctypes.CDLL(path)
+    for name, (res, args) in _header()[0].items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError as e:
+            if not strict:
+                continue
+            raise CosaError(f"{os.path.basename(path)} does not export {name} (stale build?)") from e
+        fn.restype = res
+        fn.argtypes = args
+    return L
+
+
 def lib():
     """Load libcosa_hip.so (once).  Raises CosaError if it has not been built."""
     global _lib
@@ -269,20 +120,8 @@ def lib():
             raise CosaError(
                 f"{LIB_PATH} is missing: build the HIP extension first (python -m cosa_amd.build). "
                 "cosa_amd has no CPU fallback.")
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(EXTRA_SIGS.items()):
-            try:
-                fn = getattr(L, name)
-            except AttributeError as e:
-                raise CosaError(f"libcosa_hip.so does not export {name} (stale build?)") from e
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = load(LIB_PATH)
     return _lib
-
-
-def declared_symbols():
-    return list(_SIGS) + list(EXTRA_SIGS)
 
 
 def check(rc, what=""):

@@ -459,7 +459,7 @@ def attn_fwd_f32(qkv, B, N, H, out):
     return out
 
 
-RANGE_STATS_WORDS, ATTN_STATS_WORDS = 6, 7          # COSA_ACT_STATS_RANGE_WORDS / _HEAD_WORDS (include/cosa_hip.h: the words)
+RANGE_STATS_WORDS, ATTN_STATS_WORDS = _C.constant("COSA_ACT_STATS_RANGE_WORDS"), _C.constant("COSA_ACT_STATS_HEAD_WORDS")   # (include/cosa_hip.h: the words)
 
 
 def _stats_words(out, n, what):

@@ -84,7 +84,7 @@ def pseudo_scores(label_trues, label_preds, num_classes):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # per-image scores: the counters of cosa_image_scores, the reference's assist_seg from them, the score files
 # ---------------------------------------------------------------------------------------------------------------------------------
-MAX_MAPS = 8                                      # COSA_IMAGE_SCORES_MAX_MAPS: maps per launch
+MAX_MAPS = _C.constant("COSA_IMAGE_SCORES_MAX_MAPS")     # maps per launch
 
 
 def row_words(num_classes, n_maps):

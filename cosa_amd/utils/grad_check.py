@@ -13,8 +13,8 @@ import torch
 
 from .. import _C
 
-CHUNK = 16384                                  # COSA_GRAD_CHECK_CHUNK
-RECORD = 36                                    # COSA_GRAD_CHECK_RECORD: doubles per direction
+CHUNK = _C.constant("COSA_GRAD_CHECK_CHUNK")
+RECORD = _C.constant("COSA_GRAD_CHECK_RECORD")       # doubles per direction
 G2, W2, S, FLAGS, T, LOSS, BAD_G, BAD_W = 0, 1, 2, 3, 4, 8, 33, 34
 FLAG_ZERO_GRAD, FLAG_BAD_GRAD, FLAG_BAD_WEIGHT, FLAG_NO_STEP = 1, 2, 4, 8
 FLAG_NAMES = ((FLAG_ZERO_GRAD, "zero_grad"), (FLAG_BAD_GRAD, "nonfinite_grad"), (FLAG_BAD_WEIGHT, "nonfinite_weight"), (FLAG_NO_STEP, "no_step"))
@@ -27,7 +27,7 @@ DIRS = ("all", "sites")
 DEFAULT_RHO = 1e-5
 
 _TABLE_DTYPE = np.dtype([("w", "<u8"), ("g", "<u8"), ("dst", "<u8"), ("n", "<i8"), ("dir", "<i4"), ("pad", "<i4")])
-assert _TABLE_DTYPE.itemsize == 40             # COSA_GRAD_CHECK_RECORD_BYTES
+assert _TABLE_DTYPE.itemsize == _C.constant("COSA_GRAD_CHECK_RECORD_BYTES")
 
 
 def check_mode(mode):

@@ -330,6 +330,7 @@ def _check_counters(counters, layout, who):
 # per-step pseudo-label statistics and the teacher finite check
 # --------------------------------------------------------------------------------------------
 LABEL_STATS_SLOTS = ("steps", "pix", "main", "aux", "agree", "inter", "pred", "bad_cam", "bad_cam_aux")     # cosa_label_stats_layout's order
+assert len(LABEL_STATS_SLOTS) == _C.constant("COSA_LABEL_STATS_SLOTS")
 LABEL_STATS_MAX_K = 128
 
 
@@ -369,7 +370,7 @@ def label_stats(mask_main, mask_aux, seg_logits, cls_label, img_box, cam, cam_au
     boxes = _boxes_to_device(img_box, dev)
     if step_scale is None:
         step_scale = torch.empty(1, device=dev, dtype=torch.float32)
-    ws = _C.workspace(8, dev, "label_stats")                         # COSA_LABEL_STATS_WORKSPACE_BYTES
+    ws = _C.workspace(_C.constant("COSA_LABEL_STATS_WORKSPACE_BYTES"), dev, "label_stats")
     _C.check(_C.lib().cosa_label_stats(_C.ptr(mask_main), _C.ptr(mask_aux), _C.ptr(seg_logits), _C.ptr(cls_label), _C.ptr(boxes), _C.ptr(cam),
                                        _C.ptr(cam_aux), B, K, S, h, w, int(ignore_index), _C.ptr(counters), _C.ptr(step_scale), _C.ptr(ws),
                                        _C.stream_ptr()), "cosa_label_stats")
@@ -455,6 +456,7 @@ def label_stats_summary(counters, K):
 # --gt_stats: pseudo labels and the student's prediction against the ground truth of the training crops
 # --------------------------------------------------------------------------------------------
 GT_STATS_SLOTS = ("steps", "pix", "valid", "gt_other", "main", "aux", "student")     # cosa_gt_stats_layout's order
+assert len(GT_STATS_SLOTS) == _C.constant("COSA_GT_STATS_SLOTS")
 
 
 def gt_stats_layout(K):
@@ -575,6 +577,7 @@ _TC_SET_FIELDS = ("planes", "over", "worst", "hist", "nonfinite_a", "nonfinite_b
 _TC_PAIR_FIELDS = ("pix", "agree", "ign_a", "ign_b", "cnt_a", "cnt_b", "inter")
 TEACHER_CHECK_SLOTS = ("checks",) + tuple(f"{s}.{f}" for s in TEACHER_CHECK_SETS for f in _TC_SET_FIELDS) + \
     tuple(f"{p}.{f}" for p in TEACHER_CHECK_PAIRS for f in _TC_PAIR_FIELDS)
+assert len(TEACHER_CHECK_SLOTS) == _C.constant("COSA_TEACHER_CHECK_SLOTS")
 TEACHER_CHECK_EDGES = (1e-6, 1e-5, 1e-4, 3e-4, 1e-3, 3e-3, 1e-2, float("inf"))      # upper edges of hist (as fp32), a plane in the first bin with fig <= edge
 TEACHER_CHECK_BAR = 1e-3                                          # the literal bar of tests/test_precision_gpu.py: normalised-CAM |delta| per plane
 TEACHER_CHECK_AGREE, TEACHER_CHECK_MIOU = 0.999, 0.999            # ... its label agreement and mask mIoU
@@ -750,7 +753,8 @@ def teacher_check_worst(summary):
 # --------------------------------------------------------------------------------------------
 CAM_BAR, COND_MAX, FP64_FACTOR = 1e-3, 50.0, 4.0                  # THE product's copy of the pre-registered constants (tests/test_precision_gpu.py)
 AGREE_BAR, MIOU_BAR = 0.999, 0.999                                # rule (c): label agreement per draw, pooled mask mIoU
-CONFORMANCE_FIGS = ("d", "lit", "cond", "own", "e_ref", "e_hip", "bound", "max32")      # COSA_CONFORMANCE_FIGS columns of cosa_conformance_planes
+CONFORMANCE_FIGS = ("d", "lit", "cond", "own", "e_ref", "e_hip", "bound", "max32")      # the columns of cosa_conformance_planes
+assert len(CONFORMANCE_FIGS) == _C.constant("COSA_CONFORMANCE_FIGS")
 CONFORMANCE_VERDICTS = {-1: "inactive", 0: "ok", 1: "exempt", 2: "fail"}
 
 
@@ -808,8 +812,9 @@ _SC_FIELDS = ("n", "nonfinite_a", "nonfinite_b", "max_abs", "range", "sum_d2", "
 STUDENT_CHECK_LOSSES = ("cls_loss", "cls_loss_aux", "seg_loss", "cam_loss")
 _SC_LOSS_FIELDS = ("sum_d", "sum_b", "max_abs", "n")
 STUDENT_CHECK_EDGES = (1e-3, 1e-2, 1e-1)                                        # upper edges (fp32, exclusive) of the flip histogram's first three bins
-STUDENT_CHECK_HEAD, STUDENT_CHECK_MAX_K = 62, 256                               # COSA_STUDENT_CHECK_HEAD / _MAX_K
-STUDENT_CHECK_FIXED = {"d2": (32, 10), "b2": (20, 22), "loss": (32, 10)}        # (fractional bits, a term must be < 2^int): COSA_STUDENT_CHECK_*_FRAC / _INT
+STUDENT_CHECK_HEAD, STUDENT_CHECK_MAX_K = _C.constant("COSA_STUDENT_CHECK_HEAD"), _C.constant("COSA_STUDENT_CHECK_MAX_K")
+STUDENT_CHECK_FIXED = {k: (_C.constant(f"COSA_STUDENT_CHECK_{k.upper()}_FRAC"), _C.constant(f"COSA_STUDENT_CHECK_{k.upper()}_INT"))
+                       for k in ("d2", "b2", "loss")}                           # (fractional bits, a term must be < 2^int)
 
 
 def student_check_layout(K):
@@ -1000,7 +1005,7 @@ ACT_STATS_SITES = ("q", "k", "v", "o", "h", "x")                               #
 ACT_STATS_F16_SITES = ("q", "k", "v", "o", "h")                                 # ... those an fp16x3 pass stores as fp16 halves (x is the fp32 stream)
 _AS_RANGE_FIELDS = ("finite", "absmax", "over", "near", "tiny", "nonfinite")    # cosa_range_stats_f32's six words
 _AS_HEAD_FIELDS = ("rows", "ent_fix", "top1_fix", "peaked", "smax", "sharp", "nonfinite_rows")      # cosa_attn_stats_f32's seven per head
-ACT_STATS_FRAC = 32                                                             # COSA_ACT_STATS_FRAC: ent_fix and top1_fix count 2^-32
+ACT_STATS_FRAC = _C.constant("COSA_ACT_STATS_FRAC")                             # ent_fix and top1_fix count 2^-32
 F16_MAX = 65504.0
 
 
@@ -1110,12 +1115,12 @@ def seg_loss_forward_only(seg_lr, mask_main, mask_aux, img, img_box, fg_alpha=0.
     return _seg_loss_value(_seg_loss_launch(seg_lr.detach(), mask_main, mask_aux, img, boxes, weights, rel)[0], weights)
 
 
-EXPORT_BITS = {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16,          # COSA_EXPORT_* of include/cosa_hip.h
-               "pseudo_par": 32, "pseudo_aux_par": 64}
+EXPORT_BITS = {k: _C.constant("COSA_EXPORT_" + k.upper()) for k in ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "pseudo_par", "pseudo_aux_par")}
 _EXPORT_SLOTS = ("seg", "pseudo", "pseudo_aux", "rawcam", "rawcam_aux", "rawcam_idx", "rawcam_aux_idx", "pseudo_par", "pseudo_aux_par")
-EXPORT_MAPS_MASK = 31                                    # the products cosa_export_maps writes; cosa_export_refine writes the PAR ones
+assert len(_EXPORT_SLOTS) == _C.constant("COSA_EXPORT_SLOTS")
+EXPORT_MAPS_MASK = _C.constant("COSA_EXPORT_ALL")                               # the products cosa_export_maps writes; cosa_export_refine writes the PAR ones
 EXPORT_PAR_MASK = EXPORT_BITS["pseudo_par"] | EXPORT_BITS["pseudo_aux_par"]
-EXPORT_REFINE_MIN_SIDE = 16                              # COSA_EXPORT_REFINE_MIN_SIDE
+EXPORT_REFINE_MIN_SIDE = _C.constant("COSA_EXPORT_REFINE_MIN_SIDE")
 PAR_DILATIONS, PAR_NUM_ITER = (1, 2, 4, 8, 12, 24), 10   # the refine model CoSA trains with (main.py: PAR(num_iter=10, dilations=[1,2,4,8,12,24]))
 
 
@@ -1240,7 +1245,7 @@ def export_refine(image, cam, cam_aux, cls_label, what, high_thre, low_thre, ign
     return {k: out[o:o + H * W].reshape(H, W) for k, o in offs.items() if k in ("pseudo_par", "pseudo_aux_par")}
 
 
-PREDICT_MAX_CLASSES = 256                                # COSA_PREDICT_MAX_CLASSES
+PREDICT_MAX_CLASSES = _C.constant("COSA_PREDICT_MAX_CLASSES")
 
 
 def cls_threshold_logit(cls_thre):
@@ -1313,7 +1318,7 @@ def export_overlay(image, seg, alpha=0.5, out=None, palette=None):
     return out.reshape(-1)[:3 * H * W].reshape(H, W, 3)
 
 
-CAMHEAT_MAX_CLASSES = 256                                # COSA_CAMHEAT_MAX_CLASSES
+CAMHEAT_MAX_CLASSES = _C.constant("COSA_CAMHEAT_MAX_CLASSES")
 PANEL_COLOUR = (10, 186, 181)                            # the panel's region colour (csrc/heat_kernels.hip)
 
 

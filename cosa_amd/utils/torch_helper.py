@@ -227,6 +227,7 @@ def accumulate_grads_torch(acc, grads, k, n, names=None):
 # per-tensor diagnostics: norms, the EMA gap, the blame counters
 # --------------------------------------------------------------------------------------------
 TENSOR_STATS_SLOTS =("g_sq", "w_sq", "gap_sq", "g_absmax", "g_nonfinite", "w_nonfinite")      # cosa_tensor_stats_layout's order
+assert len(TENSOR_STATS_SLOTS) == _C.constant("COSA_TENSOR_STATS_SLOTS")
 TENSOR_STATS_F64 = 4         # the first four slots of a row hold float64 bits, the last two uint64 counts
 
 

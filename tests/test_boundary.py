@@ -40,6 +40,102 @@ def test_python_binding_matches_header(built_lib):
     _C.lib()                               # resolves every symbol with its signature
 
 
+def test_parsed_signatures_of_pinned_entry_points():
+    """_C.parse_header on include/cosa_hip.h: exact (restype, argtypes) of one entry point per rule of the parser, written out here by hand"""
+    from cosa_amd import _C
+    P, I, U, LL, Z, F, D = (ctypes.c_void_p, ctypes.c_int, ctypes.c_uint, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_float, ctypes.c_double)
+    want = {
+        "cosa_last_error": (ctypes.c_char_p, []),
+        "bilateralfilter": (None, [P, I, P, I, P, I, I, I, F, F]),
+        "cosa_gemm_set_stamp_slot": (None, [P]),
+        "cosa_gmm_fit_thresholds": (I, [P, P, LL, I, D, D, I, P, P, Z, P]),
+        "cosa_export_record_layout": (Z, [I, I, I, I, U, P]),
+        "cosa_state_layout": (Z, [I, P, P]),
+        "cosa_cam2mask_multi": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, I, I, F, P, Z, P]),
+        "cosa_range_stats_f32": (I, [P, LL, I, LL, P, P]),
+        "cosa_attn_fwd_f64": (I, [P, P, I, I, I, I, D, I, I, P]),
+        "cosa_attn_fwd_f32": (I, [P, P, I, I, I, I, F, I, I, P]),
+        "cosa_image_scores": (I, [P, P, P, I, Z, I, P, P]),
+    }
+    assert len(want["cosa_cam2mask_multi"][1]) == 21
+    sigs, _ = _C.parse_header(open(os.path.join(ROOT, "include", "cosa_hip.h")).read())
+    assert sorted(sigs) == sorted(_C.declared_symbols())
+    for name, sig in want.items():
+        assert sigs[name] == sig, name
+
+
+def test_f16_twins_are_declared_like_their_bf16_entry_points():
+    """fn16 hands out `X_f16` (or _F16_TWIN[X]) for the call written against X: the header must declare the two alike"""
+    from cosa_amd import _C
+    sigs, _ = _C.parse_header(open(os.path.join(ROOT, "include", "cosa_hip.h")).read())
+    pairs = [(n[:-4], n) for n in sigs if n.endswith("_f16") and n[:-4] in sigs] + list(_C._F16_TWIN.items())
+    assert len(pairs) >= 16
+    for bf, f16 in pairs:
+        assert sigs[bf] == sigs[f16], (bf, f16)
+
+
+def test_header_parser_fails_loudly():
+    """an unknown type, a truncated prototype, a parameter without a type: CosaError naming the function, never a skipped or guessed row"""
+    from cosa_amd import _C
+    for bad in ("int cosa_x(struct Foo v);", "int cosa_x(int a", "int cosa_x(int a, float", "int cosa_x(int a\nint cosa_y(int b);",
+                "int cosa_x(int a, b);", "uint64_t cosa_x(void);", "char *cosa_x(int a, char c);", "int cosa_x(int a[4]);"):
+        with pytest.raises(_C.CosaError, match="cosa_x"):
+            _C.parse_header(bad)
+    sigs, consts = _C.parse_header('#ifdef __cplusplus\nextern "C" {\n#endif\n#define COSA_A 12u /* twelve */\n#define COSA_B 3 // three\n#define COSA_H\n'
+                                   "typedef struct T { const void *a, *b; int n; } T;\n"
+                                   "int cosa_x(const float *a /* [n] or NULL, (see) ; */, // the rest;\n    unsigned int n,\n    const T *const *t);\n"
+                                   "void cosa_y( void );\n#ifdef __cplusplus\n}\n#endif\n")
+    assert sigs == {"cosa_x": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]), "cosa_y": (None, [])}
+    assert dict(consts) == {"COSA_A": 12, "COSA_B": 3}
+    with pytest.raises(TypeError):
+        consts["COSA_A"] = 1                                                      # read-only
+
+
+def test_missing_header_is_an_error_naming_the_path(monkeypatch, tmp_path):
+    from cosa_amd import _C
+    gone = str(tmp_path / "include" / "cosa_hip.h")
+    monkeypatch.setattr(_C, "HEADER_PATH", gone)
+    _C._header.cache_clear()
+    try:
+        with pytest.raises(_C.CosaError, match=re.escape(gone)):
+            _C.declared_symbols()
+    finally:
+        monkeypatch.undo()
+        _C._header.cache_clear()
+    assert len(_C.declared_symbols()) == len(_header_symbols())
+
+
+def test_python_constants_are_the_headers():
+    """the values the Python modules held as literals before they were read from include/cosa_hip.h: the move changed none, and an edit of
+    the header that changes one is seen here"""
+    from cosa_amd import _C, nn_ops
+    from cosa_amd.utils import evaluation, grad_check as gcheck, seg_helper as sh
+    assert sh.EXPORT_BITS == {"seg": 1, "pseudo": 2, "pseudo_aux": 4, "rawcam": 8, "rawcam_aux": 16, "pseudo_par": 32, "pseudo_aux_par": 64}
+    assert sh.EXPORT_MAPS_MASK == 31 and sh.EXPORT_REFINE_MIN_SIDE == 16
+    assert sh.PREDICT_MAX_CLASSES == sh.CAMHEAT_MAX_CLASSES == 256
+    assert sh.STUDENT_CHECK_HEAD == 62 and sh.STUDENT_CHECK_MAX_K == 256
+    assert sh.STUDENT_CHECK_FIXED == {"d2": (32, 10), "b2": (20, 22), "loss": (32, 10)}
+    assert sh.ACT_STATS_FRAC == 32
+    assert nn_ops.RANGE_STATS_WORDS == 6 and nn_ops.ATTN_STATS_WORDS == 7
+    assert gcheck.CHUNK == 16384 and gcheck.RECORD == 36 and gcheck._TABLE_DTYPE.itemsize == 40
+    assert evaluation.MAX_MAPS == 8
+    assert _C.constant("COSA_LABEL_STATS_WORKSPACE_BYTES") == 8 and len(sh.CONFORMANCE_FIGS) == 8
+    assert all(type(v) is int for v in (sh.ACT_STATS_FRAC, gcheck.CHUNK, evaluation.MAX_MAPS, nn_ops.RANGE_STATS_WORDS, *sh.EXPORT_BITS.values()))
+
+
+def test_tolerant_and_strict_load(built_lib):
+    """_C.load: strict=False (an older build in an A/B run) sets what the library has; strict=True resolves every name of the header"""
+    from cosa_amd import _C
+    sigs = _C._header()[0]
+    L = _C.load(built_lib, strict=False)
+    assert L.cosa_gemm_bf16.argtypes == sigs["cosa_gemm_bf16"][1] and L.cosa_gemm_bf16.restype is ctypes.c_int
+    S = _C.load(built_lib, strict=True)
+    for name, (res, args) in sigs.items():
+        fn = getattr(S, name)
+        assert fn.restype is res and fn.argtypes == args, name
+    assert S.cosa_abi_version() >= 1
+
+
 def test_product_never_touches_the_oracle():
     bad = []
     for base, _, files in os.walk(os.path.join(ROOT, "cosa_amd")):

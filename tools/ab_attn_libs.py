@@ -5,11 +5,7 @@ import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cosa_amd import _C
-libs = [(os.path.basename(p).replace("libcosa_hip_", "").replace(".so", ""), ctypes.CDLL(os.path.abspath(p))) for p in sys.argv[1:]]
-P, I = ctypes.c_void_p, ctypes.c_int
-for _, L in libs:
-    L.cosa_attn_fwd_f16c8.argtypes = [P, P, P, I, I, I, I, ctypes.c_float, P, P]
-    L.cosa_attn_fwd_f16c8.restype = I
+libs = [(os.path.basename(p).replace("libcosa_hip_", "").replace(".so", ""), _C.load(os.path.abspath(p), strict=False)) for p in sys.argv[1:]]          # signatures from include/cosa_hip.h
 dev = torch.device("cuda", 0)
 st = _C.stream_ptr
 ptr = lambda t: ctypes.c_void_p(t.data_ptr())

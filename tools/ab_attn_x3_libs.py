@@ -4,26 +4,17 @@ INTERLEAVED in one process: half a second of warm-up, then six rounds of ten lau
 byte with the first build's, and every build with a second run of itself.  A build "wins" a shape when the slowest of its six rounds is
 faster than the fastest of the first build's six.
 usage (GPU box): python tools/ab_attn_x3_libs.py parent.so new.so [more.so ...]        (exit status 1 if any bytes differ)"""
-import ctypes, os, sys, time
+import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cosa_amd import _C, nn_ops
 names = [os.path.basename(p).replace("libcosa_hip_", "").replace(".so", "") for p in sys.argv[1:]]
-libs = [ctypes.CDLL(os.path.abspath(p)) for p in sys.argv[1:]]
+libs = [_C.load(os.path.abspath(p), strict=False) for p in sys.argv[1:]]          # signatures from include/cosa_hip.h
 if len(libs) < 2:
     sys.exit(__doc__)
-P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 FWD = {torch.float16: "cosa_attn_fwd_f16x3", torch.bfloat16: "cosa_attn_fwd_bf16x3"}
 BWD = {torch.float16: ("cosa_attn_fwd_f16", "cosa_attn_bwd_f16", "cosa_attn_bwd_workspace_bytes_f16", "cosa_attn_workspace_bytes_f16"),
        torch.bfloat16: ("cosa_attn_fwd", "cosa_attn_bwd", "cosa_attn_bwd_workspace_bytes", "cosa_attn_workspace_bytes")}
-for L in libs:
-    for n in FWD.values():
-        getattr(L, n).argtypes, getattr(L, n).restype = [P, P, P, I, I, I, I, F, I, I, P, P], I
-    for f, b, bw, fw in BWD.values():
-        getattr(L, f).argtypes, getattr(L, f).restype = [P, P, P, I, I, I, I, F, I, P, P, ctypes.c_size_t, P], I
-        getattr(L, b).argtypes, getattr(L, b).restype = [P, P, P, P, P, I, I, I, I, F, P, ctypes.c_size_t, P], I
-        for w in (bw, fw):
-            getattr(L, w).argtypes, getattr(L, w).restype = [I, I, I], ctypes.c_size_t
 dev = torch.device("cuda", 0)
 st, ptr = _C.stream_ptr, _C.ptr
 tag = {torch.float16: "fp16", torch.bfloat16: "bf16"}

@@ -8,15 +8,7 @@ import torch
 from cosa_amd import _C, nn_ops
 
 old_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(_C.LIB_PATH), "libcosa_hip_old.so")
-new, old = _C.lib(), ctypes.CDLL(old_path)
-P = ctypes.c_void_p
-for L in (old,):
-    for fn in ("cosa_gemm_bf16", "cosa_gemm_f16"):
-        getattr(L, fn).argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
-    L.cosa_gemm_f16c4.argtypes = [P, P, P, P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
-    L.cosa_gemm_f16c8.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
-    L.cosa_gemm_bf16_dual_gelu.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
-    L.cosa_gemm_bf16x3.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
+new, old = _C.lib(), _C.load(old_path, strict=False)          # signatures from include/cosa_hip.h
 dev = torch.device("cuda", 0)
 ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
 

@@ -21,24 +21,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cosa_amd import _C
 
-P, I, L, F, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t
-SIGS = {"cosa_attn_fwd_f32": [P, P, I, I, I, I, F, I, I, P], "cosa_attn_stats_f32": [P, I, I, I, I, F, L, P, P],
-        "cosa_range_stats_f32": [P, L, I, L, P, P], "cosa_gt_stats": [P] * 6 + [I] * 6 + [P, P],
-        "cosa_teacher_check": [P] * 12 + [I] * 7 + [F, P, P, Z, P]}
-SIGS.update({"cosa_seg_loss_forward_w": [P] * 10 + [I] * 5 + [P, Z, P], "cosa_seg_loss_backward_w": [P] * 9 + [F] * 4 + [I] * 5 + [P, Z, P],
-             "cosa_cam_lossv3": [P] * 4 + [I] * 5 + [P, Z, P], "cosa_cam_loss_targets_m": [P, P, P, I, P, P] + [I] * 5 + [F, I, P],
-             "cosa_cam_label": [P, P, P, I, P, P, I, I, I, F, F, I, P]})
+Z = ctypes.c_size_t
 WARMUP, TIMED = 5, 30
-
-
-def load(path):
-    lib = ctypes.CDLL(os.path.abspath(path))
-    for name, sig in SIGS.items():
-        getattr(lib, name).argtypes, getattr(lib, name).restype = sig, I
-    lib.cosa_teacher_check_workspace_bytes.argtypes, lib.cosa_teacher_check_workspace_bytes.restype = [I, I], Z
-    for name in ("cosa_teacher_check_layout", "cosa_gt_stats_layout"):
-        getattr(lib, name).argtypes, getattr(lib, name).restype = [I, P], Z
-    return lib
+load = lambda path: _C.load(os.path.abspath(path), strict=False)          # signatures from include/cosa_hip.h; an older build may lack entry points
 
 
 ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
@@ -126,7 +111,6 @@ def seg_loss(B, K, hs, ws, S, seed, settings):
     gs, gr = torch.tensor([0.1], device=dev), torch.tensor([0.05 * 1e-7], device=dev)
 
     def make(lib, has_b, w, part, which):
-        lib.cosa_seg_loss_workspace_bytes.argtypes, lib.cosa_seg_loss_workspace_bytes.restype = [I] * 4, Z
         wsp = torch.zeros(lib.cosa_seg_loss_workspace_bytes(B, K, hs, ws), dtype=torch.uint8, device=dev)
         z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
         out = dict(sums=z(8), s_seg=z(B, K, Sq, Sq), s_img=z(B, 3, Sq, Sq), roi=z(B, Sq, Sq), unlabel=z(B, Sq, Sq, dt=torch.uint8),
@@ -156,7 +140,6 @@ def cam_lossv3(B, C, h, w, S, seed):
     label = label_maps(g, 1, B, C + 1, S)[0].to(torch.uint8)
 
     def run(lib, which):
-        lib.cosa_cam_lossv3_workspace_bytes.argtypes, lib.cosa_cam_lossv3_workspace_bytes.restype = [I] * 4, Z
         wsp = torch.zeros(lib.cosa_cam_lossv3_workspace_bytes(B, C, h, w), dtype=torch.uint8, device=dev)
         out = dict(loss=torch.zeros(1, device=dev), grad=torch.zeros(B, C, h, w, device=dev))
         return (lambda: lib.cosa_cam_lossv3(ptr(cam), ptr(label), ptr(out["grad"]), ptr(out["loss"]), B, C, h, w, S, ptr(wsp), wsp.numel(),
