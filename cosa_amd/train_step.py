@@ -178,6 +178,58 @@ def teacher_products(model, args, wimg, img_denorm, img_box, cls_label, threshol
     return (cam, aux), (mask, mask_aux), tgt
 
 
+class CheckNetwork:
+    """A monitor's network of its own (parameters, 16-bit shadows, operand and CAM buffers: nn_ops._owner_of is keyed by parameter) on
+    `mode` operands, built without drawing from any RNG the run reads: it is initialised on the host and the host generators' states are
+    put back.  Its initial weights never matter -- every check begins with load().  `params`: the fp32 tensors the weights are written to,
+    in `src_params`' order -- the network's own parameters, which every family reads as they are; a host network in mode fp64 runs in
+    torch.float64 and takes them from fp32 staging copies when a pass begins."""
+
+    def __init__(self, name, args, device, mode, src_params):
+        import random
+        states = torch.get_rng_state(), np.random.get_state(), random.getstate()
+        try:
+            net = build_model(SimpleNamespace(**dict(vars(args), pretrained=False)))
+        finally:
+            torch.set_rng_state(states[0])
+            np.random.set_state(states[1])
+            random.setstate(states[2])
+        net = net.to(device)
+        for p in net.parameters():
+            p.requires_grad = False
+        if device.type == "cuda" or hasattr(net, "set_nograd_precision"):      # (a host trainer's toy network has torch operators only)
+            net.set_nograd_precision(mode)
+        params = list(net.parameters())
+        assert len(params) == len(src_params) and all(a.shape == b.shape for a, b in zip(params, src_params))
+        self._staged = device.type != "cuda" and mode == "fp64"
+        if self._staged:
+            net = net.double()
+            params = [torch.empty_like(p, dtype=torch.float32) for p in net.parameters()]
+        self.name, self.net, self.params = name, net, params
+        # not optimizer-owned: refreshed at the entry of every pass ("fp32" / "fp64" and a host network: none, the fp32 parameters are read)
+        self.shadows = nn_ops.ensure_shadows(net, net.compute_dtype) \
+            if device.type == "cuda" and net.compute_dtype not in (torch.float32, torch.float64) else None
+        self.buffers = {}                    # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
+
+    def load(self, src_params):
+        torch._foreach_copy_(self.params, src_params)
+
+    @contextlib.contextmanager
+    def run(self):
+        """what a pass of the network runs inside: no kernel-span stamps (a benchmark's slots are the training kernels') and library
+        workspaces of its own (_C.workspace_scope, named after the monitor)"""
+        if self._staged:
+            for p, s in zip(self.net.parameters(), self.params):
+                p.copy_(s)
+        held = nn_ops.stamps, nn_ops.gemm_stamps
+        nn_ops.stamps = nn_ops.gemm_stamps = None
+        try:
+            with _C.workspace_scope(self.name):
+                yield self.net
+        finally:
+            nn_ops.stamps, nn_ops.gemm_stamps = held
+
+
 class CoSATrainer:
     def __init__(self, args, device, ddp=False, seed=0):
         self.args = args
@@ -322,72 +374,55 @@ class CoSATrainer:
         if bool(getattr(args, "gt_stats", False)):
             self.gt_stats_state = seg_helper.new_gt_stats(args.num_classes, device)
             self._add_extra_state("gt_stats.counters", self.gt_stats_state)
-        # the teacher-precision monitor: off (None) unless --teacher_check_iters N > 0.  Every N-th optimizer step runs
-        # the teacher's pass once more on `model_CK`, a third network on --teacher_check_mode operands that takes the teacher's weights at
-        # that moment, and scores the two passes against each other.  The counters are state of the run (`teacher_check.counters` of
-        # extra_state); model_CK is not: every check overwrites it
-        self.teacher_check_state = self.model_CK = None
+        # The four monitors with a network of their own (_add_monitor): every N-th optimizer step (--<name>_iters N > 0; off: None) runs
+        # one more pass on a CheckNetwork loaded from the checked network at that moment.  The counters are state of the run
+        # (`<name>.counters` of extra_state); the networks are not: every pass overwrites them
+        self._checks = {}
         self._check_iters = {which: check_iters(args, which) for which in ("teacher", "student", "act_stats", "grad")}
+        # the teacher-precision monitor: the teacher's pass once more on `model_CK`, a third network on
+        # --teacher_check_mode operands that takes the teacher's weights of that step; the two passes are scored against each other
+        self.teacher_check_state = self.model_CK = None
         if self._check_iters["teacher"] > 0:
-            cm = resolve_teacher_check_mode(getattr(args, "teacher_check_mode", "auto"), tp)
-            args.teacher_check_mode = cm
-            self.model_AN.check_nograd_precision(cm)      # (on the host too: a mode the encoder is not built for fails here, not in a step)
-            if device.type == "cuda" and not on:
-                raise NotImplementedError("teacher_check_iters: the check compares 16-bit operand modes of the teacher's no-grad passes; "
-                                          "this trainer's compute dtype has none")
-            self.teacher_check_state = seg_helper.new_teacher_check(args.num_classes, device)
-            self._add_extra_state("teacher_check.counters", self.teacher_check_state)
-            if on:
-                self._build_check("teacher")
-        # the student-forward monitor: off (None) unless --student_check_iters N > 0.  Every N-th optimizer step runs the
-        # student's weights of that step through `model_SK`, a network of its own on --student_check_mode operands (fp32: the masters
-        # themselves on the fp32 family), over the batch the step trained on, and scores the training forward against that pass.  The
-        # counters are state of the run (`student_check.counters` of extra_state); model_SK is not: every check overwrites it
-        self.student_check_state = self.model_SK = self._scheck_ctx = self.student_check_last = None
+            cm = args.teacher_check_mode = resolve_teacher_check_mode(getattr(args, "teacher_check_mode", "auto"), tp)
+            self.teacher_check_state, self.model_CK = self._add_monitor(
+                "teacher_check", cm, 0, "the check compares 16-bit operand modes of the teacher's no-grad passes",
+                lambda: seg_helper.new_teacher_check(args.num_classes, device))
+        # the student-forward monitor: the student's weights of that step through `model_SK` on --student_check_mode
+        # operands (fp32: the masters themselves on the fp32 family), over the batch the step trained on; the training forward is scored
+        # against that pass
+        self.student_check_state = self.model_SK = self.student_check_last = None
         if self._check_iters["student"] > 0:
-            sm = str(getattr(args, "student_check_mode", "fp32"))
-            args.student_check_mode = sm
+            sm = args.student_check_mode = str(getattr(args, "student_check_mode", "fp32"))
             if sm.partition("-")[0] not in NOGRAD_PRECISIONS:
                 raise ValueError(f"student_check_mode {sm!r}: one of {', '.join(NOGRAD_PRECISIONS)} (VITNetwork.set_nograd_precision's names)")
-            self.student.check_nograd_precision(sm)       # (on the host too: a mode the encoder is not built for fails here, not in a step)
-            if device.type == "cuda" and not on:
-                raise NotImplementedError("student_check_iters: the check scores the 16-bit training forward; this trainer's compute dtype "
-                                          "has none")
-            self.student_check_state = seg_helper.new_student_check(args.num_classes, device)
-            self._add_extra_state("student_check.counters", self.student_check_state)
-            if on:
-                self._build_check("student")
-        # activation range and attention sharpness: off (None) unless --act_stats_iters N > 0.  Every N-th optimizer
-        # step runs the teacher's weights of that step through `model_AK`, a network of its own in mode "fp32" whose encoder carries an
-        # ActProbe, over the weak images.  The counters are state of the run (`act_stats.counters` of extra_state: the probe's table and the
-        # number of passes) and, under data parallelism, this rank's own; model_AK is not: every pass overwrites it
+            self.student_check_state, self.model_SK = self._add_monitor(
+                "student_check", sm, 1, "the check scores the 16-bit training forward",
+                lambda: seg_helper.new_student_check(args.num_classes, device))
+        # activation range and attention sharpness: the teacher's weights of that step through `model_AK` in mode
+        # "fp32", whose encoder carries an ActProbe, over the weak images.  The counters (the probe's table and the number of passes) are,
+        # under data parallelism, this rank's own
         self.act_stats_state = self.model_AK = self.act_stats_shape = None
         if self._check_iters["act_stats"] > 0:
-            self.model_AN.check_nograd_precision("fp32")
-            if device.type == "cuda" and not on:
-                raise NotImplementedError("act_stats_iters: the monitor runs the fp32 no-grad path of the HIP encoder; this trainer's compute "
-                                          "dtype has none")
-            enc = self.model_AN.encoder
-            self.act_stats_shape = (len(enc.blocks), enc.num_heads)
-            self.act_stats_state = seg_helper.new_act_stats(*self.act_stats_shape, device)
-            self._add_extra_state("act_stats.counters", self.act_stats_state)
-            if on:
-                self.model_AK = self._new_check_network("fp32")
-                self._ak_params = list(self.model_AK.parameters())
-                assert len(self._ak_params) == len(self._ema_pairs[0]) and all(a.shape == b.shape for a, b in zip(self._ak_params, self._ema_pairs[0]))
+            def new_act_stats():
+                enc = self.model_AN.encoder
+                self.act_stats_shape = (len(enc.blocks), enc.num_heads)
+                return seg_helper.new_act_stats(*self.act_stats_shape, device)
+            self.act_stats_state, self.model_AK = self._add_monitor(
+                "act_stats", "fp32", 0, "the monitor runs the fp32 no-grad path of the HIP encoder", new_act_stats)
+            if self.model_AK is not None:
                 self.model_AK.encoder.act_probe = ActProbe(*self.act_stats_shape, table=seg_helper.act_stats_table(self.act_stats_state, *self.act_stats_shape))
-                self._ak_buffers = {}                                             # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
-        # the gradient check: off (None) unless --grad_check_iters N > 0.  Every N-th optimizer step differences the
-        # step's objective along the step's own raw gradient on `model_GK`, a network of its own in --grad_check_mode (fp32 | fp64) whose
-        # fp32 parameters the perturb kernel writes.  Nothing accumulates: `grad_check_state` is the record of ONE check (overwritten by the
-        # next), so the check is no row of monitors.MONITORS and no entry of a state file
-        self.grad_check_state = self.model_GK = self._gcheck_ctx = self._gk_pending = self.grad_check_last = None
+        # the gradient check: differences the step's objective along the step's own raw gradient on `model_GK`, in
+        # --grad_check_mode (fp32 | fp64), whose fp32 parameters the perturb kernel writes; built on a host trainer too.  Nothing
+        # accumulates: `grad_check_state` is the record of ONE check (overwritten by the next), so the check is no row of
+        # monitors.MONITORS and no entry of a state file
+        self.grad_check_state = self.model_GK = self._gk_pending = self.grad_check_last = None
+        self._step_ctx = {}                  # what forward_losses keeps of a step for the checks after its backward (_student_check, _grad_check)
         if self._check_iters["grad"] > 0:
-            self.student.check_nograd_precision(args.grad_check_mode)
-            if device.type == "cuda" and not on:
-                raise NotImplementedError("grad_check_iters: the check runs the no-grad fp32 / fp64 path of the HIP encoder; this trainer's "
-                                          "compute dtype has none")
-            self._build_grad_check()
+            _, self.model_GK = self._add_monitor("grad_check", args.grad_check_mode, 1,
+                                                 "the check runs the no-grad fp32 / fp64 path of the HIP encoder", host=True)
+            self._gk_names = [n for n, _ in self.student.named_parameters()]
+            self._gk_dirs = self._gk_plan = self._gk_tables = None                       # (made by the first check: which tensors hold a gradient)
+            self.grad_check_state = True                                              # (the record itself: allocated with the plan)
         if on:
             for sh in (self._teacher_shadows, self._student_shadows):
                 if sh is not None:
@@ -471,41 +506,23 @@ class CoSATrainer:
             st.begin_eager()
         return self._s_out
 
-    def _new_check_network(self, mode):
-        """a network of its own (parameters, 16-bit shadows, operand and CAM buffers: nn_ops._owner_of is keyed by parameter) on `mode`
-        operands, built without drawing from any RNG the run reads: it is initialised on the host and the host generators' states are put
-        back.  Its initial weights never matter -- every check begins by copying the checked network's"""
-        import random
-        states = torch.get_rng_state(), np.random.get_state(), random.getstate()
-        try:
-            ck = build_model(SimpleNamespace(**dict(vars(self.args), pretrained=False)))
-        finally:
-            torch.set_rng_state(states[0])
-            np.random.set_state(states[1])
-            random.setstate(states[2])
-        ck = ck.to(self.device)
-        for p in ck.parameters():
-            p.requires_grad = False
-        if self.device.type == "cuda" or hasattr(ck, "set_nograd_precision"):      # (a host trainer's toy network has torch operators only)
-            ck.set_nograd_precision(mode)
-        return ck
-
-    def _build_grad_check(self):
-        """model_GK and the check's buffers.  `_gk_params`: the fp32 tensors the perturbed weights are written to, in _ema_pairs[1]'s order
-        -- model_GK's own parameters, which the fp32 / fp64 families read as they are; a host trainer in mode fp64 runs model_GK in
-        torch.float64 and loads it from fp32 staging copies"""
-        args, dev = self.args, self.device
-        net = self._new_check_network(args.grad_check_mode)
-        params = list(net.parameters())
-        assert len(params) == len(self._ema_pairs[1]) and all(a.shape == b.shape for a, b in zip(params, self._ema_pairs[1]))
-        self._gk_stage = dev.type != "cuda" and args.grad_check_mode == "fp64"
-        if self._gk_stage:
-            net = net.double()
-            params = [torch.empty_like(p, dtype=torch.float32) for p in net.parameters()]
-        self.model_GK, self._gk_params = net, params
-        self._gk_names = [n for n, _ in self.student.named_parameters()]
-        self._gk_dirs = self._gk_plan = self._gk_tables = None                       # (made by the first check: which tensors hold a gradient)
-        self.grad_check_state = True                                              # (the record itself: allocated with the plan)
+    def _add_monitor(self, name, mode, half, needs, new_counters=None, host=False):
+        """set-up of the monitor --<name>_iters, whose CheckNetwork on `mode` operands shadows _ema_pairs[half] (0: teacher, 1: student)
+        -> (its counters, entered into extra_state as `<name>.counters` | None without a constructor, its network | None).  A mode the
+        encoder is not built for and a trainer without the 16-bit GPU path are refused here, on the host too, not in a step; the network
+        is built on that path only, and with `host` on a host trainer as well."""
+        on = self._student_shadows is not None
+        (self.model_AN, self.student)[half].check_nograd_precision(mode)
+        if self.device.type == "cuda" and not on:
+            raise NotImplementedError(f"{name}_iters: {needs}; this trainer's compute dtype has none")
+        counters = None
+        if new_counters is not None:
+            counters = new_counters()
+            self._add_extra_state(name + ".counters", counters)
+        if not (on or host):
+            return counters, None
+        ck = self._checks[name] = CheckNetwork(name, self.args, self.device, mode, self._ema_pairs[half])
+        return counters, ck.net
 
     def _gk_make_plan(self, grads):
         args, dev = self.args, self.device
@@ -519,36 +536,10 @@ class CoSATrainer:
             self._gk_event = torch.cuda.Event()
         self._gk_has_grad = [g is not None for g in grads]
 
-    def _build_check(self, which):
-        """model_CK, the --teacher_check network, or model_SK, the --student_check one (_new_check_network on args.<which>_check_mode): two
-        networks, not one shared -- both monitors may be on in one run"""
-        tag, half = {"teacher": ("ck", 0), "student": ("sk", 1)}[which]
-        net = self._new_check_network(getattr(self.args, which + "_check_mode"))
-        params = list(net.parameters())
-        assert len(params) == len(self._ema_pairs[half]) and all(a.shape == b.shape for a, b in zip(params, self._ema_pairs[half]))
-        setattr(self, "model_" + tag.upper(), net)
-        setattr(self, f"_{tag}_params", params)
-        # not optimizer-owned: refreshed at the entry of every pass ("fp32" / "fp64": none, the check reads the network's fp32 parameters)
-        setattr(self, f"_{tag}_shadows", nn_ops.ensure_shadows(net, net.compute_dtype) if net.compute_dtype not in (torch.float32, torch.float64) else None)
-        if which == "teacher":
-            self._ck_buffers = {}                                             # its CAM buffers (seg_helper.multi_scale_camseg, `_buffers`)
-
     def _is_check_step(self, n_iter, which="teacher"):
         """the step that closes every N-th optimizer iteration (N: --<which>_check_iters); with --accum_steps its last micro-batch"""
         state = self.act_stats_state if which == "act_stats" else getattr(self, which + "_check_state")
         return state is not None and (n_iter + 1) % self._check_iters[which] == 0 and self._micro_k == self._accum_steps - 1
-
-    @contextlib.contextmanager
-    def _check_pass(self, name):
-        """what a check's extra pass runs inside: no kernel-span stamps (a benchmark's slots are the training kernels') and library
-        workspaces of its own (_C.workspace_scope)"""
-        held = nn_ops.stamps, nn_ops.gemm_stamps
-        nn_ops.stamps = nn_ops.gemm_stamps = None
-        try:
-            with _C.workspace_scope(name):
-                yield
-        finally:
-            nn_ops.stamps, nn_ops.gemm_stamps = held
 
     def _add_extra_state(self, name, tensor):
         """`tensor` travels in a state file as `aux.<name>` (checkpoint.TrainState; `extra_state` exists only once something is in it)"""
@@ -568,11 +559,11 @@ class CoSATrainer:
         re-evaluated), and the reduction.  No host sync, no RNG, and nothing the training path reads is written: model_SK's weights, shadows
         and operand buffers are its own, the library workspaces it needs are slots of their own (_C.workspace_scope), and the backward
         that read the training forward's workspaces has already run.  `student_check_last` keeps what went into the reduction."""
-        ctx, self._scheck_ctx = self._scheck_ctx, None
-        torch._foreach_copy_(self._sk_params, self._ema_pairs[1])                  # (the unwrapped student's parameters, not DDP's)
+        ctx, ck = self._step_ctx, self._checks["student_check"]
+        ck.load(self._ema_pairs[1])                                                  # (the unwrapped student's parameters, not DDP's)
         lab = ctx["cls_label"]
-        with self._check_pass("student_check"):
-            b, four = self._check_forward_losses(self.model_SK, ctx)
+        with ck.run() as net:
+            b, four = self._check_forward_losses(net, ctx)
             loss_b = torch.stack([t.reshape(()).float() for t in four])
         a, loss_a = ctx["outputs"], torch.stack([t.reshape(()).float() for t in ctx["losses"]])
         seg_helper.student_check(*[(a[k], b[k]) for k in seg_helper.STUDENT_CHECK_TENSORS], (loss_a, loss_b), lab, self.student_check_state)
@@ -582,34 +573,24 @@ class CoSATrainer:
         """`net`'s full no-grad forward over the step's strong images and the step's four dense / classification losses on its outputs,
         forward kernels only, against what `ctx` kept of the step (label maps, cam-loss targets or v3's label map, labels, boxes) and the
         step's blend weights -> ({seg, cam, cam_aux, cls, cls_aux} as contiguous fp32, (cls, cls_aux, seg, cam) losses).  Both checks
-        (_student_check, _grad_check) call it, inside their own _check_pass."""
+        (_student_check, _grad_check) call it, inside their own CheckNetwork.run."""
         args = self.args
-        lab, simg, (mask, mask_aux) = ctx["cls_label"], ctx["simg"], ctx["masks"]
+        lab, simg, masks, rels = ctx["cls_label"], ctx["simg"], ctx["masks"], ctx["rel"]
         cls_b, clsaux_b, _feat, seg_b, cam_b, aux_b = net(simg, cam_only=False, detach='none')
         cls_b, clsaux_b, seg_b, cam_b, aux_b = (t.float().contiguous() for t in (cls_b, clsaux_b, seg_b, cam_b, aux_b))
         l_cls = seg_helper.multilabel_soft_margin(cls_b, lab)
         l_cls_aux = seg_helper.multilabel_soft_margin(clsaux_b, lab)
-        rel_main, rel_aux = ctx.get("rel", (None, None))      # (--seg_reliability: the step's weight maps, so the checks see the weighted term)
-        if self.fused_losses:
-            l_seg = seg_helper.seg_loss_forward_only(seg_b, mask, mask_aux, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
-                                                     aux_alpha=args.aux_cam2seg_alpha, **self._rel_kw(rel_main, rel_aux))
-            cam_l = lambda c: seg_helper.cam_loss_from_targets(c, ctx["tgt"])
+        if self.fused_losses:                 # (rels: --seg_reliability's weight maps of the step, so the checks see the weighted term)
+            l_seg = seg_helper.seg_loss_forward_only(seg_b, *masks, simg, ctx["img_box"], fg_alpha=args.segfg_alpha,
+                                                     aux_alpha=args.aux_cam2seg_alpha, **self._rel_kw(*rels))
         else:
-            up = F.interpolate(seg_b, size=mask.shape[1:], mode='bilinear', align_corners=False)
-            l_seg = self._seg_loss_torch(up, mask, rel_main)
-            if mask_aux is not None:
-                l_seg = (1 - args.aux_cam2seg_alpha) * l_seg + args.aux_cam2seg_alpha * self._seg_loss_torch(up, mask_aux, rel_aux)
-            cam_l = lambda c: seg_helper.cam_loss(c, ctx["tgt"])
-        if self.camloss_version != "v1":               # (ctx["tgt"]: v2's targets, v3's label map)
-            cam_l = self._cam_loss_fn(ctx["tgt"])
-        l_cam = cam_l(cam_b)
-        if args.aux_seg2cam:
-            l_cam = (1 - args.aux_seg2cam_alpha) * l_cam + args.aux_seg2cam_alpha * cam_l(aux_b)
+            l_seg = self._seg_loss_torch(F.interpolate(seg_b, size=masks[0].shape[1:], mode='bilinear', align_corners=False), masks, rels)
+        l_cam = self._cam_loss(ctx["tgt"], cam_b, aux_b)
         return dict(seg=seg_b, cam=cam_b, cam_aux=aux_b, cls=cls_b, cls_aux=clsaux_b), (l_cls, l_cls_aux, l_seg, l_cam)
 
     def _check_objective(self, net, ctx):
         """the five float32 terms (cls, cls_aux, seg, cam, reg) of the step's objective on `net`, forward only, inside the caller's
-        _check_pass.  The regulariser is get_energy_loss on this pass's up-sampled seg logits: its lattice is rebuilt from the same image
+        CheckNetwork.run.  The regulariser is get_energy_loss on this pass's up-sampled seg logits: its lattice is rebuilt from the same image
         (the training step's lattice state has been consumed by the backward)."""
         outs, four = self._check_forward_losses(net, ctx)
         mask = ctx["masks"][0]
@@ -626,7 +607,7 @@ class CoSATrainer:
         [n_dirs][RECORD] is complete on the device when this returns and is on its way to the host; grad_check() waits for it -- the check's
         one sync.  No RNG, and nothing the training path reads is written: model_GK's weights and operand buffers are its own, the
         library workspaces it needs are slots of their own (_C.workspace_scope)."""
-        ctx, self._gcheck_ctx = self._gcheck_ctx, None
+        ctx, ck = self._step_ctx, self._checks["grad_check"]
         args, rho, host = self.args, self.args.grad_check_rho, self.device.type != "cuda"
         ws = self._ema_pairs[1]                                                      # (the unwrapped student's parameters)
         grads = [p.grad if p.requires_grad else None for p in ws]
@@ -636,24 +617,22 @@ class CoSATrainer:
         rec.zero_()
 
         def objective():
-            if self._gk_stage:
-                torch._foreach_copy_(list(self.model_GK.parameters()), self._gk_params)
-            with self._check_pass("grad_check"):
-                return self._check_objective(self.model_GK, ctx).double()
+            with ck.run() as net:
+                return self._check_objective(net, ctx).double()
 
-        torch._foreach_copy_(self._gk_params, ws)
+        ck.load(ws)
         rec[:, gcheck.LOSS:gcheck.LOSS + 5] = objective()
         for p, (row0, n_dirs, dirs) in enumerate(self._gk_plan):
             rows = rec[row0:row0 + n_dirs]
             if host:
                 gcheck.norms_torch(ws, grads, dirs, n_dirs, rho, rows)
             else:
-                table = self._gk_tables[p].fill(ws, grads, self._gk_params, dirs)
+                table = self._gk_tables[p].fill(ws, grads, ck.params, dirs)
                 gcheck.norms(table, n_dirs, rho, rows)
             for d in range(n_dirs):
                 for k, c in enumerate(gcheck.STEPS):
                     if host:
-                        gcheck.perturb_torch(ws, grads, self._gk_params, dirs, d, c, k, rows)
+                        gcheck.perturb_torch(ws, grads, ck.params, dirs, d, c, k, rows)
                     else:
                         gcheck.perturb(table, n_dirs, d, c, k, rows)
                     at = gcheck.LOSS + 5 * (k + 1)
@@ -682,12 +661,9 @@ class CoSATrainer:
         tools/grad_check.py: a trainer built with grad_check_iters=1, so that every step is a check step."""
         if self.model_GK is None or self._check_iters["grad"] != 1 or self._accum_steps != 1:
             raise RuntimeError("grad_check_batch: build the trainer with grad_check_iters=1 and accum_steps=1")
-        loss, _logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
-        self.optimizer.zero_grad(set_to_none=True)
-        if self.device.type == "cuda" and self._student_shadows is not None:
-            nn_ops.wgrad_arena_begin(self.device)
-        loss.backward()
+        self._forward_backward(wimg, simg, cls_label, img_box, n_iter, gt)
         self._grad_check()
+        self._step_ctx = {}
         return self.grad_check()
 
     def pop_grad_check(self):
@@ -706,12 +682,12 @@ class CoSATrainer:
         cams = (cam, cam_aux) as cam2mask read them, masks = (main, aux | None), thresholds = ((high, low), (aux high, aux low)).
         No host sync, no RNG, and nothing the training path reads is written: model_CK's weights, shadows, operand and CAM buffers are
         its own, the library workspaces it needs are slots of their own (_C.workspace_scope)."""
-        args = self.args
-        torch._foreach_copy_(self._ck_params, self._ema_pairs[0])
-        with self._check_pass("teacher_check"):
+        args, ck = self.args, self._checks["teacher_check"]
+        ck.load(self._ema_pairs[0])
+        with ck.run() as net:
             (cam_b, aux_b), (mask_b, mask_aux_b), tgt_b = teacher_products(
-                self.model_CK, args, wimg, img_denorm, img_box, cls_label, thresholds, self.fused_losses,
-                tgt.shape[-2:] if tgt is not None else None, self._ck_buffers, self.refine_model)
+                net, args, wimg, img_denorm, img_box, cls_label, thresholds, self.fused_losses,
+                tgt.shape[-2:] if tgt is not None else None, ck.buffers, self.refine_model)
         seg_helper.teacher_check((cams[0], cam_b), (cams[1], aux_b), (tgt, tgt_b) if tgt is not None else None, (masks[0], mask_b),
                                  (masks[1], mask_aux_b) if masks[1] is not None else None, None if args.use_cammix else cls_label, img_box,
                                  self.teacher_check_state, ignore_index=args.ignore_index, bar=seg_helper.TEACHER_CHECK_BAR)
@@ -727,11 +703,11 @@ class CoSATrainer:
         weak images in mode "fp32" with the encoder's probe set, its outputs dropped.  The probe's launches add into `act_stats_state`, whose
         last word counts the passes.  No host sync, no RNG, and nothing the training path reads is written: model_AK's weights, operand and
         CAM buffers are its own, the library workspaces it needs are slots of their own (_C.workspace_scope)."""
-        args = self.args
-        torch._foreach_copy_(self._ak_params, self._ema_pairs[0])
-        with self._check_pass("act_stats"):
-            seg_helper.multi_scale_camseg(self.model_AK, wimg, args.pseudo_scales, _active_labels=None if args.use_cammix else cls_label,
-                                          _seg_scales=self.fused_losses, _buffers=self._ak_buffers)
+        args, ck = self.args, self._checks["act_stats"]
+        ck.load(self._ema_pairs[0])
+        with ck.run() as net:
+            seg_helper.multi_scale_camseg(net, wimg, args.pseudo_scales, _active_labels=None if args.use_cammix else cls_label,
+                                          _seg_scales=self.fused_losses, _buffers=ck.buffers)
         self.act_stats_state[-1:] += 1
 
     def act_stats(self):
@@ -823,62 +799,40 @@ class CoSATrainer:
                                                                       **self._rel_kw(rel_main, rel_aux))
         else:
             seg_pred = F.interpolate(seg_pred, size=refine_mask_label.shape[1:], mode='bilinear', align_corners=False)
-            seg_loss = self._seg_loss_torch(seg_pred, refine_mask_label, rel_main)
-            if args.aux_cam2seg:
-                seg_loss_aux = self._seg_loss_torch(seg_pred, refine_mask_label_aux, rel_aux)
-                seg_loss = (1 - args.aux_cam2seg_alpha) * seg_loss + args.aux_cam2seg_alpha * seg_loss_aux
+            seg_loss = self._seg_loss_torch(seg_pred, (refine_mask_label, refine_mask_label_aux), (rel_main, rel_aux))
             reg_loss = seg_helper.get_energy_loss(img=simg, logit=seg_pred, label=refine_mask_label, img_box=img_box,
                                                   loss_layer=self.reg_layer)
-        check_tgt = None
-        if self.camloss_version != "v1":
-            cam_loss, check_tgt, check_tgt_s = self._cam_loss_v23(seg_ps, cls_label, wimg.shape[-1], cam_pred, cam_aux_pred)
-        elif self.fused_losses:
-            with torch.no_grad():      # seg_ps is the list of per-scale low-res teacher segs here
-                tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:], args.seg_softmaxtemp,
-                                                  after_softmax=args.after_softmax)
-            cam_loss = seg_helper.cam_loss_from_targets(cam_pred, tgt)
-            check_tgt = check_tgt_s = tgt
-            if args.aux_seg2cam:
-                cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + \
-                    args.aux_seg2cam_alpha * seg_helper.cam_loss_from_targets(cam_aux_pred, tgt)
-        else:
-            with torch.no_grad():
-                valid_seg_ps = seg_helper.seg_refine_by_label(seg_ps, cls_label, softmaxtemp=args.seg_softmaxtemp,
-                                                              after_softmax=args.after_softmax)
-            cam_loss = seg_helper.cam_loss(cam_pred, valid_seg_ps)
-            check_tgt_s = valid_seg_ps
-            if args.aux_seg2cam:
-                cam_aux_loss = seg_helper.cam_loss(cam_aux_pred, valid_seg_ps)
-                cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + args.aux_seg2cam_alpha * cam_aux_loss
+        tgt, check_tgt = self._cam_target(seg_ps, cls_label, wimg.shape[-1], cam_pred.shape[-2:])
+        cam_loss = self._cam_loss(tgt, cam_pred, cam_aux_pred)
         if self.model_CK is not None and self._is_check_step(n_iter):
             self._teacher_check(wimg, img_denorm, img_box, cls_label, (cam_ps, cam_aux_ps), (refine_mask_label, refine_mask_label_aux),
                                 ((threhigh, threlow), (auxthrehigh, auxthrelow)), check_tgt)
         if self.model_AK is not None and self._is_check_step(n_iter, "act_stats"):
             self._act_stats(wimg, cls_label)
-        if self.model_SK is not None and self._is_check_step(n_iter, "student"):
-            # what the check after this step's backward (_student_check) reads: detached references, nothing is copied or computed here
-            self._scheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux), tgt=check_tgt_s,
-                                    rel=(rel_main, rel_aux),
-                                    outputs=dict(seg=seg_lr.detach(), cam=cam_pred.detach(), cam_aux=cam_aux_pred.detach(),
-                                                 cls=cls_final.detach(), cls_aux=cls_aux.detach()),
-                                    losses=tuple(t.detach() for t in (cls_loss, cls_loss_aux, seg_loss, cam_loss)))
         tok_on = self._tokcon[0] > 0
         if tok_on:
             tok_loss = self._token_contrast(_feat, refine_mask_label)
         # main.py:230-236: the weighted sum of the five losses (warm-up: classification losses only) as one dot product
         wkey = n_iter <= args.warmup_iters
+        wl = [1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight]
+        if tok_on:                          # the sixth element: the token contrast term, 0 during warm-up like seg / cam / reg
+            wl.append(0.0 if wkey else self._tokcon[0])
         wvec = self._loss_weights.get(wkey)
         if wvec is None:
-            wl = [1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight]
-            if tok_on:                      # the sixth element: the token contrast term, 0 during warm-up like seg / cam / reg
-                wl.append(0.0 if wkey else self._tokcon[0])
             wvec = self._loss_weights[wkey] = torch.tensor(wl, device=cls_loss.device, dtype=torch.float32)
-        if self.model_GK is not None and self._is_check_step(n_iter, "grad"):
-            # what the check after this step's backward (_grad_check) reads: detached references and the loss weights as the dot product
-            # below rounds them (fp32), nothing is copied or computed here
-            wl32 = [float(np.float32(v)) for v in ([1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight])]
-            self._gcheck_ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux),
-                                    tgt=check_tgt_s, weights=wl32, rel=(rel_main, rel_aux))
+        student_due = self.model_SK is not None and self._is_check_step(n_iter, "student")
+        grad_due = self.model_GK is not None and self._is_check_step(n_iter, "grad")
+        if student_due or grad_due:
+            # what the checks after this step's backward (_student_check, _grad_check) read: detached references, nothing is copied or
+            # computed here
+            self._step_ctx = ctx = dict(simg=simg, cls_label=cls_label, img_box=img_box, masks=(refine_mask_label, refine_mask_label_aux),
+                                        tgt=tgt, rel=(rel_main, rel_aux))
+            if student_due:
+                ctx.update(outputs=dict(seg=seg_lr.detach(), cam=cam_pred.detach(), cam_aux=cam_aux_pred.detach(),
+                                        cls=cls_final.detach(), cls_aux=cls_aux.detach()),
+                           losses=tuple(t.detach() for t in (cls_loss, cls_loss_aux, seg_loss, cam_loss)))
+            if grad_due:                    # (the loss weights as the dot product below rounds them: fp32)
+                ctx.update(weights=[float(np.float32(v)) for v in wl])
         terms = [cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(), reg_loss.reshape(()).float()]
         if tok_on:
             terms.append(tok_loss.reshape(()).float())
@@ -900,11 +854,17 @@ class CoSATrainer:
         """the weight maps as the fused seg loss's keywords; none with --seg_reliability off: the call is then the one it has always been"""
         return {} if rel_main is None else dict(rel_main=rel_main, rel_aux=rel_aux)
 
-    def _seg_loss_torch(self, up, mask, rel):
-        """the torch path's seg loss of one label map: seg_loss, or seg_weightloss under its weight map (--seg_reliability)"""
-        if rel is None:
-            return seg_helper.seg_loss(up, mask, fg_alpha=self.args.segfg_alpha)
-        return seg_helper.seg_weightloss(up, mask, rel, fg_alpha=self.args.segfg_alpha)
+    def _seg_loss_torch(self, up, masks, rels):
+        """the torch path's seg loss on the up-sampled logits: per label map (main, auxiliary | None) seg_loss, or seg_weightloss under its
+        weight map (--seg_reliability), blended by --aux_cam2seg_alpha; the step and both checks share it"""
+        def one(mask, rel):
+            if rel is None:
+                return seg_helper.seg_loss(up, mask, fg_alpha=self.args.segfg_alpha)
+            return seg_helper.seg_weightloss(up, mask, rel, fg_alpha=self.args.segfg_alpha)
+        loss = one(masks[0], rels[0])
+        if masks[1] is not None:
+            loss = (1 - self.args.aux_cam2seg_alpha) * loss + self.args.aux_cam2seg_alpha * one(masks[1], rels[1])
+        return loss
 
     def seg_reliability(self):
         """the mean weights (seg_helper.reliability_summary: one dict per CAM set, main then auxiliary) of --seg_reliability since the last
@@ -930,43 +890,45 @@ class CoSATrainer:
         fn = seg_helper.token_contrast_loss if self.fused_losses else seg_helper._token_contrast_torch
         return fn(tokens, labels, temp)
 
-    def _cam_loss_fn(self, tgt):
-        """cam -> the selected --camloss_version v2 | v3 against `tgt` (v2: targets at the CAM's size on the fused path, the refined teacher
-        probabilities on the torch one; v3: the label map), by the path this trainer takes; the step and the student check share it"""
-        v3 = self.camloss_version == "v3"
+    @torch.no_grad()
+    def _cam_target(self, seg_ps, cls_label, S, out_hw):
+        """what --camloss_version's cam loss (main.py:216-224) is taken against, from the teacher's segs (fused path: the list of per-scale
+        low-res ones) -> (the target _cam_loss and the student check read, the teacher check's targets | None).  v1 / v2: targets at the
+        CAM's size `out_hw` on the fused path, the refined teacher probabilities on the torch one; v3: the label map, kept as
+        `cam_label_last`.  Made here, outside the captured teacher pass: the graph is the same for every version."""
+        args, v3 = self.args, self.camloss_version == "v3"
         if self.fused_losses:
-            return (lambda c: seg_helper.cam_lossv3(c, tgt)) if v3 else (lambda c: seg_helper.cam_lossv2_from_targets(c, tgt))
-        if v3:
-            return lambda c: seg_helper._cam_lossv3_torch(c, tgt)
-        return lambda c: seg_helper._cam_lossv2_torch(c, F.interpolate(tgt[:, 1:], size=list(c.shape[-2:]), mode='bilinear', align_corners=False))
-
-    def _cam_loss_v23(self, seg_ps, cls_label, S, cam_pred, cam_aux_pred):
-        """--camloss_version v2 | v3 (main.py:216-224) -> (cam loss, the teacher check's targets | None, the student check's target).  The
-        targets / the label map are made here, outside the captured teacher pass, as cam_loss_targets is: the graph is the same for every
-        version.  `cam_label_last` keeps v3's label map."""
-        args = self.args
-        v3 = self.camloss_version == "v3"
-        with torch.no_grad():
-            if self.fused_losses:      # seg_ps is the list of per-scale low-res teacher segs here
-                if v3:
-                    tgt = seg_helper.cam_label_from_scales(seg_ps, cls_label, S, args.seg_softmaxtemp, args.segconf_thre,
-                                                           after_softmax=args.after_softmax)
-                else:
-                    tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, S, cam_pred.shape[-2:], args.seg_softmaxtemp,
-                                                      after_softmax=args.after_softmax)
-                check_tgt = None if v3 else tgt
+            if v3:
+                tgt = seg_helper.cam_label_from_scales(seg_ps, cls_label, S, args.seg_softmaxtemp, args.segconf_thre,
+                                                       after_softmax=args.after_softmax)
             else:
-                tgt = seg_helper.seg_refine_by_label(seg_ps, cls_label, softmaxtemp=args.seg_softmaxtemp, after_softmax=args.after_softmax)
-                if v3:
-                    tgt = seg_helper._cam_label_torch(tgt, args.segconf_thre)
-                check_tgt = None
+                tgt = seg_helper.cam_loss_targets(seg_ps, cls_label, S, out_hw, args.seg_softmaxtemp, after_softmax=args.after_softmax)
+        else:
+            tgt = seg_helper.seg_refine_by_label(seg_ps, cls_label, softmaxtemp=args.seg_softmaxtemp, after_softmax=args.after_softmax)
+            if v3:
+                tgt = seg_helper._cam_label_torch(tgt, args.segconf_thre)
         if v3:
             self.cam_label_last = tgt
+        return tgt, (tgt if self.fused_losses and not v3 else None)
+
+    def _cam_loss_fn(self, tgt):
+        """cam -> the selected --camloss_version against `tgt` (_cam_target's), by the path this trainer takes"""
+        fused = self.fused_losses
+        if self.camloss_version == "v1":
+            return lambda c: (seg_helper.cam_loss_from_targets if fused else seg_helper.cam_loss)(c, tgt)
+        if self.camloss_version == "v3":
+            return lambda c: (seg_helper.cam_lossv3 if fused else seg_helper._cam_lossv3_torch)(c, tgt)
+        if fused:
+            return lambda c: seg_helper.cam_lossv2_from_targets(c, tgt)
+        return lambda c: seg_helper._cam_lossv2_torch(c, F.interpolate(tgt[:, 1:], size=list(c.shape[-2:]), mode='bilinear', align_corners=False))
+
+    def _cam_loss(self, tgt, cam, cam_aux):
+        """the cam loss of a forward against `tgt`, the auxiliary CAM's blended in under --aux_seg2cam; the step and both checks share it"""
         fn = self._cam_loss_fn(tgt)
-        cam_loss = fn(cam_pred)
-        if args.aux_seg2cam:
-            cam_loss = (1 - args.aux_seg2cam_alpha) * cam_loss + args.aux_seg2cam_alpha * fn(cam_aux_pred)
-        return cam_loss, check_tgt, tgt
+        loss = fn(cam)
+        if self.args.aux_seg2cam:
+            loss = (1 - self.args.aux_seg2cam_alpha) * loss + self.args.aux_seg2cam_alpha * fn(cam_aux)
+        return loss
 
     def prepare_ddp(self, wimg, cls_label):
         """first step under data parallelism on the GPU: warm up and CAPTURE the teacher pass, then wrap the student (see __init__)"""
@@ -988,19 +950,25 @@ class CoSATrainer:
     def step(self, wimg, simg, cls_label, img_box, n_iter, gt=None):
         if self._accum_steps > 1:
             return self._micro_step(wimg, simg, cls_label, img_box, n_iter, gt)
-        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
-        self.optimizer.zero_grad(set_to_none=True)
-        if self.device.type == "cuda" and self._student_shadows is not None:
-            nn_ops.wgrad_arena_begin(self.device)        # one clear for all weight gradients of this step (they are consumed below)
-        loss.backward()
-        if self._scheck_ctx is not None:                 # (--student_check_iters: after the backward, before the weights move)
+        logs = self._forward_backward(wimg, simg, cls_label, img_box, n_iter, gt)
+        if "outputs" in self._step_ctx:                  # (--student_check_iters: after the backward, before the weights move)
             self._student_check()
-        if self._gcheck_ctx is not None:                 # (--grad_check_iters: likewise)
+        if "weights" in self._step_ctx:                  # (--grad_check_iters: likewise)
             self._grad_check()
         return self._apply_gradients(logs)
 
+    def _forward_backward(self, wimg, simg, cls_label, img_box, n_iter, gt):
+        """forward_losses and the backward of one batch -> logs; the gradients are left in .grad"""
+        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.device.type == "cuda" and self._student_shadows is not None:
+            nn_ops.wgrad_arena_begin(self.device)        # one clear for all weight gradients of this batch (they are consumed by the caller)
+        loss.backward()
+        return logs
+
     def _apply_gradients(self, logs):
         """the optimizer's share of a step, on the gradients of one batch or on the mean left by the closing micro-step"""
+        self._step_ctx = {}                              # (the checks, if any were due, have run)
         if self._tensor_stats and self._fused_step is None:
             self._tensor_stats_torch_step()
         if self._fused_step is not None:
@@ -1024,12 +992,8 @@ class CoSATrainer:
         their mean -- optimizer, EMA, shadows, guard, the armed --tensor_stats sample.  Under DDP every call's backward all-reduces and the
         accumulator takes reduced gradients (correct by linearity; skipping the first N - 1 reductions is not built)."""
         k, n = self._micro_k, self._accum_steps
-        loss, logs = self.forward_losses(wimg, simg, cls_label, img_box, n_iter, **self._gt_kw(gt))
-        self.optimizer.zero_grad(set_to_none=True)
-        if self.device.type == "cuda" and self._student_shadows is not None:
-            nn_ops.wgrad_arena_begin(self.device)        # this micro-step's weight gradients: consumed by accumulate() below
-        loss.backward()
-        if self._gcheck_ctx is not None:                 # (--grad_check_iters: the closing micro-batch's own gradient against its own loss, before it is folded)
+        logs = self._forward_backward(wimg, simg, cls_label, img_box, n_iter, gt)
+        if "weights" in self._step_ctx:                  # (--grad_check_iters: the closing micro-batch's own gradient against its own loss, before it is folded)
             self._grad_check()
         if self._fused_step is not None:
             self._fused_step.accumulate(k)
@@ -1045,7 +1009,7 @@ class CoSATrainer:
                     if a is not None:
                         p.grad.copy_(a)
             self._accum = None
-        if self._scheck_ctx is not None:                 # (--student_check_iters: the closing micro-batch, before the weights move)
+        if "outputs" in self._step_ctx:                  # (--student_check_iters: the closing micro-batch, before the weights move)
             self._student_check()
         return self._apply_gradients(logs)
 

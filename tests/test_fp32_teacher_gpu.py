@@ -182,7 +182,7 @@ def test_fp32_check_mode_changes_no_bit_of_the_run_and_counts_its_checks():
     del plain
     tr = _trainer(teacher_check_iters=1, teacher_check_mode="fp32")
     assert tr.args.teacher_precision == "fp16x3" and tr.args.teacher_check_mode == "fp32"
-    assert tr.model_CK is not None and tr.model_CK.encoder.precision == "f32" and tr._ck_shadows is None
+    assert tr.model_CK is not None and tr.model_CK.encoder.precision == "f32" and tr._checks["teacher_check"].shadows is None
     l1 = _run(tr)
     assert torch.equal(l0.view(torch.int32), l1.view(torch.int32))
     w1 = _weights(tr)

@@ -277,7 +277,7 @@ def test_fp64_teacher_check_changes_no_bit_of_the_run_and_counts_its_checks():
     those of the run without the flags, bit for bit; 3 checks, planes > 0, nothing non-finite"""
     from cosa_amd.utils import seg_helper
     tr = _trainer(teacher_check_iters=1, teacher_check_mode="fp64")
-    assert tr.args.teacher_precision == "fp16x3" and tr.model_CK.encoder.precision == "f64" and tr._ck_shadows is None
+    assert tr.args.teacher_precision == "fp16x3" and tr.model_CK.encoder.precision == "f64" and tr._checks["teacher_check"].shadows is None
     _same_run(tr, _run(tr))
     s = tr.teacher_check()
     assert s["checks"] == 3
@@ -290,7 +290,7 @@ def test_fp64_teacher_check_changes_no_bit_of_the_run_and_counts_its_checks():
 def test_fp64_student_check_changes_no_bit_of_the_run_and_counts_its_checks():
     from cosa_amd.utils import seg_helper
     tr = _trainer(student_check_iters=1, student_check_mode="fp64")
-    assert tr.model_SK.encoder.precision == "f64" and tr._sk_shadows is None
+    assert tr.model_SK.encoder.precision == "f64" and tr._checks["student_check"].shadows is None
     _same_run(tr, _run(tr))
     s = tr.student_check()
     assert s["checks"] == 3

@@ -145,7 +145,7 @@ def _trainer(monkeypatch, seed=3, **over):
     def forward_losses(wimg, simg, cls_label, img_box, n_iter):
         loss = torch.dot(_terms(tr.student, simg, cls_label), torch.tensor(WEIGHTS))
         if tr.model_GK is not None and tr._is_check_step(n_iter, "grad"):
-            tr._gcheck_ctx = dict(x=simg, y=cls_label, weights=[float(np.float32(w)) for w in WEIGHTS])
+            tr._step_ctx = dict(x=simg, y=cls_label, weights=[float(np.float32(w)) for w in WEIGHTS])
         return loss, dict(overall_loss=loss.detach())
 
     monkeypatch.setattr(tr, "forward_losses", forward_losses)

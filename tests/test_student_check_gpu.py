@@ -187,7 +187,7 @@ def _checked_run(directory):
     from cosa_amd import nn_ops
     assert nn_ops._reference_ops is None                                                # no reference operators: reaching reference_op raises
     tr = _trainer(student_check_iters=2)
-    assert tr.args.student_check_mode == "fp32" and tr.model_SK is not None and tr.model_CK is None and tr._sk_shadows is None
+    assert tr.args.student_check_mode == "fp32" and tr.model_SK is not None and tr.model_CK is None and tr._checks["student_check"].shadows is None
     assert not {id(p) for p in tr.model_SK.parameters()} & {id(p) for p in tr.student.parameters()}
     losses, counters = [], {}
     for k in range(1, STEPS + 1):
@@ -248,16 +248,35 @@ def test_the_counters_equal_the_restatement_on_the_training_outputs_and_an_indep
     assert s["flags"] == 0 and s["seg"]["rel_l2"] > 0 and s["seg"]["nonfinite_a"] == s["seg"]["nonfinite_b"] == 0 and s["cells"] == 2 * 2 * 16
 
 
-def test_both_monitors_on_change_no_bit_of_the_run():
-    """6"""
+@pytest.mark.parametrize("flags", [dict(student_check_iters=2, teacher_check_iters=2),
+                                   dict(student_check_iters=2, teacher_check_iters=2, act_stats_iters=2, grad_check_iters=2)],
+                         ids=["student_teacher", "all_four"])
+def test_both_monitors_on_change_no_bit_of_the_run(flags):
+    """6: next to --teacher_check_iters, and with all four monitors that keep a network of their own (the gradient check at its defaults: fp64,
+    one direction)"""
     losses, state = _plain_run()
-    tr = _trainer(student_check_iters=2, teacher_check_iters=2)
-    assert tr.model_SK is not None and tr.model_CK is not None and tr.model_SK is not tr.model_CK
-    assert not {id(p) for p in tr.model_SK.parameters()} & {id(p) for p in tr.model_CK.parameters()}
-    got = torch.stack([_step(tr, k) for k in range(1, STEPS + 1)])
-    assert torch.equal(losses.view(torch.int32), got.view(torch.int32))
+    tr = _trainer(**flags)
+    all_four = len(flags) == 4
+    assert len(tr._checks) == len(flags) and tr.model_SK is not None and tr.model_CK is not None
+    assert (tr.model_AK is not None) == all_four and (tr.model_GK is not None) == all_four
+    nets = [tr.student, tr.model_AN, tr.model_SK, tr.model_CK] + ([tr.model_AK, tr.model_GK] if all_four else [])
+    ids = [{id(p) for p in net.parameters()} for net in nets]
+    assert all(not a & b for i, a in enumerate(ids) for b in ids[i + 1:])              # no parameter object is shared, pairwise
+    buffers = [tr._cam_buffers] + [ck.buffers for ck in tr._checks.values()]
+    assert len({id(b) for b in buffers}) == len(buffers)                                # nor a CAM-buffer dict
+    got, popped = [], []
+    for k in range(1, STEPS + 1):
+        got.append(_step(tr, k))
+        popped.append(tr.pop_grad_check())
+    assert torch.equal(losses.view(torch.int32), torch.stack(got).view(torch.int32))
     _assert_same_state(state, _state(tr))
     assert tr.student_check()["checks"] == 2 and tr.teacher_check()["checks"] == 2
+    if all_four:
+        assert int(tr.act_stats_state[-1]) == 2
+        assert [p is not None for p in popped] == [False, True, False, True, False]
+        assert all(d["flags"] == 0 for p in popped if p is not None for d in p)
+    else:
+        assert popped == [None] * STEPS
 
 
 def test_a_stale_weight_shadow_shows():

@@ -262,7 +262,7 @@ def _checked_run(directory):
     tr = _trainer(teacher_check_iters=2, teacher_check_mode="bf16")
     assert tr.args.teacher_precision == "fp16x3" and tr.model_CK is not None
     assert not {id(p) for p in tr.model_CK.parameters()} & {id(p) for p in tr.model_AN.parameters()}
-    assert tr._ck_shadows is not tr._teacher_shadows and not tr._ck_shadows.optimizer_owned
+    assert tr._checks["teacher_check"].shadows is not tr._teacher_shadows and not tr._checks["teacher_check"].shadows.optimizer_owned
     losses, counters = [], {}
     for k in range(1, STEPS + 1):
         if k == 5:

@@ -41,7 +41,7 @@ torch.cuda.synchronize()
 on = trainers["on"]
 _, _, cls_label, img_box = batch
 cam_a, aux_a = on._s_out[0], on._s_out[1]
-ent = next(iter(on._ck_buffers.values()))
+ent = next(iter(on._checks["teacher_check"].buffers.values()))
 cam_b, aux_b = ent["cam"], ent["aux"]
 mask_a = logs["mask"].contiguous().float()
 mask_b = torch.where(torch.rand(mask_a.shape, device=dev) < 0.01, torch.zeros_like(mask_a), mask_a)
