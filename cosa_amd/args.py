@@ -122,6 +122,12 @@ EXTRA = [
                                              # raised to the reference's --camweight_beta (in [0, 8]; read with this switch on only); the mean
                                              # weights are logged and written to <output_dir>/seg_reliability.jsonl at each evaluation
     ("seg_reliability_floor", float, 0.0),   # the weight of a pixel the CAM does not support (w = floor + (1 - floor) r^beta), in [0, 1)
+    # the soft-label seg loss: the reference's seg_softloss against the teacher's own segmentation; 0: nothing changes
+    ("seg_soft_weight", float, 0.0),         # weight of the student's seg logits' cross-entropy against softmax(mean of the teacher's seg passes / T)
+                                             # over the background and the image's classes, class-balanced by --segfg_alpha (0 during warm-up, like
+                                             # seg / cam / reg); > 0 adds `soft_loss` to the log line
+    ("seg_soft_temp", float, 1.0),           # its temperature T, in [0.05, 20]
+    ("seg_soft_conf", float, 0.0),           # a pixel whose largest target probability is not above this takes no part, in [0, 1); 0: no gate
 ]
 
 

@@ -1496,3 +1496,311 @@ extern "C" int cosa_cam_label(const float *const *seg_scales, const int *hs, con
     COSA_LAUNCH_CHECK();
     return COSA_OK;
 }
+
+// ---- the soft-label seg loss distilled from the teacher's segmentation (utils/seg_helper.py:837-861, seg_softloss) ---------
+// Per full-resolution pixel inside the image's crop box: z_k = the sum over scales and flips of the up-sampled teacher segs (what cam_target_kernel and
+// cam_label_kernel sum, by the same src_index / bilerp_fma calls), q = softmax(z / (2 n T)) over the background and the present classes,
+// l = - sum_k q_k log p_k = lse(s) - sum_k q_k s_k on the student's up-sampled logits s (the seg-loss tile, setup() and pixel_softmax).  The first
+// argmax of q puts the pixel into the background (0) or the foreground set; max q <= conf takes it out of both.
+//   forward:  {sum_bg l, n_bg, sum_fg l, n_fg} through block_sums_to_shard; one pass over the classes per pixel (an online max / sum-exp that carries
+//             sum_k e_k s_k along).
+//   backward: d/ds_k(pixel) = c_set (p_k - q_k), c_bg = (1 - a) g / (n_bg + 1e-6), c_fg = a g / (n_fg + 1e-6), into the cells of scatter_begin /
+//             scatter_flush (at most all pixels once per add: |v| <= g, the W g < 16 of the argument at fix48 with W = 1).
+// The teacher's taps are read from global memory, as the two kernels above read them: per scale and half a 32 x 32 block touches at most
+// (32 h_i / S + 2)^2 cells per class -- 8 x 8 at the 5.33x of an 8-pixel-patch encoder's 1.5 scale --, and LDS tiles of them for four scales, two
+// halves and 81 classes (166 KB) do not fit beside the backward's cells (35 KB there); the low-resolution planes of a block stay in L1 / L2.
+// A block that has no pixel inside the box returns before it reads anything; a pixel outside the box is never evaluated.
+namespace cosa {
+namespace {
+
+// one axis of a bilinear tap, kept as src_index's first index and second weight: i1 = min(i0 + 1, in - 1) and l0 = 1 - l1 are what src_index
+// itself forms from them, so they are formed again at each use -- half the registers of the four scales' taps
+struct AxisTap { int i0; float l1; };
+struct QuadTaps { AxisTap y[2], x[2], f[2]; };     // of one scale: the quad's two rows, two columns and the two mirrored columns (the flipped half)
+
+__device__ __forceinline__ AxisTap axis_tap(int dst, int in, int S)
+{
+    AxisTap a;
+    int i1;
+    float l0;
+    src_index(dst, in, (float)in / (float)S, a.i0, i1, l0, a.l1);
+    return a;
+}
+
+__device__ __forceinline__ int axis_i1(const AxisTap &a, int in) { return a.i0 < in - 1 ? a.i0 + 1 : a.i0; }
+
+__device__ __forceinline__ QuadTaps quad_taps(int Y, int X, int h, int w, int S)
+{
+    QuadTaps t;
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int py = min(Y + j, S - 1), px = min(X + j, S - 1);
+        t.y[j] = axis_tap(py, h, S);
+        t.x[j] = axis_tap(px, w, S);
+        t.f[j] = axis_tap(S - 1 - px, w, S);
+    }
+    return t;
+}
+
+// z_k of quad pixel `pix` (0..3): scale_value's sum, scale by scale in scale order
+__device__ __forceinline__ float teacher_z(const SegScales &sc, const QuadTaps (&t)[4], int pix, int b, int B, int K, int k)
+{
+    float acc = 0.f;
+#pragma unroll
+    for (int s2 = 0; s2 < 4; s2++)
+        if (s2 < sc.n) {
+            const int h = sc.h[s2], w = sc.w[s2];
+            const AxisTap &y = t[s2].y[pix >> 1], &x = t[s2].x[pix & 1], &f = t[s2].f[pix & 1];
+            const float *a = sc.p[s2] + ((size_t)b * K + k) * h * w;
+            const float *fl = sc.p[s2] + ((size_t)(b + B) * K + k) * h * w;
+            const int y1 = axis_i1(y, h);
+            const float yl0 = 1.0f - y.l1;
+            const float v = bilerp_fma(a, w, y.i0, y1, x.i0, axis_i1(x, w), yl0, y.l1, 1.0f - x.l1, x.l1) +
+                            bilerp_fma(fl, w, y.i0, y1, f.i0, axis_i1(f, w), yl0, y.l1, 1.0f - f.l1, f.l1);
+            acc = s2 == 0 ? v : acc + v;
+        }
+    return acc;
+}
+
+__device__ __forceinline__ bool soft_present(const float *__restrict__ labels, int b, int K, int k)
+{
+    return k == 0 || labels[(size_t)b * (K - 1) + k - 1] != 0.0f;
+}
+
+// the target's statistics at one pixel over the present classes, in class order: m = max z (bk its first position), se = sum exp((z - m) inv_t), so
+// q_k = exp((z_k - m) inv_t) / se and max q = 1 / se; DOT: dot = sum exp((z_k - m) inv_t) s_k on the student's logit s_k of the same pixel.
+// The forward and the backward run this one function: the same m, se and bk, so the same set and gate.
+struct SoftStat { float m, se, dot; int bk; };
+
+template <bool DOT>
+__device__ __forceinline__ SoftStat soft_stat(const SegScales &sc, const QuadTaps (&t)[4], int pix, const float *__restrict__ labels, int b, int B, int K,
+                                              float inv_t, const float *tile, const Tap &st)
+{
+    SoftStat s = {-INFINITY, 0.f, 0.f, 0};
+    for (int k = 0; k < K; k++) {
+        if (!soft_present(labels, b, K, k)) continue;
+        const float z = teacher_z(sc, t, pix, b, B, K, k);
+        const float sk = DOT ? tap(tile + k * TC * TC, st) : 0.f;
+        if (z > s.m) {
+            const float r = expf((s.m - z) * inv_t);
+            s.se = s.se * r + 1.f;
+            if (DOT) s.dot = s.dot * r + sk;
+            s.m = z;
+            s.bk = k;
+        } else {
+            const float e = expf((z - s.m) * inv_t);
+            s.se += e;
+            if (DOT) s.dot += e * sk;
+        }
+    }
+    return s;
+}
+
+// does the block's 32 x 32 pixels meet the box (y0, y1, x0, x1)?  The same answer in every thread of the block.
+__device__ __forceinline__ bool block_meets_box(const int32_t *bx)
+{
+    const int by = blockIdx.y * 32, bxx = blockIdx.x * 32;
+    return by < bx[1] && by + 32 > bx[0] && bxx < bx[3] && bxx + 32 > bx[2];
+}
+
+__device__ __forceinline__ bool in_box(const int32_t *bx, int py, int px) { return py >= bx[0] && py < bx[1] && px >= bx[2] && px < bx[3]; }
+
+// sums: 64 shards of {bg_sum, bg_cnt, fg_sum, fg_cnt} in fix32
+__global__ __launch_bounds__(256) void seg_soft_fwd_kernel(const float *__restrict__ seg_lr, SegScales sc, const float *__restrict__ labels,
+                                                          const int32_t *__restrict__ boxes, unsigned long long *__restrict__ sums,
+                                                          unsigned long long *__restrict__ flag, int B, int K, int hs, int ws, int S, float sy, float sx,
+                                                          float inv_t, float conf)
+{
+    extern __shared__ __attribute__((aligned(16))) float tile[];
+    const int b = blockIdx.z;
+    const int32_t *bx = boxes + b * 4;
+    if (!block_meets_box(bx)) return;
+    const QuadCtx c = setup(seg_lr, tile, K, hs, ws, S, sy, sx, b);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c.valid) {
+        QuadTaps t[4];
+#pragma unroll
+        for (int s2 = 0; s2 < 4; s2++)
+            if (s2 < sc.n) t[s2] = quad_taps(c.Y, c.X, sc.h[s2], sc.w[s2], S);
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            if (!in_box(bx, c.Y + (p >> 1), c.X + (p & 1))) continue;
+            float m, inv;
+            const float lse = pixel_softmax(tile, c.t[p], K, m, inv);
+            const SoftStat s = soft_stat<true>(sc, t, p, labels, b, B, K, inv_t, tile, c.t[p]);
+            if (!(1.0f / s.se <= conf)) {       // (a NaN target passes the gate and reaches the sticky flag: NaN out, not a pixel dropped in silence)
+                const float l = lse - s.dot / s.se;
+                if (s.bk == 0) { acc[0] += l; acc[1] += 1.f; }
+                else { acc[2] += l; acc[3] += 1.f; }
+            }
+        }
+    }
+    block_sums_to_shard<4>(acc, sums, flag);
+}
+
+// sums[4] in fp32 and the loss (1 - a) bg_sum / (bg_cnt + 1e-6) + a fg_sum / (fg_cnt + 1e-6): an empty set contributes 0
+__global__ void seg_soft_sums_kernel(const unsigned long long *__restrict__ fix, const unsigned long long *__restrict__ flag, float *__restrict__ sums,
+                                     float *__restrict__ loss, float fg_alpha)
+{
+    __shared__ float s[4];
+    if (threadIdx.x < 4) s[threadIdx.x] = sums[threadIdx.x] = shard_total(fix, flag, 4, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x == 0) loss[0] = (1.0f - fg_alpha) * (s[0] / (s[1] + 1e-6f)) + fg_alpha * (s[2] / (s[3] + 1e-6f));
+}
+
+__global__ __launch_bounds__(256) void seg_soft_bwd_kernel(const float *__restrict__ seg_lr, SegScales sc, const float *__restrict__ labels,
+                                                          const int32_t *__restrict__ boxes, const float *__restrict__ sums,
+                                                          const float *__restrict__ upstream, unsigned long long *__restrict__ grad,
+                                                          unsigned long long *__restrict__ flag, int B, int K, int hs, int ws, int S, float sy, float sx,
+                                                          float inv_t, float conf, float fg_alpha)
+{
+    extern __shared__ __attribute__((aligned(16))) float tile[];       // [K][TC][TC] logits, then [K][TC][TC] gradient cells (64-bit fixed point)
+    const int b = blockIdx.z;
+    const int32_t *bx = boxes + b * 4;
+    if (!block_meets_box(bx)) return;
+    const QuadCtx c = setup(seg_lr, tile, K, hs, ws, S, sy, sx, b);
+    const Scatter scat = scatter_begin(tile, c, K);
+    if (c.valid) {
+        const float g = upstream[0];
+        const float cbg = (1.0f - fg_alpha) * g / (sums[1] + 1e-6f), cfg = fg_alpha * g / (sums[3] + 1e-6f);
+        QuadTaps t[4];
+#pragma unroll
+        for (int s2 = 0; s2 < 4; s2++)
+            if (s2 < sc.n) t[s2] = quad_taps(c.Y, c.X, sc.h[s2], sc.w[s2], S);
+        float m[4], inv[4], tm[4], tinv[4], co[4];
+        bool live[4];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            m[p] = inv[p] = tm[p] = tinv[p] = co[p] = 0.f;
+            live[p] = false;
+            if (!in_box(bx, c.Y + (p >> 1), c.X + (p & 1))) continue;
+            const SoftStat s = soft_stat<false>(sc, t, p, labels, b, B, K, inv_t, tile, c.t[p]);
+            if (!(1.0f / s.se <= conf)) {
+                pixel_softmax(tile, c.t[p], K, m[p], inv[p]);
+                tm[p] = s.m;
+                tinv[p] = 1.0f / s.se;
+                co[p] = s.bk == 0 ? cbg : cfg;
+                live[p] = true;
+            }
+        }
+        for (int k = 0; k < K; k++) {
+            const float *pl = tile + k * TC * TC;
+            const bool present = soft_present(labels, b, K, k);
+            float dz[4];
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                dz[p] = 0.f;
+                if (live[p]) {
+                    const float pk = __expf(tap(pl, c.t[p]) - m[p]) * inv[p];
+                    const float qk = present ? expf((teacher_z(sc, t, p, b, B, K, k) - tm[p]) * inv_t) * tinv[p] : 0.f;
+                    dz[p] = co[p] * (pk - qk);
+                }
+            }
+            unsigned long long *gp = scat.cells + k * TC * TC;
+            if (scat.grouped || scat.same) {
+                float v00 = dz[0] * c.t[0].w00 + dz[1] * c.t[1].w00 + dz[2] * c.t[2].w00 + dz[3] * c.t[3].w00;
+                float v01 = dz[0] * c.t[0].w01 + dz[1] * c.t[1].w01 + dz[2] * c.t[2].w01 + dz[3] * c.t[3].w01;
+                float v10 = dz[0] * c.t[0].w10 + dz[1] * c.t[1].w10 + dz[2] * c.t[2].w10 + dz[3] * c.t[3].w10;
+                float v11 = dz[0] * c.t[0].w11 + dz[1] * c.t[1].w11 + dz[2] * c.t[2].w11 + dz[3] * c.t[3].w11;
+                if (scat.grouped) {
+#pragma unroll
+                    for (int sft = 0; sft < 4; sft++) {
+                        const int x = sft == 0 ? 1 : (sft == 1 ? 2 : (sft == 2 ? 16 : 32));
+                        v00 += __shfl_xor(v00, x, 64);
+                        v01 += __shfl_xor(v01, x, 64);
+                        v10 += __shfl_xor(v10, x, 64);
+                        v11 += __shfl_xor(v11, x, 64);
+                    }
+                }
+                if (!scat.grouped || ((threadIdx.y * 16 + threadIdx.x) & 0x33) == 0) {
+                    atomicAdd(gp + c.t[0].o00, fix48(v00, flag));
+                    atomicAdd(gp + c.t[0].o01, fix48(v01, flag));
+                    atomicAdd(gp + c.t[0].o10, fix48(v10, flag));
+                    atomicAdd(gp + c.t[0].o11, fix48(v11, flag));
+                }
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; p++) {
+                    if (!live[p]) continue;
+                    atomicAdd(gp + c.t[p].o00, fix48(dz[p] * c.t[p].w00, flag));
+                    atomicAdd(gp + c.t[p].o01, fix48(dz[p] * c.t[p].w01, flag));
+                    atomicAdd(gp + c.t[p].o10, fix48(dz[p] * c.t[p].w10, flag));
+                    atomicAdd(gp + c.t[p].o11, fix48(dz[p] * c.t[p].w11, flag));
+                }
+            }
+        }
+    }
+    scatter_flush(scat, c, grad, b, K, hs, ws);
+}
+
+// the shared envelope of the two entry points below (include/cosa_hip.h)
+int seg_soft_check(const char *who, const float *const *seg_scales, const int *hs_t, const int *ws_t, int n_scales, int B, int K, int hs, int ws, int S,
+                   float temp, float conf, float fg_alpha, size_t workspace_bytes, SegScales *sc)
+{
+    COSA_REQUIRE(B > 0 && B <= 65535 && hs > 0 && ws > 0 && S > 0 && (S & 1) == 0, "%s: bad shape", who);
+    COSA_REQUIRE(K >= 2 && K <= 128, "%s: 2 to 128 classes, background included (got %d)", who, K);
+    COSA_REQUIRE(S >= 8 * hs && S >= 8 * ws, "%s: needs an up-sampling factor >= 8 for the student's logits (got %d x %d -> %d)", who, hs, ws, S);
+    COSA_REQUIRE(std::isfinite(temp) && temp > 0.f, "%s: the temperature must be finite and positive (got %g)", who, (double)temp);
+    COSA_REQUIRE(conf >= 0.f && conf < 1.f, "%s: conf must lie in [0, 1) (got %g)", who, (double)conf);
+    COSA_REQUIRE(fg_alpha >= 0.f && fg_alpha <= 1.f, "%s: fg_alpha must lie in [0, 1] (got %g)", who, (double)fg_alpha);
+    if (int rc = pack_scales(who, seg_scales, hs_t, ws_t, n_scales, sc)) return rc;
+    for (int i = 0; i < n_scales; i++)
+        COSA_REQUIRE(hs_t[i] <= S && ws_t[i] <= S, "%s: scale %d (%d x %d) is larger than the full resolution %d", who, i, hs_t[i], ws_t[i], S);
+    COSA_REQUIRE(workspace_bytes >= cosa_seg_soft_workspace_bytes(B, K, hs, ws), "%s: workspace too small (size it with cosa_seg_soft_workspace_bytes)", who);
+    return COSA_OK;
+}
+
+}  // namespace
+}  // namespace cosa
+
+/* 64 shards of the 4 forward sums, the B*K*hs*ws gradient cells of the backward, the sticky flag word */
+extern "C" size_t cosa_seg_soft_workspace_bytes(int B, int K, int hs, int ws)
+{
+    if (B <= 0 || K <= 0 || hs <= 0 || ws <= 0) return 0;
+    return cosa::align_up((size_t)B * K * hs * ws * sizeof(unsigned long long) + (64 * 4 + 1) * sizeof(unsigned long long), 256);
+}
+
+extern "C" int cosa_seg_soft_forward(const float *seg_lr, const float *const *seg_scales, const int *hs_t, const int *ws_t, int n_scales,
+                                     const float *labels, const int32_t *boxes, float *sums, float *loss, int B, int K, int hs, int ws, int S,
+                                     float temp, float conf, float fg_alpha, void *workspace, size_t workspace_bytes, void *stream)
+{
+    COSA_REQUIRE(seg_lr && labels && boxes && sums && loss && workspace, "cosa_seg_soft_forward: null pointer");
+    SegScales sc;
+    if (int rc = seg_soft_check("cosa_seg_soft_forward", seg_scales, hs_t, ws_t, n_scales, B, K, hs, ws, S, temp, conf, fg_alpha, workspace_bytes, &sc))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    unsigned long long *fix = static_cast<unsigned long long *>(workspace);
+    unsigned long long *flag = fix + 64 * 4 + (size_t)B * K * hs * ws;             // reset here, read by both conversions (a forward precedes its backward)
+    COSA_HIP_CHECK(hipMemsetAsync(fix, 0, 64 * 4 * sizeof(unsigned long long), st));
+    COSA_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(unsigned long long), st));
+    const TileLaunch t = tile_launch(B, K, hs, ws, S);
+    hipLaunchKernelGGL(seg_soft_fwd_kernel, t.grid, t.blk, t.lds_fwd, st, seg_lr, sc, labels, boxes, fix, flag, B, K, hs, ws, S, t.sy, t.sx,
+                       1.0f / (2.0f * (float)n_scales * temp), conf);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(seg_soft_sums_kernel, dim3(1), dim3(64), 0, st, fix, flag, sums, loss, fg_alpha);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}
+
+extern "C" int cosa_seg_soft_backward(const float *seg_lr, const float *const *seg_scales, const int *hs_t, const int *ws_t, int n_scales,
+                                      const float *labels, const int32_t *boxes, const float *sums, const float *upstream, float *grad_seg_lr,
+                                      int B, int K, int hs, int ws, int S, float temp, float conf, float fg_alpha, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    COSA_REQUIRE(seg_lr && labels && boxes && sums && upstream && grad_seg_lr && workspace, "cosa_seg_soft_backward: null pointer");
+    SegScales sc;
+    if (int rc = seg_soft_check("cosa_seg_soft_backward", seg_scales, hs_t, ws_t, n_scales, B, K, hs, ws, S, temp, conf, fg_alpha, workspace_bytes, &sc))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    const size_t n = (size_t)B * K * hs * ws;
+    unsigned long long *fix = static_cast<unsigned long long *>(workspace) + 64 * 4;
+    unsigned long long *flag = fix + n;
+    COSA_HIP_CHECK(hipMemsetAsync(fix, 0, n * sizeof(unsigned long long), st));
+    const TileLaunch t = tile_launch(B, K, hs, ws, S);                              // (K <= 128: lds_bwd is 54 KB at the most)
+    hipLaunchKernelGGL(seg_soft_bwd_kernel, t.grid, t.blk, t.lds_bwd, st, seg_lr, sc, labels, boxes, sums, upstream, fix, flag, B, K, hs, ws, S, t.sy,
+                       t.sx, 1.0f / (2.0f * (float)n_scales * temp), conf, fg_alpha);
+    COSA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(seg_loss_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fix, flag, grad_seg_lr, n);
+    COSA_LAUNCH_CHECK();
+    return COSA_OK;
+}

@@ -26,7 +26,7 @@ from .dataloaders import build_test_loader, build_train_loader, build_val_loader
 from .evaluation_engine import evaluate
 from .models import build_model
 from .models.backbones import get_backbone
-from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher, reliability_settings, tokcon_settings
+from .train_step import CoSATrainer, check_iters, default_args, refuse_fp64_teacher, reliability_settings, seg_soft_settings, tokcon_settings
 from .utils import evaluation
 from .utils import grad_check as gcheck
 from .utils import torch_helper
@@ -82,6 +82,7 @@ def check_supported(args):
     refuse_fp64_teacher(getattr(args, "teacher_precision", "auto"), flag="--")
     tokcon_settings(args, flag="--")                              # the token contrast term: ranges, and not together with --grad_check_iters
     rel_on, rel_beta, _ = reliability_settings(args, flag="--")       # the reliability-weighted seg loss: ranges
+    seg_soft_settings(args, flag="--")                            # the soft-label seg term: ranges, and not together with --grad_check_iters
     notes = []
     if not rel_on and rel_beta != 1.0:
         notes.append("--camweight_beta: only read with --seg_reliability true")
@@ -101,35 +102,55 @@ def check_supported(args):
 BASE_KEYS = ('overall_loss', 'cls_loss', 'cls_acc', 'cls_aux_loss', 'cls_aux_acc', 'seg_loss', 'cam_loss', 'reg_loss')
 
 
-def interval_keys(tokcon_on):
-    """the keys of the interval's running sums `acc`, of the log line and of loss_dataframe.pt: the reference's eight, and `tok_loss` after
-    `reg_loss` with the token contrast term on (--tokcon_weight > 0)"""
-    return BASE_KEYS + (('tok_loss',) if tokcon_on else ())
+def interval_keys(tokcon_on, soft_on=False):
+    """the keys of the interval's running sums `acc`, of the log line and of loss_dataframe.pt: the reference's eight, `tok_loss` after
+    `reg_loss` with the token contrast term on (--tokcon_weight > 0), and `soft_loss` after that with the soft-label seg term on
+    (--seg_soft_weight > 0)"""
+    return BASE_KEYS + (('tok_loss',) if tokcon_on else ()) + (('soft_loss',) if soft_on else ())
 
 
-def interval_terms(logs, cls_acc, cls_aux_acc, tokcon_on):
+def interval_terms(logs, cls_acc, cls_aux_acc, tokcon_on, soft_on=False):
     """one step's contribution to `acc`, in interval_keys' order"""
     terms = [logs['overall_loss'], logs['cls_loss'], cls_acc, logs['cls_aux_loss'], cls_aux_acc, logs['seg_loss'], logs['cam_loss'], logs['reg_loss']]
     if tokcon_on:
         terms.append(logs['tok_loss'])
+    if soft_on:
+        terms.append(logs['soft_loss'])
     return torch.stack([t.reshape(()).double() for t in terms])
 
 
-def interval_line(head, vals, tokcon_on):
+def interval_line(head, vals, tokcon_on, soft_on=False):
     """the log line's loss part from interval_keys' values"""
     line = (" overall_loss: %.4f, cls_loss: %.4f, cls_acc: %.3f,  cls_aux_loss: %.4f, cls_aux_acc: %.3f, seg_loss: %.4f, cam_loss: %.4f, "
             "reg_loss: %.4f" % tuple(vals[:8]))
     if tokcon_on:
         line += ", tok_loss: %.4f" % vals[8]
+    if soft_on:
+        line += ", soft_loss: %.4f" % vals[9 if tokcon_on else 8]
     return head + line + " ..."
 
 
-def load_state_checked(trainer, path, tokcon_on):
-    """trainer.load_state(path); a file written under the other on / off setting of the token contrast term differs in the length of
-    `launcher.acc` (8 | 9 sums): that refusal names the flag instead of a shape"""
+EXTRA_KEYS_STATE = "launcher.extra_keys"      # a state file's tensor aux.<this>, written with the soft-label seg term on only
+
+
+def extra_keys_word(tokcon_on, soft_on, device):
+    """the set of keys beyond the reference's eight as one int64 word (bit 0: tok_loss, bit 1: soft_loss).  It travels in a state file only
+    with the soft-label seg term on: the length of `launcher.acc` cannot tell `tok_loss` alone from `soft_loss` alone, the presence of this
+    tensor can -- and files written with the term off keep the tensors they always had."""
+    return torch.tensor([int(tokcon_on) | 2 * int(soft_on)], device=device, dtype=torch.int64)
+
+
+def load_state_checked(trainer, path, tokcon_on, soft_on=False):
+    """trainer.load_state(path); a refusal over the launcher's own tensors names the flag instead of a tensor or a shape.  A file written
+    under the other on / off setting of the soft-label seg term has or lacks `aux.launcher.extra_keys`; one written under the other setting
+    of the token contrast term differs in the length of `launcher.acc`."""
     try:
         return trainer.load_state(path)
     except ValueError as e:
+        if EXTRA_KEYS_STATE in str(e):
+            raise ValueError(f"{path}: written with --seg_soft_weight {'0 (the term off)' if soft_on else '> 0 (the term on)'}, this run has "
+                             f"--seg_soft_weight {'> 0' if soft_on else '0'}: resume with the setting the file was written under "
+                             f"(its interval sums {'lack' if soft_on else 'carry'} the key soft_loss) [{e}]") from e
         if "launcher.acc" in str(e) and "differs" in str(e):
             raise ValueError(f"{path}: written with --tokcon_weight {'0 (the term off)' if tokcon_on else '> 0 (the term on)'}, this run has "
                              f"--tokcon_weight {'> 0' if tokcon_on else '0'}: resume with the setting the file was written under "
@@ -233,16 +254,19 @@ def main(args):
         return train_loader.iter_from(skip) if skip else iter(train_loader)
 
     tokcon_on = float(getattr(args, "tokcon_weight", 0.0) or 0.0) > 0           # (off: keys, line and `acc` as ever)
-    keys = interval_keys(tokcon_on)
+    soft_on = float(getattr(args, "seg_soft_weight", 0.0) or 0.0) > 0          # (likewise)
+    keys = interval_keys(tokcon_on, soft_on)
     acc = torch.zeros(len(keys), device=device, dtype=torch.float64)           # running sums of the interval, on the device
     # ... and part of a state file: saved and restored in place, no sync (next to what the trainer keeps there: --label_stats' counters)
     trainer._add_extra_state("launcher.acc", acc)
+    if soft_on:
+        trainer._add_extra_state(EXTRA_KEYS_STATE, extra_keys_word(tokcon_on, soft_on, device))
     resume = args.resume
     if resume == "auto":
         resume = checkpoint.newest_state(output_dir)                                # none: a fresh start
     resumed = None
     if resume:
-        resumed = load_state_checked(trainer, resume, tokcon_on)
+        resumed = load_state_checked(trainer, resume, tokcon_on, soft_on)
         checkpoint.unpack_rng(resumed["loader"]["rng"], device)                     # 1. the states the interrupted run built its iterator from
         it = new_iter(skip=int(resumed["loader"]["consumed"]))                      # 2./3. same sampler epoch, the consumed batches drawn and dropped
         assert pos["epoch"] == resumed["loader"]["epoch"], "the sampler epoch of the resumed iterator differs from the saved one"
@@ -273,7 +297,7 @@ def main(args):
             with torch.no_grad():                                                 # main.py:257-268, without the per-iteration .item() syncs
                 ap, ok = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_logits"].float()))
                 apa, oka = torch_helper.average_precision(cls_label, torch.sigmoid(logs["cls_aux_logits"].float()))
-                acc += interval_terms(logs, (ap * ok).sum() / ok.sum().clamp_min(1), (apa * oka).sum() / oka.sum().clamp_min(1), tokcon_on)
+                acc += interval_terms(logs, (ap * ok).sum() / ok.sum().clamp_min(1), (apa * oka).sum() / oka.sum().clamp_min(1), tokcon_on, soft_on)
         if gcheck_on and (n_iter + 1) % args.grad_check_iters == 0:              # a check step: its record is read here (the check's one sync)
             gsum = trainer.pop_grad_check()
             if gsum is not None and is_main:
@@ -291,7 +315,7 @@ def main(args):
                 loss_df['iters'].append(n_iter + 1)
                 head = "Iter: %d; Elasped: %s; ETA: %s; Itertime: %.3f; LR: %.3e; \n" % (
                     n_iter + 1, delta, str(eta).split('.')[0], itertime, trainer.optimizer.param_groups[0]['lr'])
-                line = interval_line(head, vals, tokcon_on)
+                line = interval_line(head, vals, tokcon_on, soft_on)
                 for m in monitors.MONITORS:                                                # (a monitor that is off: the line as ever)
                     if m.name in host:
                         summary = host[m.name] if m.summary is None else m.summary(trainer, args, host[m.name])

@@ -46,7 +46,8 @@ def default_args(dataset="VOC12", **over):
              act_stats_iters=0, camloss_version='v1', segconf_thre=0.25,
              grad_check_iters=0, grad_check_mode='fp64', grad_check_dirs='all', grad_check_rho=gcheck.DEFAULT_RHO,
              tokcon_weight=0.0, tokcon_temp=0.5, tokcon_purity=1.0,
-             seg_reliability=False, seg_reliability_floor=0.0, camweight_beta=1.0)
+             seg_reliability=False, seg_reliability_floor=0.0, camweight_beta=1.0,
+             seg_soft_weight=0.0, seg_soft_temp=1.0, seg_soft_conf=0.0)
     if dataset == "VOC12":
         a.update(aux_layer=-4, max_iters=32000)            # run_voc.sh:9-11
     elif dataset == "COCO":
@@ -129,6 +130,19 @@ def tokcon_settings(args, flag=""):
         raise ValueError(f"{flag}tokcon_weight {w!r} with {flag}grad_check_iters: the gradient check differences the five terms of the "
                          f"reference's objective and has no evaluator for the token contrast term; run the check with {flag}tokcon_weight 0")
     return float(w), float(t), float(p)
+
+
+def seg_soft_settings(args, flag=""):
+    """(weight, temp, conf) of the soft-label seg loss from `args` (off where the fields are missing), refused when one is
+    outside its range or when the term meets --grad_check_iters, as tokcon_settings refuses the token contrast term there; here for the
+    trainer and, with flag="--", for the launcher's check_supported"""
+    w, t, c = (getattr(args, "seg_soft_weight", 0.0) or 0.0, getattr(args, "seg_soft_temp", 1.0), getattr(args, "seg_soft_conf", 0.0))
+    t, c = (1.0 if t is None else t), (0.0 if c is None else c)
+    seg_helper.check_seg_soft_settings(w, t, c, flag=flag)
+    if float(w) > 0 and int(getattr(args, "grad_check_iters", 0) or 0) > 0:
+        raise ValueError(f"{flag}seg_soft_weight {w!r} with {flag}grad_check_iters: the gradient check differences the five terms of the "
+                         f"reference's objective and has no evaluator for the soft-label seg term; run the check with {flag}seg_soft_weight 0")
+    return float(w), float(t), float(c)
 
 
 def reliability_settings(args, flag=""):
@@ -237,6 +251,7 @@ class CoSATrainer:
         self.camloss_version = camloss_version(args)      # (before anything is built: an unknown version costs nothing)
         self._tokcon = tokcon_settings(args)              # (likewise: the token contrast term; weight 0: off)
         self._seg_rel = reliability_settings(args)        # (likewise: the reliability-weighted seg loss)
+        self._seg_soft = seg_soft_settings(args)          # (likewise: the soft-label seg loss; weight 0: off)
         # its counters, int64 [G][4] (seg_helper.new_reliability_stats): the run's, read and zeroed by seg_reliability(); None: the switch is off
         self.seg_rel_state = seg_helper.new_reliability_stats(2 if args.aux_cam2seg else 1, device) if self._seg_rel[0] else None
         if check_iters(args, "grad") > 0:                 # (--grad_check_iters, DESIGN.md section 25: refused before anything is built too)
@@ -809,14 +824,18 @@ class CoSATrainer:
                                 ((threhigh, threlow), (auxthrehigh, auxthrelow)), check_tgt)
         if self.model_AK is not None and self._is_check_step(n_iter, "act_stats"):
             self._act_stats(wimg, cls_label)
-        tok_on = self._tokcon[0] > 0
+        tok_on, soft_on = self._tokcon[0] > 0, self._seg_soft[0] > 0
         if tok_on:
             tok_loss = self._token_contrast(_feat, refine_mask_label)
+        if soft_on:
+            soft_loss = self._seg_soft_loss(seg_pred, seg_ps, cls_label, img_box, wimg.shape[-1])
         # main.py:230-236: the weighted sum of the five losses (warm-up: classification losses only) as one dot product
         wkey = n_iter <= args.warmup_iters
         wl = [1.0, 1.0, 0.0, 0.0, 0.0] if wkey else [1.0, 1.0, args.seg_weight, args.cam_weight, args.reg_weight]
         if tok_on:                          # the sixth element: the token contrast term, 0 during warm-up like seg / cam / reg
             wl.append(0.0 if wkey else self._tokcon[0])
+        if soft_on:                         # the soft-label seg term, after the token contrast element when both are on; 0 during warm-up too
+            wl.append(0.0 if wkey else self._seg_soft[0])
         wvec = self._loss_weights.get(wkey)
         if wvec is None:
             wvec = self._loss_weights[wkey] = torch.tensor(wl, device=cls_loss.device, dtype=torch.float32)
@@ -836,6 +855,8 @@ class CoSATrainer:
         terms = [cls_loss.reshape(()), cls_loss_aux.reshape(()), seg_loss.reshape(()).float(), cam_loss.reshape(()).float(), reg_loss.reshape(()).float()]
         if tok_on:
             terms.append(tok_loss.reshape(()).float())
+        if soft_on:
+            terms.append(soft_loss.reshape(()).float())
         loss = torch.dot(torch.stack(terms), wvec)
         overall = loss.detach()
         if self.label_stats_state is not None and self._skip_nonfinite:
@@ -847,6 +868,8 @@ class CoSATrainer:
                     mask=refine_mask_label, cls_logits=cls_final.detach(), cls_aux_logits=cls_aux.detach())
         if tok_on:
             logs["tok_loss"] = tok_loss.detach()
+        if soft_on:
+            logs["soft_loss"] = soft_loss.detach()
         return loss, logs
 
     @staticmethod
@@ -889,6 +912,16 @@ class CoSATrainer:
             labels = seg_helper.token_labels(mask, mask.shape[-1] // h, purity)
         fn = seg_helper.token_contrast_loss if self.fused_losses else seg_helper._token_contrast_torch
         return fn(tokens, labels, temp)
+
+    def _seg_soft_loss(self, seg_pred, seg_ps, cls_label, img_box, S):
+        """the soft-label seg term of the step, made here, outside the captured teacher pass: the student's low-res
+        logits against the teacher's per-scale low-res segs on the HIP kernels (fused_losses), or its up-sampled logits (the torch path has
+        up-sampled `seg_pred` by now) against the teacher's summed full-resolution seg on the torch composition"""
+        _, temp, conf = self._seg_soft
+        if self.fused_losses:
+            return seg_helper.seg_soft_loss(seg_pred, seg_ps, cls_label, img_box, S, temp=temp, conf=conf, fg_alpha=self.args.segfg_alpha)
+        return seg_helper.seg_soft_loss_torch(seg_pred, seg_ps, cls_label, img_box, temp, conf, self.args.segfg_alpha,
+                                              n_scales=len(self.args.pseudo_scales))
 
     @torch.no_grad()
     def _cam_target(self, seg_ps, cls_label, S, out_hw):

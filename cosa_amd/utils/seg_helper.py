@@ -2414,6 +2414,172 @@ def seg_weightloss(seg_pred, mask_label, mask_weights, fg_alpha=0.5, ignore_inde
 
 
 # --------------------------------------------------------------------------------------------
+# the soft-label seg loss distilled from the teacher's segmentation: the reference's seg_softloss / seg_softlossv2
+# (utils/seg_helper.py:837-861, called by nothing there) against a target this build makes from the teacher's own seg passes
+# --------------------------------------------------------------------------------------------
+SEG_SOFT_TEMP = (0.05, 20.0)       # --seg_soft_temp: on the MEAN of the teacher's passes
+SEG_SOFT_MAX_K = 128               # the kernels' envelope (csrc/loss_kernels.hip: seg_soft_check): classes, background included ...
+SEG_SOFT_MAX_SCALES = 4            # ... and teacher scales; the student's logits need the seg-loss tile's factor (CAM_UPSAMPLE_MIN)
+
+
+def check_seg_soft_settings(weight, temp, conf, flag=""):
+    """the term's three settings (trainer: flag "", launcher: flag "--"), or a ValueError naming the one outside its range"""
+    if not (math.isfinite(float(weight)) and float(weight) >= 0):
+        raise ValueError(f"{flag}seg_soft_weight {weight!r}: 0 (off) or a positive weight")
+    if not SEG_SOFT_TEMP[0] <= float(temp) <= SEG_SOFT_TEMP[1]:
+        raise ValueError(f"{flag}seg_soft_temp {temp!r}: a temperature in [{SEG_SOFT_TEMP[0]}, {SEG_SOFT_TEMP[1]}]")
+    if not 0.0 <= float(conf) < 1.0:
+        raise ValueError(f"{flag}seg_soft_conf {conf!r}: a probability in [0, 1); 0: no gate")
+
+
+def seg_softlossv2(seg_pred, softprobs):
+    """utils/seg_helper.py:854-861: - sum_k softprobs_k log_softmax(seg_pred)_k, averaged over the pixels ([B,K,H,W] or rows [N,K]).  The
+    reference takes `.mean()`, which is NaN for no pixel at all; here the sum is divided by (count + 1e-6), seg_loss's denominator: no pixel
+    gives 0 with a zero gradient, and a mean over n pixels moves by 1e-6 / n of itself."""
+    per = -(F.log_softmax(seg_pred, dim=1) * softprobs).sum(dim=1)
+    return per.sum() / (per.numel() + 1e-6)
+
+
+def _seg_soft_torch(seg_pred, softprobs, fg_alpha=0.5, img_box=None, conf=None):
+    """the term op by op on full-resolution logits and targets [B,K,H,W]: what the kernels are checked against, and the path of
+    fused_losses=False, host tensors and shapes outside the envelope.  A pixel is background where the first argmax of its target is 0 and
+    foreground otherwise; outside its box (img_box given) or with max q <= conf (conf given) it is in neither set.  An empty set contributes 0."""
+    assert fg_alpha >= 0 and fg_alpha <= 1, "fg_alpha should be in [0,1]"
+    value, label = torch.max(softprobs, dim=1)                  # (the lowest index at a tie, as _cam_label_torch)
+    keep = torch.ones_like(label, dtype=torch.bool) if conf is None else ~(value <= conf)
+    if img_box is not None:
+        b, _, h, w = seg_pred.shape
+        keep = keep & (_crop_mask_from_boxes(_abs_boxes(img_box, h, w), b, h, w, seg_pred.device) > 0)
+    per = -(F.log_softmax(seg_pred, dim=1) * softprobs).sum(dim=1)
+    zero = torch.zeros_like(per)
+    bg, fg = keep & (label == 0), keep & (label != 0)
+    bgloss = torch.where(bg, per, zero).sum() / (bg.sum().to(per.dtype) + 1e-6)       # (the count in the loss's own dtype: 1e-6 survives in float64)
+    fgloss = torch.where(fg, per, zero).sum() / (fg.sum().to(per.dtype) + 1e-6)
+    return (1 - fg_alpha) * bgloss + fg_alpha * fgloss
+
+
+def seg_softloss(seg_pred, softprobs, fg_alpha=0.5):
+    """utils/seg_helper.py:837-852: seg_softlossv2 over the pixels whose target's argmax is the background and over the others, blended by
+    fg_alpha.  The reference's `.mean()` over an empty set is NaN; here each set's sum is divided by (count + 1e-6), so an empty set
+    contributes 0 and a zero gradient (seg_softlossv2)."""
+    return _seg_soft_torch(seg_pred, softprobs, fg_alpha=fg_alpha)
+
+
+def _wide(t):
+    """float32 for a 16-bit tensor, any other dtype as it is (the torch compositions run in their inputs' precision: float64 in the tests)"""
+    return t.float() if t.dtype in (torch.bfloat16, torch.float16) else t
+
+
+def _abs_boxes(img_box, h, w):
+    """boxes (y0, y1, x0, x1) with the reference's slicing semantics (a negative bound counts from the end, cam2mask_multi) in absolute form"""
+    if not torch.is_tensor(img_box):
+        img_box = torch.as_tensor(img_box)
+    size = torch.tensor([h, h, w, w], device=img_box.device, dtype=img_box.dtype)
+    return torch.where(img_box < 0, img_box + size, img_box)
+
+
+def seg_soft_targets_torch(seg, cls_label, S, temp, n_scales=None):
+    """the soft target op by op -> q [B,K,S,S].  seg: the list of per-scale low-res teacher segs [2B,K,h_i,w_i] (original batch, then the
+    flipped one: multi_scale_camseg's `_seg_scales`), summed here as multi_scale_camseg sums them, or that sum itself [B,K,S,S] (seg_ps)
+    with n_scales, the number of scales it holds.  q = softmax(z / (2 n_scales temp)) over the background and the classes of cls_label,
+    0 exactly for an absent class."""
+    if isinstance(seg, (list, tuple)):
+        n, B = len(seg), seg[0].shape[0] // 2
+        z = None
+        for s in seg:
+            up = F.interpolate(s, size=(int(S), int(S)), mode="bilinear", align_corners=False)
+            v = up[:B] + up[B:].flip(-1)
+            z = v if z is None else z + v
+    else:
+        if n_scales is None:
+            raise ValueError("seg_soft_targets_torch: a summed seg_ps needs n_scales, the number of scales it holds")
+        n, z = int(n_scales), seg
+    z = z / (2.0 * n * float(temp))
+    present = torch.cat([torch.ones_like(cls_label[:, :1]), cls_label], dim=1) != 0
+    z = torch.where(present[:, :, None, None], z, torch.full_like(z, float("-inf")))
+    return F.softmax(z, dim=1)
+
+
+def seg_soft_loss_torch(seg_up, seg, cls_label, img_box, temp, conf, fg_alpha, n_scales=None):
+    """the term on the student's up-sampled logits seg_up [B,K,S,S] by the torch composition (seg, n_scales: seg_soft_targets_torch's)"""
+    with torch.no_grad():
+        q = seg_soft_targets_torch(seg, cls_label, seg_up.shape[-1], temp, n_scales=n_scales)
+    return _seg_soft_torch(_wide(seg_up), q, fg_alpha=fg_alpha, img_box=img_box, conf=conf)
+
+
+def _seg_soft_kernel_ok(seg_lr, seg_scales, cls_label, S):
+    if not (isinstance(seg_scales, (list, tuple)) and 1 <= len(seg_scales) <= SEG_SOFT_MAX_SCALES):
+        return False
+    if not (seg_lr.is_cuda and seg_lr.dtype == torch.float32 and seg_lr.dim() == 4 and cls_label.is_cuda):
+        return False
+    B, K, h, w = seg_lr.shape
+    if not (0 < B <= 65535 and 2 <= K <= SEG_SOFT_MAX_K and S % 2 == 0 and S >= CAM_UPSAMPLE_MIN * h and S >= CAM_UPSAMPLE_MIN * w):
+        return False
+    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[0] == 2 * B and t.shape[1] == K and
+               0 < t.shape[2] <= S and 0 < t.shape[3] <= S for t in seg_scales) and tuple(cls_label.shape) == (B, K - 1)
+
+
+class _SegSoftFn(Function):
+    """the value and the four sums from one forward launch (cosa_seg_soft_forward); the gradient of the student's low-res logits from one
+    backward launch that reads those sums on the device (cosa_seg_soft_backward).  The target is a constant: no other input has a gradient."""
+
+    @staticmethod
+    def forward(ctx, seg_lr, labels, boxes, S, temp, conf, fg_alpha, *seg_scales):
+        B, K, h, w = seg_lr.shape
+        L = _C.lib()
+        ptrs, hs, ws, n, _, _ = _scale_args(seg_scales)
+        sums = torch.empty(4, device=seg_lr.device, dtype=torch.float32)
+        loss = torch.empty(1, device=seg_lr.device, dtype=torch.float32)
+        wsp = _C.workspace(L.cosa_seg_soft_workspace_bytes(B, K, h, w), seg_lr.device, "seg_soft")
+        _C.check(L.cosa_seg_soft_forward(_C.ptr(seg_lr), ptrs, hs, ws, n, _C.ptr(labels), _C.ptr(boxes), _C.ptr(sums), _C.ptr(loss), B, K, h, w,
+                                         int(S), float(temp), float(conf), float(fg_alpha), _C.ptr(wsp), wsp.numel(), _C.stream_ptr()),
+                 "cosa_seg_soft_forward")
+        ctx.save_for_backward(seg_lr, labels, boxes, sums, *seg_scales)
+        ctx.cfg = (int(S), float(temp), float(conf), float(fg_alpha))
+        ctx.mark_non_differentiable(sums)
+        return loss[0], sums
+
+    @staticmethod
+    def backward(ctx, g, _g_sums):
+        seg_lr, labels, boxes, sums, *seg_scales = ctx.saved_tensors
+        S, temp, conf, fg_alpha = ctx.cfg
+        B, K, h, w = seg_lr.shape
+        L = _C.lib()
+        ptrs, hs, ws, n, _, _ = _scale_args(seg_scales)
+        up = g.detach().reshape(1).float().contiguous()
+        grad = torch.empty_like(seg_lr)
+        wsp = _C.workspace(L.cosa_seg_soft_workspace_bytes(B, K, h, w), seg_lr.device, "seg_soft")
+        _C.check(L.cosa_seg_soft_backward(_C.ptr(seg_lr), ptrs, hs, ws, n, _C.ptr(labels), _C.ptr(boxes), _C.ptr(sums), _C.ptr(up), _C.ptr(grad),
+                                          B, K, h, w, S, temp, conf, fg_alpha, _C.ptr(wsp), wsp.numel(), _C.stream_ptr()),
+                 "cosa_seg_soft_backward")
+        return (grad,) + (None,) * (6 + len(seg_scales))
+
+
+def seg_soft_loss(seg_lr, seg_scales, cls_label, img_box, S, temp=1.0, conf=0.0, fg_alpha=0.5, return_sums=False):
+    """The soft-label seg loss of the student's low-res logits seg_lr [B,K,h,w] against the teacher's per-scale low-res
+    segs seg_scales (list of [2B,K,h_i,w_i]: original batch, then the flipped one).  Per full-resolution pixel inside its box img_box[b] =
+    (y0, y1, x0, x1): z = the sum of the up-sampled passes (multi_scale_camseg's sum), q = softmax(z / (2 n_scales temp)) over the background
+    and the classes of cls_label (0 exactly for an absent class), l = - sum_k q_k log softmax(up(seg_lr))_k; background set: the first argmax of
+    q is 0, foreground set: it is not; neither where max q <= conf;
+        L = (1 - fg_alpha) sum_bg l / (n_bg + 1e-6) + fg_alpha sum_fg l / (n_fg + 1e-6)     (an empty set contributes 0).
+    The gradient goes to seg_lr only.  fp32 device tensors inside the kernels' envelope (K <= 128, at most 4 scales of at most S x S, S even
+    and >= 8 h) run on the HIP kernels, which write nothing of size [B,K,S,S]; anything else takes the torch composition.
+    -> loss (fp32 scalar), or (loss, sums = [sum_bg, n_bg, sum_fg, n_fg]) with return_sums (kernels only; None on the torch path)."""
+    check_seg_soft_settings(0.0, temp, conf)
+    S = int(S)
+    if _seg_soft_kernel_ok(seg_lr, seg_scales, cls_label, S):
+        boxes = _boxes_to_device(_abs_boxes(img_box, S, S), seg_lr.device)
+        if tuple(boxes.shape) != (seg_lr.shape[0], 4):
+            raise ValueError("seg_soft_loss: img_box must be [b,4]")
+        loss, sums = _SegSoftFn.apply(seg_lr.contiguous(), cls_label.contiguous().float(), boxes, S, float(temp), float(conf), float(fg_alpha),
+                                      *[t.contiguous() for t in seg_scales])
+        return (loss, sums) if return_sums else loss
+    up = F.interpolate(_wide(seg_lr), size=(S, S), mode="bilinear", align_corners=False)
+    loss = seg_soft_loss_torch(up, seg_scales, cls_label, img_box, temp, conf, fg_alpha)
+    return (loss, None) if return_sums else loss
+
+
+# --------------------------------------------------------------------------------------------
 # dense-CRF post-processing of the final evaluation  (utils/seg_helper.py:961-996)
 # --------------------------------------------------------------------------------------------
 class DenseCRF(object):

@@ -616,6 +616,25 @@ int cosa_cam_lossv3(const float *cam, const uint8_t *label, float *grad, float *
                     size_t workspace_bytes, void *stream);
 int cosa_cam_label(const float *const *seg_scales, const int *hs, const int *ws, int n_scales, const float *labels, uint8_t *out,
                    int B, int K, int S, float temperature, float segconf_thre, int after_softmax, void *stream);
+/* The soft-label seg loss distilled from the teacher's segmentation (utils/seg_helper.py:837-861, seg_softloss).  Per pixel
+ * (y, x) of image b inside boxes[b] = (y0, y1, x0, x1): z_k = the sum over scales and both flips of the bilinearly up-sampled teacher segs
+ * (cosa_cam_loss_targets_m's inputs and sum), q = softmax(z / (2 n_scales temp)) over the background and the classes of labels[b] (q_k = 0
+ * exactly for an absent class), l = - sum_k q_k log p_k with p the softmax of bilinear_up(seg_lr).  The pixel is background when the first
+ * argmax of q is 0 and foreground otherwise, and in neither set when max q <= conf or outside the box.
+ *   sums[4] = {sum_bg l, n_bg, sum_fg l, n_fg}     loss[0] = (1 - fg_alpha) sums[0] / (sums[1] + 1e-6) + fg_alpha sums[2] / (sums[3] + 1e-6)
+ *   grad_seg_lr [B,K,hs,ws] = upstream[0] * d loss / d seg_lr (the target is a constant), from the forward's `sums` on the device.
+ * 64-bit fixed-point sums and gradient cells, integer atomics only: the same bytes every run; a sum the fixed point cannot carry gives NaN.
+ * Nothing of size [B,K,S,S] is written, and no pixel outside its box is evaluated.  Envelope: 2 <= K <= 128, 1 to 4 scales of at most S x S,
+ * S even, S >= 8 hs and S >= 8 ws, temp finite and positive, conf in [0, 1), fg_alpha in [0, 1]; anything else is COSA_EINVAL and launches
+ * nothing.  workspace: cosa_seg_soft_workspace_bytes(B, K, hs, ws) bytes, the same buffer for a forward and its backward.                  */
+size_t cosa_seg_soft_workspace_bytes(int B, int K, int hs, int ws);
+int cosa_seg_soft_forward(const float *seg_lr, const float *const *seg_scales, const int *hs_t, const int *ws_t, int n_scales,
+                          const float *labels, const int32_t *boxes, float *sums, float *loss, int B, int K, int hs, int ws, int S,
+                          float temp, float conf, float fg_alpha, void *workspace, size_t workspace_bytes, void *stream);
+int cosa_seg_soft_backward(const float *seg_lr, const float *const *seg_scales, const int *hs_t, const int *ws_t, int n_scales,
+                           const float *labels, const int32_t *boxes, const float *sums, const float *upstream, float *grad_seg_lr,
+                           int B, int K, int hs, int ws, int S, float temp, float conf, float fg_alpha, void *workspace,
+                           size_t workspace_bytes, void *stream);
 /* utils/seg_helper.py:210-230 (get_energy_loss: F.softmax over the classes of the full-resolution logits) + :199-203 (DenseEnergyLoss.forward:
  * bilinear resize of the probabilities by 0.5 = the mean of each 2x2 quad) in one pass, and the backward of the pair:
  *   logit [B,K,H,W] (H, W even)   out / grad_out [B,K,H/2,W/2]   grad_logit [B,K,H,W]                                                     */
